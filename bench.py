@@ -17,13 +17,22 @@ the ranks (weak scaling: 100k per GPU) and ONE RCCL all-gather of the 4 B x N we
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Every run (any N) also reports `extras.pf_sharded`: config C5's per-GPU term -- 125 000 particles x 256 beams per GPU on the
-1M-triangle sphere, particles block-partitioned over the ranks, sensor update + ONE all-gather of the weights (RCCL when
-N > 1) + the {sum, max} all-reduce; at N = 8 that block IS config C5.
+A plain run does only what the headline figure needs: set-up (map, operator and, for C2, rmclhip_rcc_autotune), the W
+warm-up steps, the K timed steps and the result line; `roofline`, `cpu_baseline` and `extras` beyond the timed traversal are
+null / empty.  --full adds everything else below (the figures of earlier rounds' lines); --no-extras and --no-cpu-baseline
+trim a --full run.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events on the stream the kernel runs on
-(rmclhip_rcc_time_find / rmclhip_pf_time_update); `cpu_baseline` times the CPU oracle (a port -- the
+With --full, every run (any N) also reports `extras.pf_sharded`: config C5's per-GPU term -- 125 000 particles x 256 beams per
+GPU on the 1M-triangle sphere, particles block-partitioned over the ranks, sensor update + ONE all-gather of the weights (RCCL
+when N > 1) + the {sum, max} all-reduce; at N = 8 that block IS config C5.
+
+Prints ONE JSON line on rank 0.  `roofline` (--full) is measured live with HIP events on the stream the kernel runs on
+(rmclhip_rcc_time_find / rmclhip_pf_time_update); `cpu_baseline` (--full) times the CPU oracle (a port -- the
 reference's Embree path cannot be built here) on the host cores, rank 0, N=1 only.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy
+(float32, or float64 for integers): C2 the five find outputs, pf the gathered weights and the particle attributes.
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -82,6 +91,14 @@ def median_kernel_ms(fn, batches=9):
     return ts[len(ts) // 2]
 
 
+def _dump_outputs(out_dir, np, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array; floats as float32 (float64 stays), integers as float64 (exact up to 2^53)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32))
+
+
 def main():
     # Libraries below us write to stdout on their own (RCCL prints a version banner when its first communicator is created):
     # everything but the ONE result line goes to stderr -- fd 1 is pointed at fd 2 for the whole run and the JSON line is
@@ -99,11 +116,19 @@ def main():
     ap.add_argument("--no-autotune", action="store_true",
                     help="time the headline scan on the automatic RULE's traversal instead of the one rmclhip_rcc_autotune measures fastest "
                          "on this map / model / pose (INTEGRATION.md: the sensor set-up calls it once; results are bit-identical either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, cpu_baseline and extras (separate runs of other kernels, sizes and CPU loops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU plumbing tests)")
     ap.add_argument("--all-on-device0", action="store_true", help="testing only: every rank uses GPU 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    with_extras = args.full and not args.no_extras
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
 
     import numpy as np
     import torch
@@ -157,20 +182,26 @@ def main():
         rcc.setModel(model)
         # replicas: rank r localises a scan from a different pose inside the same map
         Tbm = T.mult(syn.pose_c2_truth(), T.transform_from_rpy((0.05 * rank, -0.03 * rank, 0.0), (0.0, 0.0, 0.11 * rank)))
-        # dominant kernel, measured live FIRST: HIP events on the rcc's own stream around back-to-back launches; median of 9
+        # --full: dominant kernel, measured live FIRST: HIP events on the rcc's own stream around back-to-back launches; median of 9
         # batches of 40 launches.  (It runs before the W + K steps on purpose: a run with few steps -- the driver's K = 20 is
         # 0.35 ms of GPU time -- would otherwise be timed on a device that has not left its idle clocks: 19.0 vs 18.2 us per
-        # step measured; the metric is steady-state rays/s.  DESIGN.md section 5.)
+        # step measured; the metric is steady-state rays/s.  DESIGN.md section 5.  A plain run skips it: the autotune's trial
+        # launches right before the steps do the same -- plain and --full time the same us per step at K = 20, 200 and 20 000.)
         rule_kind = rcc.find_variant(1)
-        rule_kernel_ms = median_kernel_ms(lambda: rcc.time_find(Tbm, iters=40))
+        rule_kernel_ms = median_kernel_ms(lambda: rcc.time_find(Tbm, iters=40)) if args.full else None
         tuned = None
         if args.variant == 15 and not args.no_autotune:
             # what INTEGRATION.md's sensor set-up does once per (map, model): the operator measures its own single-scan traversals here
             # (kinds 2 / 23 / 24 with and without the frontier start, kind 32 = the cooperative descent with a short and a long list, then
             # the tile shape) and keeps the fastest.  The step below is the same rmclhip_rcc_find_async either way.
             k_t, ms_t = rcc.autotune(Tbm)
-            tuned = {"rule_kind": rule_kind, "rule_kernel_ms": round(rule_kernel_ms, 5), "chosen_kind": k_t, "autotune_kernel_ms": round(ms_t, 5)}
-        kernel_ms = median_kernel_ms(lambda: rcc.time_find(Tbm, iters=40)) if tuned else rule_kernel_ms
+            tuned = {"rule_kind": rule_kind}
+            if rule_kernel_ms is not None:
+                tuned["rule_kernel_ms"] = round(rule_kernel_ms, 5)
+            tuned.update(chosen_kind=k_t, autotune_kernel_ms=round(ms_t, 5))
+        kernel_ms = None
+        if args.full:
+            kernel_ms = median_kernel_ms(lambda: rcc.time_find(Tbm, iters=40)) if tuned else rule_kernel_ms
         step = rcc.find_async_fn(Tbm)   # rmclhip_rcc_find_async(handle, pose) with the pose converted once: one C call per step
         for _ in range(max(args.warmup, 1)):
             step()
@@ -188,17 +219,24 @@ def main():
         torch.cuda.synchronize()
         elapsed = max_over_ranks(t1 - t0)
         units_per_step = n_rays
+        if args.dump_outputs and rank == 0:
+            # the last step's five outputs, read back before anything below launches another find on this operator
+            mv = rcc.modelView(attributes=("hits", "ranges", "points", "normals", "face_ids"))
+            _dump_outputs(args.dump_outputs, np, {k: a for k, a in mv.items() if k != "mask"})   # mask: modelView's alias of hits
 
         b_alg = algorithmic_bytes_raycast(n_rays, len(f), 1)
         kind = rcc.find_variant(1)   # the traversal that was timed: the autotuned one, the rule's (--no-autotune) or --variant's
         kname = "k_find<spherical, kind %d>" % kind
         traffic = measured_traffic("k_find_kind%d" % kind)
         if tuned is not None:
-            extras["headline_traversal"] = dict(tuned, timed_kind=kind, rule_rays_per_s=round(n_rays / (rule_kernel_ms * 1e-3), 1),
-                                                note="rmclhip_rcc_autotune ran once before the timed steps (a product call, INTEGRATION.md); "
-                                                     "--no-autotune times the automatic rule's kind; results are bit-identical")
+            ht = dict(tuned, timed_kind=kind)
+            if rule_kernel_ms is not None:
+                ht["rule_rays_per_s"] = round(n_rays / (rule_kernel_ms * 1e-3), 1)
+            ht["note"] = ("rmclhip_rcc_autotune ran once before the timed steps (a product call, INTEGRATION.md); "
+                          "--no-autotune times the automatic rule's kind; results are bit-identical")
+            extras["headline_traversal"] = ht
 
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and with_extras:
             # the boundary's Simulator surface (round 6): the MICP bundle {points, normals, hits} = 25 B/ray that Correspondences_::model_buffers_
             # carries (Correspondences.hpp:81-85) beside the five-output headline (33 B/ray); simulate() into a caller-owned
             # Bundle<Ranges, Normals> (scan_map_segmentation_embree.cpp:80-87); the free statistics_p2l on caller-owned views
@@ -514,7 +552,7 @@ def main():
             extras["pf_sharded_cabi_allreduce_stats_ms"] = round(_median_call_ms(lambda: shp.stats(), reps=9, warm=1), 4)
             shp.close()
 
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and with_extras:
             # the reference's own 1 M- and 10 M-face rows (lidar_corrector_{optix,embree}_benchmark.cpp:144-152, :161-169): maps that leave
             # the L2s (1 M: 128 MB) and the MALL (10 M: 1.29 GB)
             extras["large_maps"] = _large_maps(ra, syn, T, np, ctx)
@@ -526,7 +564,7 @@ def main():
             extras["stack_bounded_maps"] = _stack_bounded_maps(ra, syn, T, np, ctx)
 
         # config C5's per-GPU term, on every rank and for every N (the only BASELINE config that shards)
-        if not args.no_extras:
+        if with_extras:
             blk = _pf_sharded_block(ra, syn, T, np, torch, dist, ctx, rank, world)
             if rank == 0:
                 extras["pf_sharded"] = blk
@@ -535,7 +573,7 @@ def main():
             if rank == 0:
                 extras["pose_batches"] = pose_batches
 
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and with_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as orc  # cpu_baseline leg only: the oracle is the thing timed, never the product path
             m = orc.Mesh(v, f)
@@ -651,14 +689,22 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            weights = step()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         barrier()
         torch.cuda.synchronize()
         elapsed = max_over_ranks(t1 - t0)
         units_per_step = n_local * n_beams
-        kernel_ms = upd.time_update(d_poses, d_attrs, hi - lo, iters=5)
+        if args.dump_outputs and rank == 0:
+            # what a caller of the step receives (the weights, gathered over the ranks when N > 1) and the attributes it updated in place
+            outs = {"weights": weights.cpu().numpy()}
+            a = d_attrs.download()
+            for fld in ("mean", "sigma", "n_meas"):
+                outs["attrs_likelihood_" + fld] = a["likelihood"][fld]
+            outs["attrs_state_sigma"] = a["state_sigma"]
+            _dump_outputs(args.dump_outputs, np, outs)
+        kernel_ms = upd.time_update(d_poses, d_attrs, hi - lo, iters=5) if args.full else None
         b_alg = algorithmic_bytes_pf(hi - lo, n_beams)
         # (the updater runs on the library's default variant -- this workload sets none --, which launches the accumulation form:
         # capi_pf.cpp / kernels.hip launch_pf_update; a run under rmclhip_pf_set_variant would need the label re-derived)
@@ -672,16 +718,18 @@ def main():
         parallelism = "particles-sharded dp%d + all_gather(4B x N)" % world
         n_rays = units_per_step
 
-    achieved = b_alg / (kernel_ms * 1e-3) / 1e9
     # `frac` is the contract's figure (algorithmic bytes / kernel time against the HBM peak).  It is NOT what bounds these kernels:
     # measured HBM traffic is 0.44x the algorithmic bytes for the find (the map is served from L2 / MALL; the launch ends with its
     # slowest wave's chain of dependent fetches) and 1.8x for the particle filter (round 5: the order-independent accumulation keeps no
     # per-beam storage; round 4's error scratch made it ~20x) -- that kernel is bound by VALU issue and occupancy
-    roofline = {"bound": "latency / issue (frac = the contract's HBM fraction)", "contract_bound": "hbm",
-                "kernel": kname, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                "algorithmic_bytes_per_launch": b_alg, "kernel_ms": round(kernel_ms, 5),
-                "kernel_units_per_s": round(units_per_step / (kernel_ms * 1e-3), 1)}
+    roofline = None
+    if kernel_ms is not None:
+        achieved = b_alg / (kernel_ms * 1e-3) / 1e9
+        roofline = {"bound": "latency / issue (frac = the contract's HBM fraction)", "contract_bound": "hbm",
+                    "kernel": kname, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                    "algorithmic_bytes_per_launch": b_alg, "kernel_ms": round(kernel_ms, 5),
+                    "kernel_units_per_s": round(units_per_step / (kernel_ms * 1e-3), 1)}
     if rank == 0:
         out = {
             "metric": metric,

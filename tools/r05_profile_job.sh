@@ -4,11 +4,11 @@
 #   /usr/local/graft/bin/gpurun --timeout 1500 -- 'bash tools/r05_profile_job.sh'
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_form_steps20_warmup5.json 2> $O/bench_driver_form.err
-rocprofv3 --kernel-trace --stats -d $O/trh -o t -- python bench.py --no-cpu-baseline --no-extras > $O/bench_headline_under_rocprof.json 2> $O/bench_headline_under_rocprof.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_form_steps20_warmup5.json 2> $O/bench_driver_form.err
+rocprofv3 --kernel-trace --stats -d $O/trh -o t -- python bench.py --full --no-cpu-baseline --no-extras > $O/bench_headline_under_rocprof.json 2> $O/bench_headline_under_rocprof.err
 python tools/prof_summary.py $(find $O/trh -name "*results.db" | head -1) 2>&1 | cut -c1-170 > $O/kernel_stats_headline.txt
-rocprofv3 --kernel-trace --stats -d $O/trf -o t -- python bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats -d $O/trf -o t -- python bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 python tools/prof_summary.py $(find $O/trf -name "*results.db" | head -1) 2>&1 | head -60 | cut -c1-170 > $O/kernel_stats_full_bench.txt
 rm -rf $O/trh $O/trf
 bash tools/pmc_traffic.sh r05 > $O/traffic_passes.log 2>&1
