@@ -533,7 +533,8 @@ class Correspondences_<VRAM_HIP> {
     return out;
   }
   rmclhip_rcc* handle() const { return h_; }
-  // moment form of correctOnce's fixed-correspondence loop (rmclhip.h: rmclhip_rcc_set_micp_fast): 0 never, 1 automatic
+  // moment form of correctOnce's fixed-correspondence loop (rmclhip.h: rmclhip_rcc_set_micp_fast): 0 never, 1 automatic,
+  // 3 / 4 device loops (A/B)
   void setMicpFast(int mode) { check(rmclhip_rcc_set_micp_fast(h_, mode)); }
   rmclhip_micp_fast_info micpFastInfo() const {
     rmclhip_micp_fast_info info{};

@@ -397,9 +397,9 @@ rmclhip_status rmclhip_rcc_sharded_correct_batch(rmclhip_rcc_sharded* h, const r
  * hand-over among them) is a measured-and-rejected or superseded experiment that lives in librmclhip_lab.so (include/rmclhip_lab.h lists
  * them) and is accepted here only while that library is loaded (RMCLHIP_ERR_UNSUPPORTED otherwise),
  * bits 4..7 = 1 + log2(tile width) of the wave's scan-image tile (0 = automatic: 16 wide x 4 tall, 8x8 for the wave packet),
- * bit 8 = fused last-block reduction tail (A/B), bit 9 = disable the hipGraph MICP loop (A/B), bits 10..12 = form
- * of the MICP loop (0 = one launch per iteration, the default; 1 = reduce + solve launches; 2..6 = persistent
- * kernel with 16..256 blocks and a grid barrier, A/B) */
+ * bit 9 = enqueue the per-iteration MICP loop directly instead of replaying it from a hipGraph (A/B).  Bits 8 and 10..12 (a
+ * fused last-block reduction tail, reduce + solve launches, a persistent grid-barrier loop: MICP loop forms measured slower)
+ * are retired: RMCLHIP_ERR_INVALID */
 rmclhip_status rmclhip_rcc_set_variant(rmclhip_rcc* rcc, int variant);
 /* Moment form of the schedule-(R) loop of rmclhip_rcc_correct_once (refind_each_iteration = 0; micp_localization.cpp:900-964
  * iterates statistics_p2l + umeyama over FIXED correspondences): the gate |dist| < max_dist is the only part of the 16 raw
@@ -412,9 +412,9 @@ rmclhip_status rmclhip_rcc_set_variant(rmclhip_rcc* rcc, int variant);
  * 10 x 10 product of factor vectors per correspondence through f64 MFMA; a fold launch sums the per-workgroup rows and publishes
  * {82 moments, the undecided correspondences (<= 1024)} to the host -- and the ITERATIONS RUN ON THE HOST (~0.5 us each; the same
  * published set then also answers rmclhip_rcc_compute_cross_statistics without a launch, see rmclhip_ccs_info); more than 1024
- * undecided: the device loop of mode 4 on the same rows.  2 = device loop, find + moments pass + loop replayed from a hipGraph
- * behind an H2D copy node (A/B); 3 = device loop, three plain launches (A/B: the moments always in a pass of their own); 4 = device
- * loop behind a find with the moment epilogue (round 3's default, A/B: one lane of the GPU solves every iteration). */
+ * undecided: the device loop of mode 4 on the same rows.  3 = device loop, three plain launches (A/B: the moments always in a pass
+ * of their own); 4 = device loop behind a find with the moment epilogue (round 3's default, A/B: one lane of the GPU solves every
+ * iteration).  2 (the device loop replayed from a hipGraph, measured slower than direct launches) is retired: RMCLHIP_ERR_INVALID. */
 typedef struct {
   uint32_t attempts, done, cap_exits, overflows;   /* outcomes since the operator was created */
   uint32_t last_code;                              /* 0 done, 1 pre-transform left the bounds, 2 too many undecided: > 1024 leaves the host form for the device loop, > 4096 the moment form altogether */

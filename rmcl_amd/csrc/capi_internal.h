@@ -137,7 +137,6 @@ struct rmclhip_ctx {
   cstats* p2l_h_stats_dev = nullptr;
   unsigned long long* p2l_h_done = nullptr;
   unsigned long long* p2l_h_done_dev = nullptr;
-  uint32_t* p2l_tickets = nullptr;      // (the fused tail's arrival counter: unused by this path, the kernel's parameter block wants one)
   uint32_t p2l_seq = 0;
   ~rmclhip_ctx();                       // capi_map.cpp
 };
@@ -219,8 +218,6 @@ struct rmclhip_rcc {
   MicpState* h_state = nullptr;    // pinned, host-mapped
   MicpState* h_state_dev = nullptr;  // device alias of h_state
   uint32_t* d_counter = nullptr;
-  uint32_t* d_tickets = nullptr;
-  uint32_t* d_loop_barrier = nullptr;  // counter of the persistent-loop grid barrier   // one arrival counter per pose for the fused reduction tail
   // device-resident MICP loop as a static hipGraph: per-call inputs travel in one 256-B H2D copy
   MicpCall* h_call = nullptr;      // pinned
   MicpCall* d_call = nullptr;
@@ -228,20 +225,15 @@ struct rmclhip_rcc {
   hipGraph_t micp_graph = nullptr;
   struct MicpKey {
     uint32_t n_iter = 0, W = 0, H = 0, n_dataset = 0;
-    int kind = 0, variant = 0, tile = 0, fused = 0, has_mask = 0;
+    int kind = 0, variant = 0, tile = 0, has_mask = 0;
     const void* ptrs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool operator==(const MicpKey& o) const { return std::memcmp(this, &o, sizeof(MicpKey)) == 0; }
-  } micp_key, micp_fast_key;
-  bool use_graph = true;
-  bool fast_graph_dirty = true;    // same, for the moment-form graph
+  } micp_key;
+  bool use_graph = true;           // rmclhip_rcc_set_variant bit 9 clears it: the chain is enqueued directly
   bool graph_dirty = true;         // set by setModel / set_variant: by-value launch arguments changed
-  size_t tickets_cap = 0;
-  int loop_blocks = 0;             // MICP loop form (schedule R): 0 one launch per iteration (k_micp_iter), -1 classic
-                                   // reduce + solve launches, > 0 persistent k_micp_loop with this many blocks
-  bool fused_tail = false;         // true: last-block tail inside the reduction kernel (measured slower, A/B only)
   // moment form of the schedule-(R) loop (launch_micp_fast): tried first when the previous corrections say the gate
   // decisions are stable; the per-iteration form above is the fallback and the reference for the result
-  int fast_mode = 1;               // rmclhip_rcc_set_micp_fast: 0 off, 1 automatic with the iterations on the host (default), 2 / 3 / 4 device loops (A/B)
+  int fast_mode = 1;               // rmclhip_rcc_set_micp_fast: 0 off, 1 automatic with the iterations on the host (default), 3 / 4 device loops (A/B)
   DevBuf<double> d_fast_partials;
   DevBuf<unsigned long long> d_fast_mask;
   double* d_fold_rows = nullptr;      // hand-over area of the loop launch's folding workgroups (kernels.h: kMicpFoldBlocks)
@@ -262,8 +254,6 @@ struct rmclhip_rcc {
   bool cpc_tracking = true;
   bool cpc_bounded = false;        // rmclhip_rcc_set_cpc_bounded: search only within max_dist
   bool cpc_grid = true;            // rmclhip_rcc_set_cpc_grid: points without a tracking seed start from the map's near grid
-  hipGraphExec_t micp_fast_exec = nullptr;
-  hipGraph_t micp_fast_graph = nullptr;
   float fast_rho_cap = 0.02f, fast_tau_cap = 0.1f;   // bounds on |2 sin(theta/2)| and |t| of the pre-transforms
   uint32_t fast_holdoff = 0;       // corrections to skip the attempt for (after repeated overflows)
   uint32_t fast_overflows = 0;     // consecutive
@@ -415,14 +405,12 @@ struct rmclhip_resampler {
 };
 
 
+// the launch reduce_enqueue issues after the reduction: k_reduce_finalize (kTailStats) or k_batch_solve (kTailBatchSolve)
 struct ReduceTail {
   uint32_t mode = kTailNone;
-  const MicpCall* call = nullptr;
-  cstats* stats_out = nullptr;
-  xform Tbo = xidentity();
-  MicpState* state = nullptr;
-  xform* Tdelta_out = nullptr;
-  unsigned long long* done = nullptr;   // host-mapped completion tag (kTailStats, one pose, unfused tail)
+  cstats* stats_out = nullptr;          // kTailStats; kTailBatchSolve (nullable there)
+  xform* Tdelta_out = nullptr;          // kTailBatchSolve
+  unsigned long long* done = nullptr;   // host-mapped completion tag (kTailStats, one pose)
   uint32_t seq = 0;                     // ... and the sequence number it must carry
 };
 

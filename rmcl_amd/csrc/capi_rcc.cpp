@@ -61,13 +61,9 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
   if (r->h_stats) DBG_STEP(hipHostFree(r->h_stats));
   if (r->h_state) DBG_STEP(hipHostFree(r->h_state));
   if (r->d_state) DBG_STEP(hipFree(r->d_state));
-  if (r->d_loop_barrier) DBG_STEP(hipFree(r->d_loop_barrier));
   if (r->d_counter) DBG_STEP(hipFree(r->d_counter));
-  if (r->d_tickets) DBG_STEP(hipFree(r->d_tickets));
   if (r->micp_exec) DBG_STEP(hipGraphExecDestroy(r->micp_exec));
   if (r->micp_graph) DBG_STEP(hipGraphDestroy(r->micp_graph));
-  if (r->micp_fast_exec) DBG_STEP(hipGraphExecDestroy(r->micp_fast_exec));
-  if (r->micp_fast_graph) DBG_STEP(hipGraphDestroy(r->micp_fast_graph));
   if (r->h_fast_status) DBG_STEP(hipHostFree(r->h_fast_status));
   if (r->h_done) DBG_STEP(hipHostFree(r->h_done));
   if (r->h_mom) DBG_STEP(hipHostFree(r->h_mom));
@@ -104,7 +100,7 @@ rmclhip_status rmclhip_rcc_set_model_spherical(rmclhip_rcc* r, const rmclhip_sph
   HIPCHK(hipStreamSynchronize(r->stream));
   const uint32_t H = m->phi.size, W = m->theta.size;
   r->kind = kModelSpherical;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   r->W = W; r->H = H;
   r->range = m->range;
   r->orig = mk3(0.f, 0.f, 0.f);
@@ -137,7 +133,7 @@ rmclhip_status rmclhip_rcc_set_model_o1dn(rmclhip_rcc* r, uint32_t width, uint32
   HIPCHK(hipStreamSynchronize(r->stream));
   r->kind = kModelO1Dn;
   r->ang_aspect = 0.0f;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   r->W = width; r->H = height;
   r->range = range;
   r->orig = mk3(orig.x, orig.y, orig.z);
@@ -159,7 +155,7 @@ rmclhip_status rmclhip_rcc_set_model_pinhole(rmclhip_rcc* r, uint32_t width, uin
   HIPCHK(hipStreamSynchronize(r->stream));
   r->kind = kModelPinhole;
   r->ang_aspect = 0.0f;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   r->W = width; r->H = height;
   r->range = range;
   r->orig = mk3(0.f, 0.f, 0.f);
@@ -177,7 +173,7 @@ rmclhip_status rmclhip_rcc_set_model_ondn(rmclhip_rcc* r, uint32_t width, uint32
   r->ang_aspect = 0.0f;
   r->tile_planes_ok = false;
   r->tuned_kind = r->tuned_batch_kind = 0; r->tuned_frontier = r->tuned_batch_frontier = true; r->tuned_tile = 0; r->tuned_xcd_mapping = 0;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   r->W = width; r->H = height;
   r->range = range;
   r->orig = mk3(0.f, 0.f, 0.f);
@@ -299,7 +295,7 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2(rmclhip_rcc* r, const uint8_t* 
   HIPCHK(hipStreamSynchronize(r->stream));
   r->kind = kModelO1Dn;
   r->ang_aspect = 0.0f;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   r->W = ow; r->H = oh;
   r->range = range;
   r->orig = mk3(0.f, 0.f, 0.f);
@@ -467,7 +463,7 @@ RMCL_INTERNAL rmclhip_status rebuild_tile_planes(rmclhip_rcc* r, bool keep_tunin
   HIPCHK(r->d_tile_planes.reserve(static_cast<size_t>(p.tiles_x) * p.tiles_y * 16u));
   HIPCHK(launch_tile_planes(p, r->kind, r->d_tile_planes.p, r->stream));
   r->tile_planes_ok = true;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   return RMCLHIP_OK;
 }
 
@@ -493,7 +489,7 @@ RMCL_INTERNAL rmclhip_status find_enqueue(rmclhip_rcc* r, const xform& Tbm, bool
     r->ccs_loop = r->ccs_since_find != 0u;
     r->ccs_since_find = 0u; r->ccs_max_rho = 0.f; r->ccs_max_tau = 0.f;
     const int fv = find_variant(r, 1);
-    if (r->ccs_loop && r->fast_mode == 1 && !r->fused_tail && r->n_dataset != 0u && (fv == 23 || fv == 32 || fv == 2) && r->ccs_last_maxd == r->ccs_last_maxd &&
+    if (r->ccs_loop && r->fast_mode == 1 && r->n_dataset != 0u && (fv == 23 || fv == 32 || fv == 2) && r->ccs_last_maxd == r->ccs_last_maxd &&
         micp_outputs_selected(r)) {
       gate_band(r, r->ccs_last_maxd, &r->pend_lo, &r->pend_hi);
       r->pend_rho = r->fast_rho_cap; r->pend_tau = r->fast_tau_cap;
@@ -729,14 +725,6 @@ RMCL_INTERNAL rmclhip_status reduce_enqueue(rmclhip_rcc* r, const xform& Tpre, c
   if (r->n_model != n && nposes > 1) return fail(RMCLHIP_ERR_INVALID, "batch reduction needs dataset size == model size");
   const uint32_t nb = reduce_num_blocks(n, nposes);
   HIPCHK(r->d_partials.reserve(static_cast<size_t>(nposes) * nb * 16));
-  if (r->tickets_cap < nposes) {
-    if (r->d_tickets) (void)hipFree(r->d_tickets);
-    r->d_tickets = nullptr;
-    r->tickets_cap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_tickets), sizeof(uint32_t) * nposes));
-    HIPCHK(hipMemset(r->d_tickets, 0, sizeof(uint32_t) * nposes));
-    r->tickets_cap = nposes;
-  }
   ReduceParams p;
   std::memset(&p, 0, sizeof(p));
   p.dataset_points = r->ds_pts;
@@ -751,21 +739,9 @@ RMCL_INTERNAL rmclhip_status reduce_enqueue(rmclhip_rcc* r, const xform& Tpre, c
   p.Tpre_dev = Tpre_dev;
   p.partials = r->d_partials.p;
   p.nblocks = nb;
-  p.tickets = r->d_tickets;
-  p.call = tail.call;
-  p.Tsb = r->Tsb;
-  p.Tbo = tail.Tbo;
-  p.state = tail.state;
-  p.stats_out = tail.stats_out;
-  p.Tdelta_out = tail.Tdelta_out;
-  p.tail_mode = r->fused_tail ? tail.mode : static_cast<uint32_t>(kTailNone);
   HIPCHK(launch_reduce_partials(p, r->stream));
-  if (!r->fused_tail) {
-    if (tail.mode == kTailStats) HIPCHK(launch_reduce_finalize(r->d_partials.p, nb, nposes, tail.stats_out, tail.done, tail.seq, r->stream));
-    else if (tail.mode == kTailMicp) HIPCHK(launch_micp_step(r->d_partials.p, nb, r->Tsb, tail.Tbo, tail.call, tail.state, tail.state, r->stream));
-    else if (tail.mode == kTailBatchSolve)
-      HIPCHK(launch_batch_solve(r->d_partials.p, nb, nposes, r->Tsb, tail.Tdelta_out, tail.stats_out, r->stream));
-  }
+  if (tail.mode == kTailStats) HIPCHK(launch_reduce_finalize(r->d_partials.p, nb, nposes, tail.stats_out, tail.done, tail.seq, r->stream));
+  else if (tail.mode == kTailBatchSolve) HIPCHK(launch_batch_solve(r->d_partials.p, nb, nposes, r->Tsb, tail.Tdelta_out, tail.stats_out, r->stream));
   return RMCLHIP_OK;
 }
 
@@ -967,7 +943,7 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
     r->ccs_max_rho = std::max(r->ccs_max_rho, rho);
     r->ccs_max_tau = std::max(r->ccs_max_tau, tau);
     const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-    if (r->fast_mode != 0 && !r->fused_tail && nred != 0 && maxd == maxd) {
+    if (r->fast_mode != 0 && nred != 0 && maxd == maxd) {
       ++r->ccs_info.calls;
       if (r->mset_pending) HIPCHK(wait_moments(r, r->mset_seq, r->pend_lo, r->pend_hi, r->pend_rho, r->pend_tau));
       if (!micp_set_covers(r->mset, Tpre, maxd) && r->mset_passes < 2u && rho == rho && tau == tau) {
@@ -998,8 +974,8 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
   ReduceTail tail;
   tail.mode = kTailStats;
   tail.stats_out = r->h_stats_dev;  // host-mapped: the finalize launch writes the 64-B result straight to the host
-  const bool polled = !r->fused_tail;
-  if (polled) { tail.done = r->h_done_dev; tail.seq = next_seq(r); }
+  tail.done = r->h_done_dev;
+  tail.seq = next_seq(r);
   const bool timed = r->kernel_timing;
   r->find_timing_pending = false;   // the events are reused
   r->reduce_timing_pending = false;
@@ -1007,14 +983,9 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
   if (rmclhip_status st = reduce_enqueue(r, to_x(T_snew_sold), nullptr, adaptive_max_dist(r, convergence_progress), 1, tail))
     return st;
   if (timed) HIPCHK(hipEventRecord(r->ev1, r->stream));
-  if (polled) {
-    DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
-    HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
-    r->reduce_timing_pending = timed;   // the events are read when rmclhip_rcc_last_kernel_ms asks for them
-  } else {
-    HIPCHK(hipStreamSynchronize(r->stream));
-    if (timed) HIPCHK(hipEventElapsedTime(&r->last_reduce_ms, r->ev0, r->ev1));
-  }
+  DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
+  HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
+  r->reduce_timing_pending = timed;   // the events are read when rmclhip_rcc_last_kernel_ms asks for them
   from_cs(r->h_stats[0], out);
   return RMCLHIP_OK;
 }
@@ -1063,7 +1034,7 @@ rmclhip_status rmclhip_rcc_set_outputs(rmclhip_rcc* r, uint32_t mask) {
   if (mask != r->out_mask) {
     r->out_mask = mask;
     drop_moment_set(r);   // (the set summarises buffers the next find may no longer write)
-    r->graph_dirty = true; r->fast_graph_dirty = true;   // the captured chains hold the find's output pointers by value
+    r->graph_dirty = true;   // the captured chain holds the find's output pointers by value
   }
   return RMCLHIP_OK;
 }
@@ -1153,14 +1124,11 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_stats_dev), ctx->p2l_h_stats, 0);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_done), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_done_dev), ctx->p2l_h_done, 0);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->p2l_tickets), sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(ctx->p2l_tickets, 0, sizeof(uint32_t));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
       if (ctx->p2l_h_stats) (void)hipHostFree(ctx->p2l_h_stats);
       if (ctx->p2l_h_done) (void)hipHostFree(ctx->p2l_h_done);
-      if (ctx->p2l_tickets) (void)hipFree(ctx->p2l_tickets);
-      ctx->p2l_h_stats = nullptr; ctx->p2l_h_done = nullptr; ctx->p2l_tickets = nullptr;
+      ctx->p2l_h_stats = nullptr; ctx->p2l_h_done = nullptr;
       (void)hipStreamDestroy(s);
       return fail(RMCLHIP_ERR_HIP, std::string("statistics_p2l: ") + hipGetErrorString(e));
     }
@@ -1181,15 +1149,238 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
   p.n = n; p.nposes = 1; p.max_dist = max_dist;
   p.Tpre = to_x(Tpre);
   p.partials = ctx->p2l_partials; p.nblocks = nb;
-  p.tickets = ctx->p2l_tickets;
-  p.Tsb = xidentity(); p.Tbo = xidentity();
-  p.tail_mode = static_cast<uint32_t>(kTailNone);
   if (++ctx->p2l_seq == 0u) ctx->p2l_seq = 1u;
   HIPCHK(launch_reduce_partials(p, ctx->p2l_stream));
   HIPCHK(launch_reduce_finalize(ctx->p2l_partials, nb, 1, ctx->p2l_h_stats_dev, ctx->p2l_h_done_dev, ctx->p2l_seq, ctx->p2l_stream));
   DoneCheck chk; chk.base = ctx->p2l_h_stats; chk.base_bytes = sizeof(cstats);
   HIPCHK(wait_done(ctx, ctx->p2l_h_done, ctx->p2l_seq, chk, ctx->p2l_stream));
   from_cs(*ctx->p2l_h_stats, out);
+  return RMCLHIP_OK;
+}
+
+// ---- schedule (R) of rmclhip_rcc_correct_once, micp_localization.cpp:900-964: 1 find, n_iter x (reduce + solve) -----------------
+
+// the outcome of one moment-form attempt in the handle's fast_info (code 0 done: the caps follow what it met; 1 a pre-transform left
+// the caps; 2 too many undecided correspondences)
+static void micp_record_attempt(rmclhip_rcc* r, uint32_t code, uint32_t n_uncertain, float max_rho, float max_tau) {
+  rmclhip_micp_fast_info& fi = r->fast_info;
+  fi.attempts++;
+  fi.last_code = code;
+  fi.last_uncertain = n_uncertain;
+  fi.last_rho = max_rho;
+  fi.last_tau = max_tau;
+  if (code == 0u) {
+    fi.done++;
+    learn_caps(r, max_rho, max_tau);
+  } else if (code == 1u) {
+    fi.cap_exits++;
+  } else if (code == 2u) {
+    fi.overflows++;
+  }
+}
+
+// caps of the next attempt after one the per-iteration form had to finish: the pre-transform the correction ended with (sensor frame,
+// Ts) bounds the next attempt (iterates approach it monotonically in the usual case; an attempt that still leaves the caps costs one
+// more fallback and doubles them).  After an overflow (too many undecided correspondences) the caps tighten instead.
+static void micp_caps_after_fallback(rmclhip_rcc* r, const xform& Ts, bool overflow, float prev_max_rho, float prev_max_tau) {
+  const float rho = 2.0f * std::sqrt(Ts.R.x * Ts.R.x + Ts.R.y * Ts.R.y + Ts.R.z * Ts.R.z);
+  const float tau = std::sqrt(Ts.t.x * Ts.t.x + Ts.t.y * Ts.t.y + Ts.t.z * Ts.t.z);
+  if (overflow) {
+    r->fast_rho_cap = std::max(0.002f, 1.25f * rho);
+    r->fast_tau_cap = std::max(0.005f, 1.25f * tau);
+  } else {
+    r->fast_rho_cap = std::max(0.002f, std::max(2.0f * rho, 2.0f * prev_max_rho));
+    r->fast_tau_cap = std::max(0.005f, std::max(2.0f * tau, 2.0f * prev_max_tau));
+  }
+  r->fast_info.rho_cap = r->fast_rho_cap;
+  r->fast_info.tau_cap = r->fast_tau_cap;
+}
+
+// Moment form (kernels.hip "gate-stable moment form"), fast modes 1, 3 and 4, launched directly with the per-call data BY VALUE -- no
+// H2D copy node, no graph launch (a graph replay costs the host 10-16 us whatever it holds).  *out: code 0 = served, the correction
+// is in r->h_state; 1 / 2 = the caller runs the per-iteration form, which recomputes the correction from scratch.
+static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uint32_t n_iter, float maxd, uint32_t nred,
+                                           MicpFastStatus* out) {
+  HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
+  HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
+  MicpFastStatus fs{};
+  bool fs_ready = false;     // the host ran the iterations: `fs` (and r->h_state) are final, nothing to wait for
+  FindParams fp;
+  fill_find_params(r, fp, 1);
+  fp.Tsm = r->h_call->Tsm;
+  fp.Tms = r->h_call->Tms;
+  MicpCallLite cl;
+  cl.Tsb = r->Tsb; cl.Tbo = Tbo; cl.max_dist = maxd; cl.rho_cap = r->fast_rho_cap; cl.tau_cap = r->fast_tau_cap;
+  cl.gate_lo = maxd; cl.gate_hi = maxd;
+  cl.seq = r->h_call->seq;
+  const int fv = find_variant(r, 1);
+  const bool tiled = r->fast_mode != 3 && (fv == 23 || fv == 32 || fv == 2);   // the find forms the moments in its epilogue
+  if (r->fast_mode == 1) {
+    // ---- round 4 default: TWO launches (find with the moment epilogue; fold + publish), the iterations on the HOST from the 82
+    // moments + the undecided correspondences (micp_host.h): ~0.5 us per iteration instead of ~2.7 us of one lane's f64 chain
+    if (rmclhip_status st = enqueue_find_with_moments(r, r->h_call->Tsm, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, cl.seq, true)) return st;
+    HIPCHK(wait_moments(r, cl.seq, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap));
+    if (r->mset.valid) {
+      xform T_s = xidentity();
+      cstats last = cs_identity();
+      fs.code = 0u; fs.n_uncertain = r->mset.n_unc;
+      for (uint32_t it = 0; it < n_iter; ++it) {
+        const float rho = micp_rho(T_s), tau = micp_tau(T_s);
+        fs.max_rho = std::max(fs.max_rho, rho);
+        fs.max_tau = std::max(fs.max_tau, tau);
+        if (!(rho <= r->mset.rho_cap) || !(tau <= r->mset.tau_cap)) { fs.code = 1u; fs.iter = it; break; }
+        last = micp_statistics_from_set(r->mset, T_s, maxd);
+        T_s = xmul(T_s, umeyama(last));   // kernels.hip micp_advance_sensor
+      }
+      if (fs.code == 0u) {
+        // kernels.hip micp_close_sensor
+        fs.iter = n_iter;
+        const xform Tso = xmul(Tbo, r->Tsb);
+        r->h_state->T_snew_sold = T_s;
+        r->h_state->T_onew_oold = xmul(xmul(Tso, T_s), xinv(Tso));
+        r->h_state->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(r->Tsb, last)));
+      }
+      fs_ready = true;
+    } else {
+      // more undecided correspondences than the host takes: the device loop on the rows the find left (a sequence number of its own:
+      // the publish launch used this one for its hand-over flags and its tag)
+      cl.seq = r->h_call->seq = next_seq(r);
+      // kind and row layout are the ones enqueue_find_with_moments actually ran (it replaces kind 24 by 23 to get the epilogue):
+      // the loop folds THOSE rows instead of paying a moment pass of its own
+      const int ufv = r->last_moment_find_kind;
+      FindParams ufp;
+      fill_find_params(r, ufp, 1, ufv);
+      const uint32_t unb = find_moments_blocks(ufp, ufv), uwpb = (ufv == 2) ? 1u : 4u;
+      if (r->last_moment_find_tiled)
+        HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
+                                           nred, unb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, ufp.tiles_x, ufp.tile_w_log2, uwpb, n_iter,
+                                           r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
+      else
+        HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
+                                nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
+                                r->h_done_dev, r->stream, &cl));
+    }
+  } else if (tiled) {
+    // (fast_mode 4, round 3's default) TWO kernels: the find forms the moments in its epilogue (find_kernel.hip.h: the 10 x 10 factor
+    // products of its 64 correspondences per wave through f64 MFMA), one partial row per workgroup; the loop launch folds them and runs
+    // every iteration on the device
+    const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;   // partial rows, mask words per workgroup
+    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
+    HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
+    fp.mom_dataset_points = r->ds_pts;
+    fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
+    fp.mom_n = nred;
+    fp.mom_gate_lo = maxd; fp.mom_gate_hi = maxd; fp.mom_rho_cap = r->fast_rho_cap; fp.mom_tau_cap = r->fast_tau_cap;
+    fp.mom_partials = r->d_fast_partials.p;
+    fp.mom_unc_mask = r->d_fast_mask.p;
+    if (!r->d_fold_rows) {
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
+      HIPCHK(hipMemset(r->d_fold_rows, 0, kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
+      HIPCHK(hipDeviceSynchronize());
+      r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
+    }
+    r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
+    HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
+    HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
+                                       nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter,
+                                       r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
+  } else {
+    r->last_fast_rows = micp_fast_blocks(nred); r->last_fast_words = (nred + 63u) / 64u;
+    HIPCHK(launch_find(fp, r->kind, fv, r->stream));
+    HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
+                            nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
+                            r->h_done_dev, r->stream, &cl));
+  }
+  if (!fs_ready) {
+    // sum of the tag: the status block, plus the state block when the loop ran to its end (code 0)
+    DoneCheck chk; chk.base = r->h_fast_status; chk.base_bytes = sizeof(MicpFastStatus); chk.code = &r->h_fast_status->code;
+    chk.extra[0] = r->h_state; chk.extra_bytes[0] = sizeof(MicpState);
+    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
+    fs = *r->h_fast_status;
+  } else {
+    ++r->fast_info.host_loops;
+  }
+  r->last_fast = fs;
+  micp_record_attempt(r, fs.code, fs.n_uncertain, fs.max_rho, fs.max_tau);
+  r->fast_info.last_setup_clocks = fs.code == 0u ? fs.pad[0] : 0u;
+  r->fast_info.last_loop_clocks = fs.code == 0u ? fs.pad[1] : 0u;
+  if (fs.code > 2u) return fail(RMCLHIP_ERR_HIP, "correct_once: the moment-form loop did not report a status");
+  if (fs.code == 0u) r->fast_overflows = 0;
+  *out = fs;
+  return RMCLHIP_OK;
+}
+
+// the per-iteration chain on the handle's stream: the call block (H2D), the find, then ONE launch per iteration (k_micp_iter solves
+// the previous iteration in its prologue) + one closing solve -- n_iter + 1 launches instead of 2 * n_iter.  k_micp_close writes the
+// result straight into host-mapped memory (no copy node).  Without iterations: k_micp_init + a copy of that state.
+static rmclhip_status enqueue_micp_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
+  HIPCHK(hipMemcpyAsync(r->d_call, r->h_call, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream));
+  FindParams p;
+  fill_find_params(r, p, 1);
+  p.Tsm_arr = &r->d_call->Tsm;
+  p.Tms_arr = &r->d_call->Tms;
+  HIPCHK(launch_find(p, r->kind, find_variant(r, p.nposes), r->stream));
+  if (n_iter == 0) {
+    HIPCHK(launch_micp_init(r->d_state, r->stream));
+    HIPCHK(hipMemcpyAsync(r->h_state, r->d_state, sizeof(MicpState), hipMemcpyDeviceToHost, r->stream));
+    return RMCLHIP_OK;
+  }
+  const uint8_t* dmask = r->ds_has_mask ? r->ds_msk : nullptr;
+  const uint32_t nb = reduce_num_blocks(nred, 1);
+  double* part[2] = {r->d_partials.p, r->d_partials.p + static_cast<size_t>(nb) * 16};
+  for (uint32_t i = 0; i < n_iter; ++i)
+    HIPCHK(launch_micp_iter(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_call,
+                            part[(i + 1u) & 1u], part[i & 1u], r->d_state + (i & 1u), r->d_state + ((i + 1u) & 1u),
+                            i == 0, r->stream));
+  HIPCHK(launch_micp_close(part[(n_iter - 1u) & 1u], nb, r->d_call, r->d_state + (n_iter & 1u), r->h_state_dev,
+                           r->h_done_dev, r->stream));
+  return RMCLHIP_OK;
+}
+
+// The per-iteration form, captured ONCE into a hipGraph (the kernels read the per-call pose / frames / max_dist from d_call,
+// refreshed by the graph's first node), so that a correction costs one graph launch instead of 2 + n_iter host launches (~5 us each,
+// which left the GPU idle between these tiny kernels); set_variant bit 9 enqueues it directly.  Leaves the result in r->h_state.
+static rmclhip_status micp_per_iteration_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
+  // k_micp_close publishes a completion tag the host polls (a fresh sequence number: a moment-form attempt may have published one
+  // for this call already)
+  r->h_call->seq = next_seq(r);
+  if (r->use_graph) {
+    rmclhip_rcc::MicpKey key;
+    std::memset(&key, 0, sizeof(key));
+    key.n_iter = n_iter; key.W = r->W; key.H = r->H; key.n_dataset = r->n_dataset;
+    key.kind = static_cast<int>(r->kind); key.variant = r->variant; key.tile = r->tile_override;
+    key.has_mask = r->ds_has_mask ? 1 : 0;
+    key.ptrs[0] = r->d_points.p; key.ptrs[1] = r->ds_pts; key.ptrs[2] = r->d_partials.p;
+    key.ptrs[3] = r->d_model_tab.p; key.ptrs[4] = r->ds_msk; key.ptrs[5] = r->d_hits.p;
+    if (!r->micp_exec || r->graph_dirty || !(key == r->micp_key)) {
+      // the previous call returned on its completion tag, which precedes the stream's own completion: let the last node
+      // retire before its executable graph is destroyed
+      HIPCHK(hipStreamSynchronize(r->stream));
+      if (r->micp_exec) { (void)hipGraphExecDestroy(r->micp_exec); r->micp_exec = nullptr; }
+      if (r->micp_graph) { (void)hipGraphDestroy(r->micp_graph); r->micp_graph = nullptr; }
+      HIPCHK(hipStreamBeginCapture(r->stream, hipStreamCaptureModeThreadLocal));
+      r->capturing = true;
+      const rmclhip_status cst = enqueue_micp_chain(r, n_iter, nred);
+      r->capturing = false;
+      hipGraph_t g = nullptr;
+      const hipError_t ce = hipStreamEndCapture(r->stream, &g);
+      if (cst != RMCLHIP_OK) { if (g) (void)hipGraphDestroy(g); return cst; }
+      if (ce != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+      r->micp_graph = g;
+      HIPCHK(hipGraphInstantiate(&r->micp_exec, g, nullptr, nullptr, 0));
+      r->micp_key = key;
+      r->graph_dirty = false;
+    }
+    HIPCHK(hipGraphLaunch(r->micp_exec, r->stream));
+  } else if (rmclhip_status st = enqueue_micp_chain(r, n_iter, nred)) {
+    return st;
+  }
+  if (n_iter == 0) {
+    HIPCHK(hipStreamSynchronize(r->stream));
+  } else {
+    DoneCheck chk; chk.base = r->h_state; chk.base_bytes = sizeof(MicpState);
+    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
+  }
   return RMCLHIP_OK;
 }
 
@@ -1204,11 +1395,8 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
   const xform Tom = to_x(Tom_), Tbo = to_x(Tbo_);
   const float maxd = adaptive_max_dist(r, convergence_progress);
   if (!refind_each_iteration) {
-    // schedule (R), micp_localization.cpp:900-964: 1 find, n_iter x (reduce + solve); nothing returns
-    // to the host until the end: the pre-transform of iteration i+1 is produced on the device.
-    // The launch chain is captured ONCE into a hipGraph (the kernels read the per-call pose / frames /
-    // max_dist from d_call, refreshed by the graph's first node), so a correction costs one graph launch
-    // instead of 2 + 2*n_iter host launches (~5 us each, which left the GPU idle between these tiny kernels).
+    // schedule (R): nothing returns to the host until the end -- the pre-transform of iteration i+1 is produced on the device
+    // (or, in the moment form of mode 1, on the host from the moments the find published)
     const size_t n = static_cast<size_t>(r->W) * r->H;
     r->n_model = static_cast<uint32_t>(n);
     r->nposes_last = 1;
@@ -1216,19 +1404,6 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
     const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
     if (nred == 0) return fail(RMCLHIP_ERR_INVALID, "correct_once: empty dataset");
     HIPCHK(r->d_partials.reserve(std::max<size_t>(static_cast<size_t>(reduce_num_blocks(nred, 1)) * 32, 2u * 256u * 16u)));
-    if (!r->d_loop_barrier) {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_loop_barrier), sizeof(uint32_t)));
-      HIPCHK(hipMemset(r->d_loop_barrier, 0, sizeof(uint32_t)));
-    }
-    {
-      ReduceTail none;  // allocates the ticket buffer outside the capture
-      (void)none;
-      if (r->tickets_cap < 1) {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_tickets), sizeof(uint32_t)));
-        HIPCHK(hipMemset(r->d_tickets, 0, sizeof(uint32_t)));
-        r->tickets_cap = 1;
-      }
-    }
     r->h_call->Tsm = xmul(xmul(Tom, Tbo), r->Tsb);
     r->h_call->Tms = xinv(r->h_call->Tsm);
     r->h_call->Tsb = r->Tsb;
@@ -1238,278 +1413,28 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
     r->h_call->rho_cap = r->fast_rho_cap;
     r->h_call->tau_cap = r->fast_tau_cap;
     r->h_call->seq = next_seq(r);
-    // ---- moment form first (kernels.hip "gate-stable moment form"); any outcome other than "done" falls through to the
-    // per-iteration form below, which recomputes the correction from scratch
-    // (the device loops need >= 2 iterations to pay for their moment pass; the host form -- two launches, no reduction launch at all -- serves 1 as well)
-    const bool fast_eligible = r->fast_mode != 0 && r->loop_blocks == 0 && !r->fused_tail && n_iter >= ((r->fast_mode == 1) ? 1u : 2u);
+    // moment form first; any outcome other than "done" falls through to the per-iteration form (the device loops need >= 2
+    // iterations to pay for their moment pass; the host form -- two launches, no reduction launch at all -- serves 1 as well)
+    const bool fast_eligible = r->fast_mode != 0 && n_iter >= ((r->fast_mode == 1) ? 1u : 2u);
     bool fast_tried = false;
     if (fast_eligible && r->fast_holdoff > 0u) --r->fast_holdoff;
     else if (fast_eligible) {
       fast_tried = true;
-      HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
-      HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
-      rmclhip_rcc::MicpKey key;
-      std::memset(&key, 0, sizeof(key));
-      key.n_iter = n_iter; key.W = r->W; key.H = r->H; key.n_dataset = r->n_dataset;
-      key.kind = static_cast<int>(r->kind); key.variant = r->variant; key.tile = r->tile_override;
-      key.fused = 0; key.has_mask = r->ds_has_mask ? 1 : 0;
-      key.ptrs[0] = r->d_points.p; key.ptrs[1] = r->ds_pts; key.ptrs[2] = r->d_fast_partials.p;
-      key.ptrs[3] = r->d_model_tab.p; key.ptrs[4] = r->ds_msk; key.ptrs[5] = r->d_fast_mask.p;
-      MicpFastStatus fs{};
-      bool fs_ready = false;     // the host ran the iterations: `fs` (and r->h_state) are final, nothing to wait for
-      if (!r->use_graph || r->fast_mode != 2) {
-        // direct launches (fast_mode 2 replays find + moment pass + device loop from a hipGraph, A/B) with their per-call data BY VALUE --
-        // no H2D copy node, no graph launch (a graph replay costs the host 10-16 us whatever it holds)
-        FindParams fp;
-        fill_find_params(r, fp, 1);
-        fp.Tsm = r->h_call->Tsm;
-        fp.Tms = r->h_call->Tms;
-        MicpCallLite cl;
-        cl.Tsb = r->Tsb; cl.Tbo = Tbo; cl.max_dist = maxd; cl.rho_cap = r->fast_rho_cap; cl.tau_cap = r->fast_tau_cap;
-        cl.gate_lo = maxd; cl.gate_hi = maxd;
-        cl.seq = r->h_call->seq;
-        const int fv = find_variant(r, 1);
-        const bool tiled = r->fast_mode != 3 && (fv == 23 || fv == 32 || fv == 2);   // the find forms the moments in its epilogue
-        const uint32_t nb = tiled ? find_moments_blocks(fp, fv) : micp_fast_blocks(nred), wpb = (fv == 2) ? 1u : 4u;
-        bool device_loop = r->fast_mode != 1;
-        if (r->fast_mode == 1) {
-          // ---- round 4 default: TWO launches (find with the moment epilogue; fold + publish), the iterations on the HOST from the 82
-          // moments + the undecided correspondences (micp_host.h): ~0.5 us per iteration instead of ~2.7 us of one lane's f64 chain
-          if (rmclhip_status st = enqueue_find_with_moments(r, r->h_call->Tsm, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, cl.seq, true)) return st;
-          HIPCHK(wait_moments(r, cl.seq, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap));
-          if (r->mset.valid) {
-            xform T_s = xidentity();
-            cstats last = cs_identity();
-            fs.code = 0u; fs.n_uncertain = r->mset.n_unc;
-            for (uint32_t it = 0; it < n_iter; ++it) {
-              const float rho = micp_rho(T_s), tau = micp_tau(T_s);
-              fs.max_rho = std::max(fs.max_rho, rho);
-              fs.max_tau = std::max(fs.max_tau, tau);
-              if (!(rho <= r->mset.rho_cap) || !(tau <= r->mset.tau_cap)) { fs.code = 1u; fs.iter = it; break; }
-              last = micp_statistics_from_set(r->mset, T_s, maxd);
-              T_s = xmul(T_s, umeyama(last));   // kernels.hip micp_advance_sensor
-            }
-            if (fs.code == 0u) {
-              // kernels.hip micp_close_sensor
-              fs.iter = n_iter;
-              const xform Tso = xmul(Tbo, r->Tsb);
-              r->h_state->T_snew_sold = T_s;
-              r->h_state->T_onew_oold = xmul(xmul(Tso, T_s), xinv(Tso));
-              r->h_state->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(r->Tsb, last)));
-            }
-            fs_ready = true;
-          } else {
-            // more undecided correspondences than the host takes: the device loop on the rows the find left (a sequence number of its own:
-            // the publish launch used this one for its hand-over flags and its tag)
-            device_loop = true;
-            cl.seq = r->h_call->seq = next_seq(r);
-            // kind and row layout are the ones enqueue_find_with_moments actually ran (it replaces kind 24 by 23 to get the epilogue):
-            // the loop folds THOSE rows instead of paying a moment pass of its own
-            const int ufv = r->last_moment_find_kind;
-            FindParams ufp;
-            fill_find_params(r, ufp, 1, ufv);
-            const uint32_t unb = find_moments_blocks(ufp, ufv), uwpb = (ufv == 2) ? 1u : 4u;
-            if (r->last_moment_find_tiled)
-              HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
-                                                 nred, unb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, ufp.tiles_x, ufp.tile_w_log2, uwpb, n_iter,
-                                                 r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
-            else
-              HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                      nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
-                                      r->h_done_dev, r->stream, &cl));
-          }
-        } else if (tiled) {
-          // (fast_mode 4, round 3's default) TWO kernels: the find forms the moments in its epilogue (find_kernel.hip.h: the 10 x 10 factor
-          // products of its 64 correspondences per wave through f64 MFMA), one partial row per workgroup; the loop launch folds them and runs
-          // every iteration on the device
-          HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
-          HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
-          fp.mom_dataset_points = r->ds_pts;
-          fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-          fp.mom_n = nred;
-          fp.mom_gate_lo = maxd; fp.mom_gate_hi = maxd; fp.mom_rho_cap = r->fast_rho_cap; fp.mom_tau_cap = r->fast_tau_cap;
-          fp.mom_partials = r->d_fast_partials.p;
-          fp.mom_unc_mask = r->d_fast_mask.p;
-          if (!r->d_fold_rows) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-            HIPCHK(hipMemset(r->d_fold_rows, 0, kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-            HIPCHK(hipDeviceSynchronize());
-            r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
-          }
-          r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
-          HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
-          HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
-                                             nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter,
-                                             r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
-        } else {
-          r->last_fast_rows = micp_fast_blocks(nred); r->last_fast_words = (nred + 63u) / 64u;
-          HIPCHK(launch_find(fp, r->kind, fv, r->stream));
-          HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                  nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
-                                  r->h_done_dev, r->stream, &cl));
-        }
-        (void)device_loop;
-      } else if (!r->micp_fast_exec || r->fast_graph_dirty || !(key == r->micp_fast_key)) {
-        // the previous call returned on its completion tag, which precedes the stream's own completion: let the last node
-        // retire before its executable graph is destroyed
-        HIPCHK(hipStreamSynchronize(r->stream));
-        if (r->micp_fast_exec) { (void)hipGraphExecDestroy(r->micp_fast_exec); r->micp_fast_exec = nullptr; }
-        if (r->micp_fast_graph) { (void)hipGraphDestroy(r->micp_fast_graph); r->micp_fast_graph = nullptr; }
-        HIPCHK(hipStreamBeginCapture(r->stream, hipStreamCaptureModeThreadLocal));
-        r->capturing = true;
-        hipError_t le = hipMemcpyAsync(r->d_call, r->h_call, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream);
-        if (le == hipSuccess) {
-          FindParams fp;
-          fill_find_params(r, fp, 1);
-          fp.Tsm_arr = &r->d_call->Tsm;
-          fp.Tms_arr = &r->d_call->Tms;
-          le = launch_find(fp, r->kind, find_variant(r, 1), r->stream);
-        }
-        if (le == hipSuccess)
-          le = launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                r->d_call, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
-                                r->h_done_dev, r->stream);
-        r->capturing = false;
-        hipGraph_t g = nullptr;
-        const hipError_t ce = hipStreamEndCapture(r->stream, &g);
-        if (le != hipSuccess) { if (g) (void)hipGraphDestroy(g); return fail(RMCLHIP_ERR_HIP, std::string("micp fast capture: ") + hipGetErrorString(le)); }
-        if (ce != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        r->micp_fast_graph = g;
-        HIPCHK(hipGraphInstantiate(&r->micp_fast_exec, g, nullptr, nullptr, 0));
-        r->micp_fast_key = key;
-        r->fast_graph_dirty = false;
-      }
-      if (r->use_graph && r->fast_mode == 2) HIPCHK(hipGraphLaunch(r->micp_fast_exec, r->stream));
-      if (!fs_ready) {
-        // sum of the tag: the status block, plus the state block when the loop ran to its end (code 0)
-        DoneCheck chk; chk.base = r->h_fast_status; chk.base_bytes = sizeof(MicpFastStatus); chk.code = &r->h_fast_status->code;
-        chk.extra[0] = r->h_state; chk.extra_bytes[0] = sizeof(MicpState);
-        HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
-        fs = *r->h_fast_status;
-      } else {
-        ++r->fast_info.host_loops;
-      }
-      r->last_fast = fs;
-      r->fast_info.attempts++;
-      r->fast_info.last_code = fs.code;
-      r->fast_info.last_uncertain = fs.n_uncertain;
-      r->fast_info.last_rho = fs.max_rho;
-      r->fast_info.last_tau = fs.max_tau;
-      r->fast_info.last_setup_clocks = fs.code == 0u ? fs.pad[0] : 0u;
-      r->fast_info.last_loop_clocks = fs.code == 0u ? fs.pad[1] : 0u;
+      MicpFastStatus fs;
+      if (rmclhip_status st = micp_try_moment_form(r, Tbo, n_iter, maxd, nred, &fs)) return st;
       if (fs.code == 0u) {
-        r->fast_info.done++;
-        r->fast_overflows = 0;
-        r->fast_rho_cap = std::max(0.002f, std::max(2.0f * fs.max_rho, 0.9f * r->fast_rho_cap));
-        r->fast_tau_cap = std::max(0.005f, std::max(2.0f * fs.max_tau, 0.9f * r->fast_tau_cap));
-        r->fast_info.rho_cap = r->fast_rho_cap;
-        r->fast_info.tau_cap = r->fast_tau_cap;
         from_x(r->h_state->T_onew_oold, T_out);
         if (stats_out) from_cs(r->h_state->stats_o, stats_out);
         return RMCLHIP_OK;
       }
-      if (fs.code != 1u && fs.code != 2u) return fail(RMCLHIP_ERR_HIP, "correct_once: the moment-form loop did not report a status");
-      if (fs.code == 2u) r->fast_info.overflows++; else r->fast_info.cap_exits++;
     }
-    // the one-launch-per-iteration chain ends with k_micp_close, which publishes a completion tag the host polls (a fresh
-    // sequence number: the moment-form attempt above may have published one for this call already)
-    const bool polled = r->loop_blocks == 0 && !r->fused_tail && n_iter > 0;
-    r->h_call->seq = next_seq(r);
-    auto enqueue_chain = [&]() -> rmclhip_status {
-      HIPCHK(hipMemcpyAsync(r->d_call, r->h_call, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream));
-      FindParams p;
-      fill_find_params(r, p, 1);
-      p.Tsm_arr = &r->d_call->Tsm;
-      p.Tms_arr = &r->d_call->Tms;
-      const int fvariant = find_variant(r, p.nposes);
-      HIPCHK(launch_find(p, r->kind, fvariant, r->stream));
-      const bool iter_form = r->loop_blocks == 0 && !r->fused_tail && n_iter > 0;
-      if (!iter_form) HIPCHK(launch_micp_init(r->d_state, r->d_loop_barrier, r->stream));  // k_micp_iter initialises itself
-      MicpState* final_state = r->d_state;
-      const uint8_t* dmask = r->ds_has_mask ? r->ds_msk : nullptr;
-      if (r->loop_blocks > 0) {
-        // persistent loop: every iteration inside ONE launch (k_micp_loop); A/B only -- a device-wide barrier
-        // across the 8 XCDs costs more than the launch boundaries it replaces
-        HIPCHK(launch_micp_loop(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, n_iter,
-                                r->d_call, r->d_partials.p, r->d_loop_barrier, r->d_state,
-                                static_cast<uint32_t>(r->loop_blocks & 0xFFFF), (r->loop_blocks >> 16) != 0, r->stream));
-      } else if (iter_form) {
-        // default: ONE launch per iteration (k_micp_iter solves the previous iteration in its prologue) + one
-        // closing solve: n_iter + 1 launches instead of 2 * n_iter
-        const uint32_t nb = reduce_num_blocks(nred, 1);
-        double* part[2] = {r->d_partials.p, r->d_partials.p + static_cast<size_t>(nb) * 16};
-        for (uint32_t i = 0; i < n_iter; ++i)
-          HIPCHK(launch_micp_iter(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_call,
-                                  part[(i + 1u) & 1u], part[i & 1u], r->d_state + (i & 1u), r->d_state + ((i + 1u) & 1u),
-                                  i == 0, r->stream));
-        // the closing step writes the result straight into host-mapped memory (no copy node)
-        HIPCHK(launch_micp_close(part[(n_iter - 1u) & 1u], nb, r->d_call, r->d_state + (n_iter & 1u), r->h_state_dev,
-                                 r->h_done_dev, r->stream));
-        final_state = nullptr;
-      } else
-      for (uint32_t i = 0; i < n_iter; ++i) {
-        ReduceTail tail;
-        tail.mode = kTailMicp;
-        tail.Tbo = Tbo;
-        tail.state = r->d_state;
-        tail.call = r->d_call;
-        if (rmclhip_status st = reduce_enqueue(r, xidentity(), &r->d_state->T_snew_sold, maxd, 1, tail)) return st;
-      }
-      if (final_state) HIPCHK(hipMemcpyAsync(r->h_state, final_state, sizeof(MicpState), hipMemcpyDeviceToHost, r->stream));
-      return RMCLHIP_OK;
-    };
-    if (r->use_graph) {
-      rmclhip_rcc::MicpKey key;
-      std::memset(&key, 0, sizeof(key));
-      key.n_iter = n_iter; key.W = r->W; key.H = r->H; key.n_dataset = r->n_dataset;
-      key.kind = static_cast<int>(r->kind); key.variant = r->variant; key.tile = r->tile_override;
-      key.fused = (r->fused_tail ? 1 : 0) | (r->loop_blocks << 1); key.has_mask = r->ds_has_mask ? 1 : 0;
-      key.ptrs[0] = r->d_points.p; key.ptrs[1] = r->ds_pts; key.ptrs[2] = r->d_partials.p;
-      key.ptrs[3] = r->d_model_tab.p; key.ptrs[4] = r->ds_msk; key.ptrs[5] = r->d_hits.p;
-      if (!r->micp_exec || r->graph_dirty || !(key == r->micp_key)) {
-        HIPCHK(hipStreamSynchronize(r->stream));   // see the moment-form graph above
-        if (r->micp_exec) { (void)hipGraphExecDestroy(r->micp_exec); r->micp_exec = nullptr; }
-        if (r->micp_graph) { (void)hipGraphDestroy(r->micp_graph); r->micp_graph = nullptr; }
-        HIPCHK(hipStreamBeginCapture(r->stream, hipStreamCaptureModeThreadLocal));
-        r->capturing = true;
-        const rmclhip_status cst = enqueue_chain();
-        r->capturing = false;
-        hipGraph_t g = nullptr;
-        const hipError_t ce = hipStreamEndCapture(r->stream, &g);
-        if (cst != RMCLHIP_OK) { if (g) (void)hipGraphDestroy(g); return cst; }
-        if (ce != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        r->micp_graph = g;
-        HIPCHK(hipGraphInstantiate(&r->micp_exec, g, nullptr, nullptr, 0));
-        r->micp_key = key;
-        r->graph_dirty = false;
-      }
-      HIPCHK(hipGraphLaunch(r->micp_exec, r->stream));
-    } else {
-      if (rmclhip_status st = enqueue_chain()) return st;
-    }
-    if (polled) {
-      DoneCheck chk; chk.base = r->h_state; chk.base_bytes = sizeof(MicpState);
-      HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
-    }
-    else HIPCHK(hipStreamSynchronize(r->stream));
+    if (rmclhip_status st = micp_per_iteration_chain(r, n_iter, nred)) return st;
     if (fast_tried) {
-      // the pre-transform this correction ended with bounds the next attempt (iterates approach it monotonically in the
-      // usual case; an attempt that still leaves the caps costs one more fallback and doubles them)
       const xform Tb = xmul(xmul(xinv(Tbo), r->h_state->T_onew_oold), Tbo);
-      const xform Ts = xmul(xmul(xinv(r->Tsb), Tb), r->Tsb);
-      const float rho = 2.0f * std::sqrt(Ts.R.x * Ts.R.x + Ts.R.y * Ts.R.y + Ts.R.z * Ts.R.z);
-      const float tau = std::sqrt(Ts.t.x * Ts.t.x + Ts.t.y * Ts.t.y + Ts.t.z * Ts.t.z);
-      if (r->last_fast.code == 2u) {
-        // too many uncertain correspondences: tighter caps, and stop trying when that does not help either
-        r->fast_rho_cap = std::max(0.002f, 1.25f * rho);
-        r->fast_tau_cap = std::max(0.005f, 1.25f * tau);
-        if (++r->fast_overflows >= 2u) { r->fast_holdoff = 32u; r->fast_overflows = 0; }
-      } else {
-        r->fast_rho_cap = std::max(0.002f, std::max(2.0f * rho, 2.0f * r->last_fast.max_rho));
-        r->fast_tau_cap = std::max(0.005f, std::max(2.0f * tau, 2.0f * r->last_fast.max_tau));
-      }
-      r->fast_info.rho_cap = r->fast_rho_cap;
-      r->fast_info.tau_cap = r->fast_tau_cap;
+      const bool overflow = r->last_fast.code == 2u;
+      micp_caps_after_fallback(r, xmul(xmul(xinv(r->Tsb), Tb), r->Tsb), overflow, r->last_fast.max_rho, r->last_fast.max_tau);
+      // too many uncertain correspondences twice in a row: stop trying for a while
+      if (overflow && ++r->fast_overflows >= 2u) { r->fast_holdoff = 32u; r->fast_overflows = 0; }
     }
     from_x(r->h_state->T_onew_oold, T_out);
     if (stats_out) from_cs(r->h_state->stats_o, stats_out);
@@ -1524,14 +1449,11 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
     ReduceTail tail;
     tail.mode = kTailStats;
     tail.stats_out = r->h_stats_dev;
-    const bool polled = !r->fused_tail;
-    if (polled) { tail.done = r->h_done_dev; tail.seq = next_seq(r); }
+    tail.done = r->h_done_dev;
+    tail.seq = next_seq(r);
     if (rmclhip_status st = reduce_enqueue(r, xidentity(), nullptr, maxd, 1, tail)) return st;
-    if (polled) {
-      DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
-      HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
-    }
-    else HIPCHK(hipStreamSynchronize(r->stream));
+    DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
+    HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
     const cstats Cs_o = cs_transform(Tbo, cs_transform(r->Tsb, r->h_stats[0]));
     last = cs_merge(cs_identity(), Cs_o);
     T_onew_oold = xmul(T_onew_oold, umeyama(last));
@@ -1608,7 +1530,7 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
   // correspondences or a pre-transform outside its caps: the device forms below, from scratch.
   bool device_fast = fast_tried;   // the device's moment loop is tried (after the host form, when that is on and did not finish)
   bool host_form = fast_tried;
-  for (uint32_t s = 0; s < n_sensors; ++s) host_form = host_form && sensors[s]->fast_mode == 1 && !sensors[s]->fused_tail;
+  for (uint32_t s = 0; s < n_sensors; ++s) host_form = host_form && sensors[s]->fast_mode == 1;
   if (host_form) {
     float maxd[kMaxMicpSensors];
     uint32_t seqs[kMaxMicpSensors];
@@ -1657,21 +1579,12 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
     }
     for (uint32_t s = 0; s < n_sensors && hs.code != 2u; ++s) {   // (code 2: the device loop below is this call's attempt)
       rmclhip_rcc* r = sensors[s];
-      r->fast_info.attempts++;
-      r->fast_info.last_code = hs.code;
-      r->fast_info.last_uncertain = hs.n_uncertain;
-      r->fast_info.last_rho = hs.max_rho[s];
-      r->fast_info.last_tau = hs.max_tau[s];
+      micp_record_attempt(r, hs.code, hs.n_uncertain, hs.max_rho[s], hs.max_tau[s]);
       r->fast_info.last_setup_clocks = r->fast_info.last_loop_clocks = 0u;
+      if (hs.code == 0u) r->fast_info.host_loops++;
     }
     if (hs.code == 0u) {
       r0->multi_overflows = 0;
-      for (uint32_t s = 0; s < n_sensors; ++s) {
-        rmclhip_rcc* r = sensors[s];
-        r->fast_info.done++;
-        r->fast_info.host_loops++;
-        learn_caps(r, hs.max_rho[s], hs.max_tau[s]);
-      }
       from_x(T_onew_oold, T_out);
       if (merged_out) from_cs(merged, merged_out);
       return RMCLHIP_OK;
@@ -1683,7 +1596,6 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
     if (hs.code == 1u) {
       device_fast = false;
       *r0->h_multi_status = hs;
-      for (uint32_t s = 0; s < n_sensors; ++s) sensors[s]->fast_info.cap_exits++;
     }
     for (uint32_t s = 0; s < n_sensors; ++s) drop_moment_set(sensors[s]);
     h_call.seq = next_seq(r0);
@@ -1754,30 +1666,14 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
       HIPCHK(wait_done(r0->ctx, r0->h_done + 1, h_call.seq, chk, st));
     }
     const MicpMultiFastStatus fs = *r0->h_multi_status;
-    for (uint32_t s = 0; s < n_sensors; ++s) {
-      rmclhip_rcc* r = sensors[s];
-      r->fast_info.attempts++;
-      r->fast_info.last_code = fs.code;
-      r->fast_info.last_uncertain = fs.n_uncertain;
-      r->fast_info.last_rho = fs.max_rho[s];
-      r->fast_info.last_tau = fs.max_tau[s];
-    }
+    for (uint32_t s = 0; s < n_sensors; ++s) micp_record_attempt(sensors[s], fs.code, fs.n_uncertain, fs.max_rho[s], fs.max_tau[s]);
     if (fs.code == 0u) {
       r0->multi_overflows = 0;
-      for (uint32_t s = 0; s < n_sensors; ++s) {
-        rmclhip_rcc* r = sensors[s];
-        r->fast_info.done++;
-        r->fast_rho_cap = std::max(0.002f, std::max(2.0f * fs.max_rho[s], 0.9f * r->fast_rho_cap));
-        r->fast_tau_cap = std::max(0.005f, std::max(2.0f * fs.max_tau[s], 0.9f * r->fast_tau_cap));
-      }
       from_x(r0->h_multi_state->T_onew_oold, T_out);
       if (merged_out) from_cs(r0->h_multi_state->merged_o, merged_out);
       return RMCLHIP_OK;
     }
     if (fs.code != 1u && fs.code != 2u) return fail(RMCLHIP_ERR_HIP, "micp_correct_once: the moment-form loop did not report a status");
-    for (uint32_t s = 0; s < n_sensors; ++s) {
-      if (fs.code == 2u) sensors[s]->fast_info.overflows++; else sensors[s]->fast_info.cap_exits++;
-    }
   }
   // per-iteration form (fallback, or the moment form is off): the call block goes to the device.  The other sensors' finds ran on
   // their own streams: this stream waits for their events first.
@@ -1804,7 +1700,6 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
       rp.Tpre_dev = &d_state->T_snew_sold[s];
       rp.partials = r->d_partials.p;
       rp.nblocks = h_call.nblocks[s];
-      rp.tail_mode = kTailNone;
       e = launch_reduce_partials(rp, st);
     }
     if (e == hipSuccess) e = launch_micp_multi_step(d_call, d_state, st);
@@ -1816,19 +1711,8 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
   if (fast_tried) {
     // caps for the next attempt from the pre-transforms this correction ended with (see rmclhip_rcc_correct_once)
     const bool overflow = r0->h_multi_status->code == 2u;
-    for (uint32_t s = 0; s < n_sensors; ++s) {
-      rmclhip_rcc* r = sensors[s];
-      const xform Ts = h_state.T_snew_sold[s];
-      const float rho = 2.0f * std::sqrt(Ts.R.x * Ts.R.x + Ts.R.y * Ts.R.y + Ts.R.z * Ts.R.z);
-      const float tau = std::sqrt(Ts.t.x * Ts.t.x + Ts.t.y * Ts.t.y + Ts.t.z * Ts.t.z);
-      if (overflow) {
-        r->fast_rho_cap = std::max(0.002f, 1.25f * rho);
-        r->fast_tau_cap = std::max(0.005f, 1.25f * tau);
-      } else {
-        r->fast_rho_cap = std::max(0.002f, std::max(2.0f * rho, 2.0f * r0->h_multi_status->max_rho[s]));
-        r->fast_tau_cap = std::max(0.005f, std::max(2.0f * tau, 2.0f * r0->h_multi_status->max_tau[s]));
-      }
-    }
+    for (uint32_t s = 0; s < n_sensors; ++s)
+      micp_caps_after_fallback(sensors[s], h_state.T_snew_sold[s], overflow, r0->h_multi_status->max_rho[s], r0->h_multi_status->max_tau[s]);
     if (overflow && ++r0->multi_overflows >= 2u) { r0->multi_holdoff = 32u; r0->multi_overflows = 0; }
   }
   from_x(h_state.T_onew_oold, T_out);

@@ -133,7 +133,7 @@ rmclhip_status rmclhip_rcc_autotune(rmclhip_rcc* r, const rmclhip_transform* Tbm
     }
     r->tuned_xcd_mapping = best_map;
   }
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   if (chosen_kind) *chosen_kind = best->reported;
   if (kernel_ms) *kernel_ms = best_ms;
   return RMCLHIP_OK;
@@ -159,7 +159,7 @@ rmclhip_status rmclhip_rcc_autotune_batch(rmclhip_rcc* r, const rmclhip_transfor
     if (!best || t[1] < best_ms) { best = &c; best_ms = t[1]; }
   }
   r->tuned_batch_kind = best->kind; r->tuned_batch_frontier = best->frontier;
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   if (chosen_kind) *chosen_kind = best->reported;
   if (kernel_ms) *kernel_ms = best_ms;
   return RMCLHIP_OK;
@@ -257,6 +257,10 @@ rmclhip_status rmclhip_rcc_set_variant(rmclhip_rcc* r, int variant) {
   // bit 13 adds 16 to the traversal kind (kinds 16..31), bit 14 adds 32
   const int kind = (variant & 0xF) | (((variant >> 13) & 1) << 4) | (((variant >> 14) & 1) << 5), tile = (variant >> 4) & 0xF;
   if (kind == 3 || kind == 18 || kind > 32 || tile > 7 || (variant >> 15) != 0) return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: unknown variant");
+  // bit 8 (reduction tail fused into the last block) and bits 10..12 (reduce + solve launches, persistent grid-barrier loop): loop
+  // forms measured slower than the default and removed (profiles/r03_micp_loop_forms.txt)
+  if ((variant & ((1 << 8) | (7 << 10))) != 0)
+    return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: bits 8 and 10..12 (MICP loop forms) are retired");
   // (kind 1 also selects the one-lane-per-point form of the closest-point query, which the product owns)
   if (kind != 15 && kind != 1 && !find_kind_in_product(kind) && lab_hooks() == nullptr)
     return fail(RMCLHIP_ERR_UNSUPPORTED, "rcc_set_variant: this traversal kind is an experiment -- it lives in librmclhip_lab.so, "
@@ -264,15 +268,8 @@ rmclhip_status rmclhip_rcc_set_variant(rmclhip_rcc* r, int variant) {
   r->variant = kind;
   const bool tiling_changed = r->tile_override != tile;
   r->tile_override = tile;
-  r->fused_tail = ((variant >> 8) & 1) != 0;
   r->use_graph = ((variant >> 9) & 1) == 0;
-  {  // bits 10..12: MICP loop form -- 0 default (one launch per iteration, solve in the prologue), 1 classic
-     // (reduce + solve launches), 2..6 persistent loop kernel with 16..256 blocks
-    // 7: persistent loop with 32 blocks confined to one XCD (bit 16 of loop_blocks)
-    static const int kLoopBlocks[8] = {0, -1, 16, 32, 64, 128, 256, 32 | (1 << 16)};
-    r->loop_blocks = kLoopBlocks[(variant >> 10) & 7];
-  }
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   // the tile shape depends on the kind (packet: 8x8, per-ray: 16x4) and on the override: the plane table follows
   (void)tiling_changed;
   HIPCHK(hipSetDevice(r->ctx->device));
@@ -288,15 +285,18 @@ rmclhip_status rmclhip_rcc_set_descent(rmclhip_rcc* r, uint32_t final_cap, uint3
   if ((max_levels >> 8) & 0xFFu) r->descent_leaf_cap = (max_levels >> 8) & 0xFFu;   // bits 8..15 (A/B): kind 32's leaves-per-ray bound, 0 = keep
   r->xcd_mapping_override = static_cast<int>((max_levels >> 29) & 3u) - 1;   // bits 29..30 (A/B): 1 + FindParams::xcd_mapping, 0 = the tuned / default one
   r->descent_wide = (max_levels >> 31) == 0u;   // bit 31 (A/B): the four-wide nodes even where the map has the 16-wide twins
-  r->graph_dirty = true; r->fast_graph_dirty = true;
+  r->graph_dirty = true;
   return RMCLHIP_OK;
 }
 
 rmclhip_status rmclhip_rcc_set_micp_fast(rmclhip_rcc* r, int mode) {
   ApiGuard guard_("rmclhip_rcc_set_micp_fast");
   if (!r || mode < 0 || mode > 4)
-    return fail(RMCLHIP_ERR_INVALID, "rcc_set_micp_fast: mode must be 0 (off), 1 (automatic, iterations on the host), 2 (device loop replayed from a "
-                                     "hipGraph), 3 (device loop, moments in a pass of their own) or 4 (device loop, moments in the find's epilogue)");
+    return fail(RMCLHIP_ERR_INVALID, "rcc_set_micp_fast: mode must be 0 (off), 1 (automatic, iterations on the host), 3 (device loop, moments "
+                                     "in a pass of their own) or 4 (device loop, moments in the find's epilogue)");
+  // 2 (find + moment pass + device loop replayed from a hipGraph) measured slower than direct launches and was removed
+  // (profiles/r03_micp_loop_forms.txt)
+  if (mode == 2) return fail(RMCLHIP_ERR_INVALID, "rcc_set_micp_fast: mode 2 (device loop replayed from a hipGraph) is retired");
   drop_moment_set(r);
   r->fast_mode = mode;
   r->fast_holdoff = 0;

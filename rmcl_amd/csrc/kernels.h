@@ -76,9 +76,8 @@ struct FindParams {
   unsigned long long* mom_unc_mask;    // [4 * gridDim.x]: bit l of word t = lane l of (virtual) tile t holds an undecided correspondence
 };
 
-struct MicpState;
-struct MicpCall;
-enum TailMode : uint32_t { kTailNone = 0, kTailStats = 1, kTailMicp = 2, kTailBatchSolve = 3 };
+// what follows the reduction launch (capi_internal.h ReduceTail): nothing, the finalize launch or the batch solve launch
+enum TailMode : uint32_t { kTailNone, kTailStats, kTailBatchSolve };
 
 struct ReduceParams {
   const float* dataset_points;
@@ -89,18 +88,10 @@ struct ReduceParams {
   uint32_t n;                    // elements per pose
   uint32_t nposes;               // model buffers hold nposes*n elements; dataset is shared
   float max_dist;
-  const MicpCall* call;          // nullable: when set, max_dist / Tsb / Tbo are read from it (graph replay)
   xform Tpre;                    // used when Tpre_dev == nullptr
   const xform* Tpre_dev;         // per-pose pre-transform (device), nullable
   double* partials;              // [nposes][nblocks][16]
   uint32_t nblocks;
-  // fused tail executed by the last block of each pose (kTailNone: partials only)
-  uint32_t tail_mode;
-  uint32_t* tickets;             // [nposes], zero before the first launch; re-armed by the kernel
-  cstats* stats_out;             // kTailStats / kTailBatchSolve (nullable there)
-  xform Tsb, Tbo;                // kTailMicp / kTailBatchSolve
-  MicpState* state;              // kTailMicp
-  xform* Tdelta_out;             // kTailBatchSolve
 };
 
 struct PfParams {
@@ -327,28 +318,19 @@ hipError_t launch_reduce_partials(const ReduceParams& p, hipStream_t s);
 // `out` (kernels.hip publish_tag): the host polls the tag and VERIFIES the sum -- a flag alone is not enough, see capi_rcc.cpp wait_done
 hipError_t launch_reduce_finalize(const double* partials, uint32_t nblocks, uint32_t nposes, cstats* out,
                                   unsigned long long* done, uint32_t seq, hipStream_t s);
-// finalize + (Tsb*, Tbo*) + umeyama + compose; advances MicpState on the device
-hipError_t launch_micp_step(const double* partials, uint32_t nblocks, xform Tsb, xform Tbo, const MicpCall* call,
-                            const MicpState* state, MicpState* state_out, hipStream_t s);
 // closing launch of the launch_micp_iter chain: solve of the last iteration + T_onew_oold / stats_o (the chain itself works in
 // the sensor frame, kernels.hip micp_advance_sensor)
 // done (nullable, host-mapped): completion tag {call->seq, xor of the state's words}, stored after the results
 hipError_t launch_micp_close(const double* partials, uint32_t nblocks, const MicpCall* call, const MicpState* state,
                              MicpState* state_out, unsigned long long* done, hipStream_t s);
-// state: TWO MicpState slots (ping-pong of k_micp_iter); both initialised
-hipError_t launch_micp_init(MicpState* state, uint32_t* barrier, hipStream_t s);
+// state: TWO MicpState slots (ping-pong of k_micp_iter); both initialised.  Only a correction without iterations needs it
+hipError_t launch_micp_init(MicpState* state, hipStream_t s);
 // one launch per MICP iteration: finishes the previous iteration (finalize + solve, redundantly in every block)
-// and streams the next reduction; a final launch_micp_step closes the last iteration
+// and streams the next reduction; a final launch_micp_close closes the last iteration
 hipError_t launch_micp_iter(const float* dataset_points, const uint8_t* dataset_mask, const float* model_points,
                             const float* model_normals, const uint8_t* model_mask, uint32_t n, uint32_t nblocks,
                             const MicpCall* call, const double* partials_prev, double* partials_out,
                             const MicpState* state_in, MicpState* state_out, bool first, hipStream_t s);
-// persistent loop: n_iter x (reduce, barrier, finalize + solve) in one launch; nblocks <= number of CUs (the grid
-// must be co-resident); partials: 2 * nblocks * 16 doubles; barrier: one uint32, zeroed by launch_micp_init
-hipError_t launch_micp_loop(const float* dataset_points, const uint8_t* dataset_mask, const float* model_points,
-                            const float* model_normals, const uint8_t* model_mask, uint32_t n, uint32_t n_iter,
-                            const MicpCall* call, double* partials, uint32_t* barrier, MicpState* state,
-                            uint32_t nblocks, bool one_xcd, hipStream_t s);
 // batch: per pose finalize + umeyama -> Tdelta (sensor->base conjugated), stats
 hipError_t launch_batch_solve(const double* partials, uint32_t nblocks, uint32_t nposes, xform Tsb,
                               xform* Tdelta_out, cstats* stats_out, hipStream_t s);

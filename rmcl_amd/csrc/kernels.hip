@@ -4,7 +4,10 @@
 //  k_cpc_find        (traverse.hip.h) closest-point correspondences, CPCEmbree::find
 //  k_reduce_partials rm::statistics_p2l (CorrespondencesCPU.cpp:26-30; gate MICPSensorCPU.cpp:70-84)
 //  k_micp_*          the inner iterations of MICPLocalizationNode::correctOnce
-//                    (rmcl_ros/src/nodes/micp_localization.cpp:915-964) + rm::umeyama_transform
+//                    (rmcl_ros/src/nodes/micp_localization.cpp:915-964) + rm::umeyama_transform, in two forms: the
+//                    gate-stable moment form and one launch per iteration (k_micp_iter + k_micp_close).  The loop forms
+//                    measured slower (a persistent grid-barrier kernel, reduce + solve launches, a reduction tail fused
+//                    into the last block) are gone; profiles/r03_micp_loop_forms.txt holds their measurements
 //  k_pf_update_v3    PCDSensorUpdater{Embree,Optix}::update, all beams fused
 //                    (PCDSensorUpdaterEmbree.cpp:290-342, optix/BeamEvaluateProgram.cu:15-130)
 //  k_pf_motion, k_gladiator_resample, k_likelihood_stats_*, k_pose_moments*: the rest of a filter cycle
@@ -78,12 +81,11 @@ __device__ __forceinline__ double wave_sum16_lds(const double (&v)[16], double* 
 
 
 // sum the per-block partials of one pose (one wave) and turn the raw moments into CrossStatistics
-template <bool kAgentLoads = false>
 __device__ __forceinline__ cstats finalize_pose(const double* partials, uint32_t nblocks) {
   // transposed reduction: lane = 16*g + k sums moment k over the blocks b = g, g+4, ... (16 lanes read one
   // 128-B partial: coalesced), then only TWO cross-lane steps (xor 16, 32) for one double per lane and 16
   // v_readlane broadcasts -- instead of 16 moments x 6 butterfly steps = 192 dependent ds_bpermute (measured
-  // ~4.5 us of the 14 us k_micp_step)
+  // ~4.5 us of a 14 us solve step)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t k0 = lane & 15u, g = lane >> 4;
   // 32 loads in flight per lane: every batch is one L2 round trip (~0.8 us) for this lone wave, so 256 partials
@@ -94,26 +96,17 @@ __device__ __forceinline__ cstats finalize_pose(const double* partials, uint32_t
   for (; b + 124u < nblocks; b += 128u) {
     double v[32];
 #pragma unroll
-    for (int u = 0; u < 32; ++u) {
-      const double* q = partials + static_cast<size_t>(b + 4u * u) * kAcc + k0;
-      v[u] = kAgentLoads ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *q;
-    }
+    for (int u = 0; u < 32; ++u) v[u] = partials[static_cast<size_t>(b + 4u * u) * kAcc + k0];
 #pragma unroll
     for (int u = 0; u < 32; u += 8) a += ((v[u] + v[u + 1]) + (v[u + 2] + v[u + 3])) + ((v[u + 4] + v[u + 5]) + (v[u + 6] + v[u + 7]));
   }
   for (; b + 28u < nblocks; b += 32u) {
     double v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const double* q = partials + static_cast<size_t>(b + 4u * u) * kAcc + k0;
-      v[u] = kAgentLoads ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *q;
-    }
+    for (int u = 0; u < 8; ++u) v[u] = partials[static_cast<size_t>(b + 4u * u) * kAcc + k0];
     a += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
   }
-  for (; b < nblocks; b += 4u) {
-    const double* q = partials + static_cast<size_t>(b) * kAcc + k0;
-    a += kAgentLoads ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *q;
-  }
+  for (; b < nblocks; b += 4u) a += partials[static_cast<size_t>(b) * kAcc + k0];
   a += __shfl_xor(a, 16, 64);
   a += __shfl_xor(a, 32, 64);
   double acc[kAcc];
@@ -134,30 +127,16 @@ __device__ __forceinline__ cstats finalize_pose(const double* partials, uint32_t
 }
 
 
-// one MICP inner iteration from the reduced statistics, executed by ONE lane
-// micp_localization.cpp:915-964 for one sensor (merge_weight_multiplier == 1):
-//   Cs_b = Tsb * stats_s (MICPSensor.hpp:182); Cs_o = Tbo * Cs_b (:931); Cmerged = Identity += Cs_o (:936)
-//   T_inner = umeyama(Cmerged) (:952); T_onew_oold = T_onew_oold * T_inner (:963)
-//   next T_bnew_bold = ~Tbo * T_onew_oold * Tbo (:926); T_snew_sold = ~Tsb * T_bnew_bold * Tsb (MICPSensor.hpp:178)
-__device__ __forceinline__ void micp_advance(const cstats& stats_s, const xform& Tsb, const xform& Tbo, MicpState* st) {
-  const cstats Cs_b = cs_transform(Tsb, stats_s);
-  const cstats Cs_o = cs_transform(Tbo, Cs_b);
-  const cstats Cmerged = cs_merge(cs_identity(), Cs_o);
-  const xform T_inner = umeyama(Cmerged);
-  const xform T_onew_oold = xmul(st->T_onew_oold, T_inner);
-  const xform T_bnew_bold = xmul(xmul(xinv(Tbo), T_onew_oold), Tbo);
-  st->T_onew_oold = T_onew_oold;
-  st->T_snew_sold = xmul(xmul(xinv(Tsb), T_bnew_bold), Tsb);
-  st->stats_o = Cmerged;
-}
-
-// The same loop for ONE sensor, written in the sensor frame.  umeyama is equivariant under a rigid change of frame
+// One MICP inner iteration for ONE sensor, micp_localization.cpp:915-964 (merge_weight_multiplier == 1) frame by frame:
+//   Cs_o = Tbo * (Tsb * stats_s); T_inner = umeyama(Cs_o); T_onew_oold = T_onew_oold * T_inner;
+//   next T_snew_sold = ~Tsb * (~Tbo * T_onew_oold * Tbo) * Tsb
+// written here in the sensor frame.  umeyama is equivariant under a rigid change of frame
 // (umeyama(T * C) = T o umeyama(C) o T^-1 for a transform T applied to both means and the covariance), so with
 // Tso = Tbo * Tsb:  T_inner = Tso U Tso^-1 with U = umeyama(stats_s), and
 //   T_snew_sold' = Tso^-1 (T_onew_oold T_inner) Tso = T_snew_sold * U.
 // The loop therefore only needs U and one product per iteration; T_onew_oold = Tso T_snew_sold Tso^-1 and
 // stats_o = Tbo * (Tsb * stats_s) are formed once, after the last iteration (micp_close_sensor).  Same mathematics as
-// micp_advance, ~700 instead of ~2500 dependent operations per iteration for the lone lane that runs it; the rounding
+// the frame-by-frame order, ~700 instead of ~2500 dependent operations per iteration for the lone lane that runs it; the rounding
 // differs from the frame-by-frame order at the 1e-7 level (tests: 1e-5 against the oracle's frame-by-frame loop).
 __device__ __forceinline__ void micp_advance_sensor(const cstats& stats_s, xform* T_snew_sold) {
   *T_snew_sold = xmul(*T_snew_sold, umeyama(stats_s));
@@ -170,15 +149,14 @@ __device__ __forceinline__ void micp_close_sensor(const cstats& stats_s_last, co
   st->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(Tsb, stats_s_last)));
 }
 
-// kTail == kTailNone keeps the streaming kernel lean (the solve code of the fused tails costs registers and
-// scratch: with it compiled in, this kernel went from 96 to 192 VGPRs + 80 B scratch and 2.3x slower launches)
-template <uint32_t kTail>
+// one partial row of 16 sums per block and pose; k_reduce_finalize / k_batch_solve turn them into results in a launch of their own
+// (a last-block tail fused into this kernel measured slower: profiles/r03_micp_loop_forms.txt)
 __global__ void __launch_bounds__(256) k_reduce_partials(const ReduceParams p) {
   __shared__ double red[4][kAcc];
   __shared__ double s_wsum[4][64 * 17];
   const uint32_t pose = blockIdx.y;
   const xform Tpre = (p.Tpre_dev != nullptr) ? p.Tpre_dev[pose] : p.Tpre;
-  const float max_dist = (p.call != nullptr) ? p.call->max_dist : p.max_dist;
+  const float max_dist = p.max_dist;
   double acc[kAcc];
 #pragma unroll
   for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
@@ -216,40 +194,11 @@ __global__ void __launch_bounds__(256) k_reduce_partials(const ReduceParams p) {
   __syncthreads();
   if (threadIdx.x < kAcc) {
     const double v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    // agent-scope relaxed store = write-through (sc1) 8-B store: visible to the last arriver without an L2
-    // write-back fence (MI355X_MICROARCH.md, hand-off forms)
+    // agent-scope relaxed store = write-through (sc1) 8-B store (MI355X_MICROARCH.md, hand-off forms); the finalize
+    // launch reads the rows after the kernel boundary
     __hip_atomic_store(p.partials + (static_cast<size_t>(pose) * p.nblocks + blockIdx.x) * kAcc + threadIdx.x, v,
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if constexpr (kTail != kTailNone) {
-  // ---- fused tail: the LAST block of this pose to arrive finalizes.  Hand-off without fences: write-through
-  // (sc1) partial stores -> every wave s_waitcnt vmcnt(0) -> barrier -> relaxed agent-scope ticket; the last
-  // arriver reads the partials with sc1 loads (L1-bypassing).  A release fence per block (256 x buffer_wbl2)
-  // measured SLOWER than the kernel boundary it replaces (reduce 14.5 us vs 10.7 us for two launches).
-  __shared__ uint32_t s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t ticket = __hip_atomic_fetch_add(p.tickets + pose, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (ticket == gridDim.x - 1u) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_last == 0u) return;
-  if (threadIdx.x >= 64u) return;
-  const cstats st = finalize_pose<true>(p.partials + static_cast<size_t>(pose) * p.nblocks * kAcc, p.nblocks);
-  if (threadIdx.x == 0) {
-    p.tickets[pose] = 0u;  // re-armed for the next launch on this stream
-    if (kTail == kTailStats) {
-      p.stats_out[pose] = st;
-    } else if (kTail == kTailMicp) {
-      micp_advance(st, p.call ? p.call->Tsb : p.Tsb, p.call ? p.call->Tbo : p.Tbo, p.state);
-    } else {  // kTailBatchSolve: v1 corrector, Tdelta_b = Tsb * T_s * ~Tsb
-      const xform Ts = umeyama(st);
-      p.Tdelta_out[pose] = xmul(xmul(p.Tsb, Ts), xinv(p.Tsb));
-      if (p.stats_out) p.stats_out[pose] = st;
-    }
-  }
-  }  // kTail != kTailNone
 }
 
 // Completion tag of a launch chain whose results go to host-mapped memory and whose caller polls instead of waiting for the
@@ -285,119 +234,6 @@ __global__ void __launch_bounds__(64) k_reduce_finalize(const double* __restrict
     out[pose] = s;
     if (done) publish_tag(done, seq, xor_words(s));   // single-pose call with a host-mapped result (capi_rcc.cpp wait_done)
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// persistent MICP loop: ALL optimization iterations of one correction in ONE launch.
-// The per-iteration chain "reduce (grid) -> finalize + solve (one lane) -> next pre-transform" is bound by launch
-// boundaries (two ~5 us launches per iteration for ~1 us of HBM/L2 streaming).  Here a small co-resident grid
-// (gridDim.x <= number of CUs, 512 threads) keeps iterating: each block reduces its contiguous slice of the
-// correspondences (which stay L2-resident), publishes a 128-B partial with write-through stores, meets the other
-// blocks at a counter barrier, and then EVERY block finalizes and solves redundantly (same partials, same
-// order, same code => identical state) -- one barrier per iteration and no broadcast step.
-// ---------------------------------------------------------------------------------------------
-struct MicpLoopParams {
-  const float* dataset_points;
-  const uint8_t* dataset_mask;  // nullable
-  const float* model_points;
-  const float* model_normals;
-  const uint8_t* model_mask;
-  uint32_t n, n_iter;
-  const MicpCall* call;  // Tsb, Tbo, max_dist of this correction
-  double* partials;      // [2][gridDim.x][16] (double-buffered across iterations)
-  uint32_t* barrier;     // zero at launch (k_micp_init)
-  MicpState* state;      // result, written by block 0
-};
-
-// kOneXcd: the grid is 8x larger and only the blocks the dispatcher places on XCD 0 (block id % 8 == 0: observed placement,
-// used for speed only -- the barrier protocol is valid wherever the blocks land) take part, so that partials, counter and
-// correspondences meet in ONE L2 instead of crossing the fabric between eight
-template <bool kOneXcd>
-__global__ void __launch_bounds__(512) k_micp_loop(const MicpLoopParams p) {
-  __shared__ double red[8][kAcc];
-  __shared__ MicpState s_state;
-  __shared__ xform s_Tsb, s_Tbo;
-  if (kOneXcd && (blockIdx.x & 7u) != 0u) return;
-  const uint32_t G = kOneXcd ? (gridDim.x >> 3) : gridDim.x, b = kOneXcd ? (blockIdx.x >> 3) : blockIdx.x;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) {
-    s_state.T_onew_oold = xidentity();
-    s_state.T_snew_sold = xidentity();
-    s_state.stats_o = cs_identity();
-    s_Tsb = p.call->Tsb;
-    s_Tbo = p.call->Tbo;
-  }
-  const float max_dist = p.call->max_dist;
-  // contiguous slice of this block, a multiple of the block size
-  const uint32_t per = ((p.n + G - 1u) / G + 511u) & ~511u;
-  const uint32_t i0 = b * per, i1 = min(p.n, i0 + per);
-  __syncthreads();
-  for (uint32_t it = 0; it < p.n_iter; ++it) {
-    const xform Tpre = s_state.T_snew_sold;
-    double acc[kAcc];
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
-    for (uint32_t i = i0 + threadIdx.x; i < i1; i += 512u) {
-      const bool dok = (p.dataset_mask == nullptr) || (p.dataset_mask[i] > 0);
-      if (dok && p.model_mask[i] > 0) {
-        const float* dp = p.dataset_points + 3 * static_cast<size_t>(i);
-        const float* mp = p.model_points + 3 * static_cast<size_t>(i);
-        const float* mn = p.model_normals + 3 * static_cast<size_t>(i);
-        const f3 Di = xapply(Tpre, mk3(dp[0], dp[1], dp[2]));
-        const f3 Ii = mk3(mp[0], mp[1], mp[2]);
-        const f3 Ni = mk3(mn[0], mn[1], mn[2]);
-        const float spd = dot_plain(sub3(Ii, Di), Ni);
-        if (fabsf(spd) < max_dist) {
-          const f3 Mi = add3(Di, scale3(Ni, spd));
-          const double d[3] = {Di.x, Di.y, Di.z}, m[3] = {Mi.x, Mi.y, Mi.z};
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { acc[k] += d[k]; acc[3 + k] += m[k]; }
-#pragma unroll
-          for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[6 + 3 * r + c] += m[r] * d[c];
-          acc[15] += 1.0;
-        }
-      }
-    }
-    // wave reduction (halving butterfly, see k_reduce_partials), then the 8 waves through LDS
-#pragma unroll
-    for (int half = 8, off = 32; half >= 1; half >>= 1, off >>= 1) {
-      const bool hi = (lane & static_cast<uint32_t>(off)) != 0u;
-#pragma unroll
-      for (int j = 0; j < half; ++j) {
-        const double send = hi ? acc[j] : acc[j + half];
-        const double keep = hi ? acc[j + half] : acc[j];
-        acc[j] = keep + __shfl_xor(send, off, 64);
-      }
-    }
-    acc[0] += __shfl_xor(acc[0], 2, 64);
-    acc[0] += __shfl_xor(acc[0], 1, 64);
-    if ((lane & 3u) == 0u) red[wave][lane >> 2] = acc[0];
-    __syncthreads();
-    double* part = p.partials + static_cast<size_t>(it & 1u) * G * kAcc;
-    if (threadIdx.x < kAcc) {
-      double v = 0.0;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v += red[w][threadIdx.x];
-      __hip_atomic_store(part + static_cast<size_t>(b) * kAcc + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // grid barrier: write-through partial stores complete (vmcnt) -> arrive -> spin on the monotonic counter
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(p.barrier, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t target = (it + 1u) * G;
-      while (__hip_atomic_load(p.barrier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(1);
-    }
-    __syncthreads();
-    if (wave == 0u) {
-      const cstats st = finalize_pose<true>(part, G);
-      if (lane == 0u) micp_advance(st, s_Tsb, s_Tbo, &s_state);
-    }
-    __syncthreads();
-  }
-  if (b == 0u && threadIdx.x == 0u) *p.state = s_state;
 }
 
 // One MICP iteration per launch (instead of reduce + solve = two): the launch of iteration i first finishes
@@ -516,20 +352,18 @@ __global__ void __launch_bounds__(256) k_micp_iter(const MicpIterParams p) {
         ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-__global__ void k_micp_init(MicpState* st, uint32_t* barrier) {
+// the state of a correction without iterations (k_micp_iter initialises itself)
+__global__ void k_micp_init(MicpState* st) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     st->T_onew_oold = xidentity();
     st->T_snew_sold = xidentity();
     st->stats_o = cs_identity();
     st[1] = st[0];  // the state ping-pongs between two slots (k_micp_iter)
-    if (barrier) *barrier = 0u;
   }
 }
 
-// unfused form of the MICP step (kept for A/B against the fused tail of k_reduce_partials)
-// st_out may alias st (in place) or point to host-mapped memory: the closing step of a correction then delivers the
-// result without a device-to-host copy node
-// closing launch of the one-launch-per-iteration form: the last iteration's solve + the odom-frame results
+// closing launch of the one-launch-per-iteration form: the last iteration's solve + the odom-frame results.  st_out may point
+// to host-mapped memory: the correction then delivers its result without a device-to-host copy node
 __global__ void __launch_bounds__(64) k_micp_close(const double* __restrict__ partials, uint32_t nblocks, const MicpCall* call,
                                                    const MicpState* st, MicpState* st_out, unsigned long long* done) {
   const cstats stats_s = finalize_pose(partials, nblocks);
@@ -540,16 +374,6 @@ __global__ void __launch_bounds__(64) k_micp_close(const double* __restrict__ pa
     micp_close_sensor(stats_s, T_s, call->Tsb, call->Tbo, &out);
     *st_out = out;
     if (done) publish_tag(done, call->seq, xor_words(out));   // the caller polls the tag instead of waiting for the stream's signal
-  }
-}
-
-__global__ void __launch_bounds__(64) k_micp_step(const double* __restrict__ partials, uint32_t nblocks, xform Tsb,
-                                                  xform Tbo, const MicpCall* call, const MicpState* st, MicpState* st_out) {
-  const cstats stats_s = finalize_pose(partials, nblocks);
-  if (threadIdx.x == 0) {
-    MicpState local = *st;
-    micp_advance(stats_s, call ? call->Tsb : Tsb, call ? call->Tbo : Tbo, &local);
-    *st_out = local;
   }
 }
 
@@ -576,23 +400,6 @@ constexpr uint32_t kFastMaxUncertain = 4096;
 // per-iteration form, which joins with stream events -- instead of a kernel the 20 ms host fallback could never get past.
 constexpr uint32_t kDevicePollBound = 1u << 21;
 constexpr uint32_t kFastThreads = 256;   // 1 wave per SIMD: the one-lane solve may use up to 512 VGPRs (no scratch)
-
-// wave64 sum of 16 doubles per lane by the halving butterfly of k_reduce_partials: afterwards lane L holds the wave total of
-// value L >> 2 in v[0]
-__device__ __forceinline__ void wave_reduce16(double (&v)[16], uint32_t lane) {
-#pragma unroll
-  for (int half = 8, off = 32; half >= 1; half >>= 1, off >>= 1) {
-    const bool hi = (lane & static_cast<uint32_t>(off)) != 0u;
-#pragma unroll
-    for (int j = 0; j < half; ++j) {
-      const double send = hi ? v[j] : v[j + half];
-      const double keep = hi ? v[j + half] : v[j];
-      v[j] = keep + __shfl_xor(send, off, 64);
-    }
-  }
-  v[0] += __shfl_xor(v[0], 2, 64);
-  v[0] += __shfl_xor(v[0], 1, 64);
-}
 
 // raw sums of the reduction (sd[3] sm[3] smd[9] n) -> CrossStatistics, as finalize_pose does
 // ---- cheaper reciprocals for the ONE lane that solves (moment-form loops): a lone lane retires one instruction per ~5-8 cycles,
@@ -2591,11 +2398,7 @@ uint32_t reduce_num_blocks(uint32_t n, uint32_t nposes) {
 }
 
 hipError_t launch_reduce_partials(const ReduceParams& p, hipStream_t s) {
-  const dim3 grid(p.nblocks, p.nposes), block(256);
-  if (p.tail_mode == kTailStats) hipLaunchKernelGGL((k_reduce_partials<kTailStats>), grid, block, 0, s, p);
-  else if (p.tail_mode == kTailMicp) hipLaunchKernelGGL((k_reduce_partials<kTailMicp>), grid, block, 0, s, p);
-  else if (p.tail_mode == kTailBatchSolve) hipLaunchKernelGGL((k_reduce_partials<kTailBatchSolve>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((k_reduce_partials<kTailNone>), grid, block, 0, s, p);
+  hipLaunchKernelGGL(k_reduce_partials, dim3(p.nblocks, p.nposes), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
@@ -2857,17 +2660,6 @@ hipError_t launch_reduce_finalize(const double* partials, uint32_t nblocks, uint
   return hipGetLastError();
 }
 
-hipError_t launch_micp_loop(const float* dataset_points, const uint8_t* dataset_mask, const float* model_points,
-                            const float* model_normals, const uint8_t* model_mask, uint32_t n, uint32_t n_iter,
-                            const MicpCall* call, double* partials, uint32_t* barrier, MicpState* state,
-                            uint32_t nblocks, bool one_xcd, hipStream_t s) {
-  MicpLoopParams p{dataset_points, dataset_mask, model_points, model_normals, model_mask, n, n_iter, call, partials,
-                   barrier, state};
-  if (one_xcd) hipLaunchKernelGGL((k_micp_loop<true>), dim3(nblocks * 8u), dim3(512), 0, s, p);
-  else hipLaunchKernelGGL((k_micp_loop<false>), dim3(nblocks), dim3(512), 0, s, p);
-  return hipGetLastError();
-}
-
 hipError_t launch_micp_iter(const float* dataset_points, const uint8_t* dataset_mask, const float* model_points,
                             const float* model_normals, const uint8_t* model_mask, uint32_t n, uint32_t nblocks,
                             const MicpCall* call, const double* partials_prev, double* partials_out,
@@ -2976,20 +2768,14 @@ hipError_t launch_micp_multi_step(const MicpMultiCall* call, MicpMultiState* sta
   return hipGetLastError();
 }
 
-hipError_t launch_micp_init(MicpState* state, uint32_t* barrier, hipStream_t s) {
-  hipLaunchKernelGGL(k_micp_init, dim3(1), dim3(64), 0, s, state, barrier);
+hipError_t launch_micp_init(MicpState* state, hipStream_t s) {
+  hipLaunchKernelGGL(k_micp_init, dim3(1), dim3(64), 0, s, state);
   return hipGetLastError();
 }
 
 hipError_t launch_micp_close(const double* partials, uint32_t nblocks, const MicpCall* call, const MicpState* state,
                              MicpState* state_out, unsigned long long* done, hipStream_t s) {
   hipLaunchKernelGGL(k_micp_close, dim3(1), dim3(64), 0, s, partials, nblocks, call, state, state_out, done);
-  return hipGetLastError();
-}
-
-hipError_t launch_micp_step(const double* partials, uint32_t nblocks, xform Tsb, xform Tbo, const MicpCall* call,
-                            const MicpState* state, MicpState* state_out, hipStream_t s) {
-  hipLaunchKernelGGL(k_micp_step, dim3(1), dim3(64), 0, s, partials, nblocks, Tsb, Tbo, call, state, state_out);
   return hipGetLastError();
 }
 

@@ -541,8 +541,8 @@ class CorrespondencesHIP:
 
     def set_micp_fast(self, mode):
         """moment form of the schedule-(R) loop of correctOnce: 0 = never, 1 = automatic, iterations on the host from the published
-        moments (default), 2 = device loop through a hipGraph, 3 = device loop, moments in a pass of their own, 4 = device loop behind
-        a find with the moment epilogue (rmclhip.h)"""
+        moments (default), 3 = device loop, moments in a pass of their own, 4 = device loop behind a find with the moment epilogue
+        (rmclhip.h; 2, the device loop replayed from a hipGraph, is retired and refused)"""
         _capi.check(_capi.lib().rmclhip_rcc_set_micp_fast(self._h, int(mode)))
 
     def ccs_info(self):

@@ -161,12 +161,10 @@ def test_correct_batch_v1_api(ra, orc, ctx, meshes):
     assert np.all(np.abs(t1[:, 2]) <= np.abs(t0[:, 2]) + 1e-3)
 
 
-@pytest.mark.parametrize("variant_bits", [0, 1 << 8, 1 << 9, (1 << 8) | (1 << 9), 1 << 10, (1 << 10) | (1 << 9), 4 << 10,
-                                          (6 << 10) | (1 << 8), 7 << 10])
-def test_loop_variants_agree(ra, orc, ctx, meshes, variant_bits):
-    """A/B code paths of the MICP loop (fused last-block reduction tail, hipGraph replay on/off, loop form: one
-    launch per iteration / reduce + solve launches / persistent kernel with a grid barrier) give the same
-    statistics and pose as the default path; repeated calls with changing inputs exercise graph replay with
+@pytest.mark.parametrize("fast,variant_bits", [(1, 0), (1, 1 << 9), (0, 0), (0, 1 << 9)], ids=["0", "512", "fast0-0", "fast0-512"])
+def test_loop_variants_agree(ra, orc, ctx, meshes, fast, variant_bits):
+    """A/B code paths of the MICP loop (moment form on / off, hipGraph replay of the per-iteration chain on / off: set_variant
+    bit 9) give the same statistics and pose as the oracle; repeated calls with changing inputs exercise graph replay with
     fresh per-call parameters (pose, Tbo, max_dist, Tsb)."""
     from rmcl_amd import synthetic as syn, types as T
     m, hm, model = _sphere_setup(ra, orc, ctx, meshes)
@@ -175,6 +173,7 @@ def test_loop_variants_agree(ra, orc, ctx, meshes, variant_bits):
     ds, mask = om.dataset_from_ranges(model, meas["ranges"])
     rcc = ra.RCCHipSpherical(hm)
     rcc.set_variant(2 | variant_bits)   # 14 400 rays: the quad traversal, the automatic choice for this scan
+    rcc.set_micp_fast(fast)             # 0: every call runs the per-iteration chain
     rcc.setTsb(ident)
     rcc.setModel(model)
     rcc.set_dataset(ds, mask)
@@ -192,6 +191,70 @@ def test_loop_variants_agree(ra, orc, ctx, meshes, variant_bits):
         assert int(s1["n_meas"]) > 0
     Td, st = rcc.correct_batch(np.array([c[0] for c in cases], dtype=T.TRANSFORM))
     assert len(Td) == 3 and int(st[0]["n_meas"]) > 0
+
+
+def test_retired_loop_forms_are_refused(ra, orc, ctx, meshes):
+    """set_variant bits 8 and 10..12 and set_micp_fast(2) (MICP loop forms measured slower and removed) are refused without
+    changing the operator: its traversal, loop form and result stay what they were."""
+    from rmcl_amd import types as T
+    m, hm, model = _sphere_setup(ra, orc, ctx, meshes)
+    ident = T.identity()
+    meas = m.simulate_spherical(model, ident, ident, bvh=True, nthreads=8)
+    ds, mask = om.dataset_from_ranges(model, meas["ranges"])
+    rcc = ra.RCCHipSpherical(hm)
+    rcc.set_variant(2)
+    rcc.setTsb(ident)
+    rcc.setModel(model)
+    rcc.set_dataset(ds, mask)
+    rcc.set_micp_fast(0)
+    Tom = T.transform((0, 0, 0, 1), (0.0, 0.0, 0.2))
+    before = tuple(x.tobytes() for x in rcc.correct_once(Tom, ident, 4, 0.0, False))
+    for bits in (1 << 8, (1 << 8) | (1 << 9), 1 << 10, 2 << 10, 6 << 10, 7 << 10):
+        with pytest.raises(ra.RmclHipError) as e:
+            rcc.set_variant(2 | bits)
+        assert e.value.status == ra._capi.ERR_INVALID and "retired" in str(e.value)
+    with pytest.raises(ra.RmclHipError) as e:
+        rcc.set_micp_fast(2)
+    assert e.value.status == ra._capi.ERR_INVALID and "retired" in str(e.value)
+    assert rcc.find_variant(1) == 2
+    after = tuple(x.tobytes() for x in rcc.correct_once(Tom, ident, 4, 0.0, False))
+    assert after == before
+    assert rcc.micp_fast_info()["attempts"] == 0     # still mode 0
+    rcc.close()
+
+
+@pytest.mark.parametrize("fast", [0, 1])
+@pytest.mark.parametrize("variant_bits", [0, 1 << 9])
+def test_correct_once_zero_iterations_is_identity(ra, orc, ctx, meshes, fast, variant_bits):
+    """correct_once with n_iter = 0 returns the identity transform and identity statistics (n_meas 0) in schedule (R), as schedule
+    (B) does, with the hipGraph on and off and the moment form on and off; a correction with iterations on the same operator
+    afterwards still matches the oracle."""
+    from rmcl_amd import types as T
+    m, hm, model = _sphere_setup(ra, orc, ctx, meshes)
+    ident = T.identity()
+    meas = m.simulate_spherical(model, ident, ident, bvh=True, nthreads=8)
+    ds, mask = om.dataset_from_ranges(model, meas["ranges"])
+    rcc = ra.RCCHipSpherical(hm)
+    rcc.set_variant(2 | variant_bits)
+    rcc.setTsb(ident)
+    rcc.setModel(model)
+    rcc.set_dataset(ds, mask)
+    rcc.set_micp_fast(fast)
+    rcc.params.max_dist = rcc.adaptive_max_dist_min = 1.0
+    Tom = T.transform((0, 0, 0, 1), (0.0, 0.0, 0.2))
+    TB, sB = rcc.correct_once(Tom, ident, 0, 0.0, True)
+    assert int(sB["n_meas"]) == 0
+    for k in (0, 4, 0):
+        Tg, sg = rcc.correct_once(Tom, ident, k, 0.0, False)
+        if k == 0:
+            assert Tg.tobytes() == TB.tobytes() and sg.tobytes() == sB.tobytes()
+            _transform_close(Tg, ident, 0.0)
+            assert int(sg["n_meas"]) == 0
+        else:
+            To, so, _ = om.correct_once(m, model, ident, ident, Tom, ds, mask, k, 1.0, adaptive_min=1.0, nthreads=8)
+            _transform_close(Tg, To, 1e-5)
+            assert int(sg["n_meas"]) == int(so["n_meas"])
+    rcc.close()
 
 
 def test_find_batch_o1dn_pose_major(ra, orc, ctx, meshes):
