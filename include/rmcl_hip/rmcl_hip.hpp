@@ -659,7 +659,28 @@ inline void set_model(rmclhip_rcc* h, const OnDnModel& m) {
   check(rmclhip_rcc_set_model_ondn(h, m.width, m.height, m.range, reinterpret_cast<const float*>(m.origs.data()),
                                    reinterpret_cast<const float*>(m.dirs.data())));
 }
+// the models a segmentation node compares between scans (it re-sends a model to the device only when it changed)
+inline bool same_model(const SphericalModel& a, const SphericalModel& b) {
+  return a.phi.min == b.phi.min && a.phi.inc == b.phi.inc && a.phi.size == b.phi.size && a.theta.min == b.theta.min && a.theta.inc == b.theta.inc &&
+         a.theta.size == b.theta.size && a.range.min == b.range.min && a.range.max == b.range.max;
+}
+inline bool same_model(const O1DnModel& a, const O1DnModel& b) {
+  if (a.width != b.width || a.height != b.height || a.range.min != b.range.min || a.range.max != b.range.max || a.orig.x != b.orig.x ||
+      a.orig.y != b.orig.y || a.orig.z != b.orig.z || a.dirs.size() != b.dirs.size())
+    return false;
+  for (size_t i = 0; i < a.dirs.size(); i++)
+    if (a.dirs[i].x != b.dirs[i].x || a.dirs[i].y != b.dirs[i].y || a.dirs[i].z != b.dirs[i].z) return false;
+  return true;
+}
 }  // namespace detail
+
+// map_segmentation.cpp:25-41: the segmentation nodes' two thresholds (declared double, stored in float members); pint_with_origin =
+// RMCLHIP_SEG_PINT_WITH_ORIGIN (include/rmclhip.h: the reference leaves the ray origin out of pint_s when both ranges are valid)
+struct SegmentationParams {
+  float min_dist_outlier_scan = 0.15f, min_dist_outlier_map = 0.15f;
+  bool pint_with_origin = false;
+};
+struct SegmentationCounts { uint32_t outlier_scan = 0, outlier_map = 0; };
 
 // rmagine::SphereSimulatorEmbree / O1DnSimulatorEmbree / PinholeSimulatorEmbree / OnDnSimulatorEmbree (and their Optix twins) on gfx950:
 //   setTsb, setModel, simulate(const Transform&, BundleT&), simulate<BundleT>(Transform), simulate(Memory<Transform>&, BundleT&)
@@ -717,6 +738,21 @@ class SimulatorHip {
     resize_bundle(res, Tbm.size());
     run(Tbm.raw(), static_cast<uint32_t>(Tbm.size()), true, res);
     return res;
+  }
+
+  // Map segmentation (rmclhip_rcc_segment): the per-scan body of ScanMapSegmentationEmbreeNode / O1DnMapSegmentationEmbreeNode
+  // (scan_map_segmentation_embree.cpp:76-185) in one call -- simulate Bundle<Ranges, Normals> at Tbm, compare with the measured ranges,
+  // compact the two outlier clouds in buffer order, all on the device.  The clouds (and labels, if wanted) are resized to their
+  // counts (model.size()); their memory is the `data` of a PointCloud2 with fields x, y, z float32, point_step 12.
+  SegmentationCounts segment(const Transform& Tbm, MemoryView<const float, RAM> ranges, const SegmentationParams& params,
+                             Memory<Vector, VRAM_HIP>& outlier_scan, Memory<Vector, VRAM_HIP>& outlier_map,
+                             Memory<uint8_t, VRAM_HIP>* labels = nullptr) {
+    return run_segment(Tbm, ranges.raw(), ranges.size(), false, params, outlier_scan, outlier_map, labels);
+  }
+  SegmentationCounts segment(const Transform& Tbm, const DeviceView<const float>& ranges, const SegmentationParams& params,
+                             Memory<Vector, VRAM_HIP>& outlier_scan, Memory<Vector, VRAM_HIP>& outlier_map,
+                             Memory<uint8_t, VRAM_HIP>* labels = nullptr) {
+    return run_segment(Tbm, ranges.raw(), ranges.size(), true, params, outlier_scan, outlier_map, labels);
   }
 
  protected:
@@ -778,6 +814,35 @@ class SimulatorHip {
     fetch<Normals>(res, n, st_normals_);
     fetch<FaceIds>(res, n, st_face_ids_);
   }
+  SegmentationCounts run_segment(const Transform& Tbm, const float* ranges, size_t n_ranges, bool ranges_on_device, const SegmentationParams& params,
+                                 Memory<Vector, VRAM_HIP>& outlier_scan, Memory<Vector, VRAM_HIP>& outlier_map, Memory<uint8_t, VRAM_HIP>* labels) {
+    if (!m_model) throw std::runtime_error("segment: no sensor model (setModel first)");
+    const size_t n = m_model->size();
+    if (n_ranges != n) throw std::runtime_error("segment: the scan does not have model.size() ranges");
+    SegmentationCounts counts;
+    if (n == 0) return counts;
+    rmclhip_segmentation_views v{};
+    for (Memory<Vector, VRAM_HIP>* cloud : {&outlier_scan, &outlier_map}) {
+      if (!cloud->context()) cloud->setContext(sim_map_->context());
+      cloud->resize(n);   // capacity: every ray may be an outlier
+    }
+    v.outlier_scan_xyz_dev = reinterpret_cast<float*>(outlier_scan.raw());
+    v.outlier_map_xyz_dev = reinterpret_cast<float*>(outlier_map.raw());
+    if (labels) {
+      if (!labels->context()) labels->setContext(sim_map_->context());
+      labels->resize(n);
+      v.labels_dev = labels->raw();
+    }
+    const rmclhip_segmentation_params p{params.min_dist_outlier_scan, params.min_dist_outlier_map,
+                                        params.pint_with_origin ? RMCLHIP_SEG_PINT_WITH_ORIGIN : 0u};
+    uint32_t c[2] = {0u, 0u};
+    check(rmclhip_rcc_segment(sim_, &Tbm, ranges, ranges_on_device ? 1 : 0, &p, &v, c));
+    counts.outlier_scan = c[0];
+    counts.outlier_map = c[1];
+    outlier_scan.resize(c[0]);   // (grow-only: the memory stays where it is)
+    outlier_map.resize(c[1]);
+    return counts;
+  }
   HipMapPtr sim_map_;
   rmclhip_rcc* sim_ = nullptr;
   bool sim_owns_ = false;
@@ -792,6 +857,42 @@ using PinholeSimulatorHip = SimulatorHip<PinholeModel>;
 using OnDnSimulatorHip = SimulatorHip<OnDnModel>;
 using SphereSimulatorHipPtr = std::shared_ptr<SphereSimulatorHip>;
 using O1DnSimulatorHipPtr = std::shared_ptr<O1DnSimulatorHip>;
+
+// ScanMapSegmentationEmbreeNode / O1DnMapSegmentationEmbreeNode (rmcl_ros/src/nodes/filter/scan_map_segmentation_embree.cpp,
+// o1dn_map_segmentation_embree.cpp) without ROS: the nodes' members (the two thresholds of map_segmentation.cpp:25-41, scan_sim_ with an
+// identity Tsb, :38-39) and their scanCB as ONE call.  The message is replaced by its parts (sensor model, ranges); the two clouds stay in
+// device memory, sized to their counts, until the next scan.
+template <typename ModelT>
+class MapSegmentationHipNode_ {
+ public:
+  float min_dist_outlier_scan_ = 0.15f, min_dist_outlier_map_ = 0.15f;
+  bool pint_with_origin_ = false;   // RMCLHIP_SEG_PINT_WITH_ORIGIN
+  Memory<Vector, VRAM_HIP> cloud_outlier_scan_, cloud_outlier_map_;
+
+  explicit MapSegmentationHipNode_(HipMapPtr map) {
+    scan_sim_ = std::make_shared<SimulatorHip<ModelT>>(map);
+    scan_sim_->setTsb(identity());
+  }
+  // T: the sensor's pose in the map (the node's tf lookup, :58-74).  `ranges` in host memory (a message) or device memory
+  SegmentationCounts scanCB(const ModelT& model, MemoryView<const float, RAM> ranges, const Transform& T) {
+    prepare(model);
+    return scan_sim_->segment(T, ranges, params(), cloud_outlier_scan_, cloud_outlier_map_);
+  }
+  SegmentationCounts scanCB(const ModelT& model, const DeviceView<const float>& ranges, const Transform& T) {
+    prepare(model);
+    return scan_sim_->segment(T, ranges, params(), cloud_outlier_scan_, cloud_outlier_map_);
+  }
+
+ private:
+  void prepare(const ModelT& model) {
+    // the reference calls setModel per scan (:78); here that is an upload, so only when the model changed
+    if (!scan_sim_->model() || !detail::same_model(*scan_sim_->model(), model)) scan_sim_->setModel(model);
+  }
+  SegmentationParams params() const { return SegmentationParams{min_dist_outlier_scan_, min_dist_outlier_map_, pint_with_origin_}; }
+  std::shared_ptr<SimulatorHip<ModelT>> scan_sim_;
+};
+using ScanMapSegmentationHipNode = MapSegmentationHipNode_<SphericalModel>;
+using O1DnMapSegmentationHipNode = MapSegmentationHipNode_<O1DnModel>;
 
 // rmcl::RCCEmbree{Spherical, Pinhole, O1Dn, OnDn} (RCCEmbree.hpp:18-83): the correspondence operator + ModelSetter + -- protected --
 // the simulator of its model.  find() is the reference's `simulate(Tbm_est, model_buffers_)` (RCCEmbree.cpp:35) on the operator's own

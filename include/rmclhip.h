@@ -515,6 +515,45 @@ rmclhip_status rmclhip_rcc_simulate(rmclhip_rcc* rcc, const rmclhip_transform* T
                                     const rmclhip_bundle_views* out);
 rmclhip_status rmclhip_rcc_simulate_async(rmclhip_rcc* rcc, const rmclhip_transform* Tbm, uint32_t nposes, int Tbm_is_device,
                                           const rmclhip_bundle_views* out);
+/* ---- map segmentation ------------------------------------------------------------------------------------------------------------
+ * The per-scan body of ScanMapSegmentationEmbreeNode / O1DnMapSegmentationEmbreeNode (rmcl_ros/src/nodes/filter/
+ * scan_map_segmentation_embree.cpp:76-185, o1dn_map_segmentation_embree.cpp; parameters map_segmentation.cpp:25-41) in one call: simulate
+ * Bundle<Ranges, Normals> at Tsm = Tbm * Tsb, compare every simulated range with the measured one, and leave two clouds in BUFFER ORDER
+ * (vid-major, the order the reference's loops push them in).  With inside(r) = range.min <= r && r <= range.max (NaN is outside; a
+ * simulated miss is range.max + 1) for ray bid = vid * W + hid:
+ *   both inside:  pint_s = dir * r_sim (NO origin, as the reference writes it), n = normalize(normal_sim),
+ *                 plane_distance = |(preal_s - pint_s) . n| with preal_s = dir * r_real + orig;
+ *                 r_real <  r_sim: plane_distance > min_dist_outlier_scan ? outlier_scan gets preal_s : inlier
+ *                 r_real >= r_sim: plane_distance > min_dist_outlier_map  ? outlier_map  gets pint_s  : inlier
+ *   real only:    outlier_scan gets preal_s
+ *   sim only:     outlier_map gets dir * r_sim + orig
+ *   neither:      nothing
+ * Labels: one uint8 per ray, 0 none, 1 inlier, 2 outlier_scan, 3 outlier_map.  A cloud is packed xyz float32 (point_step 12: the `data`
+ * of a PointCloud2 with the reference's SegmentationPoint fields).  RMCLHIP_SEG_PINT_WITH_ORIGIN adds the origin to pint_s in the
+ * both-inside branch too (plane distance and emitted point): it only matters for O1Dn / OnDn models with an offset origin. */
+#define RMCLHIP_SEG_PINT_WITH_ORIGIN 1u
+typedef struct {
+  float min_dist_outlier_scan, min_dist_outlier_map; /* metres, >= 0 (the reference's defaults: 0.15); compared with a strict > */
+  uint32_t flags;                                    /* RMCLHIP_SEG_* */
+} rmclhip_segmentation_params;
+typedef struct {                  /* caller-owned device memory, every pointer nullable */
+  uint8_t* labels_dev;            /* W*H */
+  float* outlier_scan_xyz_dev;    /* capacity W*H points */
+  float* outlier_map_xyz_dev;     /* capacity W*H points */
+  uint32_t* counts_dev;           /* [2] = {n_outlier_scan, n_outlier_map}, for consumers that stay on the stream */
+} rmclhip_segmentation_views;
+/* ranges_real: W*H measured ranges, host memory or -- ranges_is_device != 0 -- device memory (_async: valid until the sync).  out may
+ * be NULL (counts only); counts_out (nullable) receives {n_outlier_scan, n_outlier_map}.  Everything runs on the handle's stream: the
+ * trace into the operator's own scratch, the classification, the order-preserving compaction; nothing is written beyond the counted
+ * points, and the same inputs give the same bits on every run and for every find kind.  The operator's model buffers, its dataset and
+ * whatever computeCrossStatistics has cached are NOT touched.  Empty model: no-op, counts 0.  NaN or negative thresholds, unknown flag
+ * bits, a null Tbm / ranges_real / params: RMCLHIP_ERR_INVALID.  The _async form returns once the work is enqueued (rmclhip_rcc_sync
+ * waits; the counts are then in out->counts_dev). */
+rmclhip_status rmclhip_rcc_segment(rmclhip_rcc* rcc, const rmclhip_transform* Tbm, const float* ranges_real, int ranges_is_device,
+                                   const rmclhip_segmentation_params* params, const rmclhip_segmentation_views* out,
+                                   uint32_t counts_out[2]);
+rmclhip_status rmclhip_rcc_segment_async(rmclhip_rcc* rcc, const rmclhip_transform* Tbm, const float* ranges_real, int ranges_is_device,
+                                         const rmclhip_segmentation_params* params, const rmclhip_segmentation_views* out);
 /* rm::statistics_p2l(const Transform& Tpre, const PointCloudView_<MemT>& dataset, const PointCloudView_<MemT>& model,
  * const UmeyamaReductionConstraints& params) -> CrossStatistics, as a free function on CALLER-owned device views
  * (rmcl/src/rmcl/registration/CorrespondencesCUDA.cpp:28; gate and projection pinned by rmcl_ros/src/micpl/MICPSensorCPU.cpp:70-84):

@@ -98,6 +98,20 @@ class BundleViews(C.Structure):
                 ("normals_xyz_dev", C.c_void_p), ("face_ids_dev", C.c_void_p)]
 
 
+class SegmentationParams(C.Structure):
+    """rmclhip_segmentation_params (map_segmentation.cpp:25-41: the node's two thresholds, stored as float)"""
+    _fields_ = [("min_dist_outlier_scan", C.c_float), ("min_dist_outlier_map", C.c_float), ("flags", C.c_uint32)]
+
+
+class SegmentationViews(C.Structure):
+    """rmclhip_segmentation_views: caller-owned device memory, every pointer nullable"""
+    _fields_ = [("labels_dev", C.c_void_p), ("outlier_scan_xyz_dev", C.c_void_p), ("outlier_map_xyz_dev", C.c_void_p),
+                ("counts_dev", C.c_void_p)]
+
+
+SEG_PINT_WITH_ORIGIN = 1
+SEG_NONE, SEG_INLIER, SEG_OUTLIER_SCAN, SEG_OUTLIER_MAP = 0, 1, 2, 3
+
 OUT_HITS, OUT_RANGES, OUT_POINTS, OUT_NORMALS, OUT_FACE_IDS = 1, 2, 4, 8, 16
 OUT_ALL = 31
 OUT_MICP = OUT_HITS | OUT_POINTS | OUT_NORMALS   # Correspondences_::model_buffers_ (Correspondences.hpp:81-85)
@@ -157,6 +171,9 @@ SIGNATURES = {
     "rmclhip_rcc_get_outputs": (_i32, [_vp, C.POINTER(_u32)]),
     "rmclhip_rcc_simulate": (_i32, [_vp, _vp, _u32, _i32, C.POINTER(BundleViews)]),
     "rmclhip_rcc_simulate_async": (_i32, [_vp, _vp, _u32, _i32, C.POINTER(BundleViews)]),
+    "rmclhip_rcc_segment": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(SegmentationParams), C.POINTER(SegmentationViews),
+                                   C.POINTER(_u32)]),
+    "rmclhip_rcc_segment_async": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(SegmentationParams), C.POINTER(SegmentationViews)]),
     "rmclhip_statistics_p2l": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp]),
     "rmclhip_rcc_correct_once": (_i32, [_vp, _vp, _vp, _u32, _dbl, _i32, _vp, _vp]),
     "rmclhip_micp_correct_once": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _dbl, _vp, _vp]),

@@ -3,6 +3,7 @@
 //   capi_map.cpp       context, map / scene upload, host-side algebra, device memory helpers
 //   capi_rcc.cpp       the correspondence operator: models, datasets, find, reduction, the MICP corrections (one and N sensors), pose batches
 //   capi_rcc_tune.cpp  tuning knobs, autotune, measurement aids (include/rmclhip_bench.h) and diagnostics (include/rmclhip_lab.h) of that operator
+//   capi_segment.cpp   map segmentation of that operator: trace into its own scratch, labels, compacted outlier clouds (kernels: segment.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
@@ -287,6 +288,13 @@ struct rmclhip_rcc {
   // correct_batch's results leave through pinned, host-mapped staging (grow-only): the solve launch writes them there, the call
   // returns on its completion tag and copies them out -- no device-to-host copy launches, no stream synchronisation
   xform* h_bT = nullptr; xform* h_bT_dev = nullptr; cstats* h_bS = nullptr; cstats* h_bS_dev = nullptr; uint32_t h_batch_cap = 0;
+  // map segmentation (capi_segment.cpp): grow-only scratch of its trace {ranges, normals}, the staged measured ranges, labels when the
+  // caller wants none, the per-workgroup counts; the totals arrive in pinned, host-mapped memory (created by the first call)
+  DevBuf<float> d_seg_ranges, d_seg_normals, d_seg_real;
+  DevBuf<uint8_t> d_seg_labels;
+  DevBuf<uint32_t> d_seg_block_counts;
+  uint32_t* h_seg_counts = nullptr;
+  uint32_t* h_seg_counts_dev = nullptr;
   bool capturing = false;          // inside hipStreamBeginCapture: no synchronisation allowed
   int variant = 15;       // traversal kind: 0 wave-packet, 1 one lane per ray (while-while), 2 four lanes per ray
                           // (quad-cooperative), 15 automatic: quad while the launch is bound by the slowest ray's

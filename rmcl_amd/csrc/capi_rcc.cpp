@@ -73,6 +73,8 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
   if (r->ev_join) DBG_STEP(hipEventDestroy(r->ev_join));
   if (r->d_join_flags) DBG_STEP(hipFree(r->d_join_flags));
   r->d_multi_blob.release();
+  r->d_seg_ranges.release(); r->d_seg_normals.release(); r->d_seg_real.release(); r->d_seg_labels.release(); r->d_seg_block_counts.release();
+  if (r->h_seg_counts) DBG_STEP(hipHostFree(r->h_seg_counts));
   if (r->h_multi_state) DBG_STEP(hipHostFree(r->h_multi_state));
   if (r->h_multi_status) DBG_STEP(hipHostFree(r->h_multi_status));
   if (r->h_call) DBG_STEP(hipHostFree(r->h_call));

@@ -337,6 +337,31 @@ hipError_t launch_batch_solve(const double* partials, uint32_t nblocks, uint32_t
 hipError_t launch_dataset_from_ranges(const float* ranges, const float* model_tab, uint32_t kind, uint32_t W,
                                       uint32_t H, f3 orig, const float* pin_fc, float rmin, float rmax, float* points,
                                       uint8_t* mask, uint32_t* n_valid, hipStream_t s);
+// map segmentation (segment.hip; ScanMapSegmentationEmbreeNode / O1DnMapSegmentationEmbreeNode): every ray of ONE scan is labelled from its
+// measured and its simulated range, the two outlier clouds leave compacted in buffer order
+constexpr uint32_t kSegBlock = 1024;     // rays per workgroup, one per lane
+enum SegLabel : uint8_t { kSegNone = 0, kSegInlier = 1, kSegOutlierScan = 2, kSegOutlierMap = 3 };
+struct SegmentParams {
+  const float* ranges_real;      // measured, W * H
+  const float* ranges_sim;       // the find's ranges (miss: range.max + 1)
+  const float* normals_sim;      // the find's normals, sensor frame (miss: NaN)
+  const float* model_tab;        // as FindParams::model_tab
+  uint32_t kind, W, H;
+  f3 orig;                       // O1Dn: the model's origin
+  float pin_f[2], pin_c[2];
+  float rmin, rmax;
+  float min_dist_outlier_scan, min_dist_outlier_map;
+  uint32_t pint_with_origin;     // RMCLHIP_SEG_PINT_WITH_ORIGIN
+  uint8_t* labels;               // W * H, never null (the caller's buffer or the operator's scratch): the scatter launch reads them back
+  uint32_t* block_counts;        // [ceil(W * H / kSegBlock)][2] = {scan outliers, map outliers} of a workgroup's rays
+  float* outlier_scan_xyz;       // nullable
+  float* outlier_map_xyz;        // nullable
+  uint32_t* counts_dev;          // nullable [2]
+  uint32_t* counts_host;         // nullable [2], host-mapped
+};
+// two launches: k_segment_classify (labels + per-workgroup counts), k_segment_scatter (offsets from the counts below a workgroup's
+// index, points at offset + rank, totals); the kernel boundary between them is what orders the workgroups
+hipError_t launch_segment(const SegmentParams& p, hipStream_t s);
 hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s);
 hipError_t launch_pf_extract_weights(const void* attrs, uint32_t n, float* weights, hipStream_t s);
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,

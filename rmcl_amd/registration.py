@@ -253,6 +253,8 @@ _ATTRS = ("hits", "ranges", "points", "normals", "face_ids")
 _ATTR_BIT = dict(hits=_capi.OUT_HITS, ranges=_capi.OUT_RANGES, points=_capi.OUT_POINTS, normals=_capi.OUT_NORMALS, face_ids=_capi.OUT_FACE_IDS)
 _ATTR_DTYPE = dict(hits=np.uint8, ranges=np.float32, points=np.float32, normals=np.float32, face_ids=np.uint32)
 _ATTR_SHAPE = dict(hits=(), ranges=(), points=(3,), normals=(3,), face_ids=())
+# segment(): attribute -> member of rmclhip_segmentation_views
+_SEG_FIELD = dict(labels="labels_dev", outlier_scan="outlier_scan_xyz_dev", outlier_map="outlier_map_xyz_dev")
 
 
 def statistics_p2l(ctx, Tpre, dataset_points, dataset_mask, model_points, model_normals, model_mask, n, max_dist):
@@ -376,6 +378,69 @@ class CorrespondencesHIP:
         for a, d in bundle.items():
             h = d.download()
             out[a] = h.reshape(-1, 3) if _ATTR_SHAPE[a] else h
+        return out
+
+    # -- map segmentation (scan_map_segmentation_embree.cpp / o1dn_map_segmentation_embree.cpp: the node's per-scan body) -----------
+    def segment(self, Tbm, ranges, min_dist_outlier_scan=0.15, min_dist_outlier_map=0.15, pint_with_origin=False,
+                want=("labels", "outlier_scan", "outlier_map"), into=None, sync=True):
+        """simulate at Tbm, compare every simulated range with the measured one (`ranges`: H*W values, a numpy array or a DeviceArray /
+        torch tensor on the device) and compact the two outlier clouds in buffer order, all on the device (rmclhip_rcc_segment).
+        labels: uint8 per ray, 0 none, 1 inlier, 2 outlier_scan, 3 outlier_map.  pint_with_origin: RMCLHIP_SEG_PINT_WITH_ORIGIN.
+        into=None: returns {"counts": (n_scan, n_map)} + numpy arrays of the attributes in `want`, the clouds (n, 3) and trimmed to
+        their counts.  into={"labels" / "outlier_scan" / "outlier_map" / "counts": device memory of H*W uint8 / 3*H*W float32 /
+        3*H*W float32 / 2 uint32}: fills those (nothing else is written, `want` is ignored) and returns the counts; sync=False
+        (rmclhip_rcc_segment_async) returns None once the work is enqueued -- sync() waits, the counts are in into["counts"]."""
+        H, W = self._model_shape
+        n = H * W
+        T = np.ascontiguousarray(Tbm, dtype=TRANSFORM).reshape(1)
+        if isinstance(ranges, np.ndarray) or isinstance(ranges, (list, tuple)):
+            r_host = np.ascontiguousarray(ranges, dtype=np.float32).reshape(-1)
+            if r_host.size != n:
+                raise ValueError("segment: %d ranges for a model of %d rays" % (r_host.size, n))
+            rptr, on_dev = _ptr(r_host), 0
+        else:
+            have = int(ranges.numel()) if hasattr(ranges, "numel") else int(ranges.count)
+            if have != n:
+                raise ValueError("segment: %d ranges for a model of %d rays" % (have, n))
+            rptr, on_dev = _as_ptr(ranges), 1
+        params = _capi.SegmentationParams(float(min_dist_outlier_scan), float(min_dist_outlier_map),
+                                          _capi.SEG_PINT_WITH_ORIGIN if pint_with_origin else 0)
+        own = {}
+        if into is None:
+            if not sync:
+                raise ValueError("segment: sync=False needs caller-owned buffers (into=)")
+            for a in want:
+                if a not in _SEG_FIELD:
+                    raise ValueError("unknown segmentation attribute %r" % (a,))
+                own[a] = DeviceArray(self.ctx, np.uint8 if a == "labels" else np.float32, max(n, 1) * (1 if a == "labels" else 3))
+            bufs = own
+        else:
+            unknown = [a for a in into if a not in _SEG_FIELD and a != "counts"]
+            if unknown:
+                raise ValueError("unknown segmentation attribute %r" % (unknown[0],))
+            bufs = into
+        v = _capi.SegmentationViews()
+        for a, field in _SEG_FIELD.items():
+            if a in bufs:
+                setattr(v, field, _as_ptr(bufs[a]))
+        if "counts" in bufs:
+            v.counts_dev = _as_ptr(bufs["counts"])
+        if not sync:
+            _capi.check(_capi.lib().rmclhip_rcc_segment_async(self._h, _ptr(T), rptr, on_dev, C.byref(params), C.byref(v)))
+            return None
+        counts = (C.c_uint32 * 2)()
+        _capi.check(_capi.lib().rmclhip_rcc_segment(self._h, _ptr(T), rptr, on_dev, C.byref(params), C.byref(v), counts))
+        counts = (int(counts[0]), int(counts[1]))
+        if into is not None:
+            return counts
+        out = {"counts": counts}
+        if "labels" in own:
+            out["labels"] = own["labels"].download()[:n]
+        for a, k in (("outlier_scan", counts[0]), ("outlier_map", counts[1])):
+            if a in own:
+                out[a] = own[a].download().reshape(-1, 3)[:k].copy()
+        for d in own.values():
+            d.free()
         return out
 
     # -- dataset ------------------------------------------------------------------------------
