@@ -910,11 +910,68 @@ class RCCHip_ : public CorrespondencesHIP, public ModelSetter<ModelT>, protected
     CorrespondencesHIP::setTsb(Tsb);
     SimulatorHip<ModelT>::setTsb(Tsb);
   }
+  // RCCHipSpherical only.  A sensor_msgs/PointCloud2 as received, organised or not, becomes this operator's dataset: its points are binned
+  // into the spherical model on the device (Pc2ToScanNode::convert, pc2_to_scan.cpp:105-213), the image is unpacked as
+  // MICPSphericalSensorCPU::unpackMessage does (rmclhip_rcc_set_input_pointcloud2_scan).  The model is not touched.  T_sensor_cloud:
+  // nullptr = same frame; flags: RMCLHIP_PC2SCAN_* (0 = the reference's rule); returns the range image in device memory (borrowed: valid
+  // until the next call) -- what SimulatorHip::segment / a segmentation node accept as device ranges.
+  template <typename M = ModelT>
+  DeviceView<const float> setInputPointCloud2(const uint8_t* data, size_t nbytes, const rmclhip_pointcloud2_layout& layout,
+                                              const Transform* T_sensor_cloud = nullptr, uint32_t flags = 0u, bool src_is_device = false,
+                                              rmclhip_pc2scan_stats* stats = nullptr) {
+    static_assert(std::is_same<M, SphericalModel>::value && std::is_same<M, ModelT>::value,
+                  "setInputPointCloud2 bins a cloud into a SPHERICAL model: RCCHipSpherical only");
+    if (!this->m_model) throw std::runtime_error("setInputPointCloud2: no sensor model (setModel first)");
+    const float* ranges = nullptr;
+    check(rmclhip_rcc_set_input_pointcloud2_scan(h_, data, nbytes, &layout, src_is_device ? 1 : 0, T_sensor_cloud, flags, &ranges, stats));
+    bound_points_ = bound_mask_ = ~0ull;   // the library's own dataset is current until the `dataset` member is written again
+    outdated = true;
+    DeviceView<const float> view;
+    view.ptr = ranges;
+    view.n = this->m_model->size();
+    return view;
+  }
 };
 using RCCHipSpherical = RCCHip_<SphericalModel>;
 using RCCHipO1Dn = RCCHip_<O1DnModel>;
 using RCCHipPinhole = RCCHip_<PinholeModel>;
 using RCCHipOnDn = RCCHip_<OnDnModel>;
+
+// Pc2ToScanNode (rmcl_ros/src/nodes/conversion/pc2_to_scan.cpp) without ROS: the node's members (the scan's model, the sensor frame's
+// transform in place of the tf lookup of :111-133) and its convert() on the message's bytes.  The scan stays in device memory owned by
+// this object, until the next convert().
+class Pc2ToScanHip {
+ public:
+  uint32_t flags_ = 0u;   // RMCLHIP_PC2SCAN_*: 0 = the reference's rule statement for statement
+
+  explicit Pc2ToScanHip(ContextPtr ctx) : ctx_(std::move(ctx)), ranges_(ctx_) {
+    if (!ctx_) throw std::runtime_error("NO CONTEXT");
+  }
+  void setModel(const SphericalModel& model) { model_ = model; }
+  const SphericalModel& model() const { return model_; }
+  // T_sensor_cloud; the node starts from the identity, which applies nothing
+  void setSensorTransform(const Transform& T_sensor_cloud) { T_ = T_sensor_cloud; has_T_ = true; }
+  void clearSensorTransform() { has_T_ = false; }
+  // `data`: host memory (a message) or device memory
+  DeviceView<const float> convert(const uint8_t* data, size_t nbytes, const rmclhip_pointcloud2_layout& layout, bool src_is_device = false) {
+    ranges_.resize(model_.size());
+    check(rmclhip_pointcloud2_to_scan(ctx_->handle(), data, nbytes, &layout, src_is_device ? 1 : 0, has_T_ ? &T_ : nullptr, model_.c_model(),
+                                      flags_, ranges_.raw(), 1, &stats_));
+    DeviceView<const float> view;
+    view.ptr = ranges_.raw();
+    view.n = model_.size();
+    return view;
+  }
+  const rmclhip_pc2scan_stats& stats() const { return stats_; }   // of the last convert()
+
+ private:
+  ContextPtr ctx_;
+  Memory<float, VRAM_HIP> ranges_;
+  SphericalModel model_{};
+  Transform T_ = identity();
+  bool has_T_ = false;
+  rmclhip_pc2scan_stats stats_{};
+};
 
 // rmcl::CPCEmbree (rmcl/include/rmcl/registration/CPCEmbree.hpp): closest-point correspondences
 class CPCHip : public CorrespondencesHIP {

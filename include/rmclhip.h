@@ -297,6 +297,52 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2(rmclhip_rcc* rcc, const uint8_t
                                                  const rmclhip_filter1d* filter_width, rmclhip_interval range,
                                                  int src_is_device, uint32_t* out_width, uint32_t* out_height,
                                                  uint32_t* n_valid);
+/* Wire-format input of the SPHERICAL model: the bytes of a (usually unorganised) sensor_msgs/PointCloud2 are binned into the
+ * (phi, theta) grid of a spherical model on the device -- Pc2ToScanNode::convert (rmcl_ros/src/nodes/conversion/pc2_to_scan.cpp:105-213),
+ * empty cells as scan_operations.cpp:25-39.  Per point i in buffer order (i = row * width + col at row * row_step + col * point_step):
+ *   1. x, y, z: FLOAT32, or FLOAT64 cast to float; skipped unless all three are finite (NaN and +-inf)
+ *   2. ps = T_sensor_cloud * (x, y, z) (NULL: same frame)
+ *   3. range_est = sqrtf((x*x + y*y) + z*z) of ps; theta_est = (float)atan2((double)y, (double)x);
+ *      phi_est = (float)atan2((double)z, (double)range_est)  -- the reference's rule; it is atan(sin(elevation)), see TRUE_ELEVATION
+ *   4. id = (int)(((est - min) / inc) + 0.5): the quotient in float, + 0.5 in double, truncated toward zero, compared in double with
+ *      [0, size) (NaN rejects).  inc == 0 is accepted for size == 1 only: every point then has id 0 on that axis
+ *   5. a point inside the image with range_est inside [range.min, range.max] is a candidate of cell phi_id * W + theta_id; the
+ *      candidate with the LARGEST i wins (the reference's sequential overwrite)
+ *   6. ranges[cell] = the winner's range_est, or (float)((double)range.max + 1.0) for a cell nobody hit
+ * The default repeats the reference statement for statement; each flag corrects one of its findings:
+ *   TRUE_ELEVATION  phi_est = atan2(z, sqrt(x*x + y*y)): the inverse of the model's dir(vid, hid)
+ *   FLOOR           id = floor(q + 0.5): truncation also takes q + 0.5 in (-1, 0) into cell 0
+ *   WRAP_THETA      theta ids outside [0, W) are moved by one period when 2 pi / theta.inc is a whole number (within 1e-3): for
+ *                   theta.min = -pi the column hid = 0 computes theta_est = +pi and is lost otherwise
+ *   NEAREST         a cell keeps its SMALLEST range (ties: the smaller i) instead of its last point: independent of the buffer order
+ * The winner is resolved with integer atomics on (i, range) keys: the same bits on every run.  stats (nullable): points in the
+ * layout, with finite x / y / z, inside the image, inside the image and the range interval, and the number of cells that hold a point.
+ * Unknown flag bits, a null layout / model / data with points, data shorter than its layout, a non-finite T, a zero increment with
+ * size != 1, more than 2^31 points or cells: RMCLHIP_ERR_INVALID; a datatype other than 7 / 8: RMCLHIP_ERR_UNSUPPORTED.  An empty
+ * cloud is no error: an all-empty image, zero counts. */
+#define RMCLHIP_PC2SCAN_TRUE_ELEVATION 1u
+#define RMCLHIP_PC2SCAN_FLOOR          2u
+#define RMCLHIP_PC2SCAN_WRAP_THETA     4u
+#define RMCLHIP_PC2SCAN_NEAREST        8u
+typedef struct { uint32_t n_points, n_finite, n_in_image, n_in_range, n_cells_filled; } rmclhip_pc2scan_stats;
+/* free function on a stream of the context's own (calls on one context serialise); data and ranges_out (theta.size * phi.size floats)
+ * each in host or in device memory; synchronous */
+rmclhip_status rmclhip_pointcloud2_to_scan(rmclhip_ctx* ctx, const uint8_t* data, size_t nbytes,
+                                           const rmclhip_pointcloud2_layout* layout, int src_is_device,
+                                           const rmclhip_transform* T_sensor_cloud, const rmclhip_spherical_model* model,
+                                           uint32_t flags, float* ranges_out, int ranges_is_device, rmclhip_pc2scan_stats* stats);
+/* On an operator with a spherical model (RMCLHIP_ERR_INVALID otherwise): the same image becomes the dataset, as
+ * rmclhip_rcc_set_dataset_from_ranges makes it (MICPSphericalSensorCPU::unpackMessage, :181-233: points = dir(vid, hid) * range,
+ * mask = range inside the model's interval) -- in the same pass, the image never leaves the device.  The MODEL is not touched:
+ * W, H, the tile planes and a captured graph stay valid from scan to scan (unlike rmclhip_rcc_set_input_pointcloud2, which
+ * rebuilds an O1Dn model per cloud).  Host bytes are staged in a grow-only buffer; image and per-cell scratch are grow-only members:
+ * a repeated call allocates nothing.  ranges_dev_out (nullable): the image in device memory, borrowed, valid until the next
+ * rmclhip_rcc_set_input_pointcloud2_scan call -- what rmclhip_rcc_segment accepts as device ranges.  stats->n_cells_filled is the
+ * dataset's valid count (while range.max + 1 is representable above range.max). */
+rmclhip_status rmclhip_rcc_set_input_pointcloud2_scan(rmclhip_rcc* rcc, const uint8_t* data, size_t nbytes,
+                                                      const rmclhip_pointcloud2_layout* layout, int src_is_device,
+                                                      const rmclhip_transform* T_sensor_cloud, uint32_t flags,
+                                                      const float** ranges_dev_out, rmclhip_pc2scan_stats* stats);
 /* rmcl::CPCEmbree::find (rmcl/src/rmcl/registration/CPCEmbree.cpp:18-44), closest-point correspondences (`type: CP`):
  * for every dataset point Pm = Tsm * d_i the nearest surface point of the map; model buffers (sized like the
  * dataset) receive hits = (distance <= params.max_dist), points = Tms * p_closest, normals = Tms.R * n_face

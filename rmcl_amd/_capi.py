@@ -109,6 +109,16 @@ class SegmentationViews(C.Structure):
                 ("counts_dev", C.c_void_p)]
 
 
+class Pc2ScanStats(C.Structure):
+    """rmclhip_pc2scan_stats"""
+    _fields_ = [("n_points", C.c_uint32), ("n_finite", C.c_uint32), ("n_in_image", C.c_uint32), ("n_in_range", C.c_uint32),
+                ("n_cells_filled", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PC2SCAN_TRUE_ELEVATION, PC2SCAN_FLOOR, PC2SCAN_WRAP_THETA, PC2SCAN_NEAREST = 1, 2, 4, 8
 SEG_PINT_WITH_ORIGIN = 1
 SEG_NONE, SEG_INLIER, SEG_OUTLIER_SCAN, SEG_OUTLIER_MAP = 0, 1, 2, 3
 
@@ -164,6 +174,10 @@ SIGNATURES = {
     "rmclhip_rcc_set_input_pointcloud2": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), C.POINTER(Filter1D),
                                                   C.POINTER(Filter1D), Interval, _i32, C.POINTER(_u32),
                                                   C.POINTER(_u32), C.POINTER(_u32)]),
+    "rmclhip_pointcloud2_to_scan": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), _i32, _vp, C.POINTER(SphericalModel), _u32,
+                                            _vp, _i32, C.POINTER(Pc2ScanStats)]),
+    "rmclhip_rcc_set_input_pointcloud2_scan": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), _i32, _vp, _u32, _pp,
+                                                       C.POINTER(Pc2ScanStats)]),
     "rmclhip_rcc_compute_cross_statistics": (_i32, [_vp, _vp, _dbl, _vp]),
     "rmclhip_rcc_download": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rmclhip_rcc_device_views": (_i32, [_vp, _pp, _pp, _pp, _pp, _pp, C.POINTER(_u32)]),

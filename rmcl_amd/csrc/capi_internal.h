@@ -4,6 +4,7 @@
 //   capi_rcc.cpp       the correspondence operator: models, datasets, find, reduction, the MICP corrections (one and N sensors), pose batches
 //   capi_rcc_tune.cpp  tuning knobs, autotune, measurement aids (include/rmclhip_bench.h) and diagnostics (include/rmclhip_lab.h) of that operator
 //   capi_segment.cpp   map segmentation of that operator: trace into its own scratch, labels, compacted outlier clouds (kernels: segment.hip)
+//   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
@@ -121,6 +122,21 @@ inline hipError_t upload_on(hipStream_t s, void* dst, const void* src, size_t by
   return e;
 }
 
+// PointCloud2 -> scan (capi_pc2scan.cpp): grow-only scratch of one owner (a context's free function, an operator): the per-cell keys
+// of the winner resolution, the range image, the per-workgroup counts and the host-mapped totals (created by the first call)
+struct Pc2ScanScratch {
+  DevBuf<unsigned long long> keys;
+  DevBuf<float> ranges;
+  DevBuf<uint32_t> block_counts;        // 3 per workgroup of points, then 1 per workgroup of cells
+  uint32_t* h_counters = nullptr;       // pinned, host-mapped: {finite, in image, in range, cells filled}
+  uint32_t* h_counters_dev = nullptr;
+  void release() {
+    keys.release(); ranges.release(); block_counts.release();
+    if (h_counters) (void)hipHostFree(h_counters);
+    h_counters = nullptr; h_counters_dev = nullptr;
+  }
+};
+
 struct rmclhip_ctx {
   int device = 0;
   hipDeviceProp_t props;
@@ -139,6 +155,11 @@ struct rmclhip_ctx {
   unsigned long long* p2l_h_done = nullptr;
   unsigned long long* p2l_h_done_dev = nullptr;
   uint32_t p2l_seq = 0;
+  // rmclhip_pointcloud2_to_scan (the free function): its own stream and scratch, created by the first call under its mutex
+  std::mutex pc2_mtx;
+  hipStream_t pc2_stream = nullptr;
+  Pc2ScanScratch pc2;
+  DevBuf<uint8_t> pc2_raw;              // staged host bytes
   ~rmclhip_ctx();                       // capi_map.cpp
 };
 
@@ -295,6 +316,10 @@ struct rmclhip_rcc {
   DevBuf<uint32_t> d_seg_block_counts;
   uint32_t* h_seg_counts = nullptr;
   uint32_t* h_seg_counts_dev = nullptr;
+  // rmclhip_rcc_set_input_pointcloud2_scan (capi_pc2scan.cpp): the model as set_model_spherical received it (the trig tables alone do
+  // not give the bins back), the range image the dataset was made of and the keys, grow-only; host bytes are staged in d_raw
+  rmclhip_spherical_model sph_model{{0.f, 0.f, 0u}, {0.f, 0.f, 0u}, {0.f, 0.f}};
+  Pc2ScanScratch pc2;
   bool capturing = false;          // inside hipStreamBeginCapture: no synchronisation allowed
   int variant = 15;       // traversal kind: 0 wave-packet, 1 one lane per ray (while-while), 2 four lanes per ray
                           // (quad-cooperative), 15 automatic: quad while the launch is bound by the slowest ray's

@@ -44,6 +44,12 @@ void rmclhip_ctx_destroy(rmclhip_ctx* ctx) { ctx_release(ctx); }
 
 // the scratch of rmclhip_statistics_p2l (capi_rcc.cpp) belongs to the context and goes with its last holder
 rmclhip_ctx::~rmclhip_ctx() {
+  if (pc2_stream != nullptr) {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(pc2_stream);
+    pc2.release(); pc2_raw.release();
+    (void)hipStreamDestroy(pc2_stream);
+  }
   if (p2l_stream == nullptr) return;
   (void)hipSetDevice(device);
   (void)hipStreamSynchronize(p2l_stream);

@@ -75,6 +75,7 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
   r->d_multi_blob.release();
   r->d_seg_ranges.release(); r->d_seg_normals.release(); r->d_seg_real.release(); r->d_seg_labels.release(); r->d_seg_block_counts.release();
   if (r->h_seg_counts) DBG_STEP(hipHostFree(r->h_seg_counts));
+  r->pc2.release();
   if (r->h_multi_state) DBG_STEP(hipHostFree(r->h_multi_state));
   if (r->h_multi_status) DBG_STEP(hipHostFree(r->h_multi_status));
   if (r->h_call) DBG_STEP(hipHostFree(r->h_call));
@@ -102,6 +103,7 @@ rmclhip_status rmclhip_rcc_set_model_spherical(rmclhip_rcc* r, const rmclhip_sph
   HIPCHK(hipStreamSynchronize(r->stream));
   const uint32_t H = m->phi.size, W = m->theta.size;
   r->kind = kModelSpherical;
+  r->sph_model = *m;
   r->graph_dirty = true;
   r->W = W; r->H = H;
   r->range = m->range;

@@ -362,6 +362,32 @@ struct SegmentParams {
 // two launches: k_segment_classify (labels + per-workgroup counts), k_segment_scatter (offsets from the counts below a workgroup's
 // index, points at offset + rank, totals); the kernel boundary between them is what orders the workgroups
 hipError_t launch_segment(const SegmentParams& p, hipStream_t s);
+// PointCloud2 bytes -> range image of a spherical model (pc2scan.hip; Pc2ToScanNode::convert).  The flag values are those of
+// RMCLHIP_PC2SCAN_* (include/rmclhip.h).
+constexpr uint32_t kPc2ScanBlock = 256;
+constexpr uint32_t kPc2ScanTrueElevation = 1u, kPc2ScanFloor = 2u, kPc2ScanWrapTheta = 4u, kPc2ScanNearest = 8u;
+struct Pc2ScanParams {
+  const uint8_t* data;           // device; point i = row * width + col lies at row * row_step + col * point_step
+  uint32_t n_points, width, point_step, row_step, off_x, off_y, off_z, is_f64;
+  uint32_t has_T;
+  xform T;                       // T_sensor_cloud
+  float phi_min, phi_inc, theta_min, theta_inc;
+  uint32_t W, H;                 // theta.size, phi.size
+  double theta_period;           // 2 pi / theta.inc when PC2SCAN_WRAP_THETA is set and that is a whole number, else 0
+  float rmin, rmax, range_empty; // range_empty = (float)((double)range.max + 1.0)
+  uint32_t flags;
+  unsigned long long* keys;      // W * H, set to "nobody" by the launcher
+  uint32_t* bin_counts;          // [pc2scan_blocks(n_points)][3] = {finite, in image, in range (candidates)} of a workgroup's points
+  uint32_t* cell_counts;         // [pc2scan_blocks(W * H)] = filled cells among a workgroup's cells
+  float* ranges;                 // W * H out
+  const float* model_tab;        // the operator form: the spherical model's trig tables (FindParams::model_tab) ...
+  float* ds_points;              // ... its dataset points (null: the free function) ...
+  uint8_t* ds_mask;              // ... and mask
+};
+inline uint32_t pc2scan_blocks(size_t n) { return static_cast<uint32_t>((n + kPc2ScanBlock - 1u) / kPc2ScanBlock); }
+// the keys' memset + k_pc2scan_bin + k_pc2scan_resolve + k_pc2scan_publish ({finite, in image, in range, cells filled} to the
+// host-mapped counters_host), all on s
+hipError_t launch_pc2scan(const Pc2ScanParams& p, uint32_t* counters_host, hipStream_t s);
 hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s);
 hipError_t launch_pf_extract_weights(const void* attrs, uint32_t n, float* weights, hipStream_t s);
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,

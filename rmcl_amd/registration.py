@@ -100,6 +100,26 @@ class DeviceArray:
             pass
 
 
+class DeviceView(DeviceArray):
+    """device memory BORROWED from a handle (rmagine::MemoryView<T, VRAM_HIP> analogue): same reading interface as DeviceArray, never
+    freed from here; valid as long as the call that returned it says"""
+
+    def __init__(self, ctx, dtype, count, ptr):
+        self.ctx, self.dtype, self.count, self.ptr = ctx, np.dtype(dtype), int(count), int(ptr or 0)
+
+    def free(self):
+        self.ptr = 0
+
+
+def _cloud_bytes(data, device, nbytes):
+    """(pointer, byte count, what keeps the pointer alive) of PointCloud2 data: bytes / uint8 array, or a device pointer + nbytes"""
+    if device:
+        return _as_ptr(data), int(nbytes), data
+    buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8)) if isinstance(data, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    return _ptr(buf), buf.size, buf
+
+
 class HipMap:
     """Immutable triangle mesh + BVH on the device (rm::EmbreeMap / rm::OptixMap analogue)."""
 
@@ -749,6 +769,34 @@ class RCCHipSpherical(CorrespondencesHIP):
     def setModel(self, sensor_model):
         _capi.check(_capi.lib().rmclhip_rcc_set_model_spherical(self._h, C.byref(sensor_model)))
         self._model_shape = (int(sensor_model.phi.size), int(sensor_model.theta.size))
+
+    def setInputPointCloud2(self, data, width, height, point_step, row_step, offset_x, offset_y, offset_z, datatype=7, T=None,
+                            flags=0, device=False, nbytes=None):
+        """A sensor_msgs/PointCloud2 as received, organised or not (bytes / uint8 array, or a device pointer with device=True and
+        nbytes), binned into this operator's spherical model on the device: Pc2ToScanNode::convert (pc2_to_scan.cpp:105-213), then the
+        dataset MICPSphericalSensorCPU::unpackMessage makes of the image (rmclhip_rcc_set_input_pointcloud2_scan).  T: T_sensor_cloud
+        (None: same frame).  flags: an OR of _capi.PC2SCAN_* (0 = the reference's rule statement for statement).  The model is not
+        touched.  Returns the stats dict {n_points, n_finite, n_in_image, n_in_range, n_cells_filled}; rangesView() is the image."""
+        L = _capi.PointCloud2Layout(int(width), int(height), int(point_step), int(row_step), int(offset_x), int(offset_y),
+                                    int(offset_z), int(datatype))
+        ptr, nb, _keep = _cloud_bytes(data, device, nbytes)
+        Tarr = None if T is None else np.ascontiguousarray(T, dtype=TRANSFORM).reshape(1)   # (kept alive over the call)
+        Tp = _ptr(Tarr)
+        st, rp = _capi.Pc2ScanStats(), C.c_void_p()
+        self._ranges_view = None
+        _capi.check(_capi.lib().rmclhip_rcc_set_input_pointcloud2_scan(self._h, ptr, nb, C.byref(L), int(bool(device)), Tp, int(flags),
+                                                                       C.byref(rp), C.byref(st)))
+        H, W = self._model_shape
+        self._ranges_view = DeviceView(self.ctx, np.float32, H * W, rp.value)
+        self.outdated = True
+        return st.as_dict()
+
+    def rangesView(self):
+        """the range image of the last setInputPointCloud2 in device memory (H * W float32, borrowed: valid until the next such
+        call): what segment() accepts as device ranges; .download() brings it to the host"""
+        if getattr(self, "_ranges_view", None) is None:
+            raise RuntimeError("rangesView: no setInputPointCloud2 before")
+        return self._ranges_view
 
 
 class RCCHipO1Dn(CorrespondencesHIP):

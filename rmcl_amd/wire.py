@@ -3,8 +3,12 @@ consume, restated as plain field mappings so a host without ROS bindings (or a b
 
 Reference: rmcl_ros/src/util/conversions.cpp:22-120 (ScanInfo / CameraInfo / DepthInfo / O1DnInfo / OnDnInfo ->
 rmagine models), :869-1002 (PointCloud2 -> O1Dn), PCDSensorUpdaterEmbree.cpp:290-327 (beam sampling from a
-PointCloud2).  The device-side PointCloud2 path is RCCHipO1Dn.setInputPointCloud2.
+PointCloud2), rmcl_ros/src/nodes/conversion/pc2_to_scan.cpp:105-213 (PointCloud2 -> spherical scan).  The device-side PointCloud2
+paths are RCCHipO1Dn.setInputPointCloud2 (cloud -> O1Dn model + dataset), RCCHipSpherical.setInputPointCloud2 (cloud -> the dataset
+of a spherical model) and pointcloud2_to_scan below.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import _capi
@@ -64,3 +68,25 @@ def sample_beams_pointcloud2(data, n_points, point_step, offset_x, offset_y, off
     `random_point_id * point_step` addressing), through the C ABI sampler (rmclhip_pf_sample_beams_pointcloud2)."""
     from .pf import sample_beams_pointcloud2 as _sample
     return _sample(data, n_points, 1, point_step, point_step * n_points, offset_x, offset_y, offset_z, samples, seed, datatype)
+
+
+def pointcloud2_to_scan(ctx, data, width, height, point_step, row_step, offset_x, offset_y, offset_z, model, datatype=FLOAT32,
+                        T=None, flags=0, device=False, nbytes=None, into=None):
+    """Pc2ToScanNode::convert (pc2_to_scan.cpp:105-213) on the device, without an operator (rmclhip_pointcloud2_to_scan): the cloud's
+    bytes (or a device pointer with device=True and nbytes) binned into `model` (a SphericalModel).  T: T_sensor_cloud or None;
+    flags: an OR of _capi.PC2SCAN_*.  into=None: returns (ranges as a (phi.size, theta.size) float32 array, stats dict);
+    into=device memory of phi.size * theta.size floats: fills it and returns the stats dict."""
+    from .registration import _as_ptr, _cloud_bytes
+    from .types import TRANSFORM, _ptr
+    L = _capi.PointCloud2Layout(int(width), int(height), int(point_step), int(row_step), int(offset_x), int(offset_y),
+                                int(offset_z), int(datatype))
+    ptr, nb, _keep = _cloud_bytes(data, device, nbytes)
+    Tarr = None if T is None else np.ascontiguousarray(T, dtype=TRANSFORM).reshape(1)   # (kept alive over the call)
+    Tp = _ptr(Tarr)
+    st = _capi.Pc2ScanStats()
+    H, W = int(model.phi.size), int(model.theta.size)
+    out = np.zeros((H, W), np.float32) if into is None else None
+    optr = _ptr(out) if into is None else _as_ptr(into)
+    _capi.check(_capi.lib().rmclhip_pointcloud2_to_scan(ctx.handle, ptr, nb, C.byref(L), int(bool(device)), Tp, C.byref(model),
+                                                        int(flags), optr, 0 if into is None else 1, C.byref(st)))
+    return (out, st.as_dict()) if into is None else st.as_dict()
