@@ -1326,7 +1326,9 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
   const bool active = ray_tfar >= 0.0f;
   // diagnostics (clocked lab instantiation only; stamps == nullptr folds all of it away): shader clock at the phase boundaries, after
   // everything in flight has arrived -- 0 entry, 1 frontier + planes here, 2 culled, 3 lists written, 4 + 2 L nodes of level L here,
-  // 5 + 2 L level L compacted (L < 3), 10 final list lane-resident, 11 every ray has seen every entry
+  // 5 + 2 L level L compacted (L < 3), 10 final list lane-resident, 11 every ray has seen every entry; 12 levels descended; 13 / 14 (flags, not
+  // clocks, with dbg_levels): the wave started at the root after all -- a ray entered more final leaves than the leaf cap / a lane's stack
+  // was left without room
 #define RMCL_STAMP(i) { if (stamps != nullptr) { uint64_t t_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); stamps[i] = static_cast<uint32_t>(t_); } }
   RMCL_STAMP(0)
   if constexpr (kCoop) { seed->t = ray_tfar; seed->rec = kNone; }
@@ -1543,7 +1545,10 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
       }
       // A ray that enters many of the boxes (a grazing ray along a wall) would test every one of their leaves here, where its own
       // ordered traversal stops at the first few: such a wave starts at the root like a wave whose stacks the sorted form overfills
-      if (__any(static_cast<uint32_t>(__popc(m_lo) + __popc(m_hi)) > mask_leaf_cap)) return root;
+      if (__any(static_cast<uint32_t>(__popc(m_lo) + __popc(m_hi)) > mask_leaf_cap)) {
+        if (dbg_levels) { if (stamps != nullptr) stamps[13] = 1u; }   // diagnostics: this wave took the leaf-cap fallback
+        return root;
+      }
       float best_t = ray_tfar;
       uint32_t best_rec = kNone;
       const uint32_t* Fw = reinterpret_cast<const uint32_t*>(Fl);
@@ -1582,7 +1587,10 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
     if (sp < static_cast<uint32_t>(kRows)) lds_col[sp * lds_stride] = second_ref;
     ++sp;
   }
-  if (__any(sp > min(static_cast<uint32_t>(kRows - 4), static_cast<uint32_t>(kRow0) + max_preload))) return root;
+  if (__any(sp > min(static_cast<uint32_t>(kRows - 4), static_cast<uint32_t>(kRow0) + max_preload))) {
+    if (dbg_levels) { if (stamps != nullptr) stamps[14] = 1u; }   // diagnostics: ... the stack-room fallback
+    return root;
+  }
   TraceStart st;
   st.cur = first_ref;
   st.sp = sp;

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import descent_cases as dc
 from conftest import find_kinds, assert_close_rel, golden_path
 
 pytestmark = pytest.mark.gpu
@@ -108,7 +109,7 @@ def test_c2_sphere100k_full_size(ra, orc, ctx, meshes, variant):
     ref = m.simulate_spherical(model, T.identity(), Tbm, bvh=True, nthreads=8)
     _compare(gpu, ref, "C2")
     assert gpu["hits"].all()
-    if variant in (0, 2, 15, 23, 24):     # (the product's kinds; the experiments of the lab library are pinned by _compare + the digest)
+    if variant in (0, 2, 15, 23, 24, 32):     # (the product's kinds; the experiments of the lab library are pinned by _compare + the digest)
         _brute_force_sample(orc, m, model, Tbm, gpu, 2048, seed=variant)
     with open(golden_path("g7_digests.json")) as fh:
         dig = json.load(fh)
@@ -124,7 +125,7 @@ def test_c2_sphere100k_full_size(ra, orc, ctx, meshes, variant):
     assert np.all(r <= 10.0 + 1e-4) and np.all(r >= 10.0 - 0.02)
 
 
-@pytest.mark.parametrize("kinds", [(15, 23, 2, 24), pytest.param((19, 22), marks=pytest.mark.lab)], ids=["product", "round-2 kinds"])
+@pytest.mark.parametrize("kinds", [(15, 23, 2, 24, 32), pytest.param((19, 22), marks=pytest.mark.lab)], ids=["product", "round-2 kinds"])
 def test_ragged_and_tiny_models(ra, orc, ctx, meshes, kinds):
     """edge cases: 1x1, 1x360 (2-D scanner), 7x33 (ragged tiles), empty model (find is a no-op,
     RCCOptix.cpp:30-34)."""
@@ -165,18 +166,21 @@ def test_misses_and_range_limit(ra, orc, ctx, meshes):
     f32 = np.float32
     model = T.spherical_model(f32(-0.6), f32(1.8 / 47), 48, f32(-math.pi), f32(2 * math.pi / 200), 200, f32(0.1), f32(6.0))
     Tbm = T.transform_from_rpy((1.0, 2.0, 1.5), (0.0, 0.1, -0.3))
-    rcc = ra.RCCHipSpherical(hm)
-    rcc.setTsb(T.identity())
-    rcc.setModel(model)
-    rcc.find(Tbm)
-    gpu = rcc.modelView()
     ref = m.simulate_spherical(model, T.identity(), Tbm, bvh=False)
-    _compare(gpu, ref, "misses")
-    miss = gpu["hits"] == 0
-    assert miss.any() and (~miss).any()
-    assert np.all(gpu["ranges"][miss] == f32(7.0))
-    assert np.all(gpu["face_ids"][miss] == 0xFFFFFFFF)
-    assert np.isnan(gpu["points"][miss]).all() and np.isnan(gpu["normals"][miss]).all()
+    for kind in (15, 32):
+        rcc = ra.RCCHipSpherical(hm)
+        rcc.set_traversal(kind)
+        rcc.setTsb(T.identity())
+        rcc.setModel(model)
+        rcc.find(Tbm)
+        gpu = rcc.modelView()
+        _compare(gpu, ref, "misses kind %d" % kind)
+        miss = gpu["hits"] == 0
+        assert miss.any() and (~miss).any()
+        assert np.all(gpu["ranges"][miss] == f32(7.0))
+        assert np.all(gpu["face_ids"][miss] == 0xFFFFFFFF)
+        assert np.isnan(gpu["points"][miss]).all() and np.isnan(gpu["normals"][miss]).all()
+        rcc.close()
 
 
 @pytest.mark.parametrize("variant", find_kinds(0, 2, 23, 24, 32))
@@ -224,9 +228,9 @@ def test_grow_only_buffers_and_refind(ra, orc, ctx, meshes):
         _compare(rcc.modelView(), m.simulate_spherical(model, T.identity(), Tbm, bvh=False), "regrow")
 
 
-@pytest.mark.parametrize("kind", [23, 24])
+@pytest.mark.parametrize("kind", [23, 24, 32])
 def test_frontier_plane_table_follows_model_and_tiling(ra, orc, ctx, meshes, kind):
-    """The frontier start (kinds 23 / 24) reads the pyramid of every tile from a table that belongs to (model, tiling) and is
+    """The frontier start (kinds 23 / 24, and kind 32's cooperative descent below it) reads the pyramid of every tile from a table that belongs to (model, tiling) and is
     rebuilt by the model setters and by set_variant's tile shape.  One operator walks through spherical models of three sizes,
     an O1Dn model with NaN directions, a pinhole model and three tile shapes; every scan must equal the scan of the packet
     traversal (kind 0: no table, no frontier) bit for bit -- a stale table would cull boxes the new tiles' rays enter."""
@@ -326,13 +330,17 @@ def test_far_from_origin_mesh(ra, orc, ctx):
     v = (v + off).astype(np.float32)
     m = orc.Mesh(v, f)
     hm = ra.import_hip_map(ctx, v, f)
-    rcc = ra.RCCHipSpherical(hm)
-    rcc.setTsb(T.identity())
     model = syn.model_c1()
-    rcc.setModel(model)
     Tbm = T.transform_from_rpy(tuple(off + np.array([0.4, -0.3, 0.2], dtype=np.float32)), (0.1, 0.2, 0.3))
-    rcc.find(Tbm)
-    _compare(rcc.modelView(), m.simulate_spherical(model, T.identity(), Tbm, bvh=False), "far mesh")
+    ref = m.simulate_spherical(model, T.identity(), Tbm, bvh=False)
+    for kind in (15, 32):
+        rcc = ra.RCCHipSpherical(hm)
+        rcc.set_traversal(kind)
+        rcc.setTsb(T.identity())
+        rcc.setModel(model)
+        rcc.find(Tbm)
+        _compare(rcc.modelView(), ref, "far mesh kind %d" % kind)
+        rcc.close()
 
 
 def test_c5_mesh_one_million_triangles(ra, orc, ctx):
@@ -348,7 +356,7 @@ def test_c5_mesh_one_million_triangles(ra, orc, ctx):
     model = syn.model_c2()
     Tbm = syn.pose_c2_truth()
     ref = m.simulate_spherical(model, T.identity(), Tbm, bvh=True, nthreads=8)
-    for variant in (0, 2, 23, 24):
+    for variant in (0, 2, 23, 24, 32):
         rcc = ra.RCCHipSpherical(hm)
         rcc.set_traversal(variant)
         rcc.setTsb(T.identity())
@@ -688,7 +696,7 @@ def test_deep_trees_do_not_overflow_the_frontier_start(ra, orc, ctx, shape):
     model.phi.inc = (1.45 + 0.4) / 63.0
     model.range.max = 1.0e12
     poses = [T.transform_from_rpy((0.001, -0.002, -1.0), (0.0, 0.0, 0.3)), T.transform_from_rpy((0.8, 0.3, -2.5), (0.05, -0.1, 1.0))]
-    for kind in (23, 24, 2, 15):
+    for kind in (23, 24, 2, 15, 32):
         rcc = ra.RCCHipSpherical(hm)
         rcc.set_traversal(kind)
         rcc.setTsb(T.identity())
@@ -719,7 +727,10 @@ def _hit_radius(gpu, Tbm):
     return np.linalg.norm(gpu["points"][hit].astype(np.float64) @ R.T + t, axis=1)
 
 
-@pytest.mark.parametrize("variant", [15, 24, 2])
+_FOUR_WIDE = 1 << 8    # (a flag of these tests, not of the library: kind 32 with the four-wide descent, rmclhip_rcc_set_descent bit 31)
+
+
+@pytest.mark.parametrize("variant", [15, 24, 2, 32, pytest.param(32 | _FOUR_WIDE, id="32-four-wide")])
 def test_c2_sphere1m_full_size(ra, orc, ctx, meshes, variant):
     """C2 scan on the 1 M-face sphere: the oracle's BVH4 walk on ALL 131 072 rays (hits, face ids AND ranges bit-equal), 2 048 of the
     scan's own rays against every triangle (no BVH), and every hit point on the radius-10 sphere."""
@@ -729,7 +740,9 @@ def test_c2_sphere1m_full_size(ra, orc, ctx, meshes, variant):
     hm = ra.import_hip_map(ctx, v, f)
     model = syn.model_c2()
     rcc = ra.RCCHipSpherical(hm)
-    rcc.set_traversal(variant)
+    rcc.set_traversal(variant & 63)
+    if variant & _FOUR_WIDE:
+        dc.set_knobs(rcc, (64, 24, 24, True))
     rcc.setTsb(T.identity())
     rcc.setModel(model)
     for Tbm in (syn.pose_c2_truth(), T.transform_from_rpy((-2.1, 1.3, -0.7), (0.3, -0.2, 2.5))):
@@ -767,6 +780,13 @@ def test_c2_sphere10m_full_size(ra, orc, ctx, meshes):
     gpu24 = rcc.modelView()
     for k in ("hits", "face_ids", "ranges"):
         assert np.array_equal(gpu[k], gpu24[k]), k
+    rcc.set_traversal(32)       # the cooperative descent on the 16-wide twins, then on the four-wide nodes (what maps beyond kMaxNodes16 run)
+    for knobs in ((64, 24, 24, False), (64, 24, 24, True)):
+        dc.set_knobs(rcc, knobs)
+        rcc.find(Tbm)
+        gpu32 = rcc.modelView()
+        for k in ("hits", "face_ids", "ranges"):
+            assert np.array_equal(gpu[k], gpu32[k]), (k, dc.knob_name(knobs))
     miss = np.flatnonzero(gpu["hits"] == 0)
     assert len(miss) < 1e-3 * gpu["hits"].size
     r = _hit_radius(gpu, Tbm)
@@ -808,7 +828,7 @@ def test_meshes_beyond_the_old_stack_limit_upload_and_trace(ra, orc, ctx, meshes
         model = T.spherical_model(f32(-0.4), f32(1.85 / (H - 1)), H, f32(-math.pi), f32(2 * math.pi / W), W, f32(0.0), f32(1e12))
         poses = [T.transform_from_rpy((0.001, -0.002, -1.0), (0.0, 0.0, 0.3)), T.transform_from_rpy((0.8, 0.3, -2.5), (0.05, -0.1, 1.0))]
     n_hits = 0
-    for kind in (15, 23, 24, 2, 0):
+    for kind in (15, 23, 24, 2, 0, 32):
         rcc = ra.RCCHipSpherical(hm)
         rcc.set_traversal(kind)
         rcc.setTsb(T.identity())
@@ -844,7 +864,7 @@ def test_mixed_scale_map_hall_beams_and_a_fine_object(ra, orc, ctx, meshes):
                               nthreads=16, want=("hits", "ranges", "face_ids"))
         assert np.array_equal(ref["face_ids"][idx], sub["face_ids"])
         assert ref["hits"].all(), "a closed hall: every ray ends on something"
-        for kind in (15, 23, 24, 2, 0):
+        for kind in (15, 23, 24, 2, 0, 32):
             rcc = ra.RCCHipSpherical(hm)
             rcc.set_traversal(kind)
             rcc.setTsb(T.identity())

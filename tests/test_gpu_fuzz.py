@@ -108,7 +108,7 @@ def test_cpc_and_pf_vs_brute_force_on_a_soup(ra, orc, ctx):
 
 
 def test_frontier_start_randomised_against_the_packet_traversal(ra, ctx):
-    """The frontier start (kinds 23 / 24) culls subtrees for a whole wave at once: a box dropped wrongly loses hits silently.  160
+    """The frontier start (kinds 23 / 24; kind 32 descends further below it, wave by wave) culls subtrees for a whole wave at once: a box dropped wrongly loses hits silently.  160
     random scans -- soups, a room, a tiny and a far-away mesh; spherical models from 1 x 7 to 64 x 512 rays with fields of view from
     2 to 360 degrees; O1Dn models with random (partly NaN, partly repeated) directions; sensors inside, outside, far outside and ON
     the map's bounding box; random mounts -- must equal the wave-packet traversal (kind 0: no table, no culling) bit for bit."""
@@ -154,11 +154,11 @@ def test_frontier_start_randomised_against_the_packet_traversal(ra, ctx):
                 op.setModel(model)
             op.setTsb(Tsb)
             out = {}
-            for k in (0, 23, 24):
+            for k in (0, 23, 24, 32):
                 op.set_traversal(k)
                 op.find(pose)
                 out[k] = op.modelView()
-            for k in (23, 24):
+            for k in (23, 24, 32):
                 for key in ("hits", "ranges", "points", "normals", "face_ids"):
                     assert np.array_equal(out[k][key], out[0][key], equal_nan=True), (name, case, k, key)
             n_scans += 1
