@@ -1403,7 +1403,7 @@ int orc_closest_point(const orc_mesh* m, orc_vec3 P, int use_bvh, float* d_out, 
     for (uint32_t f = 0; f < m->nf; ++f) {
       const orc_vec3 q = closest_point_triangle(&m->tris[f], P);
       const float d2 = dist2(P, q);
-      if (d2 < best || (d2 == best && f < best_f)) { best = d2; best_f = f; best_p = q; }
+      if (d2 < best || (d2 == best && f < best_f && d2 < INFINITY)) { best = d2; best_f = f; best_p = q; }
     }
   } else {
     const float p[3] = {P.x, P.y, P.z};
@@ -1417,7 +1417,7 @@ int orc_closest_point(const orc_mesh* m, orc_vec3 P, int use_bvh, float* d_out, 
           const uint32_t f = m->prim[n->left_first + i];
           const orc_vec3 q = closest_point_triangle(&m->tris[f], P);
           const float d2 = dist2(P, q);
-          if (d2 < best || (d2 == best && f < best_f)) { best = d2; best_f = f; best_p = q; }
+          if (d2 < best || (d2 == best && f < best_f && d2 < INFINITY)) { best = d2; best_f = f; best_p = q; }
         }
         continue;
       }

@@ -75,7 +75,10 @@ __global__ void __launch_bounds__(256) k_pf_update(const PfParams p) {
         // round 4: the query starts from the record of the map's near-grid cell the point falls into -- an actual candidate, so the
         // result is unchanged; beam end points are often metres from any surface, where an unseeded query cannot prune
         const uint32_t sr = (live && ok) ? near_grid_record(p.near_grid, p.gn, p.gorg, p.ginv, mean) : kNone;
-        const NearHit seed = near_seed_from_record(p.tris, sr, p.n_tris, mean, live && ok);
+        NearHit seed = near_seed_from_record(p.tris, sr, p.n_tris, mean, live && ok);
+        // a cell's record may be a triangle whose distance overflows to NaN (Ericson's products on triangles a few 1e9 long): as a bound
+        // it would prune every box (`d2 <= NaN`) and come back as the answer -- such a record is no seed (k_cpc_find: its bound check)
+        if (!(seed.d2 <= 3.0e38f)) { seed.d2 = 3.0e38f; seed.face = kInvalidFace; seed.rec = 0; seed.p = mk3(0.f, 0.f, 0.f); }
         nearest_lane_ww<16>(p.nodes, p.tris, mean, live && ok, stacks + threadIdx.x, 256u, nh, &seed);
       } else {
         nearest_lane_ww<16>(p.nodes, p.tris, mean, live && ok, stacks + threadIdx.x, 256u, nh);

@@ -1760,7 +1760,10 @@ __device__ __forceinline__ void nearest_quad(const uint32_t* __restrict__ nodes,
       f3 cq = closest_point_triangle(v0, e1, e2, P);
       const f3 df = sub3(P, cq);
       const float d2 = (df.x * df.x + df.y * df.y) + df.z * df.z;
-      const bool valid = c < cnt;
+      // a NaN distance (Ericson's products overflow to inf - inf on triangles a few 1e9 long) must lose EVERY comparison, as it does
+      // against `d2 < best` with one lane per point: left in, `od < cd` is false on both sides of the exchange, the lane that holds it
+      // keeps it, its partner keeps its own, and the four lanes of a point -- which share the stores -- end with different winners
+      const bool valid = (c < cnt) && (d2 == d2);
       float cd = valid ? d2 : __builtin_inff();
       uint32_t cf = valid ? d.w : kInvalidFace, cr = idx;
 #define RMCL_QMIN(CTRL)                                                                               \

@@ -919,16 +919,19 @@ def test_spatial_splits_leave_every_result_unchanged(ra, orc, ctx, meshes):
     assert np.allclose(a_gpu["likelihood"]["mean"], a_ref["likelihood"]["mean"], rtol=1e-5, atol=1e-12)
     upd.close()
     # closest point: ties go to the smaller face id -- a face's duplicate records tie with themselves
-    cpc = ra.CPCHip(hm)
-    cpc.setTsb(T.identity())
-    cpc.params.max_dist = 2.0
     pts = (np.random.RandomState(3).uniform(-6, 6, (4000, 3)) + np.array([0, 0, 4.0])).astype(np.float32)
-    cpc.set_dataset(pts, None)
-    cpc.find(T.identity())
-    got = cpc.modelView()
     want = m.cpc_find(T.identity(), T.identity(), pts, 2.0, bvh=False)
-    assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["face_ids"], want["face_ids"])
-    cpc.close()
+    for variant in (None, 1):       # the default (four lanes per point) and one lane per point
+        cpc = ra.CPCHip(hm)
+        if variant is not None:
+            cpc.set_variant(variant)
+        cpc.setTsb(T.identity())
+        cpc.params.max_dist = 2.0
+        cpc.set_dataset(pts, None)
+        cpc.find(T.identity())
+        got = cpc.modelView()
+        assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["face_ids"], want["face_ids"]), variant
+        cpc.close()
 
 
 def test_prebound_find_callable_equals_find(ra, orc, ctx, meshes):

@@ -75,6 +75,7 @@ def test_cpc_and_pf_vs_brute_force_on_a_soup(ra, orc, ctx):
     rng = np.random.RandomState(9)
     pts = rng.uniform(-9, 9, (700, 3)).astype(np.float32)
     I = T.identity()
+    by_variant = {}
     for variant in (1, 2):
         cpc = ra.CPCHip(hm)
         cpc.set_variant(variant)
@@ -86,7 +87,9 @@ def test_cpc_and_pf_vs_brute_force_on_a_soup(ra, orc, ctx):
         ref = m.cpc_find(I, I, pts, 0.7, bvh=False)
         assert np.array_equal(g["face_ids"].reshape(-1), ref["face_ids"]) and np.array_equal(g["hits"].reshape(-1), ref["hits"])
         assert_close_rel(g["ranges"].reshape(-1), ref["ranges"], 1e-5, 1e-7, "soup cpc distances")
+        by_variant[variant] = {k: g[k].tobytes() for k in ("hits", "ranges", "points", "normals", "face_ids")}
         cpc.close()
+    assert by_variant[1] == by_variant[2], "one lane and four lanes per point: every output byte for byte"
     poses, attrs = syn.uniform_particles(300, seed=10, bb_min=(-7, -7, -7, -0.3, -0.3, -math.pi), bb_max=(7, 7, 7, 0.3, 0.3, math.pi))
     beams = ra.beams_from_points(syn.model_directions(syn.model_pf16())[::5] * np.float32(2.5))
     a_ref = attrs.copy()
