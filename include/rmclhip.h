@@ -655,7 +655,10 @@ rmclhip_status rmclhip_pf_set_error_output(rmclhip_pf* pf, float* errors_dev);
  * (rmcl_ros/src/rmcl/particle_motion.cu:11-46) and, with check_collision != 0, the wall-collision test the CPU
  * updater adds (TFMotionUpdaterCPU.cpp:17-50,207-221): pose <- pose * T_bnew_bold;
  * n_meas -= forget_rate * n_meas; a particle whose step crosses the mesh gets likelihood {0, 0, MAX_N_MEAS}.
- * forget_rate is the already combined rate (TFMotionUpdaterCPU.cpp:172-174). */
+ * forget_rate is the already combined rate (TFMotionUpdaterCPU.cpp:172-174), a fraction in [0, 1]: a rate outside that range, or
+ * NaN, is refused with RMCLHIP_ERR_INVALID before anything is launched (the truncating store of a negative double, or of one past
+ * 2^32, into the uint32 n_meas is undefined).  The same rule holds for rmclhip_pf_sharded_motion_update and, when it is given a
+ * T_bnew_bold, for rmclhip_pf_sharded_step. */
 rmclhip_status rmclhip_pf_motion_update(rmclhip_pf* pf, rmclhip_transform* poses_dev,
                                         rmclhip_particle_attributes* attrs_dev, uint32_t n_particles,
                                         const rmclhip_transform* T_bnew_bold, double forget_rate, int check_collision);
@@ -803,7 +806,9 @@ rmclhip_status rmclhip_pf_allreduce_stats(rmclhip_pf_sharded* pf, rmclhip_likeli
 rmclhip_status rmclhip_comm_collective_ranks(rmclhip_comm* comm, uint32_t* n_ranks, int* is_rccl);
 /* RmclNode::estimateStats (rmcl_localization.cpp:642-731) over the first n_induction particles: three passes of per-device
  * moments (<= 24 doubles each: likelihood sums + bounding box, weighted quaternion outer products + translations for the
- * Markley mean, 6x6 covariance around it), each followed by one ncclAllReduce */
+ * Markley mean, 6x6 covariance around it), each followed by one ncclAllReduce.  A cloud whose first n_induction likelihoods sum
+ * to zero (every particle killed by the collision test) or to NaN has no weighted mean: RMCLHIP_ERR_INVALID ("sum to zero"), *out
+ * zeroed, as rmclhip_resampler_residual refuses the same cloud. */
 rmclhip_status rmclhip_pf_allreduce_pose_estimate(rmclhip_pf_sharded* pf, uint32_t n_induction, rmclhip_pose_estimate* out);
 /* distributed GladiatorResamplerGPU::update: all-gather of the 68-B particle records, then every device resamples its own
  * champions against the gathered cloud (Philox counter = GLOBAL champion index => identical to one GPU).  A particle count

@@ -621,6 +621,7 @@ rmclhip_status rmclhip_pf_sharded_motion_update(rmclhip_pf_sharded* h, const rmc
                                                 int check_collision) {
   ApiGuard guard_("rmclhip_pf_sharded_motion_update");
   if (!h || !T_bnew_bold) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_motion_update: null");
+  if (!(forget_rate >= 0.0 && forget_rate <= 1.0)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_motion_update: forget_rate outside [0, 1] (or NaN)");
   if (h->n_total == 0) return RMCLHIP_OK;
   trace_mark("motion:");
   if (rmclhip_status st = pf_sharded_motion_enqueue(h, T_bnew_bold, forget_rate, check_collision)) return st;
@@ -645,6 +646,8 @@ rmclhip_status rmclhip_pf_sharded_step(rmclhip_pf_sharded* h, const rmclhip_tran
   ApiGuard guard_("rmclhip_pf_sharded_step");
   if (!h || !Tsb || (n_beams && !beams)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: null");
   if (resample < 0 || resample > 2 || (resample != 0 && !cfg)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: bad resampling arguments");
+  if (T_bnew_bold && !(forget_rate >= 0.0 && forget_rate <= 1.0))
+    return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: forget_rate outside [0, 1] (or NaN)");
   if (h->n_total == 0) { if (stats_out) { stats_out->sum = 0.f; stats_out->max = 0.f; } return RMCLHIP_OK; }
   if (T_bnew_bold) {
     trace_mark("motion:");
@@ -765,6 +768,8 @@ rmclhip_status rmclhip_pf_allreduce_pose_estimate(rmclhip_pf_sharded* h, uint32_
   double m[32];
   if (rmclhip_status st = sharded_moments(h, n_use, 0, 1.0, xidentity(), m)) return st;
   const double L_sum = m[0], L_n = m[2];
+  // every particle killed by the collision test: w = L / 0, a NaN matrix into the Jacobi sweeps, a NaN pose out
+  if (!(L_sum > 0.0)) return fail(RMCLHIP_ERR_INVALID, "pf_allreduce_pose_estimate: the likelihoods sum to zero (or NaN): no weighted mean");
   const double L_mean = L_sum / L_n;
   out->n_particles = n_use;
   out->likelihood_mean = L_mean;

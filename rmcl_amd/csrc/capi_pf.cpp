@@ -221,6 +221,8 @@ rmclhip_status rmclhip_pf_motion_update(rmclhip_pf* f, rmclhip_transform* poses_
                                         int check_collision) {
   ApiGuard guard_("rmclhip_pf_motion_update");
   if (!f || !T_bnew_bold) return fail(RMCLHIP_ERR_INVALID, "pf_motion_update: null");
+  // uint32(n_meas - rate * n_meas) is undefined in C++ once the double is negative or past 2^32 (the host and the device disagree)
+  if (!(forget_rate >= 0.0 && forget_rate <= 1.0)) return fail(RMCLHIP_ERR_INVALID, "pf_motion_update: forget_rate outside [0, 1] (or NaN)");
   if (n == 0) return RMCLHIP_OK;
   if (!poses_dev || !attrs_dev) return fail(RMCLHIP_ERR_INVALID, "pf_motion_update: null buffers");
   HIPCHK(hipSetDevice(f->ctx->device));

@@ -1672,7 +1672,8 @@ __global__ void __launch_bounds__(256) k_pf_motion(const uint32_t* __restrict__ 
     const bool moving = !(static_cast<double>(length) < 0.00001);
     vec = mk3(vec.x / length, vec.y / length, vec.z / length);
     RayHit h;
-    trace_lane_bf<16, true>(nodes, tris, pose_old.t, vec, (live && moving) ? length : -1.0f, lds_dyn + threadIdx.x, h);
+    // guarded slab: a centimetre step far from the origin is axis-parallel in float32 (traverse.hip.h: make_ray_slab_guarded)
+    trace_lane_bf<16, true, false, false, true>(nodes, tris, pose_old.t, vec, (live && moving) ? length : -1.0f, lds_dyn + threadIdx.x, h);
     if (moving && h.rec != kNone) { L.mean = 0.0f; L.sigma = 0.0f; L.n_meas = max_n_meas; }
   }
   if (live) {

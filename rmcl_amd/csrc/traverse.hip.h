@@ -92,6 +92,31 @@ __device__ __forceinline__ RaySlab make_ray_slab(f3 O, f3 D) {
   return r;
 }
 
+// make_ray_slab for a ray that may start, or a map that may reach, so far out that the slab arithmetic leaves float32: the quantised
+// node test forms t = q * (scale * inv) + (origin * inv - O * inv), and with a direction component of (nearly) zero -- inv = +-1e30 --
+// O * inv overflows for |O| > 3.4e8 and origin * inv for a node as far out: the sum is then +-inf or NaN of no particular sign and
+// boxes the ray lies in are culled (a 5 mm vertical step at x = 1e11 above the 5e12-m triangles of nested200 missed them all).
+// An axis on which |inv| * max(|O|, the root box's largest |coordinate|) passes 1e37 is left out of the test instead (inv = noi =
+// NaN: fmaxf / fminf return their other operand): every term of the other axes stays below 4e37, and leaving a slab out only ever
+// adds boxes.  No ray of a map within 1e7 m of the origin meets the condition, so nothing changes there, bit for bit.
+// qnodes: the Node4Q array (layout.h); read only by lanes that trace (live).
+__device__ __forceinline__ RaySlab make_ray_slab_guarded(f3 O, f3 D, const uint32_t* __restrict__ qnodes, bool live) {
+  RaySlab r = make_ray_slab(O, D);
+  if (live) {
+    const float o[3] = {O.x, O.y, O.z};
+    float inv[3] = {r.inv.x, r.inv.y, r.inv.z}, noi[3] = {r.noi.x, r.noi.y, r.noi.z};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float og = asf(qnodes[a]), sc = asf(qnodes[3 + a]);
+      const float reach = fmaxf(fmaxf(fabsf(og), fabsf(fmaf(255.0f, sc, og))), fabsf(o[a]));
+      if (!(fabsf(inv[a]) * reach <= 1e37f)) { inv[a] = __builtin_nanf(""); noi[a] = __builtin_nanf(""); }
+    }
+    r.inv = mk3(inv[0], inv[1], inv[2]);
+    r.noi = mk3(noi[0], noi[1], noi[2]);
+  }
+  return r;
+}
+
 // The four children of inner node `cur` for one lane: seven global_load_dwordx4 (near / far plane groups of the
 // three axes + child references), twelve packed FMAs (two children per instruction), then per child one
 // max3 / min3 pair.  key = entry distance bits (>= 0, so they order like the floats) or kNone for a miss; unused
@@ -607,11 +632,13 @@ constexpr uint32_t kBfStride = 256u;  // stack row stride in dwords = threads pe
 
 // kRows: stack rows in LDS per lane INCLUDING the sentinel row 0 (row r of this lane at lds_col[r * 256]); deeper entries
 // (up to 64 in total, the builder's bound) in scratch
-template <int kRows, bool kQuant = false, bool kLeafBatch = false, bool kUniform = false>
+// kGuard (quantised nodes only): make_ray_slab_guarded, for callers whose rays may be axis-parallel far from the origin
+template <int kRows, bool kQuant = false, bool kLeafBatch = false, bool kUniform = false, bool kGuard = false>
 __device__ __forceinline__ void trace_lane_bf(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ tris, f3 O, f3 D,
                                               float ray_tfar, uint32_t* __restrict__ lds_col, RayHit& h, uint32_t* visits = nullptr) {
+  static_assert(!kGuard || kQuant, "the guard reads the root of the quantised node array");
   uint32_t nvis = 0;  // node visits of this ray
-  const RaySlab rs = make_ray_slab(O, D);
+  const RaySlab rs = kGuard ? make_ray_slab_guarded(O, D, nodes, ray_tfar >= 0.0f) : make_ray_slab(O, D);
   // do all rays of the wave share the sign octant of their direction?  (lanes without a ray do not vote)
   WaveOctant wo = {0u, 0u, 0u, 0u, 0u, 0u};
   bool uni_oct = false;
