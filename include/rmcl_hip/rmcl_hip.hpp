@@ -1090,6 +1090,69 @@ class PCDSensorUpdaterHip : public SensorUpdaterBase, public ParticleUpdater<VRA
   Transform Tsb_ = identity();
 };
 
+// rmcl::ParticleCloud<MemT> (rmcl_localization.hpp:65-77): the node's particle store
+template <typename MemT>
+struct ParticleCloud {
+  Memory<Transform, MemT> poses;
+  Memory<ParticleAttributes, MemT> attrs;
+};
+template <>
+struct ParticleCloud<VRAM_HIP> {
+  Memory<Transform, VRAM_HIP> poses;
+  Memory<ParticleAttributes, VRAM_HIP> attrs;
+  ParticleCloud() = default;
+  explicit ParticleCloud(const ContextPtr& ctx) : poses(ctx), attrs(ctx) {}
+  void resize(size_t n) { poses.resize(n); attrs.resize(n); }
+  size_t size() const { return poses.size(); }
+  DeviceView<Transform> posesView() { return DeviceView<Transform>{poses.raw(), poses.size()}; }
+  DeviceView<ParticleAttributes> attrsView() { return DeviceView<ParticleAttributes>{attrs.raw(), attrs.size()}; }
+};
+
+// RmclNode::initSamplesUniform (rmcl_localization.cpp:277-342) on the device: the views receive GLOBAL particles first ..
+// first + poses.size() - 1 of the cloud (seed, epoch) selects, uniform in [bb_min, bb_max] over x y z roll pitch yaw (the reference's
+// defaults: [-50, -50, 0, 0, 0, -pi] .. [50, 50, 0, 0, 0, pi], 50 000 particles).  The reference seeds from the clock; here the
+// caller names the stream (rmclhip.h).
+inline void initSamplesUniform(const Context& ctx, DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs, const float (&bb_min)[6],
+                               const float (&bb_max)[6], uint64_t seed, uint32_t epoch = 0, uint32_t first = 0) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("initSamplesUniform: poses.size() != attrs.size()");
+  check(rmclhip_particles_init_uniform(ctx.handle(), poses.raw(), attrs.raw(), first, static_cast<uint32_t>(poses.size()), bb_min, bb_max, seed,
+                                       epoch));
+}
+// RmclNode::initSamples(PoseWithCovarianceStamped) (:165-275): Tlm = the pose guess in the map frame, covariance = its row-major 6x6
+// (x y z roll pitch yaw; positive semidefinite -- RViz sends zero rows for z, roll, pitch).  Returns the "Cholesky Err" (:195).
+inline double initSamples(const Context& ctx, DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs, const Transform& Tlm,
+                          const double (&covariance)[36], uint64_t seed, uint32_t epoch = 0, uint32_t first = 0) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("initSamples: poses.size() != attrs.size()");
+  double err = 0.0;
+  check(rmclhip_particles_init_pose(ctx.handle(), poses.raw(), attrs.raw(), first, static_cast<uint32_t>(poses.size()), &Tlm, covariance, seed, epoch,
+                                    &err));
+  return err;
+}
+// the same two on the node's own store (`particle_cloud_gpu_`): the whole cloud, in the context its memory lives in
+inline void initSamplesUniform(ParticleCloud<VRAM_HIP>& cloud, const float (&bb_min)[6], const float (&bb_max)[6], uint64_t seed, uint32_t epoch = 0) {
+  if (!cloud.poses.context()) throw std::runtime_error("initSamplesUniform: the cloud has no context");
+  initSamplesUniform(*cloud.poses.context(), cloud.posesView(), cloud.attrsView(), bb_min, bb_max, seed, epoch);
+}
+inline double initSamples(ParticleCloud<VRAM_HIP>& cloud, const Transform& Tlm, const double (&covariance)[36], uint64_t seed, uint32_t epoch = 0) {
+  if (!cloud.poses.context()) throw std::runtime_error("initSamples: the cloud has no context");
+  return initSamples(*cloud.poses.context(), cloud.posesView(), cloud.attrsView(), Tlm, covariance, seed, epoch);
+}
+// RmclNode::visualize's per-particle loop (:856-874): x | y | z | likelihood | likelihood_sigma | likelihood_n_meas | badness, each
+// poses.size() floats, one after the other -- into host memory (28 B per particle cross the bus) ...
+inline void packVisualization(const Context& ctx, DeviceView<const Transform> poses, DeviceView<const ParticleAttributes> attrs,
+                              Memory<float, RAM>& out, uint32_t max_n_meas = 10000u) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("packVisualization: poses.size() != attrs.size()");
+  out.resize(7 * poses.size());
+  check(rmclhip_particles_pack_visualization(ctx.handle(), poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), max_n_meas, out.raw(), 0));
+}
+// ... or into device memory (a renderer that reads it there)
+inline void packVisualization(const Context& ctx, DeviceView<const Transform> poses, DeviceView<const ParticleAttributes> attrs,
+                              Memory<float, VRAM_HIP>& out, uint32_t max_n_meas = 10000u) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("packVisualization: poses.size() != attrs.size()");
+  out.resize(7 * poses.size());
+  check(rmclhip_particles_pack_visualization(ctx.handle(), poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), max_n_meas, out.raw(), 1));
+}
+
 // The particle filter of ONE process over several devices (rmclhip_comm + rmclhip_pf_sharded: RCCL ncclCommInitAll, weight
 // all-gather, moment all-reduces): sensor update, pose estimate (RmclNode::estimateStats, rmcl_localization.cpp:642-731) and
 // the distributed gladiator tournament for the single-process node (rmcl_localization.cpp:482-552).  The cloud lives in the
@@ -1120,6 +1183,18 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
     if (poses.size() != attrs.size()) throw std::runtime_error("setParticles: poses.size() != attrs.size()");
     check(rmclhip_pf_sharded_set_particles(h_, poses.data(), attrs.data(), static_cast<uint32_t>(poses.size())));
     n_ = poses.size();
+  }
+  // (re)create the cloud of n particles ON the devices, every device its own block: RmclNode::initSamplesUniform / initSamples without
+  // the host loop and the upload (rmclhip_pf_sharded_init_uniform / _pose: the single-device cloud bit for bit)
+  void initSamplesUniform(uint32_t n, const float (&bb_min)[6], const float (&bb_max)[6], uint64_t seed, uint32_t epoch = 0) {
+    check(rmclhip_pf_sharded_init_uniform(h_, n, bb_min, bb_max, seed, epoch));
+    n_ = n;
+  }
+  double initSamples(uint32_t n, const Transform& Tlm, const double (&covariance)[36], uint64_t seed, uint32_t epoch = 0) {
+    double err = 0.0;
+    check(rmclhip_pf_sharded_init_pose(h_, n, &Tlm, covariance, seed, epoch, &err));
+    n_ = n;
+    return err;
   }
   void download(std::vector<Transform>& poses, std::vector<ParticleAttributes>& attrs) const {
     poses.resize(n_);

@@ -747,6 +747,48 @@ rmclhip_status rmclhip_resampler_residual(rmclhip_resampler* rs, const rmclhip_t
                                           uint32_t n_new, uint32_t first, uint32_t count, const rmclhip_gladiator_config* config,
                                           uint64_t seed, uint32_t step, uint64_t* n_draws_out);
 
+/* ---- the particle cloud's first and last step: RmclNode::initSamplesUniform / initSamples / visualize ------------------------
+ * (rmcl_ros/src/nodes/rmcl_localization.cpp:277-342, 165-275, 797-879; particle store rmcl_localization.hpp:65-77.)
+ * The cloud is created ON the device: no host loop, no 68 B per particle upload.  poses_dev / attrs_dev hold particles
+ * first .. first+count-1 of a cloud; element k gets the values of GLOBAL particle first+k, so a cloud is the same bits whether it
+ * is filled by one call, by several calls over slices, or by the devices of a sharded filter (rmclhip_pf_sharded_init_*).
+ *
+ * Random words of particle i: a = Philox4x32-10(counter (i, epoch, 0, 1), key = seed), b = Philox(counter (i, epoch, 1, 1), key):
+ * w0..w3 = a, w4..w5 = b[0..1].  The resamplers' counters end in 0: an initialisation and a resampler may share a seed.
+ *   uniform: dimension d of x y z roll pitch yaw = float(lo_d + (hi_d - lo_d) * (w_d + 0.5) * 2^-32) in double; lo_d == hi_d gives lo_d.
+ *   pose:    z = three Box-Muller pairs of w; x = float(L z) with L the factor rmclhip_chol6_host returns for `covariance`
+ *            (row-major 6x6 over x y z roll pitch yaw, the layout of geometry_msgs/PoseWithCovariance); particle = Tlm * {EulerAngles
+ *            (x3, x4, x5), (x0, x1, x2)}, Tlm = the pose guess in the map frame.
+ * Both write the attributes the reference writes: likelihood {mean 1, sigma 0, n_meas 0}, state_sigma 0.
+ * The reference's defaults are parameters of its node, not of this interface: box [-50, -50, 0, 0, 0, -pi] .. [50, 50, 0, 0, 0, pi]
+ * and 50 000 particles for both initialisations (rmcl_localization.hpp:153-154, .cpp:356-359).
+ * THE ONE DELIBERATE DIFFERENCE from the reference: it seeds a std::mt19937 from the clock and draws sequentially (not reproducible,
+ * not parallel); here the caller passes seed and epoch, and particle i depends on (seed, epoch, i) alone -- the choice the resamplers
+ * document above.  The distributions are the reference's.
+ * count == 0: RMCLHIP_OK, nothing touched.  RMCLHIP_ERR_INVALID: null buffers with count > 0, bb_min[d] > bb_max[d], a non-finite bound
+ * or pose, a covariance rmclhip_chol6_host refuses, first + count above 2^32.  Synchronous on return. */
+rmclhip_status rmclhip_particles_init_uniform(rmclhip_ctx* ctx, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                              uint32_t first, uint32_t count, const float bb_min[6], const float bb_max[6],
+                                              uint64_t seed, uint32_t epoch);
+/* chol_err_out (nullable): the "Cholesky Err" the reference prints (:195), see rmclhip_chol6_host */
+rmclhip_status rmclhip_particles_init_pose(rmclhip_ctx* ctx, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                           uint32_t first, uint32_t count, const rmclhip_transform* Tlm, const double covariance[36],
+                                           uint64_t seed, uint32_t epoch, double* chol_err_out);
+/* HOST function (no device needed): row-major lower-triangular L with L L^T = (C + C^T) / 2, computed in double and rounded to float.
+ * Positive SEMIdefinite input is the normal case (RViz's /initialpose covariance has zero rows for z, roll and pitch): column by column
+ * with pivot d_j = C_jj - sum_k L_jk^2 and tol = 36 * 2^-24 * max_j |C_jj|; d_j < -tol: RMCLHIP_ERR_INVALID ("not positive
+ * semidefinite"); d_j <= tol: column j of L is zero; else L_jj = sqrt(d_j) and the column below it.  A non-finite entry:
+ * RMCLHIP_ERR_INVALID.  err_out (nullable): sum |L L^T - C| / 36 of the float factor. */
+rmclhip_status rmclhip_chol6_host(const double covariance[36], float L_out[36], double* err_out);
+/* RmclNode::visualize's per-particle loop: seven dense float arrays of n, one after the other in `out` (7 * n floats; host memory, or
+ * device memory with out_is_device != 0): x, y, z (pose.t), likelihood (mean), likelihood_sigma, likelihood_n_meas (float(n_meas)),
+ * badness = mean * (sigma * unc + unc) with unc = float(1.0 - double(n_meas) / double(max_n_meas)) -- 28 B per particle leave the
+ * device instead of 68 B and a host loop.  max_n_meas: rmclhip_pf_params::max_n_meas (the reference's MAX_N_MEAS, 10000); 0 is
+ * RMCLHIP_ERR_INVALID. */
+rmclhip_status rmclhip_particles_pack_visualization(rmclhip_ctx* ctx, const rmclhip_transform* poses_dev,
+                                                    const rmclhip_particle_attributes* attrs_dev, uint32_t n, uint32_t max_n_meas,
+                                                    float* out, int out_is_device);
+
 /* ---- multi-GPU: ONE process drives several devices -------------------------------------------------------------
  * (the reference's localisation node is one process: rmcl_localization.cpp:482-552; particle store rmcl_localization.hpp:65-77.
  * The reference has no distributed code -- SURVEY.md 8(e) defines this part.)  Particles are block-partitioned over the
@@ -772,6 +814,14 @@ rmclhip_status rmclhip_pf_sharded_set_params(rmclhip_pf_sharded* pf, const rmclh
 /* scatter the (host) cloud: rank r receives particles [lo_r, hi_r) */
 rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* pf, const rmclhip_transform* poses,
                                                 const rmclhip_particle_attributes* attrs, uint32_t n_total);
+/* (re)create a sharded cloud of n particles in place on its devices: every device fills its own block (rmclhip_shard_bounds) with
+ * rmclhip_particles_init_uniform / _pose's values of its global indices -- the single-device cloud bit for bit, no upload, no
+ * collective; all devices' launches are enqueued before the host waits for any.  Buffers are sized as by
+ * rmclhip_pf_sharded_set_particles; afterwards download, step and the rest work as after that call. */
+rmclhip_status rmclhip_pf_sharded_init_uniform(rmclhip_pf_sharded* pf, uint32_t n, const float bb_min[6], const float bb_max[6],
+                                               uint64_t seed, uint32_t epoch);
+rmclhip_status rmclhip_pf_sharded_init_pose(rmclhip_pf_sharded* pf, uint32_t n, const rmclhip_transform* Tlm, const double covariance[36],
+                                            uint64_t seed, uint32_t epoch, double* chol_err_out);
 rmclhip_status rmclhip_pf_sharded_download(rmclhip_pf_sharded* pf, rmclhip_transform* poses, rmclhip_particle_attributes* attrs);
 /* PCDSensorUpdater*::update on every device's block (concurrently), then rmclhip_pf_allgather_weights */
 rmclhip_status rmclhip_pf_update_sharded(rmclhip_pf_sharded* pf, const rmclhip_range_measurement* beams, uint32_t n_beams,

@@ -79,6 +79,11 @@ rmclhip_status rmclhip_debug_trace(int on, char* buf, size_t cap);
 /* how often, in this process, a host poller found ITS sequence number in a completion tag while the result words it read did not yet add
  * up to the tag's checksum -- the event the {sequence, xor} tag guards against (tools/tag_retries.py, profiles/r05_tag_handoff.txt) */
 rmclhip_status rmclhip_debug_tag_retries(unsigned long long* retries_out);
+/* MEASUREMENT aid of rmclhip_particles_init_uniform / _init_pose / _pack_visualization (tools/particle_init_time.py): on != 0 brackets
+ * what those calls enqueue on this context -- the kernel, and the pack's copy to the host -- with two HIP events; last_ms (nullable)
+ * receives the bracket of the last such call made while it was on (0 before any).  Off by default: two event records per call.
+ * Works without the experiments library. */
+rmclhip_status rmclhip_debug_particles_timing(rmclhip_ctx* ctx, int on, float* last_ms);
 
 #ifdef __cplusplus
 }

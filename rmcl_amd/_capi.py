@@ -252,12 +252,17 @@ SIGNATURES = {
                                             C.c_uint64, _u32]),
     "rmclhip_resampler_residual": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, C.POINTER(GladiatorConfig),
                                            C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
+    "rmclhip_chol6_host": (_i32, [_vp, _vp, C.POINTER(_dbl)]),
+    "rmclhip_particles_init_uniform": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32]),
+    "rmclhip_particles_init_pose": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32, C.POINTER(_dbl)]),
+    "rmclhip_particles_pack_visualization": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _i32]),
     "rmclhip_comm_create": (_i32, [_vp, _u32, _pp]),
     "rmclhip_comm_create_loopback": (_i32, [_vp, _u32, _pp]),
     "rmclhip_comm_collective_ranks": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_i32)]),
     "rmclhip_comm_loopback_set_reduce_rotation": (_i32, [_vp, _u32]),
     "rmclhip_debug_tag_retries": (_i32, [C.POINTER(C.c_ulonglong)]),
     "rmclhip_debug_trace": (_i32, [_i32, _vp, _sz]),
+    "rmclhip_debug_particles_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
     "rmclhip_comm_destroy": (None, [_vp]),
     "rmclhip_comm_size": (_u32, [_vp]),
     "rmclhip_shard_bounds": (None, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
@@ -265,6 +270,8 @@ SIGNATURES = {
     "rmclhip_pf_sharded_destroy": (None, [_vp]),
     "rmclhip_pf_sharded_set_params": (_i32, [_vp, C.POINTER(PFParams)]),
     "rmclhip_pf_sharded_set_particles": (_i32, [_vp, _vp, _vp, _u32]),
+    "rmclhip_pf_sharded_init_uniform": (_i32, [_vp, _u32, _vp, _vp, C.c_uint64, _u32]),
+    "rmclhip_pf_sharded_init_pose": (_i32, [_vp, _u32, _vp, _vp, C.c_uint64, _u32, C.POINTER(_dbl)]),
     "rmclhip_pf_sharded_download": (_i32, [_vp, _vp, _vp]),
     "rmclhip_pf_update_sharded": (_i32, [_vp, _vp, _u32, _vp]),
     "rmclhip_pf_sharded_motion_update": (_i32, [_vp, _vp, _dbl, _i32]),

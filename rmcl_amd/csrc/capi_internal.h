@@ -6,6 +6,7 @@
 //   capi_segment.cpp   map segmentation of that operator: trace into its own scratch, labels, compacted outlier clouds (kernels: segment.hip)
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
+//   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
 // entry point fails with RMCLHIP_ERR_NO_DEVICE.
@@ -160,6 +161,14 @@ struct rmclhip_ctx {
   hipStream_t pc2_stream = nullptr;
   Pc2ScanScratch pc2;
   DevBuf<uint8_t> pc2_raw;              // staged host bytes
+  // rmclhip_particles_* (capi_particles.cpp): their stream and the visualisation pack's device staging, created by the first call
+  // under the mutex, which also serialises the calls of one context
+  std::mutex part_mtx;
+  hipStream_t part_stream = nullptr;
+  DevBuf<float> part_viz;
+  bool part_timing = false;              // rmclhip_debug_particles_timing (include/rmclhip_lab.h): bracket those calls with the two events
+  hipEvent_t part_ev0 = nullptr, part_ev1 = nullptr;
+  float part_last_ms = 0.f;
   ~rmclhip_ctx();                       // capi_map.cpp
 };
 
@@ -490,5 +499,11 @@ RMCL_INTERNAL rmclhip_status residual_fill_enqueue(ResidualJob& j, bool want_n_d
 RMCL_INTERNAL rmclhip_status residual_draws_enqueue(ResidualJob& j, bool first_try);
 RMCL_INTERNAL void residual_draws_done(ResidualJob& j);
 RMCL_INTERNAL rmclhip_status residual_check(ResidualJob& j);
+// capi_particles.cpp: argument checks of the two initialisations (the pose form also factors the covariance) and their launches on `st`;
+// the sharded entry points check once and enqueue per rank
+struct ParticlesPoseJob { xform Tlm; float L[36]; double chol_err; };
+RMCL_INTERNAL rmclhip_status particles_uniform_check(const char* who, uint32_t first, uint32_t count, const float* bb_min, const float* bb_max);
+RMCL_INTERNAL rmclhip_status particles_pose_check(const char* who, uint32_t first, uint32_t count, const rmclhip_transform* Tlm, const double* covariance,
+                                                  ParticlesPoseJob* job);
 extern RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries;   // capi_rcc.cpp: polls that met their sequence number before the checksum matched
 //@@DECLS@@

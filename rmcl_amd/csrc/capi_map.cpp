@@ -44,6 +44,14 @@ void rmclhip_ctx_destroy(rmclhip_ctx* ctx) { ctx_release(ctx); }
 
 // the scratch of rmclhip_statistics_p2l (capi_rcc.cpp) belongs to the context and goes with its last holder
 rmclhip_ctx::~rmclhip_ctx() {
+  if (part_stream != nullptr) {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(part_stream);
+    part_viz.release();
+    if (part_ev0) (void)hipEventDestroy(part_ev0);
+    if (part_ev1) (void)hipEventDestroy(part_ev1);
+    (void)hipStreamDestroy(part_stream);
+  }
   if (pc2_stream != nullptr) {
     (void)hipSetDevice(device);
     (void)hipStreamSynchronize(pc2_stream);

@@ -488,12 +488,9 @@ rmclhip_status rmclhip_pf_sharded_set_params(rmclhip_pf_sharded* h, const rmclhi
 }
 
 // contiguous block partition of the particle range; shards are padded to `cap` so that the collectives
-// run on equal counts
-rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* h, const rmclhip_transform* poses,
-                                                const rmclhip_particle_attributes* attrs, uint32_t n_total) {
-  ApiGuard guard_("rmclhip_pf_sharded_set_particles");
-  if (!h || (n_total && (!poses || !attrs))) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_particles: null");
-  h->weights_fresh = false;
+// run on equal counts.  Sizes every rank's buffers for a cloud of n_total particles (grow-only), sets its bounds and clears its shard;
+// `who` names the caller in the error message.  h->n_total / h->cap are the caller's to set once its own part succeeded.
+static rmclhip_status pf_sharded_reserve(rmclhip_pf_sharded* h, uint32_t n_total, const char* who) {
   const uint32_t world = static_cast<uint32_t>(h->ranks.size());
   const uint32_t cap = (n_total + world - 1u) / world;
   for (uint32_t r = 0; r < world; ++r) {
@@ -514,14 +511,29 @@ rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* h, const rmc
         // leave no half-allocated rank behind: the next call must see "no buffers" and start over
         for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
         h->cap = 0;
-        return fail(ae == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string("pf_sharded_set_particles: ") + hipGetErrorString(ae));
+        return fail(ae == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(ae));
       }
     }
     shard_bounds(n_total, r, world, &R.lo, &R.hi);
     HIPCHK(hipMemset(R.d_poses, 0, static_cast<size_t>(std::max(cap, 1u)) * 32));
     HIPCHK(hipMemset(R.d_attrs, 0, static_cast<size_t>(std::max(cap, 1u)) * 36));
     HIPCHK(hipMemset(R.d_w_send, 0, static_cast<size_t>(std::max(cap, 1u)) * 4));
+  }
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* h, const rmclhip_transform* poses,
+                                                const rmclhip_particle_attributes* attrs, uint32_t n_total) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_particles");
+  if (!h || (n_total && (!poses || !attrs))) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_particles: null");
+  h->weights_fresh = false;
+  const uint32_t world = static_cast<uint32_t>(h->ranks.size());
+  const uint32_t cap = (n_total + world - 1u) / world;
+  if (rmclhip_status st = pf_sharded_reserve(h, n_total, "pf_sharded_set_particles")) return st;
+  for (uint32_t r = 0; r < world; ++r) {
+    PfRank& R = h->ranks[r];
     if (R.hi > R.lo) {
+      HIPCHK(hipSetDevice(R.ctx->device));
       HIPCHK(hipMemcpy(R.d_poses, poses + R.lo, static_cast<size_t>(R.hi - R.lo) * 32, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(R.d_attrs, attrs + R.lo, static_cast<size_t>(R.hi - R.lo) * 36, hipMemcpyHostToDevice));
       HIPCHK(hipDeviceSynchronize());   // consumers run on non-blocking streams (see upload_on)
@@ -529,6 +541,52 @@ rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* h, const rmc
   }
   h->n_total = n_total;
   h->cap = std::max(cap, h->cap);
+  return RMCLHIP_OK;
+}
+
+// (re)create the cloud in place: every device fills its own block with the values of the GLOBAL particles lo_r .. hi_r - 1 (the random
+// words are a function of the global index: the single-device cloud bit for bit, no collective).  Every rank's launch is enqueued on
+// its collective stream before the host waits for any.  job: the pose form (null: uniform in [bb_min, bb_max]).
+static rmclhip_status pf_sharded_init_impl(rmclhip_pf_sharded* h, uint32_t n, const float* bb_min, const float* bb_max, const ParticlesPoseJob* job,
+                                           uint64_t seed, uint32_t epoch, const char* who) {
+  h->weights_fresh = false;
+  const uint32_t world = static_cast<uint32_t>(h->ranks.size());
+  const uint32_t cap = (n + world - 1u) / world;
+  if (rmclhip_status st = pf_sharded_reserve(h, n, who)) return st;
+  h->n_total = n;
+  h->cap = std::max(cap, h->cap);
+  trace_mark("init:");
+  for (uint32_t r = 0; r < world; ++r) {
+    PfRank& R = h->ranks[r];
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    HIPCHK(hipDeviceSynchronize());   // the clears above ran on the null stream, which the collective streams do not wait for
+    if (job)
+      HIPCHK(launch_particles_init_pose(R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, job->Tlm, job->L, seed, epoch, h->comm->streams[r]));
+    else
+      HIPCHK(launch_particles_init_uniform(R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, bb_min, bb_max, seed, epoch, h->comm->streams[r]));
+    trace('E', r);
+  }
+  return comm_wait_all(h->comm);
+}
+
+rmclhip_status rmclhip_pf_sharded_init_uniform(rmclhip_pf_sharded* h, uint32_t n, const float* bb_min, const float* bb_max, uint64_t seed,
+                                               uint32_t epoch) {
+  ApiGuard guard_("rmclhip_pf_sharded_init_uniform");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_init_uniform: null");
+  if (rmclhip_status st = particles_uniform_check("pf_sharded_init_uniform", 0u, n, bb_min, bb_max)) return st;
+  return pf_sharded_init_impl(h, n, bb_min, bb_max, nullptr, seed, epoch, "pf_sharded_init_uniform");
+}
+
+rmclhip_status rmclhip_pf_sharded_init_pose(rmclhip_pf_sharded* h, uint32_t n, const rmclhip_transform* Tlm, const double* covariance,
+                                            uint64_t seed, uint32_t epoch, double* chol_err_out) {
+  ApiGuard guard_("rmclhip_pf_sharded_init_pose");
+  if (chol_err_out) *chol_err_out = 0.0;
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_init_pose: null");
+  ParticlesPoseJob job;
+  if (rmclhip_status st = particles_pose_check("pf_sharded_init_pose", 0u, n, Tlm, covariance, &job)) return st;
+  if (rmclhip_status st = pf_sharded_init_impl(h, n, nullptr, nullptr, &job, seed, epoch, "pf_sharded_init_pose")) return st;
+  if (chol_err_out) *chol_err_out = job.chol_err;
   return RMCLHIP_OK;
 }
 

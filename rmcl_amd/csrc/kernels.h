@@ -402,4 +402,15 @@ hipError_t launch_compact_shards(const float* padded, float* dense, uint32_t n_t
 hipError_t launch_compact_records(const void* padded, void* dense, uint32_t n_total, uint32_t world, uint32_t cap, uint32_t record_bytes,
                                   hipStream_t s);
 
+// the particle cloud's initialisations and visualisation channels (particles.hip; RmclNode::initSamplesUniform / initSamples / visualize).
+// poses / attrs: elements first .. first+count-1 of a cloud (poses 16-B aligned, attrs 4-B aligned); element k gets the values of GLOBAL
+// particle first + k.  One launch writes at most kMaxInitCount records (its attribute stream is indexed in 32-bit dwords).
+constexpr uint32_t kMaxInitCount = 0xFFFFFFFFu / 9u;
+hipError_t launch_particles_init_uniform(xform* poses, void* attrs, uint32_t first, uint32_t count, const float* bb_min, const float* bb_max,
+                                         uint64_t seed, uint32_t epoch, hipStream_t s);
+hipError_t launch_particles_init_pose(xform* poses, void* attrs, uint32_t first, uint32_t count, const xform& Tlm, const float* L36, uint64_t seed,
+                                      uint32_t epoch, hipStream_t s);
+// out: 7 * n floats on the device: x | y | z | likelihood | likelihood_sigma | likelihood_n_meas | badness
+hipError_t launch_particles_pack_visualization(const xform* poses, const void* attrs, uint32_t n, uint32_t max_n_meas, float* out, hipStream_t s);
+
 }  // namespace rmclhip

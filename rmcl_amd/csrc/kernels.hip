@@ -18,6 +18,7 @@
 #include "find_kernel.hip.h"
 #include "lab_hooks.h"
 #include "pf_common.hip.h"
+#include "pf_random.hip.h"
 
 
 namespace rmclhip {
@@ -1691,28 +1692,8 @@ __global__ void k_pf_extract_weights(const pattrs* __restrict__ attrs, uint32_t 
 // gladiator resampling (resampling.cu:41-219).  Random stream = Philox4x32-10 keyed by the seed with counter
 // (champion index, step, draw, 0): reproducible, independent of the launch shape and of how the particle range
 // is sharded across GPUs.  Transcendentals are evaluated in double and rounded to float (see oracle).
+// philox4x32_10, box_muller and euler_to_quat: pf_random.hip.h (shared with particles.hip).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-  const double u1 = (static_cast<double>(a) + 0.5) * (1.0 / 4294967296.0);
-  const double u2 = (static_cast<double>(b) + 0.5) * (1.0 / 4294967296.0);
-  const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925 * u2;
-  z0 = static_cast<float>(r * cos(ang));
-  z1 = static_cast<float>(r * sin(ang));
-}
-
 struct GladiatorConfig {
   float min_noise_tx, min_noise_ty, min_noise_tz, min_noise_roll, min_noise_pitch, min_noise_yaw;
   float likelihood_forget_per_meter, likelihood_forget_per_radian;
@@ -1758,13 +1739,7 @@ __global__ void __launch_bounds__(256) k_gladiator_resample(const xform* __restr
     pitch = pitch + Nd_ry * cfg.min_noise_pitch;
     yaw = yaw + Nd_rz * cfg.min_noise_yaw;
     // pose_new.R = e
-    const float cr = static_cast<float>(cos(static_cast<double>(roll / 2.0f))), sr = static_cast<float>(sin(static_cast<double>(roll / 2.0f)));
-    const float cp = static_cast<float>(cos(static_cast<double>(pitch / 2.0f))), sp = static_cast<float>(sin(static_cast<double>(pitch / 2.0f)));
-    const float cy = static_cast<float>(cos(static_cast<double>(yaw / 2.0f))), sy = static_cast<float>(sin(static_cast<double>(yaw / 2.0f)));
-    pn.R.w = cr * cp * cy + sr * sp * sy;
-    pn.R.x = sr * cp * cy - cr * sp * sy;
-    pn.R.y = cr * sp * cy + sr * cp * sy;
-    pn.R.z = cr * cp * sy - sr * sp * cy;
+    pn.R = euler_to_quat(roll, pitch, yaw);
     const xform diff = xmul(xinv(pose), pn);
     const float t2 = (diff.t.x * diff.t.x + diff.t.y * diff.t.y) + diff.t.z * diff.t.z;
     const float trans_dist = (cfg.trans_dist_metric == 1u) ? t2 : sqrtf(t2);
@@ -1950,13 +1925,7 @@ __global__ void __launch_bounds__(256) k_residual_fill(const xform* __restrict__
   roll = roll + Nd_rx * noise_roll;
   pitch = pitch + Nd_ry * noise_pitch;
   yaw = yaw + Nd_rz * noise_yaw;
-  const float cr = static_cast<float>(cos(static_cast<double>(roll / 2.0f))), sr = static_cast<float>(sin(static_cast<double>(roll / 2.0f)));
-  const float cp = static_cast<float>(cos(static_cast<double>(pitch / 2.0f))), sp = static_cast<float>(sin(static_cast<double>(pitch / 2.0f)));
-  const float cy = static_cast<float>(cos(static_cast<double>(yaw / 2.0f))), sy = static_cast<float>(sin(static_cast<double>(yaw / 2.0f)));
-  pn.R.w = cr * cp * cy + sr * sp * sy;
-  pn.R.x = sr * cp * cy - cr * sp * sy;
-  pn.R.y = cr * sp * cy + sr * cp * sy;
-  pn.R.z = cr * cp * sy - sr * sp * cy;
+  pn.R = euler_to_quat(roll, pitch, yaw);
   const xform diff = xmul(xinv(pose), pn);
   const float trans_dist = (diff.t.x * diff.t.x + diff.t.y * diff.t.y) + diff.t.z * diff.t.z;   // l2normSquared (:164)
   const float rot_dist = sqrtf(((diff.R.w * diff.R.w + diff.R.x * diff.R.x) + diff.R.y * diff.R.y) + diff.R.z * diff.R.z);

@@ -1,0 +1,49 @@
+// pf_random.hip.h -- the counter-based random stream of the particle filter and the Euler -> quaternion step its draws end in, shared
+// by the resamplers (kernels.hip) and the cloud initialisation (particles.hip): ONE text, so that a particle drawn by either is the
+// same function of (seed, counter) down to the bit.  Device code only.
+//
+// Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
+//   stream 0: the resamplers   (champion or slot index, step, draw 0..4)
+//   stream 1: the initialisers (global particle index, epoch, draw 0..1)
+// reproducible, independent of the launch shape and of how the particle range is sharded across GPUs.  Transcendentals are evaluated in
+// double and rounded to float (see oracle).
+#pragma once
+#include "devmath.h"
+
+namespace rmclhip {
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
+  const double u1 = (static_cast<double>(a) + 0.5) * (1.0 / 4294967296.0);
+  const double u2 = (static_cast<double>(b) + 0.5) * (1.0 / 4294967296.0);
+  const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925 * u2;
+  z0 = static_cast<float>(r * cos(ang));
+  z1 = static_cast<float>(r * sin(ang));
+}
+
+// rmagine Quaternion <- EulerAngles (ZYX): cos / sin of the float half angles in double, rounded to float, then float products
+__device__ __forceinline__ quat euler_to_quat(float roll, float pitch, float yaw) {
+  const float cr = static_cast<float>(cos(static_cast<double>(roll / 2.0f))), sr = static_cast<float>(sin(static_cast<double>(roll / 2.0f)));
+  const float cp = static_cast<float>(cos(static_cast<double>(pitch / 2.0f))), sp = static_cast<float>(sin(static_cast<double>(pitch / 2.0f)));
+  const float cy = static_cast<float>(cos(static_cast<double>(yaw / 2.0f))), sy = static_cast<float>(sin(static_cast<double>(yaw / 2.0f)));
+  quat q;
+  q.w = cr * cp * cy + sr * sp * sy;
+  q.x = sr * cp * cy - cr * sp * sy;
+  q.y = cr * sp * cy + sr * cp * sy;
+  q.z = cr * cp * sy - sr * sp * cy;
+  return q;
+}
+
+}  // namespace rmclhip

@@ -55,6 +55,64 @@ def combined_forget_rate(forget_rate_per_meter, forget_rate_per_second, dist_tra
     return space * tim
 
 
+def _count_of(poses, first, count):
+    if count is not None:
+        return int(count)
+    n = poses.count if hasattr(poses, "count") else poses.shape[0]
+    return int(n)
+
+
+def init_particles_uniform(ctx, poses, attrs, bb_min, bb_max, seed, epoch=0, first=0, count=None):
+    """RmclNode::initSamplesUniform (rmcl_localization.cpp:277-342) on the device (rmclhip_particles_init_uniform): poses / attrs are
+    device views of `count` particles (default: all of `poses`) that receive the GLOBAL particles first .. first+count-1 of the cloud
+    (seed, epoch) selects -- uniform in [bb_min, bb_max] over x y z roll pitch yaw, likelihood {1, 0, 0}.  The reference's defaults:
+    [-50, -50, 0, 0, 0, -pi] .. [50, 50, 0, 0, 0, pi], 50 000 particles."""
+    lo = np.ascontiguousarray(bb_min, dtype=np.float32).reshape(6)
+    hi = np.ascontiguousarray(bb_max, dtype=np.float32).reshape(6)
+    _capi.check(_capi.lib().rmclhip_particles_init_uniform(ctx.handle, _as_ptr(poses), _as_ptr(attrs), int(first),
+                                                           _count_of(poses, first, count), _ptr(lo), _ptr(hi), int(seed), int(epoch)))
+
+
+def init_particles_pose(ctx, poses, attrs, pose, covariance, seed, epoch=0, first=0, count=None):
+    """RmclNode::initSamples(PoseWithCovarianceStamped) (rmcl_localization.cpp:165-275) on the device (rmclhip_particles_init_pose):
+    particles pose * {EulerAngles(x3, x4, x5), (x0, x1, x2)} with x = L z, L L^T = covariance (6x6 over x y z roll pitch yaw, positive
+    semidefinite).  Returns the "Cholesky Err" of the factor (chol6)."""
+    T = np.ascontiguousarray(pose, dtype=TRANSFORM).reshape(1)
+    cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(36)
+    err = C.c_double(0.0)
+    _capi.check(_capi.lib().rmclhip_particles_init_pose(ctx.handle, _as_ptr(poses), _as_ptr(attrs), int(first),
+                                                        _count_of(poses, first, count), _ptr(T), _ptr(cov), int(seed), int(epoch),
+                                                        C.byref(err)))
+    return err.value
+
+
+VISUALIZATION_CHANNELS = ("x", "y", "z", "likelihood", "likelihood_sigma", "likelihood_n_meas", "badness")
+
+
+def pack_visualization(ctx, poses, attrs, n, max_n_meas=10000, out_dev=None):
+    """RmclNode::visualize's per-particle loop (rmcl_localization.cpp:856-874) on the device (rmclhip_particles_pack_visualization):
+    a dict of seven float32 arrays of n -- the point cloud's x y z and its four channels.  out_dev: a device buffer of 7 * n floats
+    that receives them instead (the dict then holds nothing: returns None)."""
+    if out_dev is not None:
+        _capi.check(_capi.lib().rmclhip_particles_pack_visualization(ctx.handle, _as_ptr(poses), _as_ptr(attrs), int(n), int(max_n_meas),
+                                                                     _as_ptr(out_dev), 1))
+        return None
+    out = np.zeros((7, int(n)), dtype=np.float32)
+    _capi.check(_capi.lib().rmclhip_particles_pack_visualization(ctx.handle, _as_ptr(poses), _as_ptr(attrs), int(n), int(max_n_meas),
+                                                                 _ptr(out), 0))
+    return {k: out[i] for i, k in enumerate(VISUALIZATION_CHANNELS)}
+
+
+def chol6(covariance):
+    """rmclhip_chol6_host (no device needed): (L, err) -- the float32 lower-triangular factor of a positive semidefinite 6x6
+    covariance, as the pose initialisation uses it, and sum |L L^T - C| / 36."""
+    cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(36)
+    L = np.zeros(36, dtype=np.float32)
+    err = C.c_double(0.0)
+    _capi.check(_capi.lib().rmclhip_chol6_host(_ptr(cov), _ptr(L), C.byref(err)))
+    return L.reshape(6, 6), err.value
+
+
 class TFMotionUpdaterHip:
     """rmcl::TFMotionUpdaterGPU on gfx950 + the wall-collision test of TFMotionUpdaterCPU (MotionUpdater<MemT>)."""
 
@@ -319,6 +377,23 @@ class ShardedParticleFilterHip:
         assert a.dtype.itemsize == 36 and len(a) == len(p)
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_particles(self._h, _ptr(p), _ptr(a), len(p)))
         self.n_total = len(p)
+
+    def init_uniform(self, n, bb_min, bb_max, seed, epoch=0):
+        """(re)create the cloud on its devices, uniform in the box (rmclhip_pf_sharded_init_uniform): every device fills its own block;
+        the single-device cloud of init_particles_uniform bit for bit"""
+        lo = np.ascontiguousarray(bb_min, dtype=np.float32).reshape(6)
+        hi = np.ascontiguousarray(bb_max, dtype=np.float32).reshape(6)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_init_uniform(self._h, int(n), _ptr(lo), _ptr(hi), int(seed), int(epoch)))
+        self.n_total = int(n)
+
+    def init_pose(self, n, pose, covariance, seed, epoch=0):
+        """(re)create the cloud around a pose guess with covariance (rmclhip_pf_sharded_init_pose); returns the "Cholesky Err" """
+        T = np.ascontiguousarray(pose, dtype=TRANSFORM).reshape(1)
+        cov = np.ascontiguousarray(covariance, dtype=np.float64).reshape(36)
+        err = C.c_double(0.0)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_init_pose(self._h, int(n), _ptr(T), _ptr(cov), int(seed), int(epoch), C.byref(err)))
+        self.n_total = int(n)
+        return err.value
 
     def download(self):
         from .types import PARTICLE_ATTRIBUTES
