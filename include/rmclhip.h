@@ -613,7 +613,9 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
                                       rmclhip_cross_statistics* out);
 
 /* ---- host-side algebra (rmagine math the callers of the hot path use) -------------- */
-/* rm::umeyama_transform(CrossStatistics) (micp_localization.cpp:952-953) */
+/* rm::umeyama_transform(CrossStatistics) (micp_localization.cpp:952-953).  A covariance of rank <= 1 (s2 <= 1e-6 s1: one wall seen by a
+ * 2-D lidar, two correspondences) leaves a family of optimal rotations; this returns the SHORTEST one, v1 -> u1 (the
+ * rank-one rule) -- the reference's SVD returns an arbitrary member.  Zero covariance: the identity rotation. */
 rmclhip_status rmclhip_umeyama_transform(const rmclhip_cross_statistics* stats, rmclhip_transform* out);
 /* CrossStatistics::operator+= (micp_localization.cpp:936-937) */
 rmclhip_status rmclhip_cross_statistics_merge(const rmclhip_cross_statistics* a,

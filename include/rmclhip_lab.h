@@ -85,6 +85,13 @@ rmclhip_status rmclhip_debug_tag_retries(unsigned long long* retries_out);
  * Works without the experiments library. */
 rmclhip_status rmclhip_debug_particles_timing(rmclhip_ctx* ctx, int on, float* last_ms);
 
+/* TEST hook of the rotation solve (tests/test_gpu_umeyama.py): out_host[i] = the solve of stats_host[i] by solver 0 = umeyama() on the
+ * host (what rmclhip_umeyama_transform calls; ctx may be null), 1 = umeyama() on the device, 2 = umeyama_fast() on the device (the
+ * moment-form loops' solve with refined reciprocals instead of divisions).  The device solvers run one thread per element, 64 threads
+ * per block.  Any other solver: RMCLHIP_ERR_INVALID.  Works without the experiments library. */
+rmclhip_status rmclhip_debug_solve(rmclhip_ctx* ctx, const rmclhip_cross_statistics* stats_host, uint32_t n, int solver,
+                                   rmclhip_transform* out_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1064,7 +1064,8 @@ static orc_quat mat_to_quat(const double* R)
 }
 
 /* rm::umeyama_transform: C = U S V^T, R = U diag(1,1,sign(det U det V)) V^T,
- * t = model_mean - R dataset_mean; identity when n_meas == 0. */
+ * t = model_mean - R dataset_mean; identity when n_meas == 0.  At rank <= 1 (s2 <= 1e-6 s1) the definition leaves the
+ * completion of U and V open; this library fixes it: the shortest rotation taking v1 to u1 (the rank-one rule). */
 orc_transform orc_umeyama_transform(const orc_cross_statistics* s)
 {
   orc_transform T = orc_transform_identity();
@@ -1072,12 +1073,47 @@ orc_transform orc_umeyama_transform(const orc_cross_statistics* s)
   double C[9], U[9], w[3], V[9];
   for (int i = 0; i < 9; ++i) C[i] = s->covariance[i];
   orc_svd3(C, U, w, V);
-  double S[3] = {1, 1, 1};
-  if (det3(U) * det3(V) < 0) S[2] = -1;
   double R[9];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-    double acc = 0; for (int k = 0; k < 3; ++k) acc += U[3 * i + k] * S[k] * V[3 * j + k];
-    R[3 * i + j] = acc;
+  if (!(w[0] > 0.0)) {
+    /* zero covariance: no rotation */
+    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  } else if (w[1] <= 1e-6 * w[0]) {
+    /* rank <= 1 (an f32 covariance carries ~1e-7 of rounding: s2 below 1e-6 s1 is noise): every rotation taking v1 to u1 is
+     * optimal, and the independently completed U, V above would pick an arbitrary one.  Take the shortest: Rodrigues about
+     * v1 x u1, or, for u1 = -v1, the half turn about an axis perpendicular to v1 (from the coordinate axis of v1's smallest
+     * |component|; components within 1e-6 of each other count as tied and the first of x, y, z wins). */
+    double v[3] = {V[0], V[3], V[6]}, u[3], nu = 0;
+    for (int r = 0; r < 3; ++r) { u[r] = C[3 * r] * v[0] + C[3 * r + 1] * v[1] + C[3 * r + 2] * v[2]; nu += u[r] * u[r]; }
+    nu = sqrt(nu);
+    for (int r = 0; r < 3; ++r) u[r] /= nu;
+    const double c = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+    if (c <= -1.0 + 1e-12) {
+      int k = 0;
+      if (fabs(v[1]) < fabs(v[k]) - 1e-6) k = 1;
+      if (fabs(v[2]) < fabs(v[k]) - 1e-6) k = 2;
+      double a[3] = {0, 0, 0}, na = 0;
+      a[k] = 1;
+      for (int r = 0; r < 3; ++r) { a[r] -= v[k] * v[r]; na += a[r] * a[r]; }
+      na = sqrt(na);
+      for (int r = 0; r < 3; ++r) a[r] /= na;
+      /* half turn about a: R = 2 a a^T - I */
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[3 * i + j] = 2.0 * a[i] * a[j] - (i == j ? 1.0 : 0.0);
+    } else {
+      /* R = I + [k]x + [k]x^2 / (1 + c), k = v1 x u1 */
+      const double k[3] = {v[1] * u[2] - v[2] * u[1], v[2] * u[0] - v[0] * u[2], v[0] * u[1] - v[1] * u[0]};
+      const double K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0};
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+        double kk = 0; for (int l = 0; l < 3; ++l) kk += K[3 * i + l] * K[3 * l + j];
+        R[3 * i + j] = (i == j ? 1.0 : 0.0) + K[3 * i + j] + kk / (1.0 + c);
+      }
+    }
+  } else {
+    double S[3] = {1, 1, 1};
+    if (det3(U) * det3(V) < 0) S[2] = -1;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
+      double acc = 0; for (int k = 0; k < 3; ++k) acc += U[3 * i + k] * S[k] * V[3 * j + k];
+      R[3 * i + j] = acc;
+    }
   }
   T.R = mat_to_quat(R);
   const orc_vec3 Rd = orc_quat_rotate(T.R, s->dataset_mean);

@@ -263,6 +263,7 @@ SIGNATURES = {
     "rmclhip_debug_tag_retries": (_i32, [C.POINTER(C.c_ulonglong)]),
     "rmclhip_debug_trace": (_i32, [_i32, _vp, _sz]),
     "rmclhip_debug_particles_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
+    "rmclhip_debug_solve": (_i32, [_vp, _vp, _u32, _i32, _vp]),
     "rmclhip_comm_destroy": (None, [_vp]),
     "rmclhip_comm_size": (_u32, [_vp]),
     "rmclhip_shard_bounds": (None, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),

@@ -405,6 +405,33 @@ rmclhip_status rmclhip_umeyama_transform(const rmclhip_cross_statistics* s, rmcl
   return RMCLHIP_OK;
 }
 
+// include/rmclhip_lab.h: the three solvers on the same statistics (tests/test_gpu_umeyama.py).  A test hook: it allocates, copies and
+// waits on every call.
+rmclhip_status rmclhip_debug_solve(rmclhip_ctx* ctx, const rmclhip_cross_statistics* stats_host, uint32_t n, int solver,
+                                   rmclhip_transform* out_host) {
+  ApiGuard guard_("rmclhip_debug_solve");
+  if (solver < 0 || solver > 2) return fail(RMCLHIP_ERR_INVALID, "debug_solve: solver must be 0 (host), 1 (device umeyama) or 2 (device umeyama_fast)");
+  if (n == 0) return RMCLHIP_OK;
+  if (!stats_host || !out_host) return fail(RMCLHIP_ERR_INVALID, "debug_solve: null");
+  if (solver == 0) {
+    for (uint32_t i = 0; i < n; ++i) from_x(umeyama(to_cs(stats_host + i)), out_host + i);
+    return RMCLHIP_OK;
+  }
+  if (!ctx) return fail(RMCLHIP_ERR_INVALID, "debug_solve: the device solvers need a context");
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf<cstats> d_in;
+  DevBuf<xform> d_out;
+  hipError_t e = d_in.reserve(n);
+  if (e == hipSuccess) e = d_out.reserve(n);
+  if (e == hipSuccess) e = hipMemcpy(d_in.p, stats_host, static_cast<size_t>(n) * sizeof(cstats), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_debug_solve(d_in.p, n, solver == 2, d_out.p, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out_host, d_out.p, static_cast<size_t>(n) * sizeof(xform), hipMemcpyDeviceToHost);
+  d_in.release();
+  d_out.release();
+  HIPCHK(e);
+  return RMCLHIP_OK;
+}
+
 rmclhip_status rmclhip_cross_statistics_merge(const rmclhip_cross_statistics* a, const rmclhip_cross_statistics* b,
                                               rmclhip_cross_statistics* out) {
   ApiGuard guard_("rmclhip_cross_statistics_merge");

@@ -282,8 +282,8 @@ RM_HD quat mat_to_quat(const double* R) {
 // convergence; Theobald 2005, "QCP"); the eigenvector is a column of adj(K - l I).  The reflection case of the
 // SVD formulation (det < 0 -> diag(1,1,-1)) needs no special handling: the eigenvector IS the best proper
 // rotation.  ~350 dependent fp64 operations instead of ~900 for the scaled-Newton polar iteration used before (a
-// lone lane retires one dependent instruction per ~5 cycles, so this is what the MICP step costs).  Returns false
-// for (nearly) degenerate inputs -- repeated largest eigenvalue, zero matrix --, where the caller falls back to
+// lone lane retires one dependent instruction per ~5 cycles, so this is what the MICP step costs).  Returns kHornDeclined
+// for (nearly) degenerate inputs of rank >= 2 -- repeated largest eigenvalue --, where the caller falls back to
 // the Jacobi SVD, which defines the semantics.  q = (x, y, z, w), normalised.
 // determinant and adjugate of a symmetric 4x4 matrix from its ten entries, by 2x2 sub-determinants (Laplace expansion);
 // written with scalars only -- indexed local arrays would live in scratch memory on the device
@@ -306,7 +306,21 @@ RM_HD double sym4_det(const sym4_minors& m) {
   return m.s0 * m.c5 - m.s1 * m.c4 + m.s2 * m.c3 + m.s3 * m.c2 - m.s4 * m.c1 + m.s5 * m.c0;
 }
 
-RM_HD bool horn_quaternion(const double* C, double* q) {
+// what horn_quaternion / horn_quaternion_fast return
+constexpr int kHornDeclined = 0;   // (nearly) repeated largest eigenvalue, no convergence: the caller takes the Jacobi SVD
+constexpr int kHornSolved = 1;
+constexpr int kHornRankLe1 = 2;    // s2 <= 1e-6 s1 (or C = 0), nothing solved: the caller takes rank1_quaternion()
+
+// Rank <= 1 from the quartic's own coefficients: its roots are the sums +-s1 +-s2 +-s3 of the singular values, so
+// c0 = det K = |C|_F^4 - 4 |adj C|_F^2 with |adj C|_F^2 = s1^2 s2^2 + s1^2 s3^2 + s2^2 s3^2, and with ss = |C|_F^2
+// "ss^2 - c0 <= 4e-12 ss^2" is s2 <= 1e-6 s1 -- an f32 covariance carries ~1e-7 of relative rounding, a second singular value below
+// that is noise.  (c0 carries a few 1e-16 ss^2 of rounding: three orders below the threshold.)
+RM_HD bool horn_rank_le1(double ss, double c0) {
+  const double s4 = ss * ss;
+  return !(s4 - c0 > 4e-12 * s4);
+}
+
+RM_HD int horn_quaternion(const double* C, double* q) {
   // C[3*r + c] = sum m_r d_c  =>  S_ab = sum d_a m_b = C[3*b + a]
   const double Sxx = C[0], Sxy = C[3], Sxz = C[6], Syx = C[1], Syy = C[4], Syz = C[7], Szx = C[2], Szy = C[5], Szz = C[8];
   sym4 K;
@@ -315,10 +329,11 @@ RM_HD bool horn_quaternion(const double* C, double* q) {
   K.k22 = -Sxx + Syy - Szz; K.k23 = Syz + Szy;
   K.k33 = -Sxx - Syy + Szz;
   const double ss = ((Sxx * Sxx + Sxy * Sxy + Sxz * Sxz) + (Syx * Syx + Syy * Syy + Syz * Syz)) + (Szx * Szx + Szy * Szy + Szz * Szz);
-  if (!(ss > 0.0)) return false;
+  if (!(ss > 0.0)) return kHornRankLe1;   // the zero matrix
   const double c2 = -2.0 * ss;
   const double c1 = -8.0 * det3(C);
   const double c0 = sym4_det(sym4_sub(K));
+  if (horn_rank_le1(ss, c0)) return kHornRankLe1;   // decided before anything is solved: the eigenvector of such a K is noise
   // largest eigenvalue of K = sum of the singular values of S <= sqrt(3) * |S|_F (Cauchy-Schwarz); starting Newton's
   // iteration at or above the largest root of the quartic keeps it monotone (P convex there), so this tighter bound
   // (the classic one is sqrt(trace K^2) = 2 |S|_F) saves iterations without changing the limit
@@ -346,7 +361,7 @@ RM_HD bool horn_quaternion(const double* C, double* q) {
     lam -= step;
     if (step <= 1e-14 * lam0) { converged = true; break; }
   }
-  if (!converged) return false;
+  if (!converged) return kHornDeclined;
   K.k00 -= lam; K.k11 -= lam; K.k22 -= lam; K.k33 -= lam;
   const sym4_minors m = sym4_sub(K);
   // adj(K - l I) = const * v v^T (symmetric): diagonal entries ~ v_c^2, take the column of the largest one
@@ -364,9 +379,9 @@ RM_HD bool horn_quaternion(const double* C, double* q) {
   if (fabs(a11) > dbest) { v0 = a01; v1 = a11; v2 = a12; v3 = a13; dbest = fabs(a11); }
   if (fabs(a22) > dbest) { v0 = a02; v1 = a12; v2 = a22; v3 = a23; dbest = fabs(a22); }
   if (fabs(a33) > dbest) { v0 = a03; v1 = a13; v2 = a23; v3 = a33; dbest = fabs(a33); }
-  if (!(dbest > 1e-10 * lam0 * lam0 * lam0)) return false;  // repeated largest eigenvalue
+  if (!(dbest > 1e-10 * lam0 * lam0 * lam0)) return kHornDeclined;  // repeated largest eigenvalue
   const double n = sqrt((v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3));
-  if (!(n > 0.0)) return false;
+  if (!(n > 0.0)) return kHornDeclined;
   const double rn = 1.0 / n;
   double w = v0 * rn, x = v1 * rn, y = v2 * rn, z = v3 * rn;
   // sign convention of mat_to_quat (Shepperd): w > 0 when trace R > 0 (|w| > 1/2), else the largest of x, y, z positive
@@ -378,7 +393,59 @@ RM_HD bool horn_quaternion(const double* C, double* q) {
   }
   if (lead < 0.0) { w = -w; x = -x; y = -y; z = -z; }
   q[0] = x; q[1] = y; q[2] = z; q[3] = w;
-  return true;
+  return kHornSolved;
+}
+
+// ---- covariances of rank <= 1 ("the rank-one rule") -----------------------------------------------
+// A scan of ONE wall by a 2-D lidar, or two correspondences, leave a cross-covariance of rank one: C = s1 u1 v1^T.  Every
+// rotation that takes v1 to u1 attains the optimum then, and an SVD that completes U and V independently returns an arbitrary
+// member of that family (a quarter turn for a wall seen 1 degree off).  The library returns the SHORTEST rotation of the family.
+// horn_quaternion() detects the case from its own coefficients (kHornRankLe1) before it solves anything.
+//
+// The rotation of a covariance of rank <= 1, q = (x, y, z, w).  v1 = right singular vector of s1: the largest row of C is
+// s1 u1_r v1^T up to s2 / s1, and one step of the power iteration on C^T C (v <- C^T (C v)) takes that error to its cube;
+// u1 = C v1 / |C v1|.  R = the shortest arc v1 -> u1; for u1 = -v1 (u1 . v1 <= -1 + 1e-12) the half turn about the axis
+// perpendicular to v1 built from the coordinate axis of v1's smallest |component| (ties -- components within 1e-6 of each
+// other, the noise the detector discards -- go to the first of x, y, z).  The zero matrix gives the identity.
+RM_HD void rank1_quaternion(const double* C, double* q) {
+  q[0] = 0.0; q[1] = 0.0; q[2] = 0.0; q[3] = 1.0;
+  const double r0 = C[0] * C[0] + C[1] * C[1] + C[2] * C[2], r1 = C[3] * C[3] + C[4] * C[4] + C[5] * C[5], r2 = C[6] * C[6] + C[7] * C[7] + C[8] * C[8];
+  double vx = C[0], vy = C[1], vz = C[2], rb = r0;
+  if (r1 > rb) { vx = C[3]; vy = C[4]; vz = C[5]; rb = r1; }
+  if (r2 > rb) { vx = C[6]; vy = C[7]; vz = C[8]; rb = r2; }
+  if (!(rb > 0.0)) return;
+  double s = 1.0 / sqrt(rb);   // normalised first: the products below stay in range at every scale of C
+  vx *= s; vy *= s; vz *= s;
+  double ux = C[0] * vx + C[1] * vy + C[2] * vz, uy = C[3] * vx + C[4] * vy + C[5] * vz, uz = C[6] * vx + C[7] * vy + C[8] * vz;
+  s = 1.0 / sqrt(ux * ux + uy * uy + uz * uz);
+  ux *= s; uy *= s; uz *= s;
+  vx = C[0] * ux + C[3] * uy + C[6] * uz; vy = C[1] * ux + C[4] * uy + C[7] * uz; vz = C[2] * ux + C[5] * uy + C[8] * uz;
+  s = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
+  vx *= s; vy *= s; vz *= s;
+  ux = C[0] * vx + C[1] * vy + C[2] * vz; uy = C[3] * vx + C[4] * vy + C[5] * vz; uz = C[6] * vx + C[7] * vy + C[8] * vz;
+  s = 1.0 / sqrt(ux * ux + uy * uy + uz * uz);
+  ux *= s; uy *= s; uz *= s;
+  const double d = ux * vx + uy * vy + uz * vz;
+  double x, y, z, w;
+  if (d <= -1.0 + 1e-12) {
+    double ax = 1.0, ay = 0.0, az = 0.0, vk = vx, best = fabs(vx);
+    if (fabs(vy) < best - 1e-6) { ax = 0.0; ay = 1.0; vk = vy; best = fabs(vy); }
+    if (fabs(vz) < best - 1e-6) { ax = 0.0; ay = 0.0; az = 1.0; vk = vz; }
+    x = ax - vk * vx; y = ay - vk * vy; z = az - vk * vz; w = 0.0;
+  } else {
+    x = vy * uz - vz * uy; y = vz * ux - vx * uz; z = vx * uy - vy * ux; w = 1.0 + d;
+  }
+  const double rn = 1.0 / sqrt((x * x + y * y) + (z * z + w * w));
+  x *= rn; y *= rn; z *= rn; w *= rn;
+  // sign convention of mat_to_quat, as horn_quaternion
+  double lead = w;
+  if (!(fabs(w) > 0.5)) {
+    if (x * x > y * y && x * x > z * z) lead = x;
+    else if (y * y > z * z) lead = y;
+    else lead = z;
+  }
+  if (lead < 0.0) { w = -w; x = -x; y = -y; z = -z; }
+  q[0] = x; q[1] = y; q[2] = z; q[3] = w;
 }
 
 RM_HD xform umeyama(const cstats& s) {
@@ -387,7 +454,9 @@ RM_HD xform umeyama(const cstats& s) {
   double C[9];
   for (int i = 0; i < 9; ++i) C[i] = static_cast<double>(s.covariance[i]);
   double q[4];
-  if (horn_quaternion(C, q)) {
+  const int horn = horn_quaternion(C, q);
+  if (horn == kHornRankLe1) rank1_quaternion(C, q);
+  if (horn != kHornDeclined) {
     T.R.x = static_cast<float>(q[0]); T.R.y = static_cast<float>(q[1]);
     T.R.z = static_cast<float>(q[2]); T.R.w = static_cast<float>(q[3]);
   } else {

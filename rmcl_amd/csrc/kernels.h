@@ -334,6 +334,8 @@ hipError_t launch_micp_iter(const float* dataset_points, const uint8_t* dataset_
 // batch: per pose finalize + umeyama -> Tdelta (sensor->base conjugated), stats
 hipError_t launch_batch_solve(const double* partials, uint32_t nblocks, uint32_t nposes, xform Tsb,
                               xform* Tdelta_out, cstats* stats_out, hipStream_t s);
+// rmclhip_debug_solve: out[i] = umeyama(stats[i]) (fast = 0) or umeyama_fast(stats[i]) (fast = 1), one thread per element, 64 per block
+hipError_t launch_debug_solve(const cstats* stats, uint32_t n, int fast, xform* out, hipStream_t s);
 hipError_t launch_dataset_from_ranges(const float* ranges, const float* model_tab, uint32_t kind, uint32_t W,
                                       uint32_t H, f3 orig, const float* pin_fc, float rmin, float rmax, float* points,
                                       uint8_t* mask, uint32_t* n_valid, hipStream_t s);

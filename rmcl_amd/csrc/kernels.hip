@@ -122,6 +122,10 @@ __device__ __forceinline__ cstats finalize_pose(const double* partials, uint32_t
     s.model_mean = mk3(static_cast<float>(mm[0]), static_cast<float>(mm[1]), static_cast<float>(mm[2]));
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) s.covariance[3 * r + c] = static_cast<float>(acc[6 + 3 * r + c] / n - mm[r] * md[c]);
+    // ONE correspondence has no covariance.  The streaming sums give exactly that; sums evaluated from the moments leave their own
+    // rounding (~1e-15) instead, a matrix of noise the solve would turn into an arbitrary rotation
+    if (n == 1.0)
+      for (int k = 0; k < 9; ++k) s.covariance[k] = 0.0f;
     s.n_meas = static_cast<uint32_t>(n);
   }
   return s;
@@ -422,8 +426,8 @@ __device__ __forceinline__ double rsq_nr(double x) {
   return y;
 }
 
-// horn_quaternion (devmath.h) with rcp_nr / rsq_nr; same formulas, same fall-back condition (false -> the caller takes umeyama())
-__device__ __forceinline__ bool horn_quaternion_fast(const double* C, double* q) {
+// horn_quaternion (devmath.h) with rcp_nr / rsq_nr; same formulas, same return codes (anything but kHornSolved -> the caller takes umeyama())
+__device__ __forceinline__ int horn_quaternion_fast(const double* C, double* q) {
   const double Sxx = C[0], Sxy = C[3], Sxz = C[6], Syx = C[1], Syy = C[4], Syz = C[7], Szx = C[2], Szy = C[5], Szz = C[8];
   sym4 K;
   K.k00 = Sxx + Syy + Szz; K.k01 = Syz - Szy; K.k02 = Szx - Sxz; K.k03 = Sxy - Syx;
@@ -431,10 +435,11 @@ __device__ __forceinline__ bool horn_quaternion_fast(const double* C, double* q)
   K.k22 = -Sxx + Syy - Szz; K.k23 = Syz + Szy;
   K.k33 = -Sxx - Syy + Szz;
   const double ss = ((Sxx * Sxx + Sxy * Sxy + Sxz * Sxz) + (Syx * Syx + Syy * Syy + Syz * Syz)) + (Szx * Szx + Szy * Szy + Szz * Szz);
-  if (!(ss > 0.0)) return false;
+  if (!(ss > 0.0)) return kHornRankLe1;   // the zero matrix
   const double c2 = -2.0 * ss;
   const double c1 = -8.0 * det3(C);
   const double c0 = sym4_det(sym4_sub(K));
+  if (horn_rank_le1(ss, c0)) return kHornRankLe1;   // decided before anything is solved: the eigenvector of such a K is noise
   const double lam0 = sqrt(3.0 * ss) * (1.0 + 1e-12);
   double lam = lam0;
   {
@@ -455,7 +460,7 @@ __device__ __forceinline__ bool horn_quaternion_fast(const double* C, double* q)
     lam -= step;
     if (step <= 1e-14 * lam0) { converged = true; break; }
   }
-  if (!converged) return false;
+  if (!converged) return kHornDeclined;
   K.k00 -= lam; K.k11 -= lam; K.k22 -= lam; K.k33 -= lam;
   const sym4_minors m = sym4_sub(K);
   const double a00 = K.k11 * m.c5 - K.k12 * m.c4 + K.k13 * m.c3;
@@ -472,9 +477,9 @@ __device__ __forceinline__ bool horn_quaternion_fast(const double* C, double* q)
   if (fabs(a11) > dbest) { v0 = a01; v1 = a11; v2 = a12; v3 = a13; dbest = fabs(a11); }
   if (fabs(a22) > dbest) { v0 = a02; v1 = a12; v2 = a22; v3 = a23; dbest = fabs(a22); }
   if (fabs(a33) > dbest) { v0 = a03; v1 = a13; v2 = a23; v3 = a33; dbest = fabs(a33); }
-  if (!(dbest > 1e-10 * lam0 * lam0 * lam0)) return false;  // repeated largest eigenvalue
+  if (!(dbest > 1e-10 * lam0 * lam0 * lam0)) return kHornDeclined;  // repeated largest eigenvalue
   const double n2 = (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
-  if (!(n2 > 0.0)) return false;
+  if (!(n2 > 0.0)) return kHornDeclined;
   const double rn = rsq_nr(n2);
   double w = v0 * rn, x = v1 * rn, y = v2 * rn, z = v3 * rn;
   double lead = w;
@@ -485,7 +490,7 @@ __device__ __forceinline__ bool horn_quaternion_fast(const double* C, double* q)
   }
   if (lead < 0.0) { w = -w; x = -x; y = -y; z = -z; }
   q[0] = x; q[1] = y; q[2] = z; q[3] = w;
-  return true;
+  return kHornSolved;
 }
 
 // umeyama() for the moment-form loops' one solving lane; degenerate inputs take the generic path
@@ -495,7 +500,8 @@ __device__ __forceinline__ xform umeyama_fast(const cstats& s) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) C[i] = static_cast<double>(s.covariance[i]);
   double q[4];
-  if (!horn_quaternion_fast(C, q)) return umeyama(s);
+  // rank <= 1 (devmath.h: the rank-one rule) and what Horn declines go to umeyama()
+  if (horn_quaternion_fast(C, q) != kHornSolved) return umeyama(s);
   xform T = xidentity();
   T.R.x = static_cast<float>(q[0]); T.R.y = static_cast<float>(q[1]);
   T.R.z = static_cast<float>(q[2]); T.R.w = static_cast<float>(q[3]);
@@ -514,6 +520,10 @@ __device__ __forceinline__ cstats cstats_from_sums(const double* acc) {
     s.model_mean = mk3(static_cast<float>(mm[0]), static_cast<float>(mm[1]), static_cast<float>(mm[2]));
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) s.covariance[3 * r + c] = static_cast<float>(acc[6 + 3 * r + c] * rn - mm[r] * md[c]);
+    // ONE correspondence has no covariance.  The streaming sums give exactly that; sums evaluated from the moments leave their own
+    // rounding (~1e-15) instead, a matrix of noise the solve would turn into an arbitrary rotation
+    if (n == 1.0)
+      for (int k = 0; k < 9; ++k) s.covariance[k] = 0.0f;
     s.n_meas = static_cast<uint32_t>(n);
   }
   return s;
@@ -1167,6 +1177,14 @@ __global__ void __launch_bounds__(64) k_batch_solve(const double* __restrict__ p
     Tdelta[pose] = xmul(xmul(Tsb, Ts), xinv(Tsb));
     if (stats) stats[pose] = s;
   }
+}
+
+// rmclhip_debug_solve (include/rmclhip_lab.h): the device's solvers on caller-supplied statistics, one thread per element
+__global__ void __launch_bounds__(64) k_debug_solve(const cstats* __restrict__ stats, uint32_t n, int fast, xform* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const cstats s = stats[i];
+  out[i] = fast ? umeyama_fast(s) : umeyama(s);
 }
 
 // MICPSphericalSensorCPU::unpackMessage / MICPO1DnSensorCPU::unpackMessage (dataset construction)
@@ -2746,6 +2764,12 @@ hipError_t launch_micp_init(MicpState* state, hipStream_t s) {
 hipError_t launch_micp_close(const double* partials, uint32_t nblocks, const MicpCall* call, const MicpState* state,
                              MicpState* state_out, unsigned long long* done, hipStream_t s) {
   hipLaunchKernelGGL(k_micp_close, dim3(1), dim3(64), 0, s, partials, nblocks, call, state, state_out, done);
+  return hipGetLastError();
+}
+
+hipError_t launch_debug_solve(const cstats* stats, uint32_t n, int fast, xform* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_debug_solve, dim3((n + 63u) / 64u), dim3(64), 0, s, stats, n, fast, out);
   return hipGetLastError();
 }
 

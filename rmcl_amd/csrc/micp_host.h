@@ -212,6 +212,10 @@ inline cstats micp_stats_from_sums(const double* acc) {
     s.model_mean = mk3(static_cast<float>(mm[0]), static_cast<float>(mm[1]), static_cast<float>(mm[2]));
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) s.covariance[3 * r + c] = static_cast<float>(acc[6 + 3 * r + c] / n - mm[r] * md[c]);
+    // ONE correspondence has no covariance.  The streaming sums give exactly that; sums evaluated from the moments leave their own
+    // rounding (~1e-15) instead, a matrix of noise the solve would turn into an arbitrary rotation
+    if (n == 1.0)
+      for (int k = 0; k < 9; ++k) s.covariance[k] = 0.0f;
     s.n_meas = static_cast<uint32_t>(n);
   }
   return s;

@@ -98,6 +98,16 @@ def umeyama_transform(s):
     return out[0].copy()
 
 
+def debug_solve(ctx, stats, solver):
+    """rmclhip_debug_solve (include/rmclhip_lab.h, a test hook): the rotation solve of every CrossStatistics of `stats` by solver
+    0 = umeyama() on the host (ctx may be None), 1 = umeyama() on the device, 2 = umeyama_fast() on the device."""
+    stats = np.ascontiguousarray(stats, dtype=CROSS_STATISTICS).reshape(-1)
+    out = np.zeros(len(stats), dtype=TRANSFORM)
+    h = ctx.handle if ctx is not None else None
+    _capi.check(_capi.lib().rmclhip_debug_solve(h, _ptr(stats), len(stats), int(solver), _ptr(out)))
+    return out
+
+
 def spherical_model(phi_min, phi_inc, phi_n, theta_min, theta_inc, theta_n, range_min, range_max):
     """rmagine::SphericalModel (fields: rmcl_ros/src/util/conversions.cpp:22-34)."""
     m = _capi.SphericalModel()

@@ -54,6 +54,30 @@ def correct_once(mesh, model, Tsb, Tbo, Tom, ds_points, ds_mask, n_iter, max_dis
     return T_onew_oold, merged, traj
 
 
+def correct_once_multi(mesh, sensors, Tom, n_iter, convergence_progress=0.0):
+    """MICPLocalizationNode::correctOnce with several sensors (micp_localization.cpp:921-963): sensors = [(model, Tsb, Tbo,
+    ds_points, ds_mask, max_dist, adaptive_min, merge_weight_multiplier)].  Returns (T_onew_oold, merged unweighted stats, the weighted
+    merged stats every iteration solved)."""
+    ident = orc.transform()
+    T_onew_oold = ident
+    merged = orc.cs_identity()
+    sims = [mesh.simulate_spherical(model, Tsb, orc.tmult(Tom, Tbo), bvh=True) for model, Tsb, Tbo, *_ in sensors]
+    solved = []
+    for _ in range(n_iter):
+        merged, merged_w = orc.cs_identity(), orc.cs_identity()
+        for sim, (model, Tsb, Tbo, ds_points, ds_mask, max_dist, adaptive_min, w) in zip(sims, sensors):
+            md = orc.adaptive_max_dist(max_dist, adaptive_min, convergence_progress)
+            T_bnew_bold = orc.tmult(orc.tmult(orc.tinv(Tbo), T_onew_oold), Tbo)
+            Cs_o = orc.cs_transform(Tbo, compute_cross_statistics_b(sim, ds_points, ds_mask, Tsb, T_bnew_bold, md))
+            Cs_w = Cs_o.copy()
+            Cs_w["n_meas"] = np.uint32(int(float(Cs_w["n_meas"]) * w))   # :934 truncates
+            merged = orc.cs_merge(merged, Cs_o)
+            merged_w = orc.cs_merge(merged_w, Cs_w)
+        solved.append(merged_w)
+        T_onew_oold = orc.tmult(T_onew_oold, orc.umeyama(merged_w))
+    return T_onew_oold, merged, solved
+
+
 def correct_batch(mesh, model, Tsb, Tbm, ds_points, ds_mask, max_dist, nthreads=1):
     """v1 SphereCorrector::correct: per pose raycast + reduce (Tpre = I) + Umeyama;
     Tdelta_b = Tsb * T_s * ~Tsb."""
