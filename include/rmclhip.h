@@ -78,7 +78,8 @@ typedef struct { rmclhip_vec3 orig, dir; float range; float cov[9]; } rmclhip_ra
 /* sensor_update.* parameters, defaults PCDSensorUpdaterEmbree.cpp:122-134
  * (== optix/EvaluationDataOptix.hpp:62-81 minus pointers) */
 typedef struct {
-  float dist_sigma;                 /* 2.0  */
+  float dist_sigma;                 /* 2.0; >= 1e-10f (rmclhip_pf_set_params refuses less: the peak eval 1 / sqrt(2 pi sigma^2)
+                                     *     must stay below 2^32, the top of the update's fixed-point accumulators) */
   float real_hit_sim_miss_error;    /* 100  */
   float real_miss_sim_hit_error;    /* 100  */
   float real_miss_sim_miss_error;   /* 0    */

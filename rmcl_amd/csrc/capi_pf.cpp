@@ -51,6 +51,10 @@ rmclhip_status rmclhip_pf_set_params(rmclhip_pf* f, const rmclhip_pf_params* p) 
   if (p->real_hit_sim_miss_error != p->real_hit_sim_miss_error || p->real_miss_sim_hit_error != p->real_miss_sim_hit_error ||
       p->real_miss_sim_miss_error != p->real_miss_sim_miss_error || p->dist_sigma != p->dist_sigma)
     return fail(RMCLHIP_ERR_INVALID, "pf_set_params: NaN parameter");
+  // the accumulating update's first fixed-point row tops out at 2^32 (kernels.hip: kAccBins1): the peak eval 1 / sqrt(2 pi sigma^2) fits
+  // it down to dist_sigma = 1e-10f (3.99e9); below, a particle on the truth would be poisoned to NaN where the reference's float chain
+  // still returns a finite value (and below 1e-19 sigma^2 underflows to 0 and the reference itself gives NaN)
+  if (p->dist_sigma < 1e-10f) return fail(RMCLHIP_ERR_INVALID, "pf_set_params: dist_sigma must be >= 1e-10");
   if (p->correspondence_type > 3u)
     return fail(RMCLHIP_ERR_INVALID, "pf_set_params: correspondence_type must be 0 (RCC), 1 (CPC), 2 (RCC, Embree rules) or 3 (RCC, OptiX rules)");
   f->params = *p;

@@ -1318,7 +1318,8 @@ __device__ __forceinline__ void leaf_pair(const uint32_t* __restrict__ tris, uin
 // exp(arg) * inv_den for arg <= 0 in float arithmetic: arg log2(e) split Cody-Waite style into an integer n and a residual r in
 // [-0.5, 0.5] (one fused multiply-add against each half of log2 e: |error of r| ~ 1e-8), 2^r by v_exp_f32 (1 ulp), the scale before
 // the exponent so that results below 2^-126 round like any other denormal.  Below 2^-149 the result is 0.  A NaN argument gives 0, not
-// NaN (fmaxf is maxnum): it can only come from NaN penalty parameters, which rmclhip_pf_set_params rejects.
+// NaN (fmaxf is maxnum): NaN penalty parameters are rejected by rmclhip_pf_set_params, and a NaN geometric error (maps
+// beyond float32's products: chain200, chain2000, nested200) is caught by the caller before the value is used.
 __device__ __forceinline__ float pf_eval_fast(float arg, float inv_den) {
   const float kL2eHi = 1.44269502162933349609375f, kL2eLo = 1.925963033500011e-08f;
   const float n = fmaxf(rintf(arg * kL2eHi), -400.0f);
@@ -1451,7 +1452,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAccum
           const double e1 = static_cast<double>(ev);
           const double w = (k < s_kc[pi]) ? s_wu[pi] : p.gpow[p.n_beams - 1u - k] * p.inv_max1;
           unsigned long long* row = s_acc + pi * static_cast<uint32_t>(kAccWords);
-          bool ok = e1 < __builtin_inf();                // false for NaN and +inf
+          // (a NaN error -- a geometric one: t = inf against a unit normal of 0 where the intersector's products leave float32, at 1e16 m
+          //  on chain200 -- must poison the particle as exp(NaN) poisons the reference's chain; pf_eval_fast turns it into 0)
+          bool ok = (error == error) && e1 < __builtin_inf();   // false for NaN and +inf
           if (ok && e1 > 0.0) {
             const double t1 = w * e1;
             ok = acc_add(row, kAccBins1, kAccEmin1, t1) && acc_add(row + kAccBins1, kAccBins2, kAccEmin2, t1 * e1);
