@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -1153,6 +1154,34 @@ inline void packVisualization(const Context& ctx, DeviceView<const Transform> po
   check(rmclhip_particles_pack_visualization(ctx.handle(), poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), max_n_meas, out.raw(), 1));
 }
 
+// The surface constraint of the motion update (rmclhip.h, "surface-constrained motion"; the reference lists a MotionUpdater constrained
+// to the mesh surface as open, docs/RMCL.md:69-72).  SurfaceParams{} holds the library's defaults: axis 0 (map +z), height 0,
+// probe_up 0.3, probe_down 1.0, min_up_cos 0.7, align 0, on_miss 0.
+struct SurfaceParams : rmclhip_surface_params {
+  SurfaceParams() { rmclhip_surface_params_default(this); }
+};
+using SurfaceStats = rmclhip_surface_stats;
+// the standalone pass, e.g. behind initSamplesUniform or a resampler's noise: every particle `height` above the mesh below it (and, with
+// align, its body z on the face normal), in place; max_n_meas: what on_miss writes (rmclhip_pf_params::max_n_meas)
+inline SurfaceStats constrainToSurface(const HipMapPtr& map, DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
+                                       const SurfaceParams& params, uint32_t max_n_meas = 10000u) {
+  if (!map) throw std::runtime_error("NO MAP");
+  if (poses.size() != attrs.size()) throw std::runtime_error("constrainToSurface: poses.size() != attrs.size()");
+  rmclhip_pf* h = nullptr;
+  check(rmclhip_pf_create(map->context()->handle(), map->handle(), &h));
+  rmclhip_pf_params pp{2.0f, 100.0f, 100.0f, 0.0f, {0.05f, 80.0f}, max_n_meas, 0u};
+  SurfaceStats st{};
+  rmclhip_status rc = rmclhip_pf_set_params(h, &pp);
+  if (rc == RMCLHIP_OK) rc = rmclhip_pf_constrain_to_surface(h, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &params, &st);
+  const std::string msg = rc == RMCLHIP_OK ? std::string() : std::string(rmclhip_last_error());
+  rmclhip_pf_destroy(h);
+  if (rc != RMCLHIP_OK) throw std::runtime_error(msg);
+  return st;
+}
+inline SurfaceStats constrainToSurface(const HipMapPtr& map, ParticleCloud<VRAM_HIP>& cloud, const SurfaceParams& params, uint32_t max_n_meas = 10000u) {
+  return constrainToSurface(map, cloud.posesView(), cloud.attrsView(), params, max_n_meas);
+}
+
 // The particle filter of ONE process over several devices (rmclhip_comm + rmclhip_pf_sharded: RCCL ncclCommInitAll, weight
 // all-gather, moment all-reduces): sensor update, pose estimate (RmclNode::estimateStats, rmcl_localization.cpp:642-731) and
 // the distributed gladiator tournament for the single-process node (rmcl_localization.cpp:482-552).  The cloud lives in the
@@ -1242,6 +1271,20 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
                                   resample, &cfg, seed, step_index, &st));
     return st;
   }
+  // the surface constraint of motionUpdate and step on every device's block (nullopt: off), and the standalone pass on the sharded
+  // cloud; the devices' counts are summed on the host
+  void setSurface(const std::optional<SurfaceParams>& params) { check(rmclhip_pf_sharded_set_surface(h_, params ? &*params : nullptr)); }
+  SurfaceStats constrainToSurface(const SurfaceParams& params) {
+    SurfaceStats st{};
+    check(rmclhip_pf_sharded_set_params(h_, &config_));
+    check(rmclhip_pf_sharded_constrain_to_surface(h_, &params, &st));
+    return st;
+  }
+  SurfaceStats surfaceStats() const {
+    SurfaceStats st{};
+    check(rmclhip_pf_sharded_get_surface_stats(h_, &st));
+    return st;
+  }
   void resample(const rmclhip_gladiator_config& cfg, uint64_t seed, uint32_t step) { check(rmclhip_pf_sharded_resample(h_, &cfg, seed, step)); }
   void resampleResidual(const rmclhip_gladiator_config& cfg, uint64_t seed, uint32_t step) { check(rmclhip_pf_sharded_resample_residual(h_, &cfg, seed, step)); }
 
@@ -1255,9 +1298,12 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
 
 // rmcl::TFMotionUpdaterGPU (+ the wall-collision test of TFMotionUpdaterCPU) on gfx950: MotionUpdater<MemT>.
 // The odometry lookup (TF) and the forget rate (TFMotionUpdaterCPU.cpp:172-174) stay with the caller.
+// surface: set, the particles are kept on the mesh in the same launch (and the collision segment is lifted by the step height).
 class TFMotionUpdaterHip : public SensorUpdaterBase {
  public:
   bool check_collision = true;
+  std::optional<SurfaceParams> surface;
+  uint32_t max_n_meas = 10000u;   // what a killed particle's n_meas becomes (rmclhip_pf_params::max_n_meas)
   explicit TFMotionUpdaterHip(HipMapPtr map) : map_(std::move(map)) {
     if (!map_) throw std::runtime_error("NO MAP");
   }
@@ -1268,9 +1314,19 @@ class TFMotionUpdaterHip : public SensorUpdaterBase {
   ParticleUpdateResults update(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
                                const Transform& T_bnew_bold, double forget_rate) {
     init();
+    rmclhip_pf_params pp{2.0f, 100.0f, 100.0f, 0.0f, {0.05f, 80.0f}, max_n_meas, 0u};
+    check(rmclhip_pf_set_params(h_, &pp));
+    check(rmclhip_pf_set_surface(h_, surface ? &*surface : nullptr));
     check(rmclhip_pf_motion_update(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &T_bnew_bold,
                                    forget_rate, check_collision ? 1 : 0));
     return {};
+  }
+  // counts of the last constrained update (zeros before the first)
+  SurfaceStats surfaceStats() {
+    init();
+    SurfaceStats st{};
+    check(rmclhip_pf_get_surface_stats(h_, &st));
+    return st;
   }
 
  private:

@@ -96,6 +96,20 @@ typedef struct {
                                      *     tmax = 1e4, every hit is a sim hit (no sensor_range.min test) */
 } rmclhip_pf_params;
 
+/* The surface constraint of the motion update (rmclhip_pf_set_surface / rmclhip_pf_constrain_to_surface below state the rule);
+ * rmclhip_surface_params_default fills the values in brackets. */
+typedef struct {
+  uint32_t axis;        /* [0] 0 = map +z, 1 = the particle's own body z, R * (0, 0, 1) */
+  float height;         /* [0.0] base frame above the contact point, metres; finite, >= 0 */
+  float probe_up;       /* [0.3] the step height the robot climbs; finite, >= 0 */
+  float probe_down;     /* [1.0] how far below the contact point the surface may be; finite, >= 0 */
+  float min_up_cos;     /* [0.7] faces with |n . a| below it are walls, not ground; in [0, 1] */
+  uint32_t align;       /* [0] 0 = position only, 1 = also put body z on the face normal */
+  uint32_t on_miss;     /* [0] 0 = leave a particle without ground as it is, 1 = likelihood {0, 0, max_n_meas} as the collision test writes it */
+} rmclhip_surface_params;
+/* what the last constrained call did: n_particles = n_snapped + n_missed + n_steep */
+typedef struct { uint32_t n_particles, n_snapped, n_missed, n_steep; } rmclhip_surface_stats;
+
 /* sensor_msgs/PointCloud2 layout of the fields this path reads (datatype: PointField FLOAT32 = 7, FLOAT64 = 8) and
  * the row / column sub-sampling of rmcl::FilterOptions2D (scan_operations.cpp:41-52) */
 typedef struct {
@@ -665,6 +679,41 @@ rmclhip_status rmclhip_pf_set_error_output(rmclhip_pf* pf, float* errors_dev);
 rmclhip_status rmclhip_pf_motion_update(rmclhip_pf* pf, rmclhip_transform* poses_dev,
                                         rmclhip_particle_attributes* attrs_dev, uint32_t n_particles,
                                         const rmclhip_transform* T_bnew_bold, double forget_rate, int check_collision);
+/* ---- surface-constrained motion: keep the particles of a ground robot on the mesh it drives on ----------------------------------
+ * (the reference lists it as open, docs/RMCL.md:69-72: "Provide a MotionUpdater constrained to the mesh surface".)  One short ray per
+ * particle; z, and with `align` roll and pitch, stop being hypotheses the sensor update has to kill.  Per particle (R, t), every
+ * operation in float32 and in this order (the library is built without contraction; tests/surface_ref.py restates it in numpy):
+ *   1. a = (0, 0, 1) (axis 0) or R * (0, 0, 1) (axis 1, the quaternion rotation of rmclhip_transform_mult).  Componentwise
+ *      c = t - height * a (the contact point), O = c + probe_up * a, D = -a, tfar = probe_up + probe_down.
+ *      A pose with a non-finite component of t or R gets no ray and counts as a miss.
+ *   2. closest hit of (O, D) on (0, tfar] with the traversal's rule (min t, then min face id).  No hit: class MISS.
+ *   3. n = the face's unit normal, d = (n.x * a.x + n.y * a.y) + n.z * a.z; d < 0: n = -n, d = -d (a map has no consistent winding).
+ *      !(d >= min_up_cos): class STEEP.
+ *   4. class SNAP: p = O + D * t_hit, t' = p + height * a (componentwise, product first).
+ *   5. align: zb = R * (0, 0, 1); w = 1 + ((zb.x * n.x + zb.y * n.y) + zb.z * n.z); w < 1e-6 (upside down): q = (R * (1, 0, 0), 0), the
+ *      half turn about the body's x; else q = (zb x n, w), the cross product unfused (zb.y * n.z - zb.z * n.y, ...).  normalise(q) =
+ *      q / sqrt(((x * x + y * y) + z * z) + w * w), four divisions.  R' = normalise(normalise(q) (x) R): the heading changes by that
+ *      shortest arc only.  (The shortest-arc construction of the rank-one Umeyama rule works in double and picks another half-turn axis;
+ *      it is not shared.)
+ *   6. MISS and STEEP leave the pose bit for bit; on_miss = 1 sets their likelihood to {0, 0, max_n_meas}.  state_sigma is never touched.
+ * In rmclhip_pf_motion_update the constraint runs on the MOVED pose, in the same launch.  With check_collision != 0 the collision
+ * segment is then lifted by the step height: it runs from O(old pose) to O(moved, not yet constrained pose) -- each with its own a --
+ * so what is lower than probe_up is climbed and what is taller is a wall; length, the 1e-5 threshold and the kill are unchanged, and
+ * the constraint runs whether or not the particle was killed.
+ * RMCLHIP_ERR_INVALID, before anything is launched: height, probe_up or probe_down negative or not finite; min_up_cos outside [0, 1]
+ * or NaN; axis, align or on_miss not 0 or 1; null buffers with n > 0. */
+void rmclhip_surface_params_default(rmclhip_surface_params* out);
+/* later rmclhip_pf_motion_update calls on this handle constrain in the same launch; NULL switches it off; a fresh handle has it off,
+ * and every call then returns the bytes it returned before this interface existed */
+rmclhip_status rmclhip_pf_set_surface(rmclhip_pf* pf, const rmclhip_surface_params* params);
+/* counts of the last constrained call on the handle (motion update with the constraint set, or rmclhip_pf_constrain_to_surface);
+ * zeros before the first */
+rmclhip_status rmclhip_pf_get_surface_stats(rmclhip_pf* pf, rmclhip_surface_stats* out);
+/* the standalone pass, e.g. after rmclhip_particles_init_uniform or a resampler's noise: steps 1-6 on n particles in place.
+ * Synchronous.  stats_out nullable.  n == 0: RMCLHIP_OK, nothing touched.  max_n_meas of on_miss: the handle's rmclhip_pf_params. */
+rmclhip_status rmclhip_pf_constrain_to_surface(rmclhip_pf* pf, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                               uint32_t n_particles, const rmclhip_surface_params* params,
+                                               rmclhip_surface_stats* stats_out);
 /* gather likelihood.mean of every particle into a dense float array (the payload of the
  * multi-GPU all-gather) */
 rmclhip_status rmclhip_pf_extract_weights(rmclhip_pf* pf, const rmclhip_particle_attributes* attrs_dev,
@@ -836,6 +885,14 @@ rmclhip_status rmclhip_pf_update_sharded(rmclhip_pf_sharded* pf, const rmclhip_r
  * that particle alone). */
 rmclhip_status rmclhip_pf_sharded_motion_update(rmclhip_pf_sharded* pf, const rmclhip_transform* T_bnew_bold, double forget_rate,
                                                 int check_collision);
+/* the surface constraint on a sharded cloud: rmclhip_pf_sharded_motion_update and rmclhip_pf_sharded_step honour the setting (NULL
+ * switches it off); the standalone pass runs on every device's own block, no collective; the devices' counts are summed on the host.
+ * Equal, bit for bit, to the single-device calls.  rmclhip_pf_sharded_get_surface_stats: the sum over the devices' last constrained
+ * launch (after a motion update, a step or the standalone pass has returned). */
+rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* pf, const rmclhip_surface_params* params);
+rmclhip_status rmclhip_pf_sharded_constrain_to_surface(rmclhip_pf_sharded* pf, const rmclhip_surface_params* params,
+                                                       rmclhip_surface_stats* stats_out);
+rmclhip_status rmclhip_pf_sharded_get_surface_stats(rmclhip_pf_sharded* pf, rmclhip_surface_stats* out);
 /* One cycle of the filter node on the sharded cloud (rmcl_localization.cpp:84, 432-552): motion update (T_bnew_bold NULL: skipped) ->
  * sensor update -> weight all-gather -> {sum, max} of the gathered weights on every device (stats_out, nullable; no collective) -> resampling (resample: 0 none, 1 gladiator
  * tournament, 2 residual; config / seed / step as rmclhip_pf_sharded_resample).  A device's motion and sensor-update launches share a

@@ -34,6 +34,11 @@ const char* rmclhip_lab_version(void);
 /* The two entry points below are exported by librmclhip.so (they need the handle's internals) but work only while
  * librmclhip_lab.so is loaded -- the instrumented kernels live there; RMCLHIP_ERR_UNSUPPORTED otherwise. */
 
+/* TEST output of the surface constraint (rmclhip.h: rmclhip_pf_set_surface / rmclhip_pf_constrain_to_surface): while faces_dev is set
+ * (borrowed device memory, one word per particle of the largest call; NULL switches it off) every constrained launch on the handle
+ * also stores the ORIGINAL id of the face each particle's probe hit, 0xFFFFFFFF for none -- what tests/test_gpu_surface.py holds
+ * against the brute-force oracle where the ray runs along shared edges.  Works without the experiments library. */
+rmclhip_status rmclhip_debug_surface_faces(rmclhip_pf* pf, uint32_t* faces_dev);
 /* tools/wave_timeline.py: one spherical find() of the current variant whose waves record their entry / exit shader clock:
  * out = n_waves x 8 dwords {s_memtime entry, exit (stores completed), s_memrealtime entry (100 MHz), tile | xcc << 24,
  * s_memtime before the traversal, after it, stores issued, 0} (all zero = wave had no tile) */

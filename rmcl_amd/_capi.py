@@ -74,6 +74,20 @@ class GladiatorConfig(C.Structure):
                 ("trans_dist_metric", C.c_uint32)]
 
 
+class SurfaceParams(C.Structure):
+    """rmclhip_surface_params (the surface constraint of the motion update)"""
+    _fields_ = [("axis", C.c_uint32), ("height", C.c_float), ("probe_up", C.c_float), ("probe_down", C.c_float),
+                ("min_up_cos", C.c_float), ("align", C.c_uint32), ("on_miss", C.c_uint32)]
+
+
+class SurfaceStats(C.Structure):
+    """rmclhip_surface_stats"""
+    _fields_ = [("n_particles", C.c_uint32), ("n_snapped", C.c_uint32), ("n_missed", C.c_uint32), ("n_steep", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class LikelihoodStats(C.Structure):
     _fields_ = [("sum", C.c_float), ("max", C.c_float)]
 
@@ -276,6 +290,14 @@ SIGNATURES = {
     "rmclhip_pf_sharded_download": (_i32, [_vp, _vp, _vp]),
     "rmclhip_pf_update_sharded": (_i32, [_vp, _vp, _u32, _vp]),
     "rmclhip_pf_sharded_motion_update": (_i32, [_vp, _vp, _dbl, _i32]),
+    "rmclhip_surface_params_default": (None, [_vp]),
+    "rmclhip_pf_set_surface": (_i32, [_vp, _vp]),
+    "rmclhip_pf_get_surface_stats": (_i32, [_vp, _vp]),
+    "rmclhip_pf_constrain_to_surface": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "rmclhip_pf_sharded_set_surface": (_i32, [_vp, _vp]),
+    "rmclhip_pf_sharded_constrain_to_surface": (_i32, [_vp, _vp, _vp]),
+    "rmclhip_pf_sharded_get_surface_stats": (_i32, [_vp, _vp]),
+    "rmclhip_debug_surface_faces": (_i32, [_vp, _vp]),
     "rmclhip_pf_sharded_step": (_i32, [_vp, _vp, _dbl, _i32, _vp, _u32, _vp, _i32, C.POINTER(GladiatorConfig), C.c_uint64, _u32,
                                        C.POINTER(LikelihoodStats)]),
     "rmclhip_pf_allgather_weights": (_i32, [_vp]),

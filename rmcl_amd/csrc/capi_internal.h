@@ -430,6 +430,13 @@ struct rmclhip_pf {
   int refill = 4;  // 0: rounds of one ray per lane; 1..4: persistent lanes (dynamic ray fetch), refill when 8/16/32/48
                    // lanes of a wave are idle (default 48: the refill block also evaluates the finished beams, which
                    // pays off with many lanes at once; measured best on sphere and room)
+  // the surface constraint (capi_surface.cpp): rmclhip_pf_set_surface; the class counts of the last constrained launch land in
+  // h_surf (pinned, 4 words) behind that launch on `stream`
+  bool surface_on = false;
+  rmclhip_surface_params surface{};
+  uint32_t* d_surf = nullptr;
+  uint32_t* h_surf = nullptr;
+  uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: borrowed device memory, one word per particle of the next constrained launches
 };
 
 // GladiatorResamplerGPU analogue: owns a stream and the scratch of the {sum, max} reduction
@@ -506,4 +513,11 @@ RMCL_INTERNAL rmclhip_status particles_uniform_check(const char* who, uint32_t f
 RMCL_INTERNAL rmclhip_status particles_pose_check(const char* who, uint32_t first, uint32_t count, const rmclhip_transform* Tlm, const double* covariance,
                                                   ParticlesPoseJob* job);
 extern RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries;   // capi_rcc.cpp: polls that met their sequence number before the checksum matched
+// capi_surface.cpp: the surface constraint's argument check, and the two launches on f->stream with the copy of their class counts to
+// f->h_surf behind them (no wait).  pf_motion_enqueue: the motion update of the handle, constrained when rmclhip_pf_set_surface says so.
+RMCL_INTERNAL rmclhip_status surface_params_check(const char* who, const rmclhip_surface_params* p);
+RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const xform& T_bnew_bold, double forget_rate,
+                                               uint32_t max_n_meas, bool collision);
+RMCL_INTERNAL rmclhip_status pf_surface_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const rmclhip_surface_params& sp, uint32_t max_n_meas);
+RMCL_INTERNAL void pf_surface_release(rmclhip_pf* f);
 //@@DECLS@@

@@ -668,8 +668,9 @@ static rmclhip_status pf_sharded_motion_enqueue(rmclhip_pf_sharded* h, const rmc
     PfRank& R = h->ranks[r];
     if (R.hi == R.lo) continue;
     HIPCHK(hipSetDevice(R.ctx->device));
-    HIPCHK(launch_pf_motion(R.map->d_qnodes, R.map->d_tris, R.d_poses, static_cast<rmclhip_particle_attributes*>(R.d_attrs), R.hi - R.lo,
-                            to_x(T_bnew_bold), forget_rate, h->params.max_n_meas, check_collision != 0, R.pf->stream));
+    if (rmclhip_status st = pf_motion_enqueue(R.pf, R.d_poses, R.d_attrs, R.hi - R.lo, to_x(T_bnew_bold), forget_rate, h->params.max_n_meas,
+                                              check_collision != 0))
+      return st;
     trace('E', static_cast<uint32_t>(r));
   }
   return RMCLHIP_OK;
@@ -690,6 +691,64 @@ rmclhip_status rmclhip_pf_sharded_motion_update(rmclhip_pf_sharded* h, const rmc
     HIPCHK(R.pf->tag.wait_chain_end(R.ctx, R.pf->stream));
     trace('W', static_cast<uint32_t>(r));
   }
+  return RMCLHIP_OK;
+}
+
+// ---- the surface constraint on the sharded cloud (capi_surface.cpp has the single-device entry points) ----
+rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* h, const rmclhip_surface_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_surface");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_surface: null");
+  if (params)
+    if (rmclhip_status st = surface_params_check("pf_sharded_set_surface", params)) return st;
+  for (PfRank& R : h->ranks)
+    if (rmclhip_status st = rmclhip_pf_set_surface(R.pf, params)) return st;
+  return RMCLHIP_OK;
+}
+
+// the sum of every device's last counts (ranks without particles launched nothing: their block is skipped)
+static void pf_sharded_sum_surface_stats(rmclhip_pf_sharded* h, rmclhip_surface_stats* out) {
+  std::memset(out, 0, sizeof(*out));
+  for (PfRank& R : h->ranks) {
+    if (R.hi == R.lo || !R.pf->h_surf) continue;
+    out->n_particles += R.pf->h_surf[0]; out->n_snapped += R.pf->h_surf[1]; out->n_missed += R.pf->h_surf[2]; out->n_steep += R.pf->h_surf[3];
+  }
+}
+
+rmclhip_status rmclhip_pf_sharded_get_surface_stats(rmclhip_pf_sharded* h, rmclhip_surface_stats* out) {
+  ApiGuard guard_("rmclhip_pf_sharded_get_surface_stats");
+  if (!h || !out) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_get_surface_stats: null");
+  for (PfRank& R : h->ranks) {   // (a step leaves the counts' copy behind the motion launch on the rank's stream)
+    if (R.hi == R.lo || !R.pf->h_surf) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    HIPCHK(hipStreamSynchronize(R.pf->stream));
+  }
+  pf_sharded_sum_surface_stats(h, out);
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_pf_sharded_constrain_to_surface(rmclhip_pf_sharded* h, const rmclhip_surface_params* params, rmclhip_surface_stats* stats_out) {
+  ApiGuard guard_("rmclhip_pf_sharded_constrain_to_surface");
+  if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_constrain_to_surface: null");
+  if (rmclhip_status st = surface_params_check("pf_sharded_constrain_to_surface", params)) return st;
+  if (h->n_total == 0) return RMCLHIP_OK;
+  if (params->on_miss != 0u) h->weights_fresh = false;
+  trace_mark("surface:");
+  for (size_t r = 0; r < h->ranks.size(); ++r) {   // every rank's launch is in flight before the host waits for any
+    PfRank& R = h->ranks[r];
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    if (rmclhip_status st = pf_surface_enqueue(R.pf, R.d_poses, R.d_attrs, R.hi - R.lo, *params, h->params.max_n_meas)) return st;
+    trace('E', static_cast<uint32_t>(r));
+  }
+  for (size_t r = 0; r < h->ranks.size(); ++r) {
+    PfRank& R = h->ranks[r];
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    HIPCHK(R.pf->tag.wait_chain_end(R.ctx, R.pf->stream));
+    trace('W', static_cast<uint32_t>(r));
+  }
+  if (stats_out) pf_sharded_sum_surface_stats(h, stats_out);
   return RMCLHIP_OK;
 }
 

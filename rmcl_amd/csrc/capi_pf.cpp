@@ -32,6 +32,7 @@ void rmclhip_pf_destroy(rmclhip_pf* f) {
   (void)hipSetDevice(f->ctx->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
   f->d_beams.release(); f->d_evals.release(); f->d_gpow.release(); f->d_order.release(); f->tag.destroy();
+  pf_surface_release(f);
   if (f->h_beams) (void)hipHostFree(f->h_beams);
   if (f->ev0) (void)hipEventDestroy(f->ev0);
   if (f->ev1) (void)hipEventDestroy(f->ev1);
@@ -230,8 +231,9 @@ rmclhip_status rmclhip_pf_motion_update(rmclhip_pf* f, rmclhip_transform* poses_
   if (n == 0) return RMCLHIP_OK;
   if (!poses_dev || !attrs_dev) return fail(RMCLHIP_ERR_INVALID, "pf_motion_update: null buffers");
   HIPCHK(hipSetDevice(f->ctx->device));
-  HIPCHK(launch_pf_motion(f->map->d_qnodes, f->map->d_tris, reinterpret_cast<xform*>(poses_dev), attrs_dev, n,
-                          to_x(T_bnew_bold), forget_rate, f->params.max_n_meas, check_collision != 0, f->stream));
+  if (rmclhip_status st = pf_motion_enqueue(f, reinterpret_cast<xform*>(poses_dev), attrs_dev, n, to_x(T_bnew_bold), forget_rate,
+                                            f->params.max_n_meas, check_collision != 0))
+    return st;
   HIPCHK(f->tag.wait_chain_end(f->ctx, f->stream));
   return RMCLHIP_OK;
 }

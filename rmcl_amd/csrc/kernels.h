@@ -392,8 +392,20 @@ inline uint32_t pc2scan_blocks(size_t n) { return static_cast<uint32_t>((n + kPc
 hipError_t launch_pc2scan(const Pc2ScanParams& p, uint32_t* counters_host, hipStream_t s);
 hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s);
 hipError_t launch_pf_extract_weights(const void* attrs, uint32_t n, float* weights, hipStream_t s);
+// rmclhip_surface_params as the kernels take it (surface.hip.h)
+struct SurfaceKernelParams {
+  uint32_t axis, align, on_miss;
+  float height, probe_up, probe_down, min_up_cos;
+};
+// surface: null = the unconstrained update; else the surface constraint runs in the same launch (move -> forget -> collision ray on the
+// lifted segment -> surface ray) and surface_stats (device, 4 words {particles, snapped, missed, steep}, zeroed by the caller) counts
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
-                            xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s);
+                            xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s,
+                            const SurfaceKernelParams* surface = nullptr, uint32_t* surface_stats = nullptr, uint32_t* surface_faces = nullptr);
+// the standalone pass (surface.hip): qnodes = the map's quantised nodes; stats as above.  faces (both launches; nullable, n words): the
+// face every particle's probe hit, kInvalidFace for none (a test output)
+hipError_t launch_surface_constrain(const uint32_t* qnodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
+                                    const SurfaceKernelParams& sp, uint32_t max_n_meas, uint32_t* stats, uint32_t* faces, hipStream_t s);
 
 // pose-estimate moments (RmclNode::estimateStats): partials = 256 * 32 doubles of scratch, out32 = 24 sums + 8 maxima (device)
 hipError_t launch_pose_moments(const xform* poses, const void* attrs, uint32_t n, int pass, double L_sum, xform Tbm,

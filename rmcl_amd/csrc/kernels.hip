@@ -19,6 +19,7 @@
 #include "lab_hooks.h"
 #include "pf_common.hip.h"
 #include "pf_random.hip.h"
+#include "surface.hip.h"
 
 
 namespace rmclhip {
@@ -1675,28 +1676,44 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAccum
 // particle_move_and_forget_kernel (rmcl_ros/src/rmcl/particle_motion.cu:11-34) + the wall-collision test of the
 // CPU updater (collision_in_between, TFMotionUpdaterCPU.cpp:17-50,207-221): one lane per particle; the occlusion
 // ray runs from the old to the new particle position with tfar = segment length.
-template <bool kCollision>
+// kSurface: the surface constraint in the same launch (surface.hip.h; include/rmclhip.h has the rule).  The collision segment is then
+// LIFTED by the step height: it runs between the probe origins of the old and of the moved pose, so that what is lower than probe_up is
+// climbed and what is taller is a wall; the probe runs on the moved pose whether or not the particle was killed.  The instantiations
+// without it are the kernel of before (`sx` is not read).
+struct SurfaceArgs { SurfaceKernelParams sp; uint32_t* stats; uint32_t* faces; };
+template <bool kCollision, bool kSurface = false>
 __global__ void __launch_bounds__(256) k_pf_motion(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ tris,
                                                    xform* __restrict__ poses, pattrs* __restrict__ attrs, uint32_t n,
-                                                   xform T_bnew_bold, double forget_rate, uint32_t max_n_meas) {
+                                                   xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, SurfaceArgs sx) {
   extern __shared__ uint32_t lds_dyn[];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < n;
   const uint32_t ii = live ? i : 0u;
   const xform pose_old = poses[ii];
   g1d L = attrs[ii].likelihood;
-  const xform pose_new = xmul(pose_old, T_bnew_bold);
+  xform pose_new = xmul(pose_old, T_bnew_bold);
   // `n_meas -= forget_rate * n_meas` on a uint32: double arithmetic, truncating store
   L.n_meas = static_cast<uint32_t>(static_cast<double>(L.n_meas) - forget_rate * static_cast<double>(L.n_meas));
+  f3 a_new = mk3(0.0f, 0.0f, 1.0f), O_new = pose_new.t, seg_from = pose_old.t;
+  if (kSurface) {
+    a_new = surface_axis(sx.sp, pose_new);
+    O_new = surface_origin(sx.sp, pose_new, a_new);
+    if (kCollision) seg_from = surface_origin(sx.sp, pose_old, surface_axis(sx.sp, pose_old));
+  }
   if (kCollision) {
-    f3 vec = sub3(pose_new.t, pose_old.t);
+    f3 vec = sub3(kSurface ? O_new : pose_new.t, seg_from);
     const float length = sqrtf((vec.x * vec.x + vec.y * vec.y) + vec.z * vec.z);
     const bool moving = !(static_cast<double>(length) < 0.00001);
     vec = mk3(vec.x / length, vec.y / length, vec.z / length);
     RayHit h;
     // guarded slab: a centimetre step far from the origin is axis-parallel in float32 (traverse.hip.h: make_ray_slab_guarded)
-    trace_lane_bf<16, true, false, false, true>(nodes, tris, pose_old.t, vec, (live && moving) ? length : -1.0f, lds_dyn + threadIdx.x, h);
+    trace_lane_bf<16, true, false, false, true>(nodes, tris, seg_from, vec, (live && moving) ? length : -1.0f, lds_dyn + threadIdx.x, h);
     if (moving && h.rec != kNone) { L.mean = 0.0f; L.sigma = 0.0f; L.n_meas = max_n_meas; }
+  }
+  if (kSurface) {
+    const uint32_t cls = surface_constrain_lane(nodes, tris, sx.sp, pose_new, a_new, O_new, live, lds_dyn + threadIdx.x, sx.faces ? sx.faces + ii : nullptr);
+    if (cls != kSurfSnap && sx.sp.on_miss != 0u) { L.mean = 0.0f; L.sigma = 0.0f; L.n_meas = max_n_meas; }
+    surface_count(sx.stats, live, cls);
   }
   if (live) {
     poses[i] = pose_new;
@@ -2849,15 +2866,28 @@ hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s) {
 }
 
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
-                            xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s) {
+                            xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s,
+                            const SurfaceKernelParams* surface, uint32_t* surface_stats, uint32_t* surface_faces) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + 255u) / 256u), block(256);
-  if (collision)
+  SurfaceArgs sx = {};
+  if (surface) {
+    if (!surface_stats) return hipErrorInvalidValue;
+    sx.sp = *surface;
+    sx.stats = surface_stats;
+    sx.faces = surface_faces;
+    if (collision)
+      hipLaunchKernelGGL((k_pf_motion<true, true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
+                         reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
+    else
+      hipLaunchKernelGGL((k_pf_motion<false, true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
+                         reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
+  } else if (collision)
     hipLaunchKernelGGL((k_pf_motion<true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
-                       reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas);
+                       reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
   else
     hipLaunchKernelGGL((k_pf_motion<false>), grid, block, 0, s, nodes, tris, poses, reinterpret_cast<pattrs*>(attrs), n,
-                       T_bnew_bold, forget_rate, max_n_meas);
+                       T_bnew_bold, forget_rate, max_n_meas, sx);
   return hipGetLastError();
 }
 

@@ -113,13 +113,39 @@ def chol6(covariance):
     return L.reshape(6, 6), err.value
 
 
+def constrain_to_surface(updater_or_map, poses, attrs, n, params):
+    """the standalone surface pass (rmclhip_pf_constrain_to_surface), e.g. after init_particles_uniform or a resampler's noise: every
+    one of the n particles is put `params.height` above the mesh below it (and, with align, its body z on the face normal), in place.
+    updater_or_map: a TFMotionUpdaterHip / PCDSensorUpdaterHip (its handle, and its max_n_meas for on_miss, are used) or a HipMap (a
+    handle is made for the call).  Returns the counts {n_particles, n_snapped, n_missed, n_steep}."""
+    st = _capi.SurfaceStats()
+    own = None
+    if hasattr(updater_or_map, "_h") and hasattr(updater_or_map, "init"):
+        updater_or_map.init()
+        h = updater_or_map._h
+    else:
+        own = C.c_void_p()
+        _capi.check(_capi.lib().rmclhip_pf_create(updater_or_map.ctx.handle, updater_or_map.handle, C.byref(own)))
+        h = own
+    try:
+        _capi.check(_capi.lib().rmclhip_pf_constrain_to_surface(h, _as_ptr(poses), _as_ptr(attrs), int(n),
+                                                                None if params is None else C.byref(params), C.byref(st)))
+    finally:
+        if own is not None:
+            _capi.lib().rmclhip_pf_destroy(own)
+    return st.as_dict()
+
+
 class TFMotionUpdaterHip:
-    """rmcl::TFMotionUpdaterGPU on gfx950 + the wall-collision test of TFMotionUpdaterCPU (MotionUpdater<MemT>)."""
+    """rmcl::TFMotionUpdaterGPU on gfx950 + the wall-collision test of TFMotionUpdaterCPU (MotionUpdater<MemT>).
+    surface: None, or types.surface_params(...) -- update() then keeps the particles on the mesh in the same launch."""
 
     def __init__(self, hip_map, check_collision=True):
         if hip_map is None:
             raise RuntimeError("NO MAP")
         self.map, self.ctx, self.check_collision = hip_map, hip_map.ctx, check_collision
+        self.surface = None
+        self.config = pf_params()   # (max_n_meas of a killed particle)
         self._h = C.c_void_p()
 
     def init(self):
@@ -132,10 +158,19 @@ class TFMotionUpdaterHip:
     def update(self, particle_poses, particle_attrs, n_particles, T_bnew_bold, forget_rate):
         self.init()
         T = np.ascontiguousarray(T_bnew_bold, dtype=TRANSFORM).reshape(1)
+        _capi.check(_capi.lib().rmclhip_pf_set_params(self._h, C.byref(self.config)))
+        _capi.check(_capi.lib().rmclhip_pf_set_surface(self._h, None if self.surface is None else C.byref(self.surface)))
         _capi.check(_capi.lib().rmclhip_pf_motion_update(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs),
                                                          int(n_particles), _ptr(T), float(forget_rate),
                                                          int(bool(self.check_collision))))
         return {}
+
+    def surface_stats(self):
+        """{n_particles, n_snapped, n_missed, n_steep} of the last constrained call on this updater (zeros before the first)"""
+        self.init()
+        st = _capi.SurfaceStats()
+        _capi.check(_capi.lib().rmclhip_pf_get_surface_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def close(self):
         if self._h:
@@ -415,6 +450,23 @@ class ShardedParticleFilterHip:
         T = np.ascontiguousarray(T_bnew_bold, dtype=TRANSFORM).reshape(1)
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_params(self._h, C.byref(self.config_)))   # (max_n_meas of a collided particle)
         _capi.check(_capi.lib().rmclhip_pf_sharded_motion_update(self._h, _ptr(T), float(forget_rate), int(bool(check_collision))))
+
+    def set_surface(self, params):
+        """the surface constraint of motion_update and step on every device's block (rmclhip_pf_sharded_set_surface); None: off"""
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_surface(self._h, None if params is None else C.byref(params)))
+
+    def constrain_to_surface(self, params):
+        """the standalone surface pass on every device's own block, no collective; returns the counts summed over the devices"""
+        st = _capi.SurfaceStats()
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_params(self._h, C.byref(self.config_)))   # (max_n_meas of on_miss)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_constrain_to_surface(self._h, None if params is None else C.byref(params), C.byref(st)))
+        return st.as_dict()
+
+    def surface_stats(self):
+        """counts of the last constrained motion_update / step / constrain_to_surface, summed over the devices"""
+        st = _capi.SurfaceStats()
+        _capi.check(_capi.lib().rmclhip_pf_sharded_get_surface_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def step(self, beams, Tsb, T_bnew_bold=None, forget_rate=0.0, check_collision=True, resample=None, cfg=None, seed=42, step=0):
         """one cycle of the filter node (rmcl_localization.cpp:84, 432-552) behind ONE C call: motion (skipped when T_bnew_bold is None)

@@ -132,6 +132,19 @@ def pf_params(dist_sigma=2.0, real_hit_sim_miss_error=100.0, real_miss_sim_hit_e
     return p
 
 
+def surface_params(axis=None, height=None, probe_up=None, probe_down=None, min_up_cos=None, align=None, on_miss=None):
+    """rmclhip_surface_params: the surface constraint of the motion update (include/rmclhip.h).  Arguments left None keep the library's
+    defaults (rmclhip_surface_params_default): axis 0 (map +z; 1 = body z), height 0, probe_up 0.3, probe_down 1.0, min_up_cos 0.7,
+    align 0, on_miss 0."""
+    p = _capi.SurfaceParams()
+    _capi.lib().rmclhip_surface_params_default(C.byref(p))
+    for k, v in (("axis", axis), ("height", height), ("probe_up", probe_up), ("probe_down", probe_down), ("min_up_cos", min_up_cos),
+                 ("align", align), ("on_miss", on_miss)):
+        if v is not None:
+            setattr(p, k, int(v) if k in ("axis", "align", "on_miss") else float(v))
+    return p
+
+
 def gladiator_config(min_noise_tx=0.03, min_noise_ty=0.03, min_noise_tz=0.0, min_noise_roll=0.0, min_noise_pitch=0.0,
                      min_noise_yaw=0.01, likelihood_forget_per_meter=0.3, likelihood_forget_per_radian=0.2,
                      trans_dist_metric=0):
