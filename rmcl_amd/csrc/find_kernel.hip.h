@@ -314,6 +314,7 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     if constexpr (kMoments) find_moments_idle_wave<kQuad>(p, s_mom_red, s_mom_piece, kQuad ? vb : (vb * 4u + wave), wave, threadIdx.x & 63u);
     return;
   }
+  tile = __builtin_amdgcn_readfirstlane(tile);   // one tile per wave, which the compiler cannot see through threadIdx.x >> 6: the division below runs on the scalar unit
   const uint32_t ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
   const uint32_t twl = p.tile_w_log2;
   const uint32_t lx = lane & ((1u << twl) - 1u), ly = lane >> twl;
@@ -376,20 +377,23 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     start.cur = (ray_tfar >= 0.0f) ? 0u : 0x7FFFFFFFu;
     start.sp = kWwStack ? 0u : 1u;
     const TraceStart* sp0 = &start;
+    // the ray's slab constants (three IEEE divisions): ONCE per ray, by reference to the frontier start and to the traversal behind it
+    // -- each used to build its own, and the first sat under the branches below where the compiler could not merge the two
+    const RaySlab rs = make_ray_slab(org_m, dir_m);
     if constexpr (find_frontier(kTrav) && kModel != kModelOnDn) {   // (OnDn: one origin per ray, no common pyramid)
       if (p.tile_planes != nullptr) {     // (no table: the rays start at the root)
         const float* planes = p.tile_planes + static_cast<size_t>(__builtin_amdgcn_readfirstlane(tile)) * 16u;
         if (kTrav == 31 || kTrav == 32)
           start = frontier_descent_start<kFindBfRows, 1, kTrav == 32>(p.frontier, p.n_frontier, p.cnodes, p.cnodes16, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar,
-                                                         org_m, dir_m, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload,
+                                                         org_m, dir_m, rs, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload,
                                                          lds_dyn + kFind31ListsAt + wave * kDescentWaveDwords, min(p.descent_final_cap, kDescentCap), p.descent_levels, kClock ? &clk_descent : nullptr,
                                                          kClock ? clk_stamps : nullptr, p.tris, &coop_seed);
         else if (kTrav == 23 || (kTrav >= 26 && kTrav <= 30))
           start = frontier_start<kFindBfRows, 1>(p.frontier, p.n_frontier, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar, org_m,
-                                                 dir_m, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload);
+                                                 dir_m, rs, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload);
         else
           start = frontier_start<16, 0>(p.frontier, p.n_frontier, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar, org_m, dir_m,
-                                        ray_tfar, lane, lds_dyn + threadIdx.x, blockDim.x, p.frontier_max_preload);
+                                        rs, ray_tfar, lane, lds_dyn + threadIdx.x, blockDim.x, p.frontier_max_preload);
       }
     }
     if (kClock && p.wave_clock != nullptr) {   // the start (frontier cull / cooperative descent) ends here
@@ -399,7 +403,7 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     }
     if (kTrav == 4) trace_lane_ww<16, true>(p.qnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h);
     else if (kTrav == 22 || kTrav == 24)
-      trace_lane_ww<16, true, false, true>(p.qnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h, sp0);
+      trace_lane_ww<16, true, false, true>(p.qnodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h, sp0);
     else if (kTrav == 21)
       trace_lane_ww_tail<16, 0, false, true>(
           p.nodes, p.cnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, lds_dyn + 16u * 256u,
@@ -408,7 +412,7 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     else if (kTrav == 1) trace_lane_bf<kFindBfRows>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
     else if (kTrav == 12) trace_lane_bf<kFindBfRows, false, true>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
     else if (kTrav == 16 || kTrav == 17 || kTrav == 19 || kTrav == 20 || kTrav == 23 || (kTrav >= 26 && kTrav <= 32))
-      trace_lane_bf_tail<kFindBfRows, kTrav != 16 && kTrav != 20, find_leaf_trigger(kTrav), kTrav == 26, kTrav == 27, kTrav == 28, (kTrav == 29 ? 4 : (kTrav == 30 ? 3 : 5)), kTrav < 31>(kTrav == 26 ? p.qnodes : p.nodes, p.cnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x,
+      trace_lane_bf_tail<kFindBfRows, kTrav != 16 && kTrav != 20, find_leaf_trigger(kTrav), kTrav == 26, kTrav == 27, kTrav == 28, (kTrav == 29 ? 4 : (kTrav == 30 ? 3 : 5)), kTrav < 31>(kTrav == 26 ? p.qnodes : p.nodes, p.cnodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x,
                                                    lds_dyn + kFindBfRows * 256u,
                                                    lds_dyn + kFindBfRows * 256u + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
                                                    kClock ? &clk_visits : nullptr, sp0, kClock ? clk_dbg : nullptr, &pre_nrec, &pre_rec, (kTrav == 32) ? &coop_seed : nullptr);

@@ -489,9 +489,8 @@ struct TraceStart {
 
 template <int kLdsEntries, bool kQuant = false, bool kLeafBatch = false, bool kVote = false>  // stack entries kept in LDS ([entry][lane]); the rest (up to 64 total) in scratch
 __device__ __forceinline__ void trace_lane_ww(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ tris,
-                                              f3 O, f3 D, float ray_tfar, uint32_t* __restrict__ lds_stack,
+                                              f3 O, f3 D, const RaySlab& rs, float ray_tfar, uint32_t* __restrict__ lds_stack,
                                               uint32_t lds_stride, RayHit& h, const TraceStart* start = nullptr) {
-  const RaySlab rs = make_ray_slab(O, D);
   float best_t = ray_tfar;
   uint32_t best_rec = kNone;
   constexpr uint32_t kDone = 0x7FFFFFFFu;
@@ -534,6 +533,14 @@ __device__ __forceinline__ void trace_lane_ww(const uint32_t* __restrict__ nodes
 #undef RMCL_POP
   h.t = best_t;
   h.rec = best_rec;
+}
+// the same for a caller without a slab of its own (k_find builds one per ray and shares it with the frontier start)
+template <int kLdsEntries, bool kQuant = false, bool kLeafBatch = false, bool kVote = false>
+__device__ __forceinline__ void trace_lane_ww(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ tris,
+                                              f3 O, f3 D, float ray_tfar, uint32_t* __restrict__ lds_stack,
+                                              uint32_t lds_stride, RayHit& h, const TraceStart* start = nullptr) {
+  const RaySlab rs = make_ray_slab(O, D);
+  trace_lane_ww<kLdsEntries, kQuant, kLeafBatch, kVote>(nodes, tris, O, D, rs, ray_tfar, lds_stack, lds_stride, h, start);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -939,14 +946,13 @@ __device__ __forceinline__ void trace_lane_ww_tail(const uint32_t* __restrict__ 
 // instructions shorter.
 template <int kRows, bool kLeafBatch, int kLeafTrigger = 0, bool kQuant = false, bool kPre = false, bool kPipe = false, int kSortSteps = 5, bool kTail = true>   // kQuant: `nodes` are the 64-B quantised twins; kTail = false: no hand-over of the last rays to quads (qstack / xfer_wave unused)
 __device__ __forceinline__ void trace_lane_bf_tail(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ cnodes,
-                                                   const uint32_t* __restrict__ tris, f3 O, f3 D, float ray_tfar,
+                                                   const uint32_t* __restrict__ tris, f3 O, f3 D, const RaySlab& rs, float ray_tfar,
                                                    uint32_t* __restrict__ lds_col, uint32_t* __restrict__ qstack,
                                                    uint32_t* __restrict__ xfer_wave, RayHit& h, uint32_t* visits = nullptr,
                                                    const TraceStart* start = nullptr, uint32_t* dbg = nullptr, uint4* pre = nullptr,
                                                    uint32_t* pre_rec = nullptr, const RayHit* seed = nullptr) {
   uint4 pre_v = uint4{0u, 0u, 0u, 0u};
   uint32_t pre_r = kNone;
-  const RaySlab rs = make_ray_slab(O, D);
   float best_t = seed ? seed->t : ray_tfar;          // (kind 32: the closest hit among the leaves the wave tested together)
   uint32_t best_rec = seed ? seed->rec : kNone;
   uint32_t nvis = 0;  // node visits of this ray
@@ -1129,6 +1135,18 @@ __device__ __forceinline__ void trace_lane_bf_tail(const uint32_t* __restrict__ 
   if (visits) *visits = nvis;
   if (dbg) { dbg[0] = dbg_slow; dbg[1] = dbg_na; dbg[2] = dbg_tail; dbg[3] = dbg_leaf; }   // dbg[3]: leaf visits of this lane before the quad tail
 }
+// the same for a caller without a slab of its own
+template <int kRows, bool kLeafBatch, int kLeafTrigger = 0, bool kQuant = false, bool kPre = false, bool kPipe = false, int kSortSteps = 5, bool kTail = true>
+__device__ __forceinline__ void trace_lane_bf_tail(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ cnodes,
+                                                   const uint32_t* __restrict__ tris, f3 O, f3 D, float ray_tfar,
+                                                   uint32_t* __restrict__ lds_col, uint32_t* __restrict__ qstack,
+                                                   uint32_t* __restrict__ xfer_wave, RayHit& h, uint32_t* visits = nullptr,
+                                                   const TraceStart* start = nullptr, uint32_t* dbg = nullptr, uint4* pre = nullptr,
+                                                   uint32_t* pre_rec = nullptr, const RayHit* seed = nullptr) {
+  const RaySlab rs = make_ray_slab(O, D);
+  trace_lane_bf_tail<kRows, kLeafBatch, kLeafTrigger, kQuant, kPre, kPipe, kSortSteps, kTail>(nodes, cnodes, tris, O, D, rs, ray_tfar, lds_col, qstack, xfer_wave, h,
+                                                                                             visits, start, dbg, pre, pre_rec, seed);
+}
 
 // ---------------------------------------------------------------------------------------------
 // FRONTIER START (round 3).  The 64 rays of a wave leave ONE origin through one tile of the scan image, and every one of them
@@ -1200,15 +1218,88 @@ __device__ __forceinline__ void tile_planes_wave(f3 D, bool active, uint32_t til
   }
 }
 
+// The tile's pyramid in the MAP frame as the cull uses it: the four rotated normals and, per plane, twice the offset in metres at the
+// farthest possible hit (+ slack for the rounding of the rotation and of the test).  All sixteen values are the same in every lane,
+// and gfx950 has no scalar float ALU -- so lane l computes plane (l & 3) only (one 16-B load, one qrot, one offset: the arithmetic
+// every lane used to do four times, same expressions in the same order: the same bits) and the values are taken from lanes 0 - 3 with
+// v_readlane: they reach the cull as SGPR operands.  |n| for the paired form (which has no |.| modifier) is broadcast inside every
+// quad instead (DPP quad_perm: lane l & 3 of a quad holds plane l & 3) and stays in VGPRs: twelve more scalar registers made kind 32
+// spill 22 SGPRs instead of 6.
+// INVARIANT: every lane of a live wave is active here, lanes 0 - 3 among them -- every `return` of k_find and of the two frontier
+// starts above this point is wave-uniform (a wave has one tile), and a lane without a ray only has ray_tfar < 0: it computes like
+// any other.
+// reach: the farthest a hit can be from the origin (wave-uniform)
+struct WavePyramid {
+  f2 nx[2], ny[2], nz[2];   // planes (0, 1) and (2, 3) side by side (SGPR pairs)
+  f2 ax[2], ay[2], az[2];   // |n| (VGPRs; only the paired test reads them)
+  f2 off2[2];
+};
+__device__ __forceinline__ WavePyramid wave_pyramid(const float* __restrict__ planes, quat Rsm, float reach, uint32_t lane) {
+  const uint4 P = reinterpret_cast<const uint4*>(planes)[lane & 3u];
+  const f3 nl = qrot(Rsm, mk3(asf(P.x), asf(P.y), asf(P.z)));
+  const float off = asf(P.w) * reach - 1e-4f * reach - 1e-6f;
+  const float off2 = 2.0f * off;
+  const f3 al = mk3(fabsf(nl.x), fabsf(nl.y), fabsf(nl.z));
+  WavePyramid w;
+#pragma unroll
+  for (uint32_t h = 0; h < 2u; ++h) {
+    w.nx[h] = f2{lane_bcast(nl.x, 2u * h), lane_bcast(nl.x, 2u * h + 1u)};
+    w.ny[h] = f2{lane_bcast(nl.y, 2u * h), lane_bcast(nl.y, 2u * h + 1u)};
+    w.nz[h] = f2{lane_bcast(nl.z, 2u * h), lane_bcast(nl.z, 2u * h + 1u)};
+    w.ax[h] = h ? f2{dpp_f32<0xAA>(al.x), dpp_f32<0xFF>(al.x)} : f2{dpp_f32<0x00>(al.x), dpp_f32<0x55>(al.x)};
+    w.ay[h] = h ? f2{dpp_f32<0xAA>(al.y), dpp_f32<0xFF>(al.y)} : f2{dpp_f32<0x00>(al.y), dpp_f32<0x55>(al.y)};
+    w.az[h] = h ? f2{dpp_f32<0xAA>(al.z), dpp_f32<0xFF>(al.z)} : f2{dpp_f32<0x00>(al.z), dpp_f32<0x55>(al.z)};
+    w.off2[h] = f2{lane_bcast(off2, 2u * h), lane_bcast(off2, 2u * h + 1u)};
+  }
+  return w;
+}
+// a box {lo, hi} against the pyramid: its vertex farthest along n ("positive vertex") is at n.c + |n|.h from the origin (c = centre - O,
+// h = half extent); in doubled quantities (2c = lo + hi - 2 O, 2h = hi - lo) that is six FMAs per plane.  Conservative; NaN keeps.
+// kPairs: two planes per FMA (v_pk_fma_f32; half the instructions, two dependent chains of six) -- the frontier start's form, whose
+// four boxes per lane are independent work; false: four chains of six with the plane values as scalar operands and |n| as a source
+// modifier -- the descent's form: in its level loop a lane tests ONE box, and the paired form left a lone wave's issue waiting on its
+// own results (round 6: -4.8 % VALU instructions, 4 % slower)
+template <bool kPairs>
+__device__ __forceinline__ bool box_in_pyramid(const WavePyramid& w, f3 O2, f3 lo, f3 hi) {
+  const f3 c2 = mk3((lo.x + hi.x) - O2.x, (lo.y + hi.y) - O2.y, (lo.z + hi.z) - O2.z);
+  const f3 h2 = mk3(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z);
+  if constexpr (!kPairs) {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float nx = (q & 1) ? w.nx[q >> 1].y : w.nx[q >> 1].x, ny = (q & 1) ? w.ny[q >> 1].y : w.ny[q >> 1].x;
+      const float nz = (q & 1) ? w.nz[q >> 1].y : w.nz[q >> 1].x, o2 = (q & 1) ? w.off2[q >> 1].y : w.off2[q >> 1].x;
+      const float v = fmaf(fabsf(nz), h2.z, fmaf(fabsf(ny), h2.y, fmaf(fabsf(nx), h2.x, fmaf(nz, c2.z, fmaf(ny, c2.y, nx * c2.x)))));
+      ok = ok && !(v < o2);
+    }
+    return ok;
+  }
+  const f2 cx = {c2.x, c2.x}, cy = {c2.y, c2.y}, cz = {c2.z, c2.z}, hx = {h2.x, h2.x}, hy = {h2.y, h2.y}, hz = {h2.z, h2.z};
+  bool ok = true;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    f2 v = w.nx[h] * cx;
+    v = __builtin_elementwise_fma(w.ny[h], cy, v);
+    v = __builtin_elementwise_fma(w.nz[h], cz, v);
+    v = __builtin_elementwise_fma(w.ax[h], hx, v);
+    v = __builtin_elementwise_fma(w.ay[h], hy, v);
+    v = __builtin_elementwise_fma(w.az[h], hz, v);
+    ok &= !(v.x < w.off2[h].x) & !(v.y < w.off2[h].y);   // (no short circuit: straight-line FMAs, not four branches)
+  }
+  return ok;
+}
+
 // Frontier start: instead of walking the top levels of the tree, the wave culls the map's frontier table (the <= 256 child
 // references of BFS depth kFrontierDepth with their boxes) against the pyramid of its tile, then every lane tests the few
 // survivors against its own ray and starts with the accepted ones on its stack, the two nearest on top.
 // planes: this tile's 16 floats of the model's plane table (uniform address); Rsm: the pose's rotation sensor -> map.
+// The pyramid is computed once per wave (wave_pyramid above: one plane per lane, then broadcast); rs: the ray's slab constants, built
+// by the caller and shared with the traversal that follows (an overload below builds them itself).
 template <int kRows, int kRow0>
 __device__ __forceinline__ TraceStart frontier_start(const uint32_t* __restrict__ frontier, uint32_t n_frontier, f3 scene_center,
                                                      float scene_half_diag, const float* __restrict__ planes, quat Rsm, float tfar,
-                                                     f3 O, f3 D, float ray_tfar, uint32_t lane, uint32_t* __restrict__ lds_col,
-                                                     uint32_t lds_stride, uint32_t max_preload) {
+                                                     f3 O, f3 D, const RaySlab& rs, float ray_tfar, uint32_t lane,
+                                                     uint32_t* __restrict__ lds_col, uint32_t lds_stride, uint32_t max_preload) {
   // max_preload (FindParams::frontier_max_preload, uniform): entries the start may leave on a lane's stack = the stack's 64 entries
   // minus what the deepest descent of THIS map's tree can still push (the builder's stack_need bounds a descent from the root, hence
   // from any frontier entry): a deep tree starts more waves at the root instead of overflowing the stack
@@ -1227,45 +1318,19 @@ __device__ __forceinline__ TraceStart frontier_start(const uint32_t* __restrict_
     ea[k] = F[2u * idx];
     eb[k] = F[2u * idx + 1u];
   }
-  // 1. the tile's pyramid in the map frame
-  const uint4 P0 = sload4(reinterpret_cast<const uint32_t*>(planes), 0u), P1 = sload4(reinterpret_cast<const uint32_t*>(planes), 16u);
-  const uint4 P2 = sload4(reinterpret_cast<const uint32_t*>(planes), 32u), P3 = sload4(reinterpret_cast<const uint32_t*>(planes), 48u);
-  f3 n[4] = {qrot(Rsm, mk3(asf(P0.x), asf(P0.y), asf(P0.z))), qrot(Rsm, mk3(asf(P1.x), asf(P1.y), asf(P1.z))),
-             qrot(Rsm, mk3(asf(P2.x), asf(P2.y), asf(P2.z))), qrot(Rsm, mk3(asf(P3.x), asf(P3.y), asf(P3.z)))};
-  const float mq[4] = {asf(P0.w), asf(P1.w), asf(P2.w), asf(P3.w)};
-  // the farthest a hit can be from this origin: inside the map's bounding sphere, and within the sensor's range
+  // 1. the tile's pyramid in the map frame, out to the farthest a hit can be from this origin: inside the map's bounding sphere, and
+  // within the sensor's range
   const f3 oc = sub3(O, scene_center);
   const float reach = fminf(tfar, sqrtf((oc.x * oc.x + oc.y * oc.y) + oc.z * oc.z) + scene_half_diag);
-  float off[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)   // offset in metres at the farthest possible hit + slack for the rounding of the rotation and of this test
-    off[k] = mq[k] * reach - 1e-4f * reach - 1e-6f;
-  // 2. my entries against the pyramid: the box's vertex farthest along n ("positive vertex") is at n.c + |n|.h from the origin
-  // (c = centre - O, h = half extent); in doubled quantities (2c = lo + hi - 2 O, 2h = hi - lo) that is six FMAs per plane
-  f3 an[4];
-  float off2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    an[q] = mk3(fabsf(n[q].x), fabsf(n[q].y), fabsf(n[q].z));
-    off2[q] = 2.0f * off[q];
-  }
+  const WavePyramid pyr = wave_pyramid(planes, Rsm, reach, lane);
+  // 2. my entries against the pyramid
   const f3 O2 = mk3(2.0f * O.x, 2.0f * O.y, 2.0f * O.z);
   bool acc[4];
 #pragma unroll
-  for (uint32_t k = 0; k < 4u; ++k) {
-    const f3 lo = mk3(asf(ea[k].x), asf(ea[k].y), asf(ea[k].z)), hi = mk3(asf(ea[k].w), asf(eb[k].x), asf(eb[k].y));
-    const f3 c2 = mk3((lo.x + hi.x) - O2.x, (lo.y + hi.y) - O2.y, (lo.z + hi.z) - O2.z);
-    const f3 h2 = mk3(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z);
-    bool ok = (lane + 64u * k) < n_frontier;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float v = fmaf(an[q].z, h2.z, fmaf(an[q].y, h2.y, fmaf(an[q].x, h2.x, fmaf(n[q].z, c2.z, fmaf(n[q].y, c2.y, n[q].x * c2.x)))));
-      ok = ok && !(v < off2[q]);   // NaN -> keep
-    }
-    acc[k] = ok;
-  }
+  for (uint32_t k = 0; k < 4u; ++k)
+    acc[k] = ((lane + 64u * k) < n_frontier) &
+             box_in_pyramid<true>(pyr, O2, mk3(asf(ea[k].x), asf(ea[k].y), asf(ea[k].z)), mk3(asf(ea[k].w), asf(eb[k].x), asf(eb[k].y)));
   // 3. every surviving entry against every ray of the wave
-  const RaySlab rs = make_ray_slab(O, D);
   // the two nearest accepted entries stay in registers (entered first / on top of the stack); the others go below them in
   // table order.  (Only the nearest: the room's hardest ray walks 28 instead of 19 nodes, tools/wavesim.py.)
   uint32_t first_ref = kDone, first_key = 0xFFFFFFFFu, second_ref = kDone, second_key = 0xFFFFFFFFu, sp = static_cast<uint32_t>(kRow0);
@@ -1310,6 +1375,15 @@ __device__ __forceinline__ TraceStart frontier_start(const uint32_t* __restrict_
   st.sp = sp;
   return st;
 }
+template <int kRows, int kRow0>
+__device__ __forceinline__ TraceStart frontier_start(const uint32_t* __restrict__ frontier, uint32_t n_frontier, f3 scene_center,
+                                                     float scene_half_diag, const float* __restrict__ planes, quat Rsm, float tfar,
+                                                     f3 O, f3 D, float ray_tfar, uint32_t lane, uint32_t* __restrict__ lds_col,
+                                                     uint32_t lds_stride, uint32_t max_preload) {
+  const RaySlab rs = make_ray_slab(O, D);
+  return frontier_start<kRows, kRow0>(frontier, n_frontier, scene_center, scene_half_diag, planes, Rsm, tfar, O, D, rs, ray_tfar, lane, lds_col,
+                                      lds_stride, max_preload);
+}
 
 // ---------------------------------------------------------------------------------------------
 // COOPERATIVE DESCENT below the frontier (round 6, kinds 31 and 32).  The frontier start replaces the top four levels of every ray's descent
@@ -1327,6 +1401,8 @@ __device__ __forceinline__ TraceStart frontier_start(const uint32_t* __restrict_
 // box lies outside the pyramid that contains every ray of the wave (up to the farthest possible hit), hence every subtree a ray's own
 // descent would enter is entered; the closest hit (min t, then min face id) does not depend on the order.  Bit-identical to kind 23.
 // ws: this wave's scratch, kDescentWaveDwords dwords, 16-B aligned.
+// The pyramid is computed once per wave (wave_pyramid: one plane per lane, broadcast from lanes 0 - 3; the level loop reads its
+// sixteen values as scalar operands); rs: the ray's slab constants, built once by the caller and shared with the traversal behind.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kDescentCap = 64u, kDescentInnerCap = 32u;       // entries ({box, ref} = 8 dwords each) of the final list / of an inner list
 constexpr uint32_t kDescentWaveDwords = (kDescentCap + 2u * kDescentInnerCap) * 8u;   // final list | inner list A | inner list B: 4 KB per wave
@@ -1344,7 +1420,7 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
                                                              const uint32_t* __restrict__ cnodes, const uint32_t* __restrict__ cnodes16,
                                                              f3 scene_center, float scene_half_diag,
                                                              const float* __restrict__ planes, quat Rsm, float tfar, f3 O, f3 D,
-                                                             float ray_tfar, uint32_t lane, uint32_t* __restrict__ lds_col,
+                                                             const RaySlab& rs, float ray_tfar, uint32_t lane, uint32_t* __restrict__ lds_col,
                                                              uint32_t lds_stride, uint32_t max_preload, uint32_t* __restrict__ ws,
                                                              uint32_t final_cap, uint32_t max_levels, uint32_t* dbg_levels = nullptr,
                                                              uint32_t* stamps = nullptr, const uint32_t* __restrict__ tris = nullptr,
@@ -1373,41 +1449,20 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
     ea[k] = Ft[2u * idx];
     eb[k] = Ft[2u * idx + 1u];
   }
-  // the tile's pyramid in the map frame (frontier_start, steps 1 and 2)
-  const uint4 P0 = sload4(reinterpret_cast<const uint32_t*>(planes), 0u), P1 = sload4(reinterpret_cast<const uint32_t*>(planes), 16u);
-  const uint4 P2 = sload4(reinterpret_cast<const uint32_t*>(planes), 32u), P3 = sload4(reinterpret_cast<const uint32_t*>(planes), 48u);
-  f3 n[4] = {qrot(Rsm, mk3(asf(P0.x), asf(P0.y), asf(P0.z))), qrot(Rsm, mk3(asf(P1.x), asf(P1.y), asf(P1.z))),
-             qrot(Rsm, mk3(asf(P2.x), asf(P2.y), asf(P2.z))), qrot(Rsm, mk3(asf(P3.x), asf(P3.y), asf(P3.z)))};
-  const float mq[4] = {asf(P0.w), asf(P1.w), asf(P2.w), asf(P3.w)};
-  RMCL_STAMP(1)
+  // the tile's pyramid in the map frame (frontier_start, steps 1 and 2): once per wave, wave_pyramid
   const f3 oc = sub3(O, scene_center);
   const float reach = fminf(tfar, sqrtf((oc.x * oc.x + oc.y * oc.y) + oc.z * oc.z) + scene_half_diag);
-  f3 an[4];
-  float off2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    an[q] = mk3(fabsf(n[q].x), fabsf(n[q].y), fabsf(n[q].z));
-    off2[q] = 2.0f * (mq[q] * reach - 1e-4f * reach - 1e-6f);
-  }
+  const WavePyramid pyr = wave_pyramid(planes, Rsm, reach, lane);
+  RMCL_STAMP(1)
   const f3 O2 = mk3(2.0f * O.x, 2.0f * O.y, 2.0f * O.z);
-  // a box {a.xyz = lo, a.w b.x b.y = hi} against the pyramid: its vertex farthest along every plane normal (conservative; NaN keeps)
+  // a box {a.xyz = lo, a.w b.x b.y = hi} against the pyramid
   auto in_pyramid = [&](const uint4& a, const uint4& b) -> bool {
-    const f3 lo = mk3(asf(a.x), asf(a.y), asf(a.z)), hi = mk3(asf(a.w), asf(b.x), asf(b.y));
-    const f3 c2 = mk3((lo.x + hi.x) - O2.x, (lo.y + hi.y) - O2.y, (lo.z + hi.z) - O2.z);
-    const f3 h2 = mk3(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z);
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float v = fmaf(an[q].z, h2.z, fmaf(an[q].y, h2.y, fmaf(an[q].x, h2.x, fmaf(n[q].z, c2.z, fmaf(n[q].y, c2.y, n[q].x * c2.x)))));
-      ok = ok && !(v < off2[q]);
-    }
-    return ok;
+    return box_in_pyramid<false>(pyr, O2, mk3(asf(a.x), asf(a.y), asf(a.z)), mk3(asf(a.w), asf(b.x), asf(b.y)));
   };
   bool acc[4];
 #pragma unroll
   for (uint32_t k = 0; k < 4u; ++k) acc[k] = ((lane + 64u * k) < n_frontier) && in_pyramid(ea[k], eb[k]);
 
-  const RaySlab rs = make_ray_slab(O, D);
   uint32_t first_ref = kDone, first_key = 0xFFFFFFFFu, second_ref = kDone, second_key = 0xFFFFFFFFu, sp = static_cast<uint32_t>(kRow0);
   // one entry {box, ref} (wave-uniform values) against this lane's ray: the traversal's own slab test; the two nearest accepted entries
   // stay in registers (entered first / on top of the stack), the others go below them in list order
