@@ -1405,4 +1405,46 @@ class ResidualResamplerHip : public SensorUpdaterBase {
   uint32_t step_ = 0;
 };
 
+// A Resampler plugin that chooses the particle count (the reference's open item, docs/RMCL.md "reduce the number of particles more
+// intelligently"): the KLD-sampling bound on the occupied bins of pose space, then systematic resampling to that size.  poses_new /
+// attrs_new give the room; the node adopts the returned n_particles (rmcl_localization.cpp:633-639).  Same noise parameters as the
+// gladiator (every copy of a particle after the first is perturbed as a winning enemy).
+class AdaptiveResamplerHip : public SensorUpdaterBase {
+ public:
+  rmclhip_gladiator_config config_{0.03f, 0.03f, 0.0f, 0.0f, 0.0f, 0.01f, 0.3f, 0.2f, 0u};
+  rmclhip_kld_params kld_;
+  uint64_t seed = 1234;
+  uint32_t last_bins = 0;   // occupied bins the last update counted
+
+  explicit AdaptiveResamplerHip(ContextPtr ctx) : ctx_(std::move(ctx)) {
+    if (!ctx_) throw std::runtime_error("NO CONTEXT");
+    rmclhip_kld_params_default(&kld_);
+  }
+  ~AdaptiveResamplerHip() override { rmclhip_resampler_destroy(h_); }
+  void init() override {
+    if (!h_) check(rmclhip_resampler_create(ctx_->handle(), &h_));
+  }
+  void reset() override { step_ = 0; }
+  uint32_t countBins(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs) {
+    init();
+    uint32_t k = 0;
+    check(rmclhip_particles_count_bins(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &kld_, &k, nullptr));
+    return k;
+  }
+  ParticleUpdateDynamicResults update(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
+                                      DeviceView<Transform> poses_new, DeviceView<ParticleAttributes> attrs_new,
+                                      const ParticleUpdateDynamicConfig& = {}) {
+    init();
+    uint32_t n_new = 0;
+    check(rmclhip_resampler_adaptive(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), poses_new.raw(), attrs_new.raw(),
+                                     static_cast<uint32_t>(poses_new.size()), &kld_, &config_, seed, step_++, &n_new, &last_bins));
+    return {n_new};
+  }
+
+ private:
+  ContextPtr ctx_;
+  rmclhip_resampler* h_ = nullptr;
+  uint32_t step_ = 0;
+};
+
 }  // namespace rmcl_hip

@@ -799,6 +799,66 @@ rmclhip_status rmclhip_resampler_residual(rmclhip_resampler* rs, const rmclhip_t
                                           uint32_t n_new, uint32_t first, uint32_t count, const rmclhip_gladiator_config* config,
                                           uint64_t seed, uint32_t step, uint64_t* n_draws_out);
 
+/* ---- a particle count that follows the posterior: KLD-sampling bound + systematic resampling ------------------------------------
+ * The reference lists it as open ("Improve strategies to reduce the number of particles more intelligently", docs/RMCL.md); its node
+ * already adopts the count a resampler returns (res.n_particles, rmcl_localization.cpp:633-639).  Neither resampler above can shrink
+ * a converged cloud: the gladiator keeps the count, and the residual resampler's shares size_t(L / sum * n_new) of an evenly weighted
+ * cloud all truncate to zero once n_new < n.  Two parts:
+ *   the size the cloud needs -- the KLD-sampling bound (Fox 2003, the rule of AMCL) from the number k of occupied bins of pose space;
+ *   a resampler that produces any requested size from any weights -- systematic (low-variance) resampling.
+ * Random words: the resamplers' stream (counter (index, step, draw, 0)), draws 5, 6 and 7.
+ *
+ * BINS.  The bin of a particle is six int32: floor(t_d / bin_xyz[d]) in float, clamped to [-8192, 8191], and floor((angle_d + pi_f) /
+ * bin_rpy[d]) in float, clamped to [0, 126], for roll, pitch, yaw of the textbook ZYX extraction (float products, atan2 / asin in
+ * double, rounded to float -- as the gladiator's noise step extracts them).  A bin size of 0 ignores the dimension (index 0); x, y and
+ * yaw alone is AMCL's form.  A particle is counted iff its seven pose components and its likelihood.mean L are finite, L > 0 (what the
+ * collision test killed never counts) and L >= min_likelihood_rel * max (float product; max = rmclhip_resampler_compute_stats's).
+ * k = the number of distinct six-tuples among the counted particles: the same for every schedule and order of the cloud.
+ * rmclhip_kld_params_default fills the values in brackets. */
+typedef struct {
+  float bin_xyz[3];          /* [0.5 0.5 0.5] metres; 0 = dimension ignored; finite, >= 0 */
+  float bin_rpy[3];          /* [0.17453292 x3] radians; 0 = ignored; else >= 0.05 */
+  float min_likelihood_rel;  /* [0.01] in [0, 1] */
+  double epsilon;            /* [0.01] bound on the KL divergence; > 0 */
+  double z;                  /* [2.3263479] upper 1 - delta quantile of N(0, 1) (delta = 0.01) */
+  uint32_t n_min, n_max;     /* [500, 0xFFFFFFFF]; n_min >= 1, n_min <= n_max */
+} rmclhip_kld_params;
+void rmclhip_kld_params_default(rmclhip_kld_params* out);
+/* k_out = occupied bins, n_counted_out (nullable) = particles that were counted.  Reads bin_xyz, bin_rpy and min_likelihood_rel of p.
+ * n == 0: both 0.  The table of bins (64-bit words, a power of two >= 2 n) belongs to the handle and grows with n. */
+rmclhip_status rmclhip_particles_count_bins(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
+                                            const rmclhip_particle_attributes* attrs_dev, uint32_t n, const rmclhip_kld_params* p,
+                                            uint32_t* k_out, uint32_t* n_counted_out);
+/* HOST function (no device needed), in double: k < 2 gives n_min; else a = 2 / (9 (k - 1)), x = (1 - a) + sqrt(a) * z,
+ * n = ceil((k - 1) / (2 epsilon) * ((x * x) * x)), clamped to [n_min, n_max] (saturating at 2^32 - 1).  RMCLHIP_ERR_INVALID: epsilon <= 0,
+ * a non-finite epsilon or z, n_min == 0, n_min > n_max. */
+rmclhip_status rmclhip_kld_bound_host(uint32_t k, double epsilon, double z, uint32_t n_min, uint32_t n_max, uint32_t* n_out);
+/* SYSTEMATIC RESAMPLING to n_new particles.  Integer weights w_i = uint64(rint(double(L_i) / double(max) * 2^24)) (L_i negative or
+ * not finite: 0), C = their inclusive 64-bit prefix sums, T = C[n - 1]: exact, whatever the launch shape.  u0 = (r[0] + 0.5) * 2^-32
+ * in double, r = philox(0, step, 5, 0).  Slot j reads pos_j = min(T - 1, uint64(floor((double(j) + u0) * (double(T) / double(n_new)))));
+ * its source is the first i with C[i] > pos_j.  The first slot of a run (slot 0, or source_j != source_j-1) is a bit-for-bit copy of
+ * its source; every further copy is perturbed as the gladiator perturbs a winning enemy (widths min_noise_*, unscaled; the same Euler
+ * step and n_meas rule, trans_dist_metric honoured), Gaussians from philox(j, step, 6, 0) and philox(j, step, 7, 0) in the gladiator's
+ * word order (a[1] a[2] | a[3] b[0] | b[1] b[2]).  Hence an evenly weighted cloud resampled to its own size comes back unchanged, and
+ * every particle gets within one copy of n_new * w_i / T.  Slots first .. first+count-1 land in [0, count); a call that starts at
+ * first > 0 finds the source of slot first - 1 by its own search, so slices equal the whole.  Out of place.
+ * RMCLHIP_ERR_INVALID: max <= 0 or not finite, n_new == 0, first + count > n_new, null buffers with count > 0.  count == 0: OK,
+ * nothing touched. */
+rmclhip_status rmclhip_resampler_systematic(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
+                                            const rmclhip_particle_attributes* attrs_dev, uint32_t n_particles,
+                                            rmclhip_transform* poses_new_dev, rmclhip_particle_attributes* attrs_new_dev,
+                                            uint32_t n_new, uint32_t first, uint32_t count, const rmclhip_gladiator_config* config,
+                                            uint64_t seed, uint32_t step);
+/* what a Resampler::update does with res.n_particles = *n_new_out: statistics -> occupied bins -> bound, with n_max (and, where it is
+ * smaller, n_min) limited by capacity_new, the particles poses_new_dev / attrs_new_dev hold -> systematic resampling to that size.
+ * The result of the three calls made one after the other.  k_out: nullable. */
+rmclhip_status rmclhip_resampler_adaptive(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
+                                          const rmclhip_particle_attributes* attrs_dev, uint32_t n_particles,
+                                          rmclhip_transform* poses_new_dev, rmclhip_particle_attributes* attrs_new_dev,
+                                          uint32_t capacity_new, const rmclhip_kld_params* kld_params,
+                                          const rmclhip_gladiator_config* config, uint64_t seed, uint32_t step, uint32_t* n_new_out,
+                                          uint32_t* k_out);
+
 /* ---- the particle cloud's first and last step: RmclNode::initSamplesUniform / initSamples / visualize ------------------------
  * (rmcl_ros/src/nodes/rmcl_localization.cpp:277-342, 165-275, 797-879; particle store rmcl_localization.hpp:65-77.)
  * The cloud is created ON the device: no host loop, no 68 B per particle upload.  poses_dev / attrs_dev hold particles

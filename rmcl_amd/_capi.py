@@ -88,6 +88,12 @@ class SurfaceStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class KldParams(C.Structure):
+    """rmclhip_kld_params (occupied bins of pose space + the KLD-sampling bound)"""
+    _fields_ = [("bin_xyz", C.c_float * 3), ("bin_rpy", C.c_float * 3), ("min_likelihood_rel", C.c_float), ("epsilon", C.c_double),
+                ("z", C.c_double), ("n_min", C.c_uint32), ("n_max", C.c_uint32)]
+
+
 class LikelihoodStats(C.Structure):
     _fields_ = [("sum", C.c_float), ("max", C.c_float)]
 
@@ -266,6 +272,13 @@ SIGNATURES = {
                                             C.c_uint64, _u32]),
     "rmclhip_resampler_residual": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, C.POINTER(GladiatorConfig),
                                            C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
+    "rmclhip_kld_params_default": (None, [_vp]),
+    "rmclhip_particles_count_bins": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(KldParams), C.POINTER(_u32), C.POINTER(_u32)]),
+    "rmclhip_kld_bound_host": (_i32, [_u32, _dbl, _dbl, _u32, _u32, C.POINTER(_u32)]),
+    "rmclhip_resampler_systematic": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, C.POINTER(GladiatorConfig),
+                                             C.c_uint64, _u32]),
+    "rmclhip_resampler_adaptive": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(KldParams), C.POINTER(GladiatorConfig),
+                                           C.c_uint64, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "rmclhip_chol6_host": (_i32, [_vp, _vp, C.POINTER(_dbl)]),
     "rmclhip_particles_init_uniform": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32]),
     "rmclhip_particles_init_pose": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32, C.POINTER(_dbl)]),

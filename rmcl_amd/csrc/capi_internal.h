@@ -451,6 +451,10 @@ struct rmclhip_resampler {
   // residual resampling: {double sum, double max, u64 expect, u64 n_draws} on the device, the draws' particle / count / prefix sums
   DevBuf<unsigned long long> d_res_stats, d_res_incl, d_res_btot;
   DevBuf<uint32_t> d_res_idx, d_res_cnt;
+  // adaptive count (capi_adaptive.cpp): the bin table (grown to a power of two >= 2 n, cleared per call) and its two counters (landing
+  // in h_res[5]); the systematic resampler's prefix sums and block totals
+  DevBuf<unsigned long long> d_kld_table, d_sys_incl, d_sys_btot;
+  DevBuf<uint32_t> d_kld_cnt;
 };
 
 

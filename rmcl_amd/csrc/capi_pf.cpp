@@ -411,6 +411,7 @@ void rmclhip_resampler_destroy(rmclhip_resampler* r) {
   r->d_pmax.release();
   r->d_out.release();
   r->d_res_stats.release(); r->d_res_incl.release(); r->d_res_btot.release(); r->d_res_idx.release(); r->d_res_cnt.release();
+  r->d_kld_table.release(); r->d_sys_incl.release(); r->d_sys_btot.release(); r->d_kld_cnt.release();
   if (r->h_out) (void)hipHostFree(r->h_out);
   if (r->h_res) (void)hipHostFree(r->h_res);
   r->tag.destroy();

@@ -3,7 +3,7 @@
 // same function of (seed, counter) down to the bit.  Device code only.
 //
 // Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
-//   stream 0: the resamplers   (champion or slot index, step, draw 0..4)
+//   stream 0: the resamplers   (champion or slot index, step, draw 0..7: gladiator 0 1, residual 2 3 4, systematic 5 6 7)
 //   stream 1: the initialisers (global particle index, epoch, draw 0..1)
 // reproducible, independent of the launch shape and of how the particle range is sharded across GPUs.  Transcendentals are evaluated in
 // double and rounded to float (see oracle).
@@ -44,6 +44,20 @@ __device__ __forceinline__ quat euler_to_quat(float roll, float pitch, float yaw
   q.y = cr * sp * cy + sr * cp * sy;
   q.z = cr * cp * sy - sr * sp * cy;
   return q;
+}
+
+// rmagine EulerAngles <- Quaternion (textbook ZYX extraction): float products, atan2 / asin in double, rounded to float -- the
+// statement k_gladiator_resample, k_residual_fill and the pose moments carry inline
+__device__ __forceinline__ void quat_to_euler(quat q, float& roll, float& pitch, float& yaw) {
+  const float sinr_cosp = 2.0f * (q.w * q.x + q.y * q.z);
+  const float cosr_cosp = 1.0f - 2.0f * (q.x * q.x + q.y * q.y);
+  const float sinp = 2.0f * (q.w * q.y - q.z * q.x);
+  const float siny_cosp = 2.0f * (q.w * q.z + q.x * q.y);
+  const float cosy_cosp = 1.0f - 2.0f * (q.y * q.y + q.z * q.z);
+  roll = static_cast<float>(atan2(static_cast<double>(sinr_cosp), static_cast<double>(cosr_cosp)));
+  pitch = (fabsf(sinp) >= 1.0f) ? copysignf(static_cast<float>(3.14159265358979323846 / 2.0), sinp)
+                                : static_cast<float>(asin(static_cast<double>(sinp)));
+  yaw = static_cast<float>(atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp)));
 }
 
 }  // namespace rmclhip

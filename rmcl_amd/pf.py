@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi
 from .registration import _as_ptr
-from .types import RANGE_MEASUREMENT, TRANSFORM, _ptr, gladiator_config, pf_params
+from .types import RANGE_MEASUREMENT, TRANSFORM, _ptr, gladiator_config, kld_params, pf_params
 
 
 def beams_from_points(points):
@@ -379,6 +379,64 @@ class ResidualResamplerHip(GladiatorResamplerHip):
         self.step += 1
         self.last_draws = int(nd.value)
         return {"n_particles": int(count)}
+
+
+def kld_bound(k, epsilon=0.01, z=2.3263479, n_min=500, n_max=0xFFFFFFFF):
+    """rmclhip_kld_bound_host (no device needed): the KLD-sampling bound (Fox 2003) on the particle count for k occupied bins,
+    clamped to [n_min, n_max]"""
+    n = C.c_uint32(0)
+    _capi.check(_capi.lib().rmclhip_kld_bound_host(int(k), float(epsilon), float(z), int(n_min), int(n_max), C.byref(n)))
+    return int(n.value)
+
+
+class AdaptiveResamplerHip(GladiatorResamplerHip):
+    """A resampler that chooses the particle count: the KLD-sampling bound on the occupied bins of pose space, then systematic
+    (low-variance) resampling to that size -- the reference's open item "reduce the number of particles more intelligently"
+    (docs/RMCL.md); its node adopts the returned count (rmcl_localization.cpp:633-639).  `config`: the gladiator's noise (every copy
+    of a particle after the first is perturbed as the gladiator perturbs a winner); `kld`: types.kld_params()."""
+
+    def __init__(self, ctx, seed=1234):
+        super().__init__(ctx, seed)
+        self.kld = kld_params()
+
+    def count_bins(self, particle_poses, particle_attrs, n_particles):
+        """{"bins": occupied bins of pose space, "counted": particles above the likelihood floor} (rmclhip_particles_count_bins)"""
+        self.init()
+        k, c = C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_particles_count_bins(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs), int(n_particles),
+                                                             C.byref(self.kld), C.byref(k), C.byref(c)))
+        return {"bins": int(k.value), "counted": int(c.value)}
+
+    def kld_bound(self, k, capacity=None):
+        """the bound for k bins with this resampler's parameters; capacity limits n_max (and n_min) as update() does"""
+        n_max = int(self.kld.n_max) if capacity is None else min(int(self.kld.n_max), int(capacity))
+        return kld_bound(k, self.kld.epsilon, self.kld.z, min(int(self.kld.n_min), n_max), n_max)
+
+    def update_systematic(self, particle_poses, particle_attrs, particle_poses_new, particle_attrs_new, n_particles, n_particles_new=None,
+                          first=0, count=None):
+        """slots first..first+count-1 (default: all) of a new cloud of n_particles_new (default n_particles) particles by systematic
+        resampling (rmclhip_resampler_systematic); results in particle_*_new[0..count)."""
+        self.init()
+        n_new = int(n_particles if n_particles_new is None else n_particles_new)
+        if count is None:
+            count = n_new - int(first)
+        _capi.check(_capi.lib().rmclhip_resampler_systematic(
+            self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs), int(n_particles), _as_ptr(particle_poses_new),
+            _as_ptr(particle_attrs_new), n_new, int(first), int(count), C.byref(self.config), self.seed, self.step))
+        self.step += 1
+        return {"n_particles": int(count)}
+
+    def update(self, particle_poses, particle_attrs, particle_poses_new, particle_attrs_new, n_particles, capacity_new=None):
+        """Resampler::update with a count of its own: particle_*_new (room for capacity_new particles, default n_particles) receive
+        n_new particles; returns {"n_particles": n_new, "bins": k} (rmclhip_resampler_adaptive)."""
+        self.init()
+        cap = int(n_particles if capacity_new is None else capacity_new)
+        n_new, k = C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_resampler_adaptive(
+            self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs), int(n_particles), _as_ptr(particle_poses_new),
+            _as_ptr(particle_attrs_new), cap, C.byref(self.kld), C.byref(self.config), self.seed, self.step, C.byref(n_new), C.byref(k)))
+        self.step += 1
+        return {"n_particles": int(n_new.value), "bins": int(k.value)}
 
 
 class ShardedParticleFilterHip:

@@ -145,6 +145,24 @@ def surface_params(axis=None, height=None, probe_up=None, probe_down=None, min_u
     return p
 
 
+def kld_params(bin_xyz=None, bin_rpy=None, min_likelihood_rel=None, epsilon=None, z=None, n_min=None, n_max=None):
+    """rmclhip_kld_params: the bins of pose space and the KLD-sampling bound of the adaptive resampler (include/rmclhip.h).  Arguments
+    left None keep the library's defaults (rmclhip_kld_params_default): bins of 0.5 m and 10 degrees (0 ignores a dimension; x, y and
+    yaw alone is AMCL's form), likelihood floor 0.01 of the maximum, epsilon 0.01, z 2.3263479 (delta 0.01), n_min 500, n_max 2^32 - 1."""
+    p = _capi.KldParams()
+    _capi.lib().rmclhip_kld_params_default(C.byref(p))
+    for k, v in (("bin_xyz", bin_xyz), ("bin_rpy", bin_rpy)):
+        if v is not None:
+            setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]))
+    for k, v in (("min_likelihood_rel", min_likelihood_rel), ("epsilon", epsilon), ("z", z)):
+        if v is not None:
+            setattr(p, k, float(v))
+    for k, v in (("n_min", n_min), ("n_max", n_max)):
+        if v is not None:
+            setattr(p, k, int(v))
+    return p
+
+
 def gladiator_config(min_noise_tx=0.03, min_noise_ty=0.03, min_noise_tz=0.0, min_noise_roll=0.0, min_noise_pitch=0.0,
                      min_noise_yaw=0.01, likelihood_forget_per_meter=0.3, likelihood_forget_per_radian=0.2,
                      trans_dist_metric=0):
