@@ -768,7 +768,15 @@ rmclhip_status rmclhip_pf_sample_beams_pointcloud2(const uint8_t* data, size_t n
  * (enemy: copied, perturbed by the min_noise_* Gaussians, n_meas *= remember_rate) lands in
  * poses_new_dev / attrs_new_dev [0 .. count).  first/count let one GPU resample its shard of an all-gathered
  * cloud.  Random numbers: Philox4x32-10, key = seed, counter = (champion index, step, draw, 0) -- reproducible
- * and independent of the sharding (the reference's cuRAND / mt19937 streams are not reproducible). */
+ * and independent of the sharding (the reference's cuRAND / mt19937 streams are not reproducible).
+ * The configuration of EVERY resampler below (gladiator, residual, systematic, adaptive, and the sharded resampling calls) is checked
+ * before anything is launched, like the motion update's forget_rate: likelihood_forget_per_meter and likelihood_forget_per_radian are
+ * fractions in [0, 1] -- outside that range pow() of a negative base is NaN --, the min_noise_* widths are finite; anything else, NaN
+ * included, is refused with RMCLHIP_ERR_INVALID and the output buffers are not touched.
+ * The store into the uint32 n_meas, uint32(float(n_meas) * rate), is pinned where C++ leaves the conversion undefined: NaN or a
+ * product <= 0 gives 0, a product >= 2^32 gives 0xFFFFFFFF (float(n_meas) is 2^32 for every n_meas >= 2^32 - 128), anything else is
+ * truncated.  That is what the CUDA reference's conversion does (resampling.cu:188); the reference's x86 CPU resamplers are undefined
+ * for those values (they give 0 when built with gcc). */
 rmclhip_status rmclhip_resampler_create(rmclhip_ctx* ctx, rmclhip_resampler** out);
 void rmclhip_resampler_destroy(rmclhip_resampler* rs);
 rmclhip_status rmclhip_resampler_compute_stats(rmclhip_resampler* rs, const rmclhip_particle_attributes* attrs_dev,
@@ -792,7 +800,8 @@ rmclhip_status rmclhip_resampler_gladiator(rmclhip_resampler* rs, const rmclhip_
  * with the sequential loop's result.  Slots first .. first+count-1 land in poses_new_dev / attrs_new_dev [0 .. count) (a GPU
  * can fill its shard of an all-gathered cloud).  config: the gladiator's struct (trans_dist_metric is ignored).
  * n_draws_out (nullable): draws the sequential loop uses -- set when the call fills the LAST slot.  Errors: likelihoods that
- * sum to zero; shares that all truncate to zero (the reference's loop would not terminate). */
+ * sum to zero, to a negative value or to NaN (one NaN likelihood is enough); shares that all truncate to zero (the reference's loop
+ * would not terminate).  A negative likelihood in a cloud whose sum is positive has a non-positive share and is never inserted. */
 rmclhip_status rmclhip_resampler_residual(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
                                           const rmclhip_particle_attributes* attrs_dev, uint32_t n_particles,
                                           rmclhip_transform* poses_new_dev, rmclhip_particle_attributes* attrs_new_dev,

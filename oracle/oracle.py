@@ -177,6 +177,9 @@ def lib():
     L.orc_likelihood_stats_compute.argtypes = [vp, u32]
     L.orc_quat_to_euler.argtypes = [Quat, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]
     L.orc_gladiator_resample.argtypes = [vp, vp, u32, vp, vp, u32, u32, C.POINTER(GladiatorConfig), C.c_uint64, u32]
+    L.orc_philox_word0.argtypes = [u32, u32, u32, u32, C.c_uint64, vp]
+    L.orc_n_meas_scaled.restype = u32
+    L.orc_n_meas_scaled.argtypes = [u32, f32]
     L.orc_residual_resample.restype = u32
     L.orc_residual_resample.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(GladiatorConfig), C.c_uint64, u32, C.c_uint64, C.POINTER(C.c_uint64)]
     _lib = L
@@ -535,6 +538,18 @@ def philox4x32_10(ctr, key):
     out = np.zeros(4, dtype=np.uint32)
     lib().orc_philox4x32_10(_p(c), _p(k), _p(out))
     return out
+
+
+def philox_word0(first, count, step, draw, seed):
+    """word 0 of philox(first + i, step, draw, 0), i < count: the enemy (draw 0) or source (draw 2) stream before the modulo"""
+    out = np.zeros(int(count), dtype=np.uint32)
+    lib().orc_philox_word0(int(first), int(count), int(step), int(draw), int(seed), _p(out))
+    return out
+
+
+def n_meas_scaled(n_meas, rate):
+    """uint32(float(n_meas) * rate) with the pinned conversion (orc_n_meas_scaled)"""
+    return int(lib().orc_n_meas_scaled(int(n_meas), float(rate)))
 
 
 def likelihood_stats(attrs):

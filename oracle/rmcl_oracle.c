@@ -1513,6 +1513,18 @@ void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t ou
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+/* word 0 of philox(first + i, step, draw, 0) for i < count: the draw streams of the resamplers, for tests that search them */
+void orc_philox_word0(uint32_t first, uint32_t count, uint32_t step, uint32_t draw, uint64_t seed, uint32_t* out)
+{
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t c[4] = {first + i, step, draw, 0u};
+    uint32_t r[4];
+    orc_philox4x32_10(c, key, r);
+    out[i] = r[0];
+  }
+}
+
 /* simple_stats_kernel (resampling.cu:41-81): {sum, max} of likelihood.mean, max seeded with 0 like the kernel's
  * shared-memory init (:52-53); the sum is accumulated in double (order independent to float precision). */
 orc_likelihood_stats orc_likelihood_stats_compute(const orc_particle_attributes* attrs, uint32_t n)
@@ -1562,6 +1574,18 @@ static void box_muller(uint32_t a, uint32_t b, float* z0, float* z1)
   *z1 = (float)(r * sin(ang));
 }
 
+/* n_meas after a resampler forgets: uint32(float(n_meas) * rate) (resampling.cu:188) with the conversion PINNED.  C leaves the
+ * conversion of NaN, of a negative value and of one >= 2^32 undefined, and float(n_meas) is 2^32 for every n_meas >= 2^32 - 128:
+ * the reference's x86 CPU resamplers are undefined there (gcc's cvttss2si turns it into 0), its CUDA kernel saturates.  The rule is
+ * the CUDA one, written out: NaN or <= 0 -> 0; >= 2^32 -> 0xFFFFFFFF; otherwise truncate. */
+uint32_t orc_n_meas_scaled(uint32_t n_meas, float rate)
+{
+  const float v = (float)n_meas * rate;
+  if (!(v > 0.0f)) return 0u;
+  if (v >= 4294967296.0f) return 0xFFFFFFFFu;
+  return (uint32_t)v;
+}
+
 void orc_gladiator_resample(const orc_transform* poses, const orc_particle_attributes* attrs, uint32_t n,
                             orc_transform* poses_new, orc_particle_attributes* attrs_new, uint32_t first,
                             uint32_t count, const orc_gladiator_config* cfg, uint64_t seed, uint32_t step)
@@ -1601,7 +1625,7 @@ void orc_gladiator_resample(const orc_transform* poses, const orc_particle_attri
       const float frr = (float)(1.0 - pow(1.0 - (double)cfg->likelihood_forget_per_radian, (double)rot_dist));
       const float forget_rate = (frs > frr) ? frs : frr;
       const float remember_rate = (float)(1.0 - (double)forget_rate);
-      attrs_n.likelihood.n_meas = (uint32_t)((float)attrs_n.likelihood.n_meas * remember_rate);
+      attrs_n.likelihood.n_meas = orc_n_meas_scaled(attrs_n.likelihood.n_meas, remember_rate);
       poses_new[k] = pose_new;
       attrs_new[k] = attrs_n;
     } else {
@@ -1681,7 +1705,7 @@ uint32_t orc_residual_resample(const orc_transform* poses, const orc_particle_at
       const float rot_dist = sqrtf(((diff.R.w * diff.R.w + diff.R.x * diff.R.x) + diff.R.y * diff.R.y) + diff.R.z * diff.R.z);
       const float reduction_factor = (float)pow((double)cfg->likelihood_forget_per_meter, (double)trans_dist) *
                                      (float)pow((double)cfg->likelihood_forget_per_radian, (double)rot_dist);
-      attrs_n.likelihood.n_meas = (uint32_t)((float)attrs_n.likelihood.n_meas * reduction_factor);
+      attrs_n.likelihood.n_meas = orc_n_meas_scaled(attrs_n.likelihood.n_meas, reduction_factor);
       poses_new[j] = pose_new;
       attrs_new[j] = attrs_n;
     }

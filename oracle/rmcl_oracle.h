@@ -192,8 +192,12 @@ typedef struct {
 } orc_gladiator_config;
 typedef struct { float sum, max; } orc_likelihood_stats;
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+void orc_philox_word0(uint32_t first, uint32_t count, uint32_t step, uint32_t draw, uint64_t seed, uint32_t* out);
 orc_likelihood_stats orc_likelihood_stats_compute(const orc_particle_attributes* attrs, uint32_t n);
 void orc_quat_to_euler(orc_quat q, float* roll, float* pitch, float* yaw);
+/* uint32(float(n_meas) * rate) with the conversion pinned: NaN or <= 0 -> 0, >= 2^32 -> 0xFFFFFFFF, else truncate (the CUDA
+ * reference's behaviour; the x86 CPU reference is undefined for these values) */
+uint32_t orc_n_meas_scaled(uint32_t n_meas, float rate);
 /* champions first .. first+count-1 fight a random enemy out of the n particles; the winners land in
  * poses_new / attrs_new [0 .. count) */
 void orc_gladiator_resample(const orc_transform* poses, const orc_particle_attributes* attrs, uint32_t n,

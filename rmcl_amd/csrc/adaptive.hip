@@ -233,7 +233,7 @@ __global__ void __launch_bounds__(kBlock) k_sys_fill(const xform* __restrict__ p
   const float frr = static_cast<float>(1.0 - pow(1.0 - static_cast<double>(cfg.likelihood_forget_per_radian), static_cast<double>(rot_dist)));
   const float forget_rate = (frs > frr) ? frs : frr;
   const float remember_rate = static_cast<float>(1.0 - static_cast<double>(forget_rate));
-  an.n_meas = static_cast<uint32_t>(static_cast<float>(an.n_meas) * remember_rate);
+  an.n_meas = n_meas_scaled(an.n_meas, remember_rate);
   poses_new[t] = pn;
   attrs_new[t] = an;
 }

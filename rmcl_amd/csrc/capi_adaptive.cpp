@@ -94,9 +94,9 @@ static rmclhip_status systematic_check(const char* who_, rmclhip_resampler* r, c
                                        const rmclhip_gladiator_config* cfg) {
   const std::string who(who_);
   if (!r || !cfg) return fail(RMCLHIP_ERR_INVALID, who + ": null");
+  if (rmclhip_status cs = resampler_config_check(who_, cfg)) return cs;
   if (n_new == 0) return fail(RMCLHIP_ERR_INVALID, who + ": a new cloud of 0 particles");
   if (static_cast<uint64_t>(first) + count > n_new) return fail(RMCLHIP_ERR_INVALID, who + ": slot range exceeds the new cloud");
-  if (cfg->trans_dist_metric > 1u) return fail(RMCLHIP_ERR_INVALID, who + ": trans_dist_metric must be 0 or 1");
   if (count == 0) return RMCLHIP_OK;
   if (!poses_dev || !attrs_dev || !poses_new_dev || !attrs_new_dev || n_particles == 0) return fail(RMCLHIP_ERR_INVALID, who + ": null particle buffers");
   if (poses_new_dev == poses_dev || attrs_new_dev == attrs_dev) return fail(RMCLHIP_ERR_INVALID, who + ": out of place (double buffers)");

@@ -504,6 +504,8 @@ RMCL_INTERNAL rmclhip_status find_batch_enqueue(rmclhip_rcc* r, const rmclhip_tr
 RMCL_INTERNAL rmclhip_status batch_order_enqueue(rmclhip_rcc* r, FindParams& p, int variant);   // pose batches in world order (capi_rcc_tune.cpp)
 RMCL_INTERNAL rmclhip_status ensure_near_grid(rmclhip_map* m, hipStream_t stream, bool full, const NearGrid** out);
 RMCL_INTERNAL rmclhip_status map_upload(rmclhip_ctx* ctx, const BvhHost& bvh, rmclhip_map** out);
+// forget rates outside [0, 1] or NaN, non-finite noise widths, a trans_dist_metric above 1: RMCLHIP_ERR_INVALID (rmclhip.h states the rule)
+RMCL_INTERNAL rmclhip_status resampler_config_check(const char* who, const rmclhip_gladiator_config* cfg);
 RMCL_INTERNAL rmclhip_status gladiator_enqueue(rmclhip_resampler* r, const rmclhip_transform* poses_dev, const rmclhip_particle_attributes* attrs_dev, uint32_t n_particles, rmclhip_transform* poses_new_dev, rmclhip_particle_attributes* attrs_new_dev, uint32_t first, uint32_t count, const rmclhip_gladiator_config* cfg, uint64_t seed, uint32_t step, hipStream_t st);
 RMCL_INTERNAL rmclhip_status residual_prepare_enqueue(ResidualJob& j);
 RMCL_INTERNAL rmclhip_status residual_fill_enqueue(ResidualJob& j, bool want_n_draws);

@@ -765,6 +765,11 @@ rmclhip_status rmclhip_pf_sharded_step(rmclhip_pf_sharded* h, const rmclhip_tran
   if (resample < 0 || resample > 2 || (resample != 0 && !cfg)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: bad resampling arguments");
   if (T_bnew_bold && !(forget_rate >= 0.0 && forget_rate <= 1.0))
     return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: forget_rate outside [0, 1] (or NaN)");
+  if (resample != 0) {   // the resampler's own rule, before the motion and sensor updates change the cloud
+    rmclhip_gladiator_config c = *cfg;
+    if (resample == 2) c.trans_dist_metric = 0u;
+    if (rmclhip_status cs = resampler_config_check("pf_sharded_step", &c)) return cs;
+  }
   if (h->n_total == 0) { if (stats_out) { stats_out->sum = 0.f; stats_out->max = 0.f; } return RMCLHIP_OK; }
   if (T_bnew_bold) {
     trace_mark("motion:");
@@ -926,6 +931,11 @@ rmclhip_status rmclhip_pf_sharded_resample_residual(rmclhip_pf_sharded* h, const
 static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmclhip_gladiator_config* cfg, uint64_t seed, uint32_t step,
                                               bool residual) {
   if (!h || !cfg) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_resample: null");
+  {   // before the all-gather: a refused call leaves the cloud, and the gathered copies, alone
+    rmclhip_gladiator_config c = *cfg;
+    if (residual) c.trans_dist_metric = 0u;   // ignored by the residual resampler
+    if (rmclhip_status cs = resampler_config_check(residual ? "pf_sharded_resample_residual" : "pf_sharded_resample", &c)) return cs;
+  }
   if (h->n_total == 0) return RMCLHIP_OK;
   h->weights_fresh = false;   // the cloud is about to be replaced
   const uint32_t world = static_cast<uint32_t>(h->ranks.size()), cap = (h->n_total + world - 1u) / world;

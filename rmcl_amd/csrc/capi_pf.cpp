@@ -448,17 +448,32 @@ rmclhip_status rmclhip_resampler_compute_stats_weights(rmclhip_resampler* r, con
 // The resamplers as ENQUEUE + WAIT (round 4): the sharded entry points enqueue every device's part before they wait for any
 // (pf_sharded_resample_impl); the public single-device calls are enqueue + one wait.  `st`: the stream the work goes to (the
 // resampler's own, or the communicator's stream of that device behind the all-gather of the cloud).
+// one check of the resampling parameters for every resampler: a forget rate outside [0, 1] makes pow() of a negative base NaN, and the
+// NaN (or a product past 2^32) would reach the store into the uint32 n_meas; a non-finite noise width makes every perturbed pose NaN
+RMCL_INTERNAL rmclhip_status resampler_config_check(const char* who_, const rmclhip_gladiator_config* cfg) {
+  const std::string who(who_);
+  if (!cfg) return fail(RMCLHIP_ERR_INVALID, who + ": null");
+  if (cfg->trans_dist_metric > 1u) return fail(RMCLHIP_ERR_INVALID, who + ": trans_dist_metric must be 0 or 1");
+  if (!(cfg->likelihood_forget_per_meter >= 0.0f && cfg->likelihood_forget_per_meter <= 1.0f) ||
+      !(cfg->likelihood_forget_per_radian >= 0.0f && cfg->likelihood_forget_per_radian <= 1.0f))
+    return fail(RMCLHIP_ERR_INVALID, who + ": likelihood_forget_per_meter / _per_radian outside [0, 1] (or NaN)");
+  const float w[6] = {cfg->min_noise_tx, cfg->min_noise_ty, cfg->min_noise_tz, cfg->min_noise_roll, cfg->min_noise_pitch, cfg->min_noise_yaw};
+  for (float v : w)
+    if (!std::isfinite(v)) return fail(RMCLHIP_ERR_INVALID, who + ": a min_noise_* width is not finite");
+  return RMCLHIP_OK;
+}
+
 RMCL_INTERNAL rmclhip_status gladiator_enqueue(rmclhip_resampler* r, const rmclhip_transform* poses_dev, const rmclhip_particle_attributes* attrs_dev,
                                         uint32_t n_particles, rmclhip_transform* poses_new_dev, rmclhip_particle_attributes* attrs_new_dev,
                                         uint32_t first, uint32_t count, const rmclhip_gladiator_config* cfg, uint64_t seed, uint32_t step,
                                         hipStream_t st) {
   if (!r || !cfg) return fail(RMCLHIP_ERR_INVALID, "resampler_gladiator: null");
+  if (rmclhip_status cs = resampler_config_check("resampler_gladiator", cfg)) return cs;
   if (count == 0) return RMCLHIP_OK;
   if (!poses_dev || !attrs_dev || !poses_new_dev || !attrs_new_dev || n_particles == 0)
     return fail(RMCLHIP_ERR_INVALID, "resampler_gladiator: null particle buffers");
   if (static_cast<uint64_t>(first) + count > n_particles)
     return fail(RMCLHIP_ERR_INVALID, "resampler_gladiator: champion range exceeds the particle count");
-  if (cfg->trans_dist_metric > 1u) return fail(RMCLHIP_ERR_INVALID, "resampler_gladiator: trans_dist_metric must be 0 or 1");
   if (poses_new_dev == poses_dev || attrs_new_dev == attrs_dev)
     return fail(RMCLHIP_ERR_INVALID, "resampler_gladiator: the tournament is out of place (double buffers)");
   HIPCHK(hipSetDevice(r->ctx->device));
@@ -489,6 +504,11 @@ rmclhip_status rmclhip_resampler_gladiator(rmclhip_resampler* r, const rmclhip_t
 RMCL_INTERNAL rmclhip_status residual_check(ResidualJob& j) {
   j.active = false;
   if (!j.r || !j.cfg) return fail(RMCLHIP_ERR_INVALID, "resampler_residual: null");
+  {   // (trans_dist_metric is ignored by this resampler: not refused for it)
+    rmclhip_gladiator_config c = *j.cfg;
+    c.trans_dist_metric = 0u;
+    if (rmclhip_status cs = resampler_config_check("resampler_residual", &c)) return cs;
+  }
   if (j.n_new == 0 || j.count == 0) return RMCLHIP_OK;
   if (!j.poses || !j.attrs || !j.poses_new || !j.attrs_new || j.n_particles == 0)
     return fail(RMCLHIP_ERR_INVALID, "resampler_residual: null particle buffers");

@@ -1786,7 +1786,7 @@ __global__ void __launch_bounds__(256) k_gladiator_resample(const xform* __restr
     const float frr = static_cast<float>(1.0 - pow(1.0 - static_cast<double>(cfg.likelihood_forget_per_radian), static_cast<double>(rot_dist)));
     const float forget_rate = (frs > frr) ? frs : frr;
     const float remember_rate = static_cast<float>(1.0 - static_cast<double>(forget_rate));
-    an.likelihood.n_meas = static_cast<uint32_t>(static_cast<float>(an.likelihood.n_meas) * remember_rate);
+    an.likelihood.n_meas = n_meas_scaled(an.likelihood.n_meas, remember_rate);
     poses_new[k] = pn;
     attrs_new[k] = an;
   } else {
@@ -1969,7 +1969,7 @@ __global__ void __launch_bounds__(256) k_residual_fill(const xform* __restrict__
   const float rot_dist = sqrtf(((diff.R.w * diff.R.w + diff.R.x * diff.R.x) + diff.R.y * diff.R.y) + diff.R.z * diff.R.z);
   const float reduction_factor = static_cast<float>(pow(static_cast<double>(cfg.likelihood_forget_per_meter), static_cast<double>(trans_dist))) *
                                  static_cast<float>(pow(static_cast<double>(cfg.likelihood_forget_per_radian), static_cast<double>(rot_dist)));
-  an.likelihood.n_meas = static_cast<uint32_t>(static_cast<float>(an.likelihood.n_meas) * reduction_factor);
+  an.likelihood.n_meas = n_meas_scaled(an.likelihood.n_meas, reduction_factor);
   poses_new[t] = pn;
   attrs_new[t] = an;
 }

@@ -60,4 +60,16 @@ __device__ __forceinline__ void quat_to_euler(quat q, float& roll, float& pitch,
   yaw = static_cast<float>(atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp)));
 }
 
+// n_meas after a resampler forgets: uint32(float(n_meas) * rate), the reference's statement (resampling.cu:188), with the
+// conversion written out -- C++ leaves a float -> uint32 conversion of NaN, of a negative value or of one >= 2^32 undefined, and
+// float(n_meas) IS 2^32 for every n_meas >= 2^32 - 128.  The rule (what the CUDA reference's conversion instruction does; its x86
+// CPU resamplers are undefined here): NaN or <= 0 -> 0; >= 2^32 -> 0xFFFFFFFF; otherwise truncate.  Used by k_gladiator_resample,
+// k_residual_fill (kernels.hip) and k_sys_fill (adaptive.hip); oracle/rmcl_oracle.c: orc_n_meas_scaled pins the same text.
+__host__ __device__ __forceinline__ uint32_t n_meas_scaled(uint32_t n_meas, float rate) {
+  const float v = static_cast<float>(n_meas) * rate;
+  if (!(v > 0.0f)) return 0u;
+  if (v >= 4294967296.0f) return 0xFFFFFFFFu;
+  return static_cast<uint32_t>(v);
+}
+
 }  // namespace rmclhip

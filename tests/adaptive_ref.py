@@ -187,6 +187,17 @@ def _qrot(q, p):
     return r[0], r[1], r[2]
 
 
+def n_meas_scaled(n_meas, rate):
+    """uint32(float(n_meas) * rate) with the library's pinned conversion (pf_random.hip.h: n_meas_scaled): NaN or <= 0 -> 0,
+    >= 2^32 -> 0xFFFFFFFF, otherwise truncate"""
+    v = np.asarray(n_meas, dtype=np.uint32).astype(f32) * np.asarray(rate, dtype=f32)
+    big, mid = v >= f32(4294967296.0), (v > 0) & (v < f32(4294967296.0))
+    out = np.zeros(v.shape, dtype=np.uint32)
+    out[big] = 0xFFFFFFFF
+    out[mid] = v[mid].astype(np.int64).astype(np.uint32)
+    return out
+
+
 def perturb(poses, attrs, slots, cfg, seed, step):
     """the gladiator's winning enemy (kernels.hip: k_gladiator_resample) with the Gaussians of the GLOBAL slot indices `slots` from
     draws 6 and 7; poses / attrs: the sources, one per slot"""
@@ -220,7 +231,7 @@ def perturb(poses, attrs, slots, cfg, seed, step):
         pn["t"][k] = v
     for k, v in zip("xyzw", qn):
         pn["R"][k] = v
-    an["likelihood"]["n_meas"] = (attrs["likelihood"]["n_meas"].astype(f32) * remember).astype(np.uint32)
+    an["likelihood"]["n_meas"] = n_meas_scaled(attrs["likelihood"]["n_meas"], remember)
     return pn, an
 
 
