@@ -1255,6 +1255,17 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
     check(rmclhip_pf_allreduce_pose_estimate(h_, max_induction_particles, &e));
     return e;
   }
+  // the clusters of the whole cloud's occupied bins, heaviest first (rmclhip_pf_sharded_pose_hypotheses): the records are gathered and
+  // rank 0 runs PoseEstimatorHip's path; the cloud is not changed.  n_clusters_out: nullable
+  std::vector<rmclhip_pose_hypothesis> estimateHypotheses(const rmclhip_kld_params& bins, uint32_t max_hypotheses = 8,
+                                                          uint32_t* n_clusters_out = nullptr) const {
+    std::vector<rmclhip_pose_hypothesis> out(max_hypotheses ? max_hypotheses : 1u);
+    uint32_t n_out = 0, n_clusters = 0;
+    check(rmclhip_pf_sharded_pose_hypotheses(h_, &bins, max_hypotheses, out.data(), &n_out, &n_clusters));
+    out.resize(n_out);
+    if (n_clusters_out) *n_clusters_out = n_clusters;
+    return out;
+  }
   // MotionUpdater<MemT>::update on every device's block, in place (rmcl_localization.cpp:432-480; particle_motion.cu:11-46 + the collision
   // ray of TFMotionUpdaterCPU.cpp:17-50): the odometry lookup and the combined forget rate stay with the caller, as for TFMotionUpdaterHip
   void motionUpdate(const Transform& T_bnew_bold, double forget_rate, bool check_collision = true) {
@@ -1445,6 +1456,54 @@ class AdaptiveResamplerHip : public SensorUpdaterBase {
   ContextPtr ctx_;
   rmclhip_resampler* h_ = nullptr;
   uint32_t step_ = 0;
+};
+
+// RmclNode::estimateStats (rmcl_localization.cpp:642-731) for a cloud on one device, and its answer while the posterior still has
+// several modes: pose hypotheses -- the connected components of the occupied bins AdaptiveResamplerHip counts, weighed and ranked, each
+// with a mean and covariance of its own (rmclhip.h, POSE HYPOTHESES).  kld_: bin_xyz, bin_rpy and min_likelihood_rel are read.
+class PoseEstimatorHip {
+ public:
+  rmclhip_kld_params kld_;
+  uint32_t last_clusters = 0;   // clusters the last estimateHypotheses found
+
+  explicit PoseEstimatorHip(ContextPtr ctx) : ctx_(std::move(ctx)) {
+    if (!ctx_) throw std::runtime_error("NO CONTEXT");
+    rmclhip_kld_params_default(&kld_);
+  }
+  PoseEstimatorHip(const PoseEstimatorHip&) = delete;
+  PoseEstimatorHip& operator=(const PoseEstimatorHip&) = delete;
+  ~PoseEstimatorHip() { rmclhip_resampler_destroy(h_); }
+  void init() {
+    if (!h_) check(rmclhip_resampler_create(ctx_->handle(), &h_));
+  }
+  rmclhip_pose_estimate estimateStats(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
+                                      uint32_t max_induction_particles = 0xFFFFFFFFu) {
+    init();
+    rmclhip_pose_estimate e{};
+    check(rmclhip_particles_pose_estimate(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), max_induction_particles, &e));
+    return e;
+  }
+  rmclhip_pose_estimate estimateStats(ParticleCloud<VRAM_HIP>& cloud, uint32_t max_induction_particles = 0xFFFFFFFFu) {
+    return estimateStats(cloud.posesView(), cloud.attrsView(), max_induction_particles);
+  }
+  // heaviest first; labels_dev (nullable): device uint32 per particle, the rank of its cluster or 0xFFFFFFFF
+  std::vector<rmclhip_pose_hypothesis> estimateHypotheses(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
+                                                          uint32_t max_hypotheses = 8, uint32_t* labels_dev = nullptr) {
+    init();
+    std::vector<rmclhip_pose_hypothesis> out(max_hypotheses ? max_hypotheses : 1u);
+    uint32_t n_out = 0;
+    check(rmclhip_particles_pose_hypotheses(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &kld_, max_hypotheses, out.data(),
+                                            &n_out, &last_clusters, labels_dev));
+    out.resize(n_out);
+    return out;
+  }
+  std::vector<rmclhip_pose_hypothesis> estimateHypotheses(ParticleCloud<VRAM_HIP>& cloud, uint32_t max_hypotheses = 8, uint32_t* labels_dev = nullptr) {
+    return estimateHypotheses(cloud.posesView(), cloud.attrsView(), max_hypotheses, labels_dev);
+  }
+
+ private:
+  ContextPtr ctx_;
+  rmclhip_resampler* h_ = nullptr;
 };
 
 }  // namespace rmcl_hip

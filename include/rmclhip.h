@@ -997,6 +997,58 @@ rmclhip_status rmclhip_pf_sharded_resample(rmclhip_pf_sharded* pf, const rmclhip
  * gathered one -- identical to one GPU (draws and Gaussians are functions of global indices) */
 rmclhip_status rmclhip_pf_sharded_resample_residual(rmclhip_pf_sharded* pf, const rmclhip_gladiator_config* config, uint64_t seed, uint32_t step);
 
+/* ---- pose hypotheses: the clusters of the cloud's occupied bins ------------------------------------------------------------------
+ * While the posterior still has two or more modes (a symmetric corridor, a repeated room: the phase uniform initialisation and the
+ * KLD bound exist for), the one Markley mean of estimateStats lies between them.  AMCL, whose bound is adopted above, answers with
+ * cluster statistics: group the occupied bins, weigh each group, report the heaviest group's mean and covariance.  Every quantity
+ * marked EXACT is the same for every launch shape, every order of the cloud and every shard count.
+ *
+ * BINS.  rmclhip_particles_count_bins's: the same six fields, clamps, ignored dimensions, counted-particle rule and likelihood floor
+ * min_likelihood_rel * max (max = rmclhip_resampler_compute_stats's).  A particle that is not counted belongs to no bin and no cluster;
+ * a bin that only uncounted particles fall into does not exist and joins nothing.  The 63-bit key of a bin: (x + 8192) | (y + 8192) << 14
+ * | (z + 8192) << 28 | roll << 42 | pitch << 49 | yaw << 56.
+ * ADJACENCY.  Two occupied bins are neighbours iff they are adjacent in every one of the six fields.  x, y, z and pitch: |i - j| <= 1.
+ * roll and yaw, which wrap: |i - j| <= 1, or min(i, j) == 0 && max(i, j) >= last - 1, last = the index the bin rule gives the angle pi_f
+ * (floor((3.14159265f + pi_f) / width) in float, clamped).  The last - 1 is deliberate: with the default 10 degree width `last` is a sliver
+ * bin that holds +pi alone, and the particles just below +pi sit in last - 1.  An ignored dimension has a constant index and never
+ * separates bins; a rule with d active fields has 3^d - 1 neighbours per bin (a few more at the wrap).
+ * CLUSTERS.  The connected components of that graph.  key_min: the smallest key among a cluster's bins, its id (EXACT).  n_bins and
+ * estimate.n_particles: its bins and its counted particles (EXACT).  weight: the sum over its counted particles of the systematic
+ * resampler's integer weight uint64(rint(double(L_i) / double(max) * 2^24)) (EXACT).  weight_share: double(weight) / double(total weight
+ * of all counted particles).
+ * ORDER.  By weight descending, then key_min ascending (keys are distinct: a total order).  Hypothesis r is the cluster of rank r, for
+ * r < min(max_hypotheses, n_clusters).
+ * ESTIMATE.  A rmclhip_pose_estimate filled as rmclhip_pf_allreduce_pose_estimate fills it, over the cluster's counted particles alone,
+ * in ascending particle index, without an n_induction cut: likelihood statistics and translation box, the Markley mean with weights
+ * L_i / L_sum (L_sum the cluster's own sum, in double), the covariance around that mean.
+ * LABELS.  Optional device uint32[n]: entry i = the rank of particle i's cluster if that rank is below max_hypotheses, else
+ * 0xFFFFFFFF; uncounted particles get 0xFFFFFFFF (EXACT). */
+typedef struct {
+  rmclhip_pose_estimate estimate;
+  uint64_t key_min, weight;
+  double weight_share;
+  uint32_t n_bins, reserved;
+} rmclhip_pose_hypothesis;
+/* RmclNode::estimateStats (rmcl_localization.cpp:642-731) over the first min(n, n_induction) particles of a cloud on ONE device:
+ * rmclhip_pf_allreduce_pose_estimate on a one-rank sharded filter, bit for bit (the same kernels and the same host code), its
+ * refusals included: RMCLHIP_ERR_INVALID "no particles" (n or n_induction 0), "sum to zero".  *out is zeroed first.  Synchronous. */
+rmclhip_status rmclhip_particles_pose_estimate(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
+                                               const rmclhip_particle_attributes* attrs_dev, uint32_t n, uint32_t n_induction,
+                                               rmclhip_pose_estimate* out);
+/* Reads bin_xyz, bin_rpy and min_likelihood_rel of bins (checked as count_bins checks them).  max_hypotheses in [1, 64], else
+ * RMCLHIP_ERR_INVALID; out holds max_hypotheses records, the first *n_out = min(max_hypotheses, *n_clusters_out) are written.  n == 0 or
+ * no counted particle (a maximum <= 0 or not finite included): RMCLHIP_OK, both counts 0, nothing written to out, labels all
+ * 0xFFFFFFFF.  At most 2^30 particles.  The scratch belongs to the handle and grows as the bin table does; a later
+ * rmclhip_particles_count_bins / rmclhip_resampler_adaptive on the handle returns what it returned before.  Synchronous. */
+rmclhip_status rmclhip_particles_pose_hypotheses(rmclhip_resampler* rs, const rmclhip_transform* poses_dev,
+                                                 const rmclhip_particle_attributes* attrs_dev, uint32_t n, const rmclhip_kld_params* bins,
+                                                 uint32_t max_hypotheses, rmclhip_pose_hypothesis* out, uint32_t* n_out,
+                                                 uint32_t* n_clusters_out, uint32_t* labels_dev /* nullable */);
+/* the sharded cloud's hypotheses: the particle records are gathered as rmclhip_pf_sharded_resample gathers them, then the
+ * single-device path runs on rank 0's gathered copy -- the single-device bytes.  The cloud is not changed. */
+rmclhip_status rmclhip_pf_sharded_pose_hypotheses(rmclhip_pf_sharded* pf, const rmclhip_kld_params* bins, uint32_t max_hypotheses,
+                                                  rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out);
+
 /* ---- device memory helpers for hosts without their own allocator ---------------------- */
 rmclhip_status rmclhip_malloc(rmclhip_ctx* ctx, size_t bytes, void** out_dev);
 rmclhip_status rmclhip_free(rmclhip_ctx* ctx, void* ptr_dev);

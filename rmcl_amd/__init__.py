@@ -7,7 +7,7 @@ from . import _capi, types, synthetic, wire  # noqa: F401
 from ._capi import NoDeviceError, RmclHipError  # noqa: F401
 from .micp import MICPLocalization, MICPSensor  # noqa: F401
 from . import pf  # noqa: F401
-from .pf import (AdaptiveResamplerHip, GladiatorResamplerHip, PCDSensorUpdaterHip, ResidualResamplerHip, ShardedParticleFilterHip,  # noqa: F401
+from .pf import (AdaptiveResamplerHip, GladiatorResamplerHip, PCDSensorUpdaterHip, PoseEstimatorHip, ResidualResamplerHip, ShardedParticleFilterHip,  # noqa: F401
                  TFMotionUpdaterHip, beams_from_points, chol6, combined_forget_rate, constrain_to_surface, init_particles_pose,
                  init_particles_uniform, kld_bound, kld_params, pack_visualization, sample_beams)
 from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, HipMap, MapMap, RCCHipO1Dn,  # noqa: F401

@@ -105,6 +105,12 @@ class PoseEstimate(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class PoseHypothesis(C.Structure):
+    """rmclhip_pose_hypothesis: one cluster of the cloud's occupied bins"""
+    _fields_ = [("estimate", PoseEstimate), ("key_min", C.c_uint64), ("weight", C.c_uint64), ("weight_share", C.c_double),
+                ("n_bins", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MapInfo(C.Structure):
     _fields_ = [("n_faces", C.c_uint32), ("n_vertices", C.c_uint32), ("n_nodes", C.c_uint32),
                 ("n_tri_records", C.c_uint32), ("max_depth", C.c_uint32), ("stack_need", C.c_uint32),
@@ -279,6 +285,9 @@ SIGNATURES = {
                                              C.c_uint64, _u32]),
     "rmclhip_resampler_adaptive": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, C.POINTER(KldParams), C.POINTER(GladiatorConfig),
                                            C.c_uint64, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "rmclhip_particles_pose_estimate": (_i32, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PoseEstimate)]),
+    "rmclhip_particles_pose_hypotheses": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(KldParams), _u32, C.POINTER(PoseHypothesis), C.POINTER(_u32),
+                                                  C.POINTER(_u32), _vp]),
     "rmclhip_chol6_host": (_i32, [_vp, _vp, C.POINTER(_dbl)]),
     "rmclhip_particles_init_uniform": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32]),
     "rmclhip_particles_init_pose": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32, C.POINTER(_dbl)]),
@@ -317,6 +326,7 @@ SIGNATURES = {
     "rmclhip_pf_sharded_get_weights": (_i32, [_vp, _u32, _vp]),
     "rmclhip_pf_allreduce_stats": (_i32, [_vp, C.POINTER(LikelihoodStats)]),
     "rmclhip_pf_allreduce_pose_estimate": (_i32, [_vp, _u32, C.POINTER(PoseEstimate)]),
+    "rmclhip_pf_sharded_pose_hypotheses": (_i32, [_vp, C.POINTER(KldParams), _u32, C.POINTER(PoseHypothesis), C.POINTER(_u32), C.POINTER(_u32)]),
     "rmclhip_pf_sharded_resample": (_i32, [_vp, C.POINTER(GladiatorConfig), C.c_uint64, _u32]),
     "rmclhip_pf_sharded_resample_residual": (_i32, [_vp, C.POINTER(GladiatorConfig), C.c_uint64, _u32]),
     "rmclhip_malloc": (_i32, [_vp, _sz, _pp]),

@@ -15,43 +15,17 @@
 //                      search).  The first slot of a run of equal sources is a copy, every further one is perturbed as the gladiator
 //                      perturbs a winning enemy.
 #include "kernels.h"
+#include "kld_bins.hip.h"
 #include "pf_random.hip.h"
 
 namespace rmclhip {
 namespace {
 
 constexpr uint32_t kBlock = 256;
-constexpr unsigned long long kEmptySlot = ~0ull;   // a key has bit 63 clear
-
-struct pattr36 { float mean, sigma; uint32_t n_meas; float state_sigma[6]; };
-static_assert(sizeof(pattr36) == 36, "ParticleAttributes must be 36 B");
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }   // false for NaN and +-inf
 
 // ---------------------------------------------------------------------------------------------
-// occupied bins
+// occupied bins (the key rule and the table's hash: kld_bins.hip.h, shared with hypotheses.hip)
 // ---------------------------------------------------------------------------------------------
-struct KldBins { float bin_xyz[3], bin_rpy[3]; float floor_l; };
-
-__device__ __forceinline__ unsigned long long bin_lin(float t, float width) {
-  if (width == 0.0f) return 8192ull;                                   // dimension ignored: index 0
-  const float f = fminf(fmaxf(floorf(t / width), -8192.0f), 8191.0f);   // (t finite, width > 0: never NaN)
-  return static_cast<unsigned long long>(static_cast<int32_t>(f) + 8192);
-}
-__device__ __forceinline__ unsigned long long bin_ang(float a, float width) {
-  if (width == 0.0f) return 0ull;
-  const float f = fminf(fmaxf(floorf((a + 3.14159265358979323846f) / width), 0.0f), 126.0f);
-  return static_cast<unsigned long long>(static_cast<int32_t>(f));
-}
-
-// splitmix64's finaliser: neighbouring bins differ in a few low bits of one field
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 // counts[0] = distinct keys, counts[1] = counted particles.  table: mask + 1 words (a power of two >= 2 n), all kEmptySlot on entry.
 // No lane leaves before the ballots: every wave of the launch reaches them whole.
 __global__ void __launch_bounds__(kBlock) k_kld_count_bins(const xform* __restrict__ poses, const pattr36* __restrict__ attrs, uint32_t n,
@@ -62,13 +36,9 @@ __global__ void __launch_bounds__(kBlock) k_kld_count_bins(const xform* __restri
   if (i < n) {
     const xform T = poses[i];
     const float L = attrs[i].mean;
-    counted = finite_f(T.R.x) && finite_f(T.R.y) && finite_f(T.R.z) && finite_f(T.R.w) && finite_f(T.t.x) && finite_f(T.t.y) &&
-              finite_f(T.t.z) && finite_f(L) && L > 0.0f && L >= b.floor_l;
+    unsigned long long key = 0ull;
+    counted = kld_particle_key(T, L, b, key);   // kld_bins.hip.h
     if (counted) {
-      float roll, pitch, yaw;
-      quat_to_euler(T.R, roll, pitch, yaw);
-      const unsigned long long key = bin_lin(T.t.x, b.bin_xyz[0]) | (bin_lin(T.t.y, b.bin_xyz[1]) << 14) | (bin_lin(T.t.z, b.bin_xyz[2]) << 28) |
-                                     (bin_ang(roll, b.bin_rpy[0]) << 42) | (bin_ang(pitch, b.bin_rpy[1]) << 49) | (bin_ang(yaw, b.bin_rpy[2]) << 56);
       // at most n keys are ever stored and the table has >= 2 n words: a probe sequence meets its key or an empty word before it
       // has gone round, whatever the other lanes do -- the loop ends by construction
       // A word changes once, from empty to its key: a load that finds a key has found the final one and needs no atomic (a converged
@@ -96,11 +66,6 @@ __global__ void __launch_bounds__(kBlock) k_kld_count_bins(const xform* __restri
 // ---------------------------------------------------------------------------------------------
 // systematic resampling
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long sys_weight(float L, double max_l) {
-  if (!finite_f(L) || !(L > 0.0f)) return 0ull;
-  return static_cast<unsigned long long>(rint((static_cast<double>(L) / max_l) * 16777216.0));
-}
-
 // inclusive scan over the 256 threads of a block (the residual resampler's block_scan_256)
 __device__ __forceinline__ unsigned long long sys_block_scan(unsigned long long v, unsigned long long* s_wave, unsigned long long& total) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;

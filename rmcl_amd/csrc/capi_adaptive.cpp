@@ -32,7 +32,7 @@ rmclhip_status rmclhip_kld_bound_host(uint32_t k, double epsilon, double z, uint
   return RMCLHIP_OK;
 }
 
-static rmclhip_status kld_bins_check(const char* who_, const rmclhip_kld_params* p) {
+rmclhip_status kld_bins_check(const char* who_, const rmclhip_kld_params* p) {
   const std::string who(who_);
   if (!p) return fail(RMCLHIP_ERR_INVALID, who + ": null KLD parameters");
   for (int d = 0; d < 3; ++d) {
@@ -45,7 +45,7 @@ static rmclhip_status kld_bins_check(const char* who_, const rmclhip_kld_params*
 }
 
 // {sum, max} of the likelihoods on the resampler's stream, landed on the host
-static rmclhip_status resampler_stats(rmclhip_resampler* r, const rmclhip_particle_attributes* attrs_dev, uint32_t n, float* max_out) {
+rmclhip_status resampler_stats(rmclhip_resampler* r, const rmclhip_particle_attributes* attrs_dev, uint32_t n, float* max_out) {
   HIPCHK(launch_likelihood_stats(attrs_dev, n, r->d_psum.p, r->d_pmax.p, r->d_out.p, r->stream));
   HIPCHK(hipMemcpyAsync(r->h_out, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -54,10 +54,9 @@ static rmclhip_status resampler_stats(rmclhip_resampler* r, const rmclhip_partic
 }
 
 // the arguments are checked; max_l: the statistics' maximum
-static rmclhip_status count_bins_run(rmclhip_resampler* r, const rmclhip_transform* poses_dev, const rmclhip_particle_attributes* attrs_dev,
+rmclhip_status count_bins_run(rmclhip_resampler* r, const rmclhip_transform* poses_dev, const rmclhip_particle_attributes* attrs_dev,
                                      uint32_t n, const rmclhip_kld_params* p, float max_l, uint32_t* k_out, uint32_t* n_counted_out) {
-  uint64_t words = 64;
-  while (words < 2ull * n) words <<= 1;
+  const uint64_t words = kld_table_words(n);
   HIPCHK(r->d_kld_table.reserve(words));
   HIPCHK(r->d_kld_cnt.reserve(2));
   HIPCHK(hipMemsetAsync(r->d_kld_table.p, 0xFF, words * sizeof(unsigned long long), r->stream));

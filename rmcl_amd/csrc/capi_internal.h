@@ -7,6 +7,7 @@
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
+//   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
 // entry point fails with RMCLHIP_ERR_NO_DEVICE.
@@ -455,6 +456,12 @@ struct rmclhip_resampler {
   // in h_res[5]); the systematic resampler's prefix sums and block totals
   DevBuf<unsigned long long> d_kld_table, d_sys_incl, d_sys_btot;
   DevBuf<uint32_t> d_kld_cnt;
+  // pose hypotheses (capi_hypotheses.cpp), grow-only as the bin table: four 32-bit words per table word {parent, rank, bins, particles},
+  // one 64-bit word per table word (weight) followed by the counters, the particles' labels, the cluster records (4 words per occupied
+  // bin) followed by the kMaxHypotheses winners; the moment passes' partials (256 * 32) + result (32), also rmclhip_particles_pose_estimate's
+  DevBuf<uint32_t> d_hyp_u32, d_hyp_labels;
+  DevBuf<unsigned long long> d_hyp_u64, d_hyp_rec;
+  DevBuf<double> d_hyp_mom;
 };
 
 
@@ -526,4 +533,19 @@ RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void
                                                uint32_t max_n_meas, bool collision);
 RMCL_INTERNAL rmclhip_status pf_surface_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const rmclhip_surface_params& sp, uint32_t max_n_meas);
 RMCL_INTERNAL void pf_surface_release(rmclhip_pf* f);
+// capi_adaptive.cpp: the checks and launches the pose hypotheses share with the adaptive count.  kld_table_words: the size of the bin
+// table count_bins_run fills for n particles; resampler_stats: the likelihoods' maximum, landed on the host
+inline uint64_t kld_table_words(uint32_t n) { uint64_t words = 64; while (words < 2ull * n) words <<= 1; return words; }
+RMCL_INTERNAL rmclhip_status kld_bins_check(const char* who, const rmclhip_kld_params* p);
+RMCL_INTERNAL rmclhip_status resampler_stats(rmclhip_resampler* r, const rmclhip_particle_attributes* attrs_dev, uint32_t n, float* max_out);
+RMCL_INTERNAL rmclhip_status count_bins_run(rmclhip_resampler* r, const rmclhip_transform* poses_dev, const rmclhip_particle_attributes* attrs_dev,
+                                            uint32_t n, const rmclhip_kld_params* p, float max_l, uint32_t* k_out, uint32_t* n_counted_out);
+// capi_hypotheses.cpp: the argument check and the single-device path of the pose hypotheses (the sharded filter runs it on rank 0's
+// gathered cloud); labels_dev: nullable
+RMCL_INTERNAL rmclhip_status pose_hypotheses_check(const char* who, rmclhip_resampler* r, const rmclhip_kld_params* bins, uint32_t max_hypotheses,
+                                                   rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out);
+RMCL_INTERNAL rmclhip_status pose_hypotheses_run(const char* who, rmclhip_resampler* r, const rmclhip_transform* poses_dev,
+                                                 const rmclhip_particle_attributes* attrs_dev, uint32_t n, const rmclhip_kld_params* bins,
+                                                 uint32_t max_hypotheses, rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out,
+                                                 uint32_t* labels_dev);
 //@@DECLS@@

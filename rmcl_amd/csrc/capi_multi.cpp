@@ -1,5 +1,6 @@
 // capi_multi.cpp -- see capi_internal.h
 #include "capi_internal.h"
+#include "pose_estimate_host.h"
 
 // ---- pose batches sharded over devices (north_star: pose-corrections/s at 1/2/4/8 GPUs; SURVEY 8(e): "MICP pose batches: shard
 // poses, no exchange at all").  One process, one operator replica per device over ONE host BVH build (as rmclhip_pf_sharded_create
@@ -850,68 +851,14 @@ rmclhip_status rmclhip_pf_allreduce_stats(rmclhip_pf_sharded* h, rmclhip_likelih
   return RMCLHIP_OK;
 }
 
-// largest eigenvector of a symmetric 4x4 matrix (cyclic Jacobi, double)
-static void sym4_largest_eigenvector(const double* M10, double* q) {
-  double A[4][4], V[4][4];
-  int k = 0;
-  for (int a = 0; a < 4; ++a) for (int b = a; b < 4; ++b) { A[a][b] = A[b][a] = M10[k++]; }
-  for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) V[a][b] = (a == b) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    double off = 0.0;
-    for (int a = 0; a < 4; ++a) for (int b = a + 1; b < 4; ++b) off += A[a][b] * A[a][b];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 3; ++p)
-      for (int qq = p + 1; qq < 4; ++qq) {
-        if (A[p][qq] == 0.0) continue;
-        const double theta = (A[qq][qq] - A[p][p]) / (2.0 * A[p][qq]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-        for (int i = 0; i < 4; ++i) { const double ip = A[i][p], iq = A[i][qq]; A[i][p] = c * ip - sn * iq; A[i][qq] = sn * ip + c * iq; }
-        for (int i = 0; i < 4; ++i) { const double pi_ = A[p][i], qi = A[qq][i]; A[p][i] = c * pi_ - sn * qi; A[qq][i] = sn * pi_ + c * qi; }
-        for (int i = 0; i < 4; ++i) { const double ip = V[i][p], iq = V[i][qq]; V[i][p] = c * ip - sn * iq; V[i][qq] = sn * ip + c * iq; }
-      }
-  }
-  int best = 0;
-  for (int a = 1; a < 4; ++a) if (A[a][a] > A[best][best]) best = a;
-  double n = 0.0;
-  for (int a = 0; a < 4; ++a) n += V[a][best] * V[a][best];
-  n = std::sqrt(n);
-  const double sgn = (V[3][best] < 0.0) ? -1.0 : 1.0;   // canonical sign: w >= 0
-  for (int a = 0; a < 4; ++a) q[a] = sgn * V[a][best] / n;
-}
-
-// RmclNode::estimateStats (rmcl_localization.cpp:642-731) over the first n_induction particles of the sharded cloud
+// RmclNode::estimateStats (rmcl_localization.cpp:642-731) over the first n_induction particles of the sharded cloud (the passes'
+// host side: pose_estimate_host.h)
 rmclhip_status rmclhip_pf_allreduce_pose_estimate(rmclhip_pf_sharded* h, uint32_t n_induction, rmclhip_pose_estimate* out) {
   ApiGuard guard_("rmclhip_pf_allreduce_pose_estimate");
   if (!h || !out) return fail(RMCLHIP_ERR_INVALID, "pf_allreduce_pose_estimate: null");
-  std::memset(out, 0, sizeof(*out));
   const uint32_t n_use = std::min(n_induction, h->n_total);
-  if (n_use == 0) return fail(RMCLHIP_ERR_INVALID, "pf_allreduce_pose_estimate: no particles");
-  double m[32];
-  if (rmclhip_status st = sharded_moments(h, n_use, 0, 1.0, xidentity(), m)) return st;
-  const double L_sum = m[0], L_n = m[2];
-  // every particle killed by the collision test: w = L / 0, a NaN matrix into the Jacobi sweeps, a NaN pose out
-  if (!(L_sum > 0.0)) return fail(RMCLHIP_ERR_INVALID, "pf_allreduce_pose_estimate: the likelihoods sum to zero (or NaN): no weighted mean");
-  const double L_mean = L_sum / L_n;
-  out->n_particles = n_use;
-  out->likelihood_mean = L_mean;
-  out->likelihood_sigma = std::sqrt(std::max(m[1] / L_n - L_mean * L_mean, 0.0));
-  out->likelihood_max = std::max(m[24], 0.0);   // L_max starts at 0.0 in the reference (:665)
-  out->likelihood_min = -m[25];
-  for (int k = 0; k < 3; ++k) { out->trans_bb_max[k] = static_cast<float>(m[26 + k]); out->trans_bb_min[k] = static_cast<float>(-m[29 + k]); }
-  // first pass: mean (rm::markley_mean with weights L_i / L_sum)
-  if (rmclhip_status st = sharded_moments(h, n_use, 1, L_sum, xidentity(), m)) return st;
-  double q[4];
-  sym4_largest_eigenvector(m, q);
-  xform Tbm = xidentity();
-  Tbm.R.x = static_cast<float>(q[0]); Tbm.R.y = static_cast<float>(q[1]); Tbm.R.z = static_cast<float>(q[2]); Tbm.R.w = static_cast<float>(q[3]);
-  Tbm.t = mk3(static_cast<float>(m[10]), static_cast<float>(m[11]), static_cast<float>(m[12]));
-  from_x(Tbm, &out->pose);
-  // second pass: covariance around the mean
-  if (rmclhip_status st = sharded_moments(h, n_use, 2, L_sum, Tbm, m)) return st;
-  int k = 0;
-  for (int a = 0; a < 6; ++a) for (int b = a; b < 6; ++b) { out->covariance[6 * a + b] = out->covariance[6 * b + a] = m[k++]; }
-  return RMCLHIP_OK;
+  return pose_estimate_passes("pf_allreduce_pose_estimate", n_use,
+                              [&](int pass, double L_sum, const xform& Tbm, double* m) { return sharded_moments(h, n_use, pass, L_sum, Tbm, m); }, out);
 }
 
 // distributed gladiator tournament: the enemy of a champion may live on any rank, so the cloud (68 B per
@@ -928,16 +875,9 @@ rmclhip_status rmclhip_pf_sharded_resample_residual(rmclhip_pf_sharded* h, const
   return pf_sharded_resample_impl(h, cfg, seed, step, true);
 }
 
-static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmclhip_gladiator_config* cfg, uint64_t seed, uint32_t step,
-                                              bool residual) {
-  if (!h || !cfg) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_resample: null");
-  {   // before the all-gather: a refused call leaves the cloud, and the gathered copies, alone
-    rmclhip_gladiator_config c = *cfg;
-    if (residual) c.trans_dist_metric = 0u;   // ignored by the residual resampler
-    if (rmclhip_status cs = resampler_config_check(residual ? "pf_sharded_resample_residual" : "pf_sharded_resample", &c)) return cs;
-  }
-  if (h->n_total == 0) return RMCLHIP_OK;
-  h->weights_fresh = false;   // the cloud is about to be replaced
+// all-gather of the particle records (68 B per particle) on every rank's collective stream: afterwards -- in stream order, nothing
+// here waits -- every rank's d_poses_all / d_attrs_all hold the dense cloud.  The shards are not touched.
+static rmclhip_status pf_sharded_gather_records(rmclhip_pf_sharded* h, const char* who, const char* mark) {
   const uint32_t world = static_cast<uint32_t>(h->ranks.size()), cap = (h->n_total + world - 1u) / world;
   // a ragged partition (n_total not a multiple of the number of devices): the all-gather needs equal counts, so the padded shards
   // land in a second buffer and one kernel per record type squeezes the padding out (68 B x N read + written once more per rank)
@@ -954,7 +894,7 @@ static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmcl
       if (ae == hipSuccess) ae = hipMalloc(&R.d_attrs_pad, c * 36);
       if (ae != hipSuccess) {
         if (R.d_poses_pad) { (void)hipFree(R.d_poses_pad); R.d_poses_pad = nullptr; }
-        return fail(ae == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string("pf_sharded_resample: ") + hipGetErrorString(ae));
+        return fail(ae == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(ae));
       }
       R.pad_cap = std::max(cap, h->cap);
     }
@@ -965,7 +905,7 @@ static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmcl
   // whole cloud instead of an indexed exchange of the winners costs 68 B x N x (world - 1) / world per rank: C5 = 59.5 MB per rank,
   // ~0.2 ms at the ~300 GB/s an 8-GPU RCCL all-gather reaches over xGMI (an estimate: no node to measure on) against a 2.9 ms
   // sensor update per resampling step -- accepted, stated, and the first thing to replace if a profile says otherwise.
-  trace_mark("resample:");
+  trace_mark(mark);
   std::vector<const void*> sp(world), sa(world);
   std::vector<void*> rp(world), ra_(world);
   for (uint32_t r = 0; r < world; ++r) {
@@ -983,6 +923,21 @@ static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmcl
       HIPCHK(launch_compact_records(R.d_attrs_pad, R.d_attrs_all, h->n_total, world, cap, 36u, h->comm->streams[r]));
     }
   }
+  return RMCLHIP_OK;
+}
+
+static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmclhip_gladiator_config* cfg, uint64_t seed, uint32_t step,
+                                              bool residual) {
+  if (!h || !cfg) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_resample: null");
+  {   // before the all-gather: a refused call leaves the cloud, and the gathered copies, alone
+    rmclhip_gladiator_config c = *cfg;
+    if (residual) c.trans_dist_metric = 0u;   // ignored by the residual resampler
+    if (rmclhip_status cs = resampler_config_check(residual ? "pf_sharded_resample_residual" : "pf_sharded_resample", &c)) return cs;
+  }
+  if (h->n_total == 0) return RMCLHIP_OK;
+  h->weights_fresh = false;   // the cloud is about to be replaced
+  const uint32_t world = static_cast<uint32_t>(h->ranks.size());
+  if (rmclhip_status st = pf_sharded_gather_records(h, "pf_sharded_resample", "resample:")) return st;
   if (!residual) {
     for (uint32_t r = 0; r < world; ++r) {
       PfRank& R = h->ranks[r];
@@ -1034,3 +989,21 @@ static rmclhip_status pf_sharded_resample_impl(rmclhip_pf_sharded* h, const rmcl
   return RMCLHIP_OK;
 }
 
+
+// pose hypotheses of the sharded cloud: the records are gathered as the resamplers gather them, then rank 0 runs the single-device
+// path (capi_hypotheses.cpp) on its gathered copy with its own resampler handle -- the single-device bytes.  The shards stay as they are.
+rmclhip_status rmclhip_pf_sharded_pose_hypotheses(rmclhip_pf_sharded* h, const rmclhip_kld_params* bins, uint32_t max_hypotheses,
+                                                  rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out) {
+  ApiGuard guard_("rmclhip_pf_sharded_pose_hypotheses");
+  if (n_out) *n_out = 0;
+  if (n_clusters_out) *n_clusters_out = 0;
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_pose_hypotheses: null");
+  if (rmclhip_status st = pose_hypotheses_check("pf_sharded_pose_hypotheses", h->ranks[0].rs, bins, max_hypotheses, out, n_out, n_clusters_out)) return st;
+  if (h->n_total == 0) return RMCLHIP_OK;
+  if (rmclhip_status st = pf_sharded_gather_records(h, "pf_sharded_pose_hypotheses", "hypotheses:")) return st;
+  if (rmclhip_status st = comm_wait_all(h->comm)) return st;
+  PfRank& R0 = h->ranks[0];
+  return pose_hypotheses_run("pf_sharded_pose_hypotheses", R0.rs, reinterpret_cast<const rmclhip_transform*>(R0.d_poses_all),
+                             static_cast<const rmclhip_particle_attributes*>(R0.d_attrs_all), h->n_total, bins, max_hypotheses, out, n_out,
+                             n_clusters_out, nullptr);
+}

@@ -412,6 +412,7 @@ void rmclhip_resampler_destroy(rmclhip_resampler* r) {
   r->d_out.release();
   r->d_res_stats.release(); r->d_res_incl.release(); r->d_res_btot.release(); r->d_res_idx.release(); r->d_res_cnt.release();
   r->d_kld_table.release(); r->d_sys_incl.release(); r->d_sys_btot.release(); r->d_kld_cnt.release();
+  r->d_hyp_u32.release(); r->d_hyp_u64.release(); r->d_hyp_labels.release(); r->d_hyp_rec.release(); r->d_hyp_mom.release();
   if (r->h_out) (void)hipHostFree(r->h_out);
   if (r->h_res) (void)hipHostFree(r->h_res);
   r->tag.destroy();

@@ -407,9 +407,10 @@ hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* 
 hipError_t launch_surface_constrain(const uint32_t* qnodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
                                     const SurfaceKernelParams& sp, uint32_t max_n_meas, uint32_t* stats, uint32_t* faces, hipStream_t s);
 
-// pose-estimate moments (RmclNode::estimateStats): partials = 256 * 32 doubles of scratch, out32 = 24 sums + 8 maxima (device)
+// pose-estimate moments (RmclNode::estimateStats): partials = 256 * 32 doubles of scratch, out32 = 24 sums + 8 maxima (device).
+// labels (nullable, n words): only the particles with labels[i] == want take part -- the moments of one pose hypothesis
 hipError_t launch_pose_moments(const xform* poses, const void* attrs, uint32_t n, int pass, double L_sum, xform Tbm,
-                               double* partials, double* out32, hipStream_t s);
+                               double* partials, double* out32, hipStream_t s, const uint32_t* labels = nullptr, uint32_t want = 0u);
 hipError_t launch_loopback_allreduce(const double* const* send, uint32_t world, double* recv, uint32_t count, bool is_max, hipStream_t s);
 hipError_t launch_compact_shards(const float* padded, float* dense, uint32_t n_total, uint32_t world, uint32_t cap, hipStream_t s);
 // the same for records of record_bytes (a multiple of 4): the padded all-gather layout of a ragged partition -> the dense cloud
@@ -436,5 +437,20 @@ hipError_t launch_sys_scan(const void* attrs, uint32_t n, double max_l, unsigned
 hipError_t launch_sys_fill(const xform* poses, const void* attrs, const unsigned long long* incl, uint32_t n, xform* poses_new, void* attrs_new,
                            uint32_t n_new, uint32_t first, uint32_t count, const float* cfg8, uint32_t trans_dist_metric, uint64_t seed,
                            uint32_t step, hipStream_t s);
+
+// hypotheses.hip: pose hypotheses = connected components of the occupied bins (include/rmclhip.h, POSE HYPOTHESES).  `table` is what
+// launch_kld_count_bins left (table_words words, k of them occupied).  Scratch, all the caller's: parent / rank / n_bins / n_part:
+// table_words words of 32 bits each, weight: table_words words of 64 bits, labels: n words, records: 4 * k words of 64 bits,
+// counters: kHypCounters words of 64 bits, hyps: kMaxHypotheses records.  Everything is enqueued on s; nothing waits.
+constexpr uint32_t kMaxHypotheses = 64u;
+constexpr uint32_t kHypCounters = 4u;     // {clusters, total weight, records written, unused}
+struct HypRecord { unsigned long long key_min, weight; uint32_t n_bins, n_particles, root, pad; };   // 32 B
+struct HypScratch {
+  uint32_t* parent; uint32_t* rank; uint32_t* n_bins; uint32_t* n_part; unsigned long long* weight;
+  unsigned long long* records; unsigned long long* counters; HypRecord* hyps;
+};
+hipError_t launch_hypotheses(const xform* poses, const void* attrs, uint32_t n, const float* bin_xyz, const float* bin_rpy, float floor_l,
+                             double max_l, const unsigned long long* table, uint64_t table_words, uint32_t k_bins, uint32_t max_hypotheses,
+                             const HypScratch& sc, uint32_t* labels, hipStream_t s);
 
 }  // namespace rmclhip

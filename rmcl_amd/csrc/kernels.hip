@@ -2030,8 +2030,11 @@ __global__ void __launch_bounds__(64) k_likelihood_stats_final(const double* __r
 // ---------------------------------------------------------------------------------------------
 constexpr int kMomSums = 24, kMomMax = 8;
 
+// labels (nullable): only the particles with labels[i] == want take part (the moments of one pose hypothesis, hypotheses.hip); the
+// arithmetic of a particle that takes part, and the order of the sums, do not depend on it.
 __global__ void __launch_bounds__(256) k_pose_moments(const xform* __restrict__ poses, const pattrs* __restrict__ attrs, uint32_t n,
-                                                      int pass, double L_sum, xform Tbm, double* __restrict__ partials) {
+                                                      int pass, double L_sum, xform Tbm, double* __restrict__ partials,
+                                                      const uint32_t* __restrict__ labels, uint32_t want) {
   __shared__ double red[4][kMomSums + kMomMax];
   double acc[kMomSums];
   float mx[kMomMax];
@@ -2041,6 +2044,7 @@ __global__ void __launch_bounds__(256) k_pose_moments(const xform* __restrict__ 
   for (int k = 0; k < kMomMax; ++k) mx[k] = -3.402823466e38f;
   const xform Tmb = xinv(Tbm);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (labels != nullptr && labels[i] != want) continue;
     const xform T = poses[i];
     const float Lf = attrs[i].likelihood.mean;
     const double L = static_cast<double>(Lf);
@@ -2988,12 +2992,12 @@ hipError_t launch_pointcloud2_unpack(const uint8_t* data, uint32_t point_step, u
 }
 
 hipError_t launch_pose_moments(const xform* poses, const void* attrs, uint32_t n, int pass, double L_sum, xform Tbm,
-                               double* partials, double* out32, hipStream_t s) {
+                               double* partials, double* out32, hipStream_t s, const uint32_t* labels, uint32_t want) {
   uint32_t nblocks = (n + 1023u) / 1024u;
   if (nblocks < 1u) nblocks = 1u;
   if (nblocks > 256u) nblocks = 256u;
   hipLaunchKernelGGL(k_pose_moments, dim3(nblocks), dim3(256), 0, s, poses, reinterpret_cast<const pattrs*>(attrs), n, pass, L_sum, Tbm,
-                     partials);
+                     partials, labels, want);
   hipLaunchKernelGGL(k_pose_moments_final, dim3(1), dim3(256), 0, s, partials, nblocks, out32);
   return hipGetLastError();
 }

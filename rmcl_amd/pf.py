@@ -439,6 +439,70 @@ class AdaptiveResamplerHip(GladiatorResamplerHip):
         return {"n_particles": int(n_new.value), "bins": int(k.value)}
 
 
+def _estimate_dict(e):
+    """rmclhip_pose_estimate -> the dict RmclNode::estimateStats' message maps to"""
+    pose = np.frombuffer(bytes(bytearray(memoryview(e.pose))), dtype=TRANSFORM)[0].copy()
+    return {"pose": pose, "covariance": np.array(e.covariance, dtype=np.float64).reshape(6, 6),
+            "likelihood": {"mean": e.likelihood_mean, "sigma": e.likelihood_sigma, "min": e.likelihood_min, "max": e.likelihood_max},
+            "trans_bb_min": np.array(e.trans_bb_min), "trans_bb_max": np.array(e.trans_bb_max), "nparticles": e.n_particles}
+
+
+def _hypotheses_dict(out, n_out, n_clusters):
+    hyps = []
+    for k in range(int(n_out)):
+        d = _estimate_dict(out[k].estimate)
+        d.update(key_min=int(out[k].key_min), weight=int(out[k].weight), weight_share=float(out[k].weight_share), n_bins=int(out[k].n_bins))
+        hyps.append(d)
+    return {"n_clusters": int(n_clusters), "hypotheses": hyps}
+
+
+class PoseEstimatorHip:
+    """RmclNode::estimateStats for a cloud on one device, and the answer to a posterior with several modes: pose hypotheses -- the
+    connected components of the cloud's occupied bins (the bins of AdaptiveResamplerHip.count_bins), weighed, ranked, each with a mean
+    and covariance of its own.  Owns a rmclhip_resampler (stream + scratch); `kld`: types.kld_params(), of which bin_xyz, bin_rpy and
+    min_likelihood_rel are read."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.kld = kld_params()
+        self._h = C.c_void_p()
+
+    def init(self):
+        if not self._h:
+            _capi.check(_capi.lib().rmclhip_resampler_create(self.ctx.handle, C.byref(self._h)))
+
+    def estimate(self, particle_poses, particle_attrs, n_particles, max_induction_particles=0xFFFFFFFF):
+        """the one mean and covariance over the first min(n_particles, max_induction_particles) particles
+        (rmclhip_particles_pose_estimate): ShardedParticleFilterHip.pose_estimate on one rank, bit for bit"""
+        self.init()
+        e = _capi.PoseEstimate()
+        _capi.check(_capi.lib().rmclhip_particles_pose_estimate(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs), int(n_particles),
+                                                                int(min(max_induction_particles, 0xFFFFFFFF)), C.byref(e)))
+        return _estimate_dict(e)
+
+    def hypotheses(self, particle_poses, particle_attrs, n_particles, max_hypotheses=8, labels=None):
+        """{"n_clusters", "hypotheses": [estimate dict + key_min, weight, weight_share, n_bins, ...]}, heaviest first
+        (rmclhip_particles_pose_hypotheses); labels: optional device uint32[n_particles], the rank of every particle's cluster"""
+        self.init()
+        out = (_capi.PoseHypothesis * max(1, min(int(max_hypotheses), 64)))()
+        n_out, n_clusters = C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_particles_pose_hypotheses(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs), int(n_particles),
+                                                                  C.byref(self.kld), int(max_hypotheses), out, C.byref(n_out),
+                                                                  C.byref(n_clusters), _as_ptr(labels)))
+        return _hypotheses_dict(out, n_out.value, n_clusters.value)
+
+    def close(self):
+        if self._h:
+            _capi.lib().rmclhip_resampler_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedParticleFilterHip:
     """A particle cloud block-partitioned over the devices of ONE process (rmclhip_comm / rmclhip_pf_sharded: RCCL
     ncclCommInitAll + all-gather / all-reduce over xGMI) -- the multi-GPU form of PCDSensorUpdater + GladiatorResampler +
@@ -566,10 +630,16 @@ class ShardedParticleFilterHip:
     def pose_estimate(self, max_induction_particles=0xFFFFFFFF):
         e = _capi.PoseEstimate()
         _capi.check(_capi.lib().rmclhip_pf_allreduce_pose_estimate(self._h, int(min(max_induction_particles, 0xFFFFFFFF)), C.byref(e)))
-        pose = np.frombuffer(bytes(bytearray(memoryview(e.pose))), dtype=TRANSFORM)[0].copy()
-        return {"pose": pose, "covariance": np.array(e.covariance, dtype=np.float64).reshape(6, 6),
-                "likelihood": {"mean": e.likelihood_mean, "sigma": e.likelihood_sigma, "min": e.likelihood_min, "max": e.likelihood_max},
-                "trans_bb_min": np.array(e.trans_bb_min), "trans_bb_max": np.array(e.trans_bb_max), "nparticles": e.n_particles}
+        return _estimate_dict(e)
+
+    def pose_hypotheses(self, kld, max_hypotheses=8):
+        """PoseEstimatorHip.hypotheses of the whole sharded cloud (rmclhip_pf_sharded_pose_hypotheses): the records are gathered, rank 0
+        runs the single-device path; the cloud is not changed.  kld: types.kld_params()"""
+        out = (_capi.PoseHypothesis * max(1, min(int(max_hypotheses), 64)))()
+        n_out, n_clusters = C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_pose_hypotheses(self._h, C.byref(kld), int(max_hypotheses), out, C.byref(n_out),
+                                                                   C.byref(n_clusters)))
+        return _hypotheses_dict(out, n_out.value, n_clusters.value)
 
     def resample(self, cfg=None, seed=42, step=0, residual=False):
         """all-gather the cloud, then every device resamples its shard: the gladiator tournament (default) or the residual resampler"""
