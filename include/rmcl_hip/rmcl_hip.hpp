@@ -17,6 +17,7 @@
 // (micp_localization.cpp:613, PCDSensorUpdaterOptix.cpp:179-192).
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -37,6 +38,10 @@ using Vector = rmclhip_vec3;
 using Quaternion = rmclhip_quat;
 using Transform = rmclhip_transform;
 using CrossStatistics = rmclhip_cross_statistics;
+// the point-to-plane information matrix of a correction's correspondences and what the host makes of it (rmclhip.h, POSE COVARIANCE)
+using PoseInformation = rmclhip_pose_information;
+using PoseCovariance = rmclhip_pose_covariance;
+using PoseCovarianceParams = rmclhip_pose_covariance_params;
 using ParticleAttributes = rmclhip_particle_attributes;
 using RangeMeasurement = rmclhip_range_measurement;
 
@@ -107,6 +112,12 @@ inline rmclhip_cross_statistics& operator+=(rmclhip_cross_statistics& a, const r
   a = r;
   return a;
 }
+// Transform * PoseInformation: the frame change, the way Transform * CrossStatistics reads
+inline rmclhip_pose_information operator*(const rmclhip_transform& T, const rmclhip_pose_information& s) {
+  rmclhip_pose_information r;
+  rmcl_hip::check(rmclhip_pose_information_transform(&T, &s, &r));
+  return r;
+}
 // rmagine::Vector arithmetic the callers of simulate() use on its results (scan_map_segmentation_embree.cpp:125-135)
 inline rmclhip_vec3 operator*(const rmclhip_vec3& a, float s) { return rmclhip_vec3{a.x * s, a.y * s, a.z * s}; }
 inline rmclhip_vec3 operator+(const rmclhip_vec3& a, const rmclhip_vec3& b) { return rmclhip_vec3{a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -123,6 +134,29 @@ inline Transform umeyama_transform(const CrossStatistics& s) {
   Transform r;
   check(rmclhip_umeyama_transform(&s, &r));
   return r;
+}
+
+// a += weight * b for A, g and rss; the counts add (merge_weight_multiplier, micp_localization.cpp:934-944)
+inline PoseInformation& merge(PoseInformation& a, const PoseInformation& b, double weight = 1.0) {
+  check(rmclhip_pose_information_merge(&a, &b, weight, &a));
+  return a;
+}
+inline PoseCovarianceParams poseCovarianceParams() {
+  PoseCovarianceParams p;
+  rmclhip_pose_covariance_params_default(&p);
+  return p;
+}
+// covariance (row-major 6 x 6, geometry_msgs' order) + degeneracy report of a pose information
+inline PoseCovariance poseCovariance(const PoseInformation& info, const PoseCovarianceParams& params = poseCovarianceParams()) {
+  PoseCovariance c;
+  check(rmclhip_pose_covariance_host(&info, &params, &c));
+  return c;
+}
+// the Gauss-Newton step xi = A^+ g = (dt, dtheta)
+inline std::array<double, 6> solve(const PoseInformation& info, double rcond = 1e-9) {
+  std::array<double, 6> xi;
+  check(rmclhip_pose_information_solve_host(&info, rcond, xi.data()));
+  return xi;
 }
 
 struct UmeyamaReductionConstraints { float max_dist = 1.0f; };
@@ -361,6 +395,22 @@ inline CrossStatistics statistics_p2l(const Transform& Tpre, const PointCloudVie
                                model.mask.size() ? model.mask.raw() : nullptr, static_cast<uint32_t>(n), params.max_dist, &out));
   return out;
 }
+// the point-to-plane information {A, g, rss, n_meas} over exactly the correspondences statistics_p2l keeps, on the same views
+inline PoseInformation pose_information_p2l(const Transform& Tpre, const PointCloudView_<VRAM_HIP>& dataset, const PointCloudView_<VRAM_HIP>& model,
+                                            const UmeyamaReductionConstraints& params) {
+  rmclhip_ctx* ctx = dataset.ctx ? dataset.ctx : model.ctx;
+  if (!ctx) throw std::runtime_error("pose_information_p2l: views without a context (use watch() / modelView())");
+  if (dataset.ctx && model.ctx && dataset.ctx != model.ctx) throw std::runtime_error("pose_information_p2l: dataset and model live on different contexts");
+  if (model.normals.size() < model.points.size()) throw std::runtime_error("pose_information_p2l: the model view needs normals");
+  if ((dataset.mask.size() && dataset.mask.size() < dataset.points.size()) || (model.mask.size() && model.mask.size() < model.points.size()))
+    throw std::runtime_error("pose_information_p2l: mask shorter than its points");
+  const size_t n = dataset.points.size() < model.points.size() ? dataset.points.size() : model.points.size();
+  PoseInformation out;
+  check(rmclhip_pose_information_p2l(ctx, &Tpre, reinterpret_cast<const float*>(dataset.points.raw()), dataset.mask.size() ? dataset.mask.raw() : nullptr,
+                                     reinterpret_cast<const float*>(model.points.raw()), reinterpret_cast<const float*>(model.normals.raw()),
+                                     model.mask.size() ? model.mask.raw() : nullptr, static_cast<uint32_t>(n), params.max_dist, &out));
+  return out;
+}
 
 // ---- rmagine::Bundle and its attributes (rmagine/simulation/SimulationResults.hpp as used by Correspondences.hpp:81-85,
 // scan_map_segmentation_embree.cpp:82-85, lidar_corrector_embree_benchmark.cpp:95-100) -------------------------------------------
@@ -442,6 +492,24 @@ class Correspondences_<VRAM_HIP> {
     check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
     CrossStatistics out;
     check(rmclhip_rcc_compute_cross_statistics(h_, &T_snew_sold, convergence_progress, &out));
+    return out;
+  }
+  // the point-to-plane information over the correspondences computeCrossStatistics(T_snew_sold, convergence_progress) keeps, sensor
+  // frame; reads the buffers of the last find and changes nothing
+  virtual PoseInformation computePoseInformation(const Transform& T_snew_sold, double convergence_progress = 0.0) const {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    PoseInformation out;
+    check(rmclhip_rcc_pose_information(h_, &T_snew_sold, convergence_progress, &out));
+    return out;
+  }
+  // one per pose of the last correctBatch (identity pre-transform)
+  std::vector<PoseInformation> computePoseInformationBatch(uint32_t nposes, double convergence_progress = 0.0) const {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    std::vector<PoseInformation> out(nposes);
+    PoseInformation none;
+    check(rmclhip_rcc_pose_information_batch(h_, nposes, convergence_progress, nposes ? out.data() : &none));
     return out;
   }
   // dataset {points, mask}: host or device source (the CUDA sensors upload once per scan,

@@ -1049,6 +1049,74 @@ rmclhip_status rmclhip_particles_pose_hypotheses(rmclhip_resampler* rs, const rm
 rmclhip_status rmclhip_pf_sharded_pose_hypotheses(rmclhip_pf_sharded* pf, const rmclhip_kld_params* bins, uint32_t max_hypotheses,
                                                   rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out);
 
+/* ---- POSE COVARIANCE: the point-to-plane information matrix of a correction's correspondences -----------------------------------
+ * MICPLocalizationNode::publishPose (micp_localization.cpp:1062-1076) fills the covariance of the PoseWithCovarianceStamped it
+ * publishes with (1 - convergence_progress) + pose_noise on the diagonal -- "just some bad guess of the covariance".  The quantity
+ * that tells a corridor from a room is the 6 x 6 normal matrix of the point-to-plane problem over the correspondences the
+ * correction used.  It is fourth order in the data: CrossStatistics and the published moments do not contain it.
+ *
+ * CORRESPONDENCES.  Exactly those of rmclhip_statistics_p2l: both masks non-zero (a NULL mask: all valid), Di = Tpre * dataset_points[i]
+ * and r_i = (Ii - Di) . Ni in f32 by the arithmetic of that reduction, kept iff |r_i| < max_dist (strict).  n_meas therefore EQUALS
+ * the n_meas of rmclhip_statistics_p2l on the same inputs, always.  A masked-out or rejected element does not touch the sums (a miss's
+ * NaN point and normal included).
+ * SUMS.  In double, from the f32 values Di, Ni, r_i: u_i = [ Ni ; Di x Ni ; r_i ] (7 values).  A small motion xi = (dt, dtheta) of the
+ * dataset points in their own frame, D' = D + dt + dtheta x D, changes the residual to r_i - J_i xi with J_i = u_i[0:6], so
+ *   A = sum J_i^T J_i   (6 x 6, symmetric, row-major; order x y z rot-x rot-y rot-z: geometry_msgs' covariance order to first order)
+ *   g = sum J_i^T r_i   (6)          rss = sum r_i^2          n_meas
+ * -- the 28 distinct entries of sum u_i u_i^T and the count.  trace(A[0:3, 0:3]) / n_meas = 1 (unit normals).  The Gauss-Newton step
+ * is A xi = g.  Summation order is fixed: the same inputs give the same bytes on every call. */
+typedef struct { double A[36]; double g[6]; double rss; uint32_t n_meas; uint32_t pad; } rmclhip_pose_information;
+/* the twin of rmclhip_statistics_p2l on caller-owned device views: same arguments, same stream and scratch owner (the context), synchronous,
+ * calls on one context serialise.  n == 0: all zeros. */
+rmclhip_status rmclhip_pose_information_p2l(rmclhip_ctx* ctx, const rmclhip_transform* Tpre, const float* dataset_points_xyz_dev,
+                                            const uint8_t* dataset_mask_dev, const float* model_points_xyz_dev,
+                                            const float* model_normals_xyz_dev, const uint8_t* model_mask_dev, uint32_t n, float max_dist,
+                                            rmclhip_pose_information* out);
+/* the twin of rmclhip_rcc_compute_cross_statistics after a find: the operator's dataset against its model buffers, sensor frame,
+ * max_dist' = max_dist (1 - convergence_progress) + adaptive_max_dist_min convergence_progress.  RMCLHIP_ERR_INVALID when no find has
+ * run, when the last find was a batch, or when rmclhip_rcc_set_outputs deselected hits, points or normals.  Only reads buffers: the
+ * published moment set, rmclhip_ccs_info and what rmclhip_rcc_compute_cross_statistics returns are untouched.  Synchronous. */
+rmclhip_status rmclhip_rcc_pose_information(rmclhip_rcc* rcc, const rmclhip_transform* T_snew_sold, double convergence_progress,
+                                            rmclhip_pose_information* out);
+/* after rmclhip_rcc_find_batch / rmclhip_rcc_correct_batch of nposes poses: out[nposes], pose p's model buffers against the shared
+ * dataset with the identity pre-transform.  RMCLHIP_ERR_INVALID when nposes is not what the last find held (and as above).  After a
+ * single find that is nposes == 1: the batch form then equals rmclhip_rcc_pose_information with the identity pre-transform. */
+rmclhip_status rmclhip_rcc_pose_information_batch(rmclhip_rcc* rcc, uint32_t nposes, double convergence_progress,
+                                                  rmclhip_pose_information* out);
+/* ---- host algebra on rmclhip_pose_information (double; out may alias an input) ----
+ * Frame change, the role rmclhip_cross_statistics_transform has: with T = (R, t), J' = [R n ; R (D x n) + t x R n], so with
+ * X = [[R, 0], [[t]x R, R]]: A' = X A X^T, g' = X g; rss and n_meas are unchanged.  R is the rotation of T's quaternion normalised in
+ * double (a float32 quaternion is a unit one to 1e-7 only); a zero or non-finite quaternion: RMCLHIP_ERR_INVALID. */
+rmclhip_status rmclhip_pose_information_transform(const rmclhip_transform* T, const rmclhip_pose_information* in,
+                                                  rmclhip_pose_information* out);
+/* out = a + weight_b * b for A, g and rss (micp_localization.cpp:936-944, merge_weight_multiplier); n_meas adds unscaled.
+ * weight_b must be finite and >= 0. */
+rmclhip_status rmclhip_pose_information_merge(const rmclhip_pose_information* a, const rmclhip_pose_information* b, double weight_b,
+                                              rmclhip_pose_information* out);
+/* xi = A^+ g, the Gauss-Newton step (a cross-check against rmclhip_umeyama_transform).  A^+: the pseudo-inverse from the symmetric
+ * eigen-decomposition (cyclic Jacobi), eigenvalues <= rcond * lambda_max dropped. */
+rmclhip_status rmclhip_pose_information_solve_host(const rmclhip_pose_information* in, double rcond, double xi_out[6]);
+typedef struct {
+  double sigma;                /* range noise (m); <= 0: estimated from the residuals, s2 = rss / (n_meas - 6), which needs n_meas > 6 */
+  double rcond;                /* an eigenvalue of A <= rcond * lambda_max is a direction the scan does not constrain */
+  double degenerate_variance;  /* the variance reported along such a direction */
+  double min_eig_trans, min_eig_rot;   /* thresholds of the degeneracy report (eigenvalues of the diagonal blocks of A / n_meas) */
+} rmclhip_pose_covariance_params;
+typedef struct {
+  double covariance[36];       /* V diag(c_k) V^T, (lambda_k, V) the eigenpairs of A, c_k = s2 / lambda_k where lambda_k > rcond * lambda_max,
+                                * else degenerate_variance; row-major, the order of A */
+  double eig_trans[3], eigvec_trans[9];   /* eigenpairs of A[0:3, 0:3] / n_meas, ascending; eigenvector k = eigvec_trans[3 k .. 3 k + 2] */
+  double eig_rot[3], eigvec_rot[9];       /* the same of A[3:6, 3:6] / n_meas (m^2: depends on where the frame's origin lies) */
+  uint32_t n_degenerate_trans, n_degenerate_rot;   /* block eigenvalues below min_eig_trans / min_eig_rot */
+  double s2;                   /* the residual variance used */
+} rmclhip_pose_covariance;
+/* sigma 0 (estimated), rcond 1e-9, degenerate_variance 1e6, min_eig_trans 1e-3, min_eig_rot 1e-3 */
+void rmclhip_pose_covariance_params_default(rmclhip_pose_covariance_params* out);
+/* RMCLHIP_ERR_INVALID: sigma <= 0 with n_meas <= 6, a negative or non-finite rcond / degenerate_variance, non-finite entries of A.
+ * n_meas == 0 with sigma > 0: every direction is degenerate. */
+rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
+                                            rmclhip_pose_covariance* out);
+
 /* ---- device memory helpers for hosts without their own allocator ---------------------- */
 rmclhip_status rmclhip_malloc(rmclhip_ctx* ctx, size_t bytes, void** out_dev);
 rmclhip_status rmclhip_free(rmclhip_ctx* ctx, void* ptr_dev);

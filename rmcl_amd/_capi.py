@@ -111,6 +111,12 @@ class PoseHypothesis(C.Structure):
                 ("n_bins", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PoseCovarianceParams(C.Structure):
+    """rmclhip_pose_covariance_params"""
+    _fields_ = [("sigma", C.c_double), ("rcond", C.c_double), ("degenerate_variance", C.c_double), ("min_eig_trans", C.c_double),
+                ("min_eig_rot", C.c_double)]
+
+
 class MapInfo(C.Structure):
     _fields_ = [("n_faces", C.c_uint32), ("n_vertices", C.c_uint32), ("n_nodes", C.c_uint32),
                 ("n_tri_records", C.c_uint32), ("max_depth", C.c_uint32), ("stack_need", C.c_uint32),
@@ -329,6 +335,14 @@ SIGNATURES = {
     "rmclhip_pf_sharded_pose_hypotheses": (_i32, [_vp, C.POINTER(KldParams), _u32, C.POINTER(PoseHypothesis), C.POINTER(_u32), C.POINTER(_u32)]),
     "rmclhip_pf_sharded_resample": (_i32, [_vp, C.POINTER(GladiatorConfig), C.c_uint64, _u32]),
     "rmclhip_pf_sharded_resample_residual": (_i32, [_vp, C.POINTER(GladiatorConfig), C.c_uint64, _u32]),
+    "rmclhip_pose_information_p2l": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp]),
+    "rmclhip_rcc_pose_information": (_i32, [_vp, _vp, _dbl, _vp]),
+    "rmclhip_rcc_pose_information_batch": (_i32, [_vp, _u32, _dbl, _vp]),
+    "rmclhip_pose_information_transform": (_i32, [_vp, _vp, _vp]),
+    "rmclhip_pose_information_merge": (_i32, [_vp, _vp, _dbl, _vp]),
+    "rmclhip_pose_information_solve_host": (_i32, [_vp, _dbl, _vp]),
+    "rmclhip_pose_covariance_params_default": (None, [C.POINTER(PoseCovarianceParams)]),
+    "rmclhip_pose_covariance_host": (_i32, [_vp, C.POINTER(PoseCovarianceParams), _vp]),
     "rmclhip_malloc": (_i32, [_vp, _sz, _pp]),
     "rmclhip_free": (_i32, [_vp, _vp]),
     "rmclhip_memcpy_h2d": (_i32, [_vp, _vp, _vp, _sz]),

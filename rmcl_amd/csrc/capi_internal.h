@@ -8,6 +8,7 @@
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
+//   capi_pose_information.cpp the point-to-plane information matrix of a find's correspondences and its host algebra: covariance, degeneracy (kernels: pose_information.hip)
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
 // entry point fails with RMCLHIP_ERR_NO_DEVICE.
@@ -157,6 +158,7 @@ struct rmclhip_ctx {
   unsigned long long* p2l_h_done = nullptr;
   unsigned long long* p2l_h_done_dev = nullptr;
   uint32_t p2l_seq = 0;
+  DevBuf<double> pinfo_partials, pinfo_rows;   // rmclhip_pose_information_p2l: its rows per workgroup and its result row, same stream and mutex
   // rmclhip_pointcloud2_to_scan (the free function): its own stream and scratch, created by the first call under its mutex
   std::mutex pc2_mtx;
   hipStream_t pc2_stream = nullptr;
@@ -244,6 +246,7 @@ struct rmclhip_rcc {
   uint32_t out_mask = RMCLHIP_OUT_ALL;   // rmclhip_rcc_set_outputs: which model buffers find / find_batch write
   // reduction
   DevBuf<double> d_partials;
+  DevBuf<double> d_pinfo_partials, d_pinfo_rows;   // rmclhip_rcc_pose_information[_batch] (capi_pose_information.cpp): rows per workgroup, result rows per pose
   cstats* h_stats = nullptr;       // pinned, host-mapped
   cstats* h_stats_dev = nullptr;   // device alias of h_stats
   MicpState* d_state = nullptr;
@@ -548,4 +551,7 @@ RMCL_INTERNAL rmclhip_status pose_hypotheses_run(const char* who, rmclhip_resamp
                                                  const rmclhip_particle_attributes* attrs_dev, uint32_t n, const rmclhip_kld_params* bins,
                                                  uint32_t max_hypotheses, rmclhip_pose_hypothesis* out, uint32_t* n_out, uint32_t* n_clusters_out,
                                                  uint32_t* labels_dev);
+// capi_rcc.cpp: the stream and host-mapped scratch of the free functions on caller-owned views (rmclhip_statistics_p2l,
+// rmclhip_pose_information_p2l), created by the first call; the caller holds ctx->p2l_mtx
+RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx);
 //@@DECLS@@

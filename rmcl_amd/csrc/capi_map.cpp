@@ -62,6 +62,7 @@ rmclhip_ctx::~rmclhip_ctx() {
   (void)hipSetDevice(device);
   (void)hipStreamSynchronize(p2l_stream);
   if (p2l_partials) (void)hipFree(p2l_partials);
+  pinfo_partials.release(); pinfo_rows.release();
   if (p2l_h_stats) (void)hipHostFree(p2l_h_stats);
   if (p2l_h_done) (void)hipHostFree(p2l_h_done);
   (void)hipStreamDestroy(p2l_stream);

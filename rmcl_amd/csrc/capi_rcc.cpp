@@ -52,7 +52,7 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
   if (r->stream) DBG_STEP(hipStreamSynchronize(r->stream));
   r->d_model_tab.release(); r->d_ds_points.release(); r->d_ds_mask.release();
   r->d_hits.release(); r->d_ranges.release(); r->d_points.release(); r->d_normals.release(); r->d_face_ids.release();
-  r->d_partials.release(); r->d_Tbm.release(); r->d_Tsm.release(); r->d_Tms.release(); r->d_Tdelta.release();
+  r->d_partials.release(); r->d_pinfo_partials.release(); r->d_pinfo_rows.release(); r->d_Tbm.release(); r->d_Tsm.release(); r->d_Tms.release(); r->d_Tdelta.release();
   r->d_bstats.release();
   if (r->h_bT) DBG_STEP(hipHostFree(r->h_bT));
   if (r->h_bS) DBG_STEP(hipHostFree(r->h_bS));
@@ -1111,6 +1111,27 @@ rmclhip_status rmclhip_rcc_simulate(rmclhip_rcc* r, const rmclhip_transform* Tbm
   return RMCLHIP_OK;
 }
 
+RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx) {
+  if (ctx->p2l_stream != nullptr) return RMCLHIP_OK;
+  hipStream_t s = nullptr;
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_stats), sizeof(cstats), hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_stats_dev), ctx->p2l_h_stats, 0);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_done), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_done_dev), ctx->p2l_h_done, 0);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (ctx->p2l_h_stats) (void)hipHostFree(ctx->p2l_h_stats);
+    if (ctx->p2l_h_done) (void)hipHostFree(ctx->p2l_h_done);
+    ctx->p2l_h_stats = nullptr; ctx->p2l_h_done = nullptr;
+    (void)hipStreamDestroy(s);
+    return fail(RMCLHIP_ERR_HIP, std::string("statistics_p2l: ") + hipGetErrorString(e));
+  }
+  *ctx->p2l_h_done = 0ull;
+  ctx->p2l_stream = s;   // last: the destructor frees the scratch iff the stream exists
+  return RMCLHIP_OK;
+}
+
 // rm::statistics_p2l on caller-owned device views: the operator's streaming reduction with the context's own scratch
 rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform* Tpre, const float* dataset_points,
                                       const uint8_t* dataset_mask, const float* model_points, const float* model_normals,
@@ -1121,24 +1142,7 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
   if (!dataset_points || !model_points || !model_normals) return fail(RMCLHIP_ERR_INVALID, "statistics_p2l: null view");
   std::lock_guard<std::mutex> lock(ctx->p2l_mtx);
   HIPCHK(hipSetDevice(ctx->device));
-  if (ctx->p2l_stream == nullptr) {
-    hipStream_t s = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_stats), sizeof(cstats), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_stats_dev), ctx->p2l_h_stats, 0);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_done), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_done_dev), ctx->p2l_h_done, 0);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-      if (ctx->p2l_h_stats) (void)hipHostFree(ctx->p2l_h_stats);
-      if (ctx->p2l_h_done) (void)hipHostFree(ctx->p2l_h_done);
-      ctx->p2l_h_stats = nullptr; ctx->p2l_h_done = nullptr;
-      (void)hipStreamDestroy(s);
-      return fail(RMCLHIP_ERR_HIP, std::string("statistics_p2l: ") + hipGetErrorString(e));
-    }
-    *ctx->p2l_h_done = 0ull;
-    ctx->p2l_stream = s;   // last: the destructor frees the scratch iff the stream exists
-  }
+  if (rmclhip_status st = ctx_p2l_ensure(ctx)) return st;
   const uint32_t nb = reduce_num_blocks(n, 1);
   if (ctx->p2l_partials_cap < static_cast<size_t>(nb) * 16u) {
     if (ctx->p2l_partials) (void)hipFree(ctx->p2l_partials);

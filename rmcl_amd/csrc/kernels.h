@@ -453,4 +453,12 @@ hipError_t launch_hypotheses(const xform* poses, const void* attrs, uint32_t n, 
                              double max_l, const unsigned long long* table, uint64_t table_words, uint32_t k_bins, uint32_t max_hypotheses,
                              const HypScratch& sc, uint32_t* labels, hipStream_t s);
 
+
+// pose_information.hip: the point-to-plane normal matrix over the correspondences of statistics_p2l (include/rmclhip.h, POSE
+// COVARIANCE).  Same inputs and grid as launch_reduce_partials (p.partials: [nposes][p.nblocks][kPoseInfoRow] doubles), then one wave
+// per pose folds the rows in a fixed order into rows_out[pose][kPoseInfoRow] = {the 28 entries of sum u u^T, upper triangle row by row,
+// u = [N ; D x N ; r] | the count | 3 x 0}.  No atomics: the same inputs give the same bytes.
+constexpr uint32_t kPoseInfoRow = 32u;
+hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s);
+
 }  // namespace rmclhip

@@ -20,6 +20,7 @@
 #include "pf_common.hip.h"
 #include "pf_random.hip.h"
 #include "surface.hip.h"
+#include "wave_sum.hip.h"
 
 
 namespace rmclhip {
@@ -61,26 +62,6 @@ __global__ void k_compose_poses(const xform* __restrict__ Tbm, xform Tsb, xform*
 // statistics_p2l
 // ---------------------------------------------------------------------------------------------
 constexpr int kAcc = 16;  // sd[3] sm[3] smd[9] cnt
-
-// wave64 sum of 16 doubles per lane through LDS instead of cross-lane shuffles: every lane stores its 16 values (row = lane),
-// lane L adds column L & 15 over the 16 rows of slice L >> 4, two xor steps join the four slices.  The 17 shuffles of the
-// halving butterfly are a chain of dependent ds_bpermute round trips (~3.4k clocks measured for a lone wave); here all stores
-// and all loads are independent (~0.6k).  scratch: 64 x 17 doubles owned by this wave; LDS operations of one wave complete in
-// order, so no barrier is needed.  Afterwards lanes 0..15 hold the totals of values 0..15.
-__device__ __forceinline__ double wave_sum16_lds(const double (&v)[16], double* scratch, uint32_t lane) {
-#pragma unroll
-  for (int k = 0; k < 16; ++k) scratch[lane * 17u + static_cast<uint32_t>(k)] = v[k];
-  const uint32_t col = lane & 15u, row0 = (lane >> 4) * 16u;
-  double a[16];
-#pragma unroll
-  for (uint32_t r = 0; r < 16u; ++r) a[r] = scratch[(row0 + r) * 17u + col];
-  double t = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  t += ((a[8] + a[9]) + (a[10] + a[11])) + ((a[12] + a[13]) + (a[14] + a[15]));
-  t += __shfl_xor(t, 16, 64);
-  t += __shfl_xor(t, 32, 64);
-  return t;
-}
-
 
 // sum the per-block partials of one pose (one wave) and turn the raw moments into CrossStatistics
 __device__ __forceinline__ cstats finalize_pose(const double* partials, uint32_t nblocks) {

@@ -120,6 +120,22 @@ class MICPLocalization:
                 record.append(T_onew_oold.copy())
         return self._finish(Tom, T_onew_oold, Cmerged_o, valid_measurements)
 
+    def poseInformation(self, T_onew_oold=None, covariance_params=None):
+        """What publishPose (micp_localization.cpp:1062-1076) needs instead of its guessed diagonal: the sensors' point-to-plane
+        information over the correspondences of their last find, each carried sensor -> base (Tsb) -> odom (Tbo) and merged with the
+        sensor's merge_weight_multiplier.  T_onew_oold: the correction the loop ended with (None: identity), the pre-transform of the
+        last iteration's statistics.  Returns (POSE_INFORMATION, POSE_COVARIANCE) in the odom frame (the base frame where Tbo is the
+        identity); covariance_params: types.pose_covariance_params(...)."""
+        T_onew_oold = T.identity() if T_onew_oold is None else T_onew_oold
+        merged = T.pose_information_identity()
+        for s in self.sensors_vec_:
+            T_bnew_bold = T.mult(T.mult(T.inv(s.Tbo), T_onew_oold), s.Tbo)
+            T_snew_sold = T.mult(T.mult(T.inv(s.Tsb), T_bnew_bold), s.Tsb)
+            info_s = s.correspondences_.computePoseInformation(T_snew_sold, self.convergence_progress_)
+            info_o = T.pose_information_transform(s.Tbo, T.pose_information_transform(s.Tsb, info_s))
+            merged = T.pose_information_merge(merged, info_o, s.merge_weight_multiplier)
+        return merged, T.pose_covariance(merged, covariance_params)
+
     def _finish(self, Tom, T_onew_oold, Cmerged_o, valid_measurements):
         T_onew_map = T.mult(Tom, T_onew_oold)                                             # :972
         n_meas = int(Cmerged_o["n_meas"])

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .types import CROSS_STATISTICS, TRANSFORM, _ptr
+from .types import CROSS_STATISTICS, POSE_INFORMATION, TRANSFORM, _ptr
 
 
 def _as_ptr(x):
@@ -289,6 +289,17 @@ def statistics_p2l(ctx, Tpre, dataset_points, dataset_mask, model_points, model_
     return out[0].copy()
 
 
+def pose_information_p2l(ctx, Tpre, dataset_points, dataset_mask, model_points, model_normals, model_mask, n, max_dist):
+    """the point-to-plane information matrix {A, g, rss, n_meas} over exactly the correspondences statistics_p2l keeps, on the same
+    caller-owned DEVICE views (rmclhip_pose_information_p2l).  Returns a POSE_INFORMATION record on the host."""
+    T = np.ascontiguousarray(Tpre, dtype=TRANSFORM).reshape(1)
+    out = np.zeros(1, dtype=POSE_INFORMATION)
+    _capi.check(_capi.lib().rmclhip_pose_information_p2l(ctx.handle, _ptr(T), _as_ptr(dataset_points), _as_ptr(dataset_mask),
+                                                         _as_ptr(model_points), _as_ptr(model_normals), _as_ptr(model_mask), int(n),
+                                                         float(max_dist), _ptr(out)))
+    return out[0].copy()
+
+
 class UmeyamaReductionConstraints:
     """rmagine::UmeyamaReductionConstraints (only max_dist is used, micp_localization.cpp:525-526)."""
 
@@ -335,6 +346,23 @@ class CorrespondencesHIP:
         _capi.check(_capi.lib().rmclhip_rcc_compute_cross_statistics(self._h, _ptr(T), float(convergence_progress),
                                                                      _ptr(out)))
         return out[0].copy()
+
+    def computePoseInformation(self, T_snew_sold, convergence_progress=0.0):
+        """the point-to-plane information matrix over the correspondences computeCrossStatistics(T_snew_sold, convergence_progress)
+        keeps, sensor frame (rmclhip_rcc_pose_information); reads the buffers of the last find, changes nothing"""
+        self._push_params()
+        T = np.ascontiguousarray(T_snew_sold, dtype=TRANSFORM).reshape(1)
+        out = np.zeros(1, dtype=POSE_INFORMATION)
+        _capi.check(_capi.lib().rmclhip_rcc_pose_information(self._h, _ptr(T), float(convergence_progress), _ptr(out)))
+        return out[0].copy()
+
+    def computePoseInformationBatch(self, nposes, convergence_progress=0.0):
+        """one pose information per pose of the last find_batch / correct_batch (identity pre-transform): POSE_INFORMATION[nposes]
+        (rmclhip_rcc_pose_information_batch); nposes must be what that batch held"""
+        self._push_params()
+        out = np.zeros(max(int(nposes), 1), dtype=POSE_INFORMATION)
+        _capi.check(_capi.lib().rmclhip_rcc_pose_information_batch(self._h, int(nposes), float(convergence_progress), _ptr(out)))
+        return out[:int(nposes)].copy()
 
     def modelView(self, attributes=None):
         """host copy of {points, mask(hits), normals} (+ ranges, face_ids) of the last find; `attributes`: a subset of the five names

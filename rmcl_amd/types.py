@@ -20,7 +20,14 @@ CROSS_STATISTICS = np.dtype([("dataset_mean", VEC3), ("model_mean", VEC3),
 GAUSSIAN1D = np.dtype([("mean", "<f4"), ("sigma", "<f4"), ("n_meas", "<u4")])
 PARTICLE_ATTRIBUTES = np.dtype([("likelihood", GAUSSIAN1D), ("state_sigma", "<f4", (6,))])
 RANGE_MEASUREMENT = np.dtype([("orig", VEC3), ("dir", VEC3), ("range", "<f4"), ("cov", "<f4", (9,))])
+# rmclhip_pose_information / rmclhip_pose_covariance (include/rmclhip.h, POSE COVARIANCE): A and covariance row-major 6 x 6 in the
+# order x y z rot-x rot-y rot-z; eigenvector k of a block = row k of eigvec_*
+POSE_INFORMATION = np.dtype([("A", "<f8", (6, 6)), ("g", "<f8", (6,)), ("rss", "<f8"), ("n_meas", "<u4"), ("pad", "<u4")])
+POSE_COVARIANCE = np.dtype([("covariance", "<f8", (6, 6)), ("eig_trans", "<f8", (3,)), ("eigvec_trans", "<f8", (3, 3)),
+                            ("eig_rot", "<f8", (3,)), ("eigvec_rot", "<f8", (3, 3)), ("n_degenerate_trans", "<u4"),
+                            ("n_degenerate_rot", "<u4"), ("s2", "<f8")])
 assert TRANSFORM.itemsize == 32 and CROSS_STATISTICS.itemsize == 64
+assert POSE_INFORMATION.itemsize == 352 and POSE_COVARIANCE.itemsize == 496
 assert PARTICLE_ATTRIBUTES.itemsize == 36 and RANGE_MEASUREMENT.itemsize == 64
 
 MAX_N_MEAS = 10000  # ParticleAttributes.hpp:34
@@ -95,6 +102,53 @@ def umeyama_transform(s):
     """rm::umeyama_transform (micp_localization.cpp:952-953)."""
     s, out = _one(s, CROSS_STATISTICS), np.zeros(1, dtype=TRANSFORM)
     _capi.check(_capi.lib().rmclhip_umeyama_transform(_ptr(s), _ptr(out)))
+    return out[0].copy()
+
+
+def pose_information_identity():
+    """nothing measured: the neutral element of pose_information_merge"""
+    return np.zeros((), dtype=POSE_INFORMATION)
+
+
+def pose_information_transform(T, info):
+    """the frame change of a pose information, the role cross_statistics_transform has (rmclhip_pose_information_transform)"""
+    T, info, out = _one(T, TRANSFORM), _one(info, POSE_INFORMATION), np.zeros(1, dtype=POSE_INFORMATION)
+    _capi.check(_capi.lib().rmclhip_pose_information_transform(_ptr(T), _ptr(info), _ptr(out)))
+    return out[0].copy()
+
+
+def pose_information_merge(a, b, weight_b=1.0):
+    """a + weight_b * b for A, g and rss; the counts add unscaled (rmclhip_pose_information_merge)"""
+    a, b, out = _one(a, POSE_INFORMATION), _one(b, POSE_INFORMATION), np.zeros(1, dtype=POSE_INFORMATION)
+    _capi.check(_capi.lib().rmclhip_pose_information_merge(_ptr(a), _ptr(b), float(weight_b), _ptr(out)))
+    return out[0].copy()
+
+
+def pose_information_solve(info, rcond=1e-9):
+    """the Gauss-Newton step xi = A^+ g = (dt, dtheta) of the dataset in its own frame (rmclhip_pose_information_solve_host)"""
+    info, out = _one(info, POSE_INFORMATION), np.zeros(6, dtype=np.float64)
+    _capi.check(_capi.lib().rmclhip_pose_information_solve_host(_ptr(info), float(rcond), _ptr(out)))
+    return out
+
+
+def pose_covariance_params(sigma=None, rcond=None, degenerate_variance=None, min_eig_trans=None, min_eig_rot=None):
+    """rmclhip_pose_covariance_params; arguments left None keep the library's defaults (rmclhip_pose_covariance_params_default):
+    sigma 0 (the noise is estimated from the residuals), rcond 1e-9, degenerate_variance 1e6, min_eig_trans 1e-3, min_eig_rot 1e-3"""
+    p = _capi.PoseCovarianceParams()
+    _capi.lib().rmclhip_pose_covariance_params_default(C.byref(p))
+    for k, v in (("sigma", sigma), ("rcond", rcond), ("degenerate_variance", degenerate_variance), ("min_eig_trans", min_eig_trans),
+                 ("min_eig_rot", min_eig_rot)):
+        if v is not None:
+            setattr(p, k, float(v))
+    return p
+
+
+def pose_covariance(info, params=None, **kw):
+    """covariance + degeneracy report of a pose information (rmclhip_pose_covariance_host); params: pose_covariance_params(...) or
+    its keyword arguments"""
+    p = params if params is not None else pose_covariance_params(**kw)
+    info, out = _one(info, POSE_INFORMATION), np.zeros(1, dtype=POSE_COVARIANCE)
+    _capi.check(_capi.lib().rmclhip_pose_covariance_host(_ptr(info), C.byref(p), _ptr(out)))
     return out[0].copy()
 
 
