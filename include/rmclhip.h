@@ -412,7 +412,10 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* rcc, const rmclhip_transfor
  * sensor at Tbm = Tom * Tbo[s], then n_iter x { per sensor statistics at T_snew_sold (MICPSensor.hpp:178) in its own frame,
  * Cs_o = Tbo * (Tsb * stats_s), Cmerged_o += Cs_o, Cmerged_weighted_o += Cs_o with n_meas *= merge_weight_multiplier[s]
  * (truncating, :934), T_onew_oold *= umeyama(Cmerged_weighted_o) } -- all on the device, one synchronisation at the end.
- * merge_weight_multiplier may be NULL (all 1).  merged_out: the UNWEIGHTED statistics of the last iteration (:1010-1011).
+ * merge_weight_multiplier may be NULL (all 1); every weight must be finite and >= 0 (RMCLHIP_ERR_INVALID names the sensor otherwise:
+ * the truncating conversion of a negative or non-finite product is undefined and differs between host and device).  A product
+ * n_meas * weight of 2^32 or more is not checked and is the caller's to avoid.
+ * merged_out: the UNWEIGHTED statistics of the last iteration (:1010-1011).
  * Every sensor's find (and moment pass) is enqueued on that sensor's OWN stream, so the scans run concurrently; the loop runs on
  * sensor 0's stream behind all of them (an in-kernel flag per sensor; stream events in the per-iteration fallback).  When the call
  * returns, all of it is complete and every sensor's model buffers hold its scan at Tom * Tbo[s]. */

@@ -1491,6 +1491,10 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
     if (r->kind == kModelNone || r->W == 0 || r->H == 0) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: sensor without a model");
     if (r->n_dataset == 0) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: sensor without a dataset");
     if (!micp_outputs_selected(r)) return fail(RMCLHIP_ERR_INVALID, kNeedMicpOutputs);
+    // n_meas * weight is converted to uint32 on the host in one loop form and on the device in the other two: a negative or
+    // non-finite product has no defined conversion, and the forms would part
+    if (merge_weight_multiplier && !(std::isfinite(merge_weight_multiplier[s]) && merge_weight_multiplier[s] >= 0.0))
+      return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: merge_weight_multiplier of sensor " + std::to_string(s) + " is negative or not finite");
   }
   HIPCHK(hipSetDevice(r0->ctx->device));
   hipStream_t st = r0->stream;

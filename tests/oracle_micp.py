@@ -54,18 +54,47 @@ def correct_once(mesh, model, Tsb, Tbo, Tom, ds_points, ds_mask, n_iter, max_dis
     return T_onew_oold, merged, traj
 
 
-def correct_once_multi(mesh, sensors, Tom, n_iter, convergence_progress=0.0):
+def simulate_model(mesh, model, Tsb, Tbm):
+    """one scan of any of the four sensor models.  `model`: an rmagine SphericalModel, or a dict with "kind" in spherical
+    ("model"), o1dn ("width", "height", "range_min", "range_max", "orig", "dirs"), ondn (the same with "origs") and pinhole
+    ("width", "height", "range_min", "range_max", "f", "c")."""
+    if not isinstance(model, dict):
+        return mesh.simulate_spherical(model, Tsb, Tbm, bvh=True)
+    k = model["kind"]
+    if k == "spherical":
+        return mesh.simulate_spherical(model["model"], Tsb, Tbm, bvh=True)
+    size = (model["width"], model["height"], model["range_min"], model["range_max"])
+    if k == "o1dn":
+        return mesh.simulate_o1dn(*size, model["orig"], model["dirs"], Tsb, Tbm, bvh=True)
+    if k == "ondn":
+        return mesh.simulate_ondn(*size, model["origs"], model["dirs"], Tsb, Tbm, bvh=True)
+    if k == "pinhole":
+        return mesh.simulate_pinhole(*size, model["f"], model["c"], Tsb, Tbm, bvh=True)
+    raise ValueError("unknown sensor model kind %r" % (k,))
+
+
+def reduced(sim, ds_points, ds_mask):
+    """the correspondences the statistics run over: the first nred = min(n_dataset, n_model) of both sides"""
+    ds_points = np.asarray(ds_points, np.float32).reshape(-1, 3)
+    nred = min(len(ds_points), len(sim["hits"]))
+    cut = {k: sim[k][:nred] for k in ("points", "normals", "hits")}
+    return cut, ds_points[:nred], None if ds_mask is None else np.asarray(ds_mask, np.uint8).reshape(-1)[:nred]
+
+
+def correct_once_multi(mesh, sensors, Tom, n_iter, convergence_progress=0.0, want_traj=False):
     """MICPLocalizationNode::correctOnce with several sensors (micp_localization.cpp:921-963): sensors = [(model, Tsb, Tbo,
-    ds_points, ds_mask, max_dist, adaptive_min, merge_weight_multiplier)].  Returns (T_onew_oold, merged unweighted stats, the weighted
-    merged stats every iteration solved)."""
+    ds_points, ds_mask, max_dist, adaptive_min, merge_weight_multiplier)], `model` as simulate_model takes it (a bare
+    SphericalModel: spherical); ds_mask may be None and the dataset shorter than the model.  Returns (T_onew_oold, merged unweighted
+    stats, the weighted merged stats every iteration solved) and, with want_traj, T_onew_oold after every iteration as a fourth."""
     ident = orc.transform()
     T_onew_oold = ident
     merged = orc.cs_identity()
-    sims = [mesh.simulate_spherical(model, Tsb, orc.tmult(Tom, Tbo), bvh=True) for model, Tsb, Tbo, *_ in sensors]
-    solved = []
+    sims = [reduced(simulate_model(mesh, model, Tsb, orc.tmult(Tom, Tbo)), ds_points, ds_mask)
+            for model, Tsb, Tbo, ds_points, ds_mask, *_ in sensors]
+    solved, traj = [], []
     for _ in range(n_iter):
         merged, merged_w = orc.cs_identity(), orc.cs_identity()
-        for sim, (model, Tsb, Tbo, ds_points, ds_mask, max_dist, adaptive_min, w) in zip(sims, sensors):
+        for (sim, ds_points, ds_mask), (model, Tsb, Tbo, _p, _m, max_dist, adaptive_min, w) in zip(sims, sensors):
             md = orc.adaptive_max_dist(max_dist, adaptive_min, convergence_progress)
             T_bnew_bold = orc.tmult(orc.tmult(orc.tinv(Tbo), T_onew_oold), Tbo)
             Cs_o = orc.cs_transform(Tbo, compute_cross_statistics_b(sim, ds_points, ds_mask, Tsb, T_bnew_bold, md))
@@ -75,6 +104,9 @@ def correct_once_multi(mesh, sensors, Tom, n_iter, convergence_progress=0.0):
             merged_w = orc.cs_merge(merged_w, Cs_w)
         solved.append(merged_w)
         T_onew_oold = orc.tmult(T_onew_oold, orc.umeyama(merged_w))
+        traj.append(T_onew_oold.copy())
+    if want_traj:
+        return T_onew_oold, merged, solved, traj
     return T_onew_oold, merged, solved
 
 

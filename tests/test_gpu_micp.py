@@ -282,7 +282,11 @@ def test_two_sensor_device_loop_equals_host_loop(ra, orc, ctx, meshes):
     """MICPLocalizationNode::correctOnce with TWO sensors (micp_localization.cpp:921-938: per-sensor statistics, optimal +
     weighted merge, one solve per iteration): the device-resident loop (rmclhip_micp_correct_once) must equal the host loop
     that calls computeCrossStatistics per sensor and iteration -- different models, mounts, odometry stamps (Tbo) and merge
-    weights, including a weight that truncates (n_meas *= 0.37)."""
+    weights, including a weight that truncates (n_meas *= 0.37).
+    Which loop form serves these calls today (sensors in the default mode, set_micp_fast(1)): the small correction (est_near)
+    completes in the HOST form, iterations on the host from the published moments; the large one (est_far) is tried, gives up and
+    ends in the per-iteration form (k_micp_multi_step).  Nothing here completes in the device's moment loop
+    (k_micp_multi_fast_loop); tests/test_gpu_micp_multi.py forces and proves each form."""
     from rmcl_amd import synthetic as syn, types as T
     v, f = meshes("room30k")
     m = orc.Mesh(v, f)
@@ -351,10 +355,12 @@ def test_two_sensor_device_loop_equals_host_loop(ra, orc, ctx, meshes):
 
 
 def test_six_sensor_device_loop_equals_host_loop(ra, orc, ctx, meshes):
-    """the N-sensor device loop with SIX sensors (more than the four waves of its workgroup: wave w evaluates sensors w and w + 4;
-    lanes 0..5 of wave 0 own one sensor each): different models, mounts, odometry offsets and merge weights (one of them 0:
-    the sensor counts in the optimal merge only).  Equal to the host loop -- per sensor and iteration one computeCrossStatistics --
-    in the moment form (small correction) and in its fallback (large correction)."""
+    """rmclhip_micp_correct_once with SIX sensors: different models, mounts, odometry offsets and merge weights (one of them 0: the
+    sensor counts in the optimal merge only).  Equal to the host loop -- per sensor and iteration one computeCrossStatistics.
+    Which loop form serves these calls today (sensors in the default mode, set_micp_fast(1)): the small correction completes in
+    the HOST form (iterations on the host from the published moments), the large one ends in the per-iteration form.  The wave
+    layout of the device's moment loop (wave w sums sensors w and w + 4, lanes 0..5 of wave 0 own one sensor each), which this
+    test was written for, is not reached from here any more: tests/test_gpu_micp_multi.py runs it (cases cube6 and eight)."""
     from rmcl_amd import synthetic as syn, types as T
     v, f = meshes("room30k")
     m = orc.Mesh(v, f)

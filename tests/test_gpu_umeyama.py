@@ -153,8 +153,11 @@ def test_correct_batch_on_degenerate_scenes(ra, ctx, maps, name):
 @pytest.mark.parametrize("name", SCENES)
 def test_two_sensors_on_degenerate_scenes(ra, ctx, maps, name):
     """MICPLocalization.correctOnce with two sensors of the scene's model, the second mounted 1.5 m beside the first and merged
-    at half weight: the device-resident N-sensor loop (k_micp_multi_step / k_micp_multi_fast_loop) and the host loop, against the
-    oracle's loop.  Both 2-D lidars see the one wall: the merged statistics are still of rank one.  cube_1 becomes two points."""
+    at half weight: rmclhip_micp_correct_once (device_loop=True) and the Python host loop, against the oracle's loop.  The sensors
+    are in the default mode, so every scene's three calls end in the HOST form of that entry point -- moments published by the
+    finds, iterations and umeyama() on the host --, unless a call gives up and takes the per-iteration form (k_micp_multi_step); the
+    device's moment loop (k_micp_multi_fast_loop, umeyama_fast) is not reached from here: tests/test_gpu_micp_multi.py.
+    Both 2-D lidars see the one wall: the merged statistics are still of rank one.  cube_1 becomes two points."""
     sc = uc.scenes()[name]
     spec = uc.two_sensor_spec(sc)
     To, so, _ = om.correct_once_multi(sc.mesh, spec, sc.Tom, 4)
