@@ -297,6 +297,11 @@ hipError_t launch_residual_fill(const xform* poses, const void* attrs, const uin
 hipError_t launch_gladiator_resample(const xform* poses, const void* attrs, uint32_t n, xform* poses_new, void* attrs_new,
                                      uint32_t first, uint32_t count, const float* cfg8, uint32_t trans_dist_metric,
                                      uint64_t seed, uint32_t step, hipStream_t s);
+// blocks of the reductions that leave one partial per block (likelihood statistics, pose moments): 1024 particles each, 1 .. 256
+inline uint32_t partial_blocks(uint32_t n) {
+  const uint32_t nblocks = (n + 1023u) / 1024u;
+  return nblocks < 1u ? 1u : (nblocks > 256u ? 256u : nblocks);
+}
 // psum / pmax: scratch of 256 entries each; out2: {sum, max} (device)
 hipError_t launch_likelihood_stats(const void* attrs, uint32_t n, double* psum, float* pmax, float* out2, hipStream_t s);
 // the same {sum, max} of a DENSE weight vector (the gathered likelihood.mean of a sharded cloud): bit-identical to the call above on
@@ -429,8 +434,8 @@ hipError_t launch_particles_init_pose(xform* poses, void* attrs, uint32_t first,
 hipError_t launch_particles_pack_visualization(const xform* poses, const void* attrs, uint32_t n, uint32_t max_n_meas, float* out, hipStream_t s);
 
 // adaptive.hip: occupied bins of pose space (counts2 = {distinct bins, counted particles}, zeroed by the caller; table: table_words
-// 64-bit words, a power of two >= 2 n, all-ones on entry), and systematic resampling: the integer weights' inclusive prefix sums
-// (incl: n words, block_tot: ceil(n / 1024) words), then the slots [first, first + count) of the new cloud
+// 64-bit words, a power of two >= 2 n, all-ones on entry); resample.hip: systematic resampling -- the integer weights' inclusive
+// prefix sums (incl: n words, block_tot: ceil(n / 1024) words), then the slots [first, first + count) of the new cloud
 hipError_t launch_kld_count_bins(const xform* poses, const void* attrs, uint32_t n, const float* bin_xyz, const float* bin_rpy, float floor_l,
                                  unsigned long long* table, uint64_t table_words, uint32_t* counts2, hipStream_t s);
 hipError_t launch_sys_scan(const void* attrs, uint32_t n, double max_l, unsigned long long* incl, unsigned long long* block_tot, hipStream_t s);

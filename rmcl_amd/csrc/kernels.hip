@@ -10,7 +10,7 @@
 //                    into the last block) are gone; profiles/r03_micp_loop_forms.txt holds their measurements
 //  k_pf_update_v3    PCDSensorUpdater{Embree,Optix}::update, all beams fused
 //                    (PCDSensorUpdaterEmbree.cpp:290-342, optix/BeamEvaluateProgram.cu:15-130)
-//  k_pf_motion, k_gladiator_resample, k_likelihood_stats_*, k_pose_moments*: the rest of a filter cycle
+//  k_pf_motion, k_pose_moments*: the rest of a filter cycle (the resamplers and the likelihood statistics: resample.hip)
 //
 // Experiments (rejected traversal kinds, probes, the round-2 particle-filter kernels) live in kernels_lab.hip and ship in
 // librmclhip_lab.so; launch_find / launch_pf_update hand kinds they do not own to that library when it is loaded
@@ -1702,303 +1702,6 @@ __global__ void __launch_bounds__(256) k_pf_motion(const uint32_t* __restrict__ 
   }
 }
 
-__global__ void k_pf_extract_weights(const pattrs* __restrict__ attrs, uint32_t n, float* __restrict__ w) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] = attrs[i].likelihood.mean;
-}
-
-// ---------------------------------------------------------------------------------------------
-// gladiator resampling (resampling.cu:41-219).  Random stream = Philox4x32-10 keyed by the seed with counter
-// (champion index, step, draw, 0): reproducible, independent of the launch shape and of how the particle range
-// is sharded across GPUs.  Transcendentals are evaluated in double and rounded to float (see oracle).
-// philox4x32_10, box_muller and euler_to_quat: pf_random.hip.h (shared with particles.hip).
-// ---------------------------------------------------------------------------------------------
-struct GladiatorConfig {
-  float min_noise_tx, min_noise_ty, min_noise_tz, min_noise_roll, min_noise_pitch, min_noise_yaw;
-  float likelihood_forget_per_meter, likelihood_forget_per_radian;
-  uint32_t trans_dist_metric;
-};
-
-__global__ void __launch_bounds__(256) k_gladiator_resample(const xform* __restrict__ poses, const pattrs* __restrict__ attrs,
-                                                            uint32_t n, xform* __restrict__ poses_new,
-                                                            pattrs* __restrict__ attrs_new, uint32_t first, uint32_t count,
-                                                            GladiatorConfig cfg, uint32_t key0, uint32_t key1,
-                                                            uint32_t step) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= count) return;
-  const uint32_t champion = first + k;
-  uint32_t ra[4], rb[4];
-  philox4x32_10(champion, step, 0u, 0u, key0, key1, ra);
-  philox4x32_10(champion, step, 1u, 0u, key0, key1, rb);
-  const uint32_t enemy = ra[0] % n;
-  const float Lc = attrs[champion].likelihood.mean, Le = attrs[enemy].likelihood.mean;
-  if (Le > Lc) {
-    float Nd_tx, Nd_ty, Nd_tz, Nd_rx, Nd_ry, Nd_rz;
-    box_muller(ra[1], ra[2], Nd_tx, Nd_ty);
-    box_muller(ra[3], rb[0], Nd_tz, Nd_rx);
-    box_muller(rb[1], rb[2], Nd_ry, Nd_rz);
-    const xform pose = poses[enemy];
-    xform pn = pose;
-    pattrs an = attrs[enemy];
-    pn.t.x = pn.t.x + Nd_tx * cfg.min_noise_tx;
-    pn.t.y = pn.t.y + Nd_ty * cfg.min_noise_ty;
-    pn.t.z = pn.t.z + Nd_tz * cfg.min_noise_tz;
-    // EulerAngles e = pose_new.R (textbook ZYX extraction)
-    const quat q = pn.R;
-    const float sinr_cosp = 2.0f * (q.w * q.x + q.y * q.z);
-    const float cosr_cosp = 1.0f - 2.0f * (q.x * q.x + q.y * q.y);
-    const float sinp = 2.0f * (q.w * q.y - q.z * q.x);
-    const float siny_cosp = 2.0f * (q.w * q.z + q.x * q.y);
-    const float cosy_cosp = 1.0f - 2.0f * (q.y * q.y + q.z * q.z);
-    float roll = static_cast<float>(atan2(static_cast<double>(sinr_cosp), static_cast<double>(cosr_cosp)));
-    float pitch = (fabsf(sinp) >= 1.0f) ? copysignf(static_cast<float>(3.14159265358979323846 / 2.0), sinp)
-                                        : static_cast<float>(asin(static_cast<double>(sinp)));
-    float yaw = static_cast<float>(atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp)));
-    roll = roll + Nd_rx * cfg.min_noise_roll;
-    pitch = pitch + Nd_ry * cfg.min_noise_pitch;
-    yaw = yaw + Nd_rz * cfg.min_noise_yaw;
-    // pose_new.R = e
-    pn.R = euler_to_quat(roll, pitch, yaw);
-    const xform diff = xmul(xinv(pose), pn);
-    const float t2 = (diff.t.x * diff.t.x + diff.t.y * diff.t.y) + diff.t.z * diff.t.z;
-    const float trans_dist = (cfg.trans_dist_metric == 1u) ? t2 : sqrtf(t2);
-    const float rot_dist = sqrtf(((diff.R.w * diff.R.w + diff.R.x * diff.R.x) + diff.R.y * diff.R.y) + diff.R.z * diff.R.z);
-    const float frs = static_cast<float>(1.0 - pow(1.0 - static_cast<double>(cfg.likelihood_forget_per_meter), static_cast<double>(trans_dist)));
-    const float frr = static_cast<float>(1.0 - pow(1.0 - static_cast<double>(cfg.likelihood_forget_per_radian), static_cast<double>(rot_dist)));
-    const float forget_rate = (frs > frr) ? frs : frr;
-    const float remember_rate = static_cast<float>(1.0 - static_cast<double>(forget_rate));
-    an.likelihood.n_meas = n_meas_scaled(an.likelihood.n_meas, remember_rate);
-    poses_new[k] = pn;
-    attrs_new[k] = an;
-  } else {
-    poses_new[k] = poses[champion];
-    attrs_new[k] = attrs[champion];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// residual resampling (ResidualResamplerCPU.cpp:55-203) -- the reference's SEQUENTIAL loop "draw a particle, insert
-// size_t(L / sum * N_new) perturbed copies, until the new cloud is full" as four data-parallel passes over a block of draws:
-//   counts   c_k = copies draw k inserts (the draw's particle and its share; independent of every other draw),
-//   scan     inclusive prefix sums of c_k (64-bit): draw k fills slots [incl_k - c_k, incl_k),
-//   fill     slot j finds its draw by binary search, perturbs the copy with ITS Gaussians (Philox counter = slot index).
-// Same stream, same arithmetic as oracle/rmcl_oracle.c: orc_residual_resample (which restates the loop statement by statement):
-// particles, likelihoods and n_meas bit-exact, poses to float rounding of the double-evaluated transcendentals.
-// ---------------------------------------------------------------------------------------------
-struct ResidualStats {
-  double sum, max;
-  unsigned long long expect;   // sum over the particles of their share's integer part = n * E[c_k]
-  unsigned long long n_draws;  // written by k_residual_fill: draws the sequential loop would have used
-};
-
-__global__ void __launch_bounds__(64) k_residual_stats_final(const double* __restrict__ psum, const float* __restrict__ pmax,
-                                                            uint32_t nblocks, ResidualStats* __restrict__ out) {
-  // fixed order: lane l sums blocks l, l + 64, ...; then a fixed butterfly
-  double s = 0.0;
-  float m = 0.0f;
-  for (uint32_t b = threadIdx.x; b < nblocks; b += 64u) { s += psum[b]; m = fmaxf(m, pmax[b]); }
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_down(s, off);
-    m = fmaxf(m, __shfl_down(m, off));
-  }
-  if (threadIdx.x == 0) { out->sum = s; out->max = static_cast<double>(m); out->expect = 0ull; out->n_draws = 0ull; }
-}
-
-// copies a draw of particle likelihood L inserts when `left` slots are free: the reference's size_t(L / sum * N_new), clamped
-__device__ __forceinline__ uint32_t residual_share(float Lf, double weight_sum, uint32_t n_new) {
-  const double share = (static_cast<double>(Lf) / weight_sum) * static_cast<double>(n_new);
-  if (!(share > 0.0)) return 0u;
-  return (share >= static_cast<double>(n_new)) ? n_new : static_cast<uint32_t>(share);
-}
-
-__global__ void __launch_bounds__(256) k_residual_expect(const pattrs* __restrict__ attrs, uint32_t n, uint32_t n_new,
-                                                         ResidualStats* __restrict__ st) {
-  __shared__ unsigned long long s_part[4];
-  const double sum = st->sum;
-  unsigned long long acc = 0ull;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    acc += residual_share(attrs[i].likelihood.mean, sum, n_new);
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(&st->expect, (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]));   // integers: order independent
-}
-
-__global__ void __launch_bounds__(256) k_residual_counts(const pattrs* __restrict__ attrs, uint32_t n, uint32_t n_new,
-                                                         const ResidualStats* __restrict__ st, uint32_t n_draws, uint32_t key0,
-                                                         uint32_t key1, uint32_t step, uint32_t* __restrict__ idx_out,
-                                                         uint32_t* __restrict__ cnt_out) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n_draws) return;
-  uint32_t r[4];
-  philox4x32_10(k, step, 2u, 0u, key0, key1, r);
-  const uint32_t random_index = r[0] % n;
-  idx_out[k] = random_index;
-  cnt_out[k] = residual_share(attrs[random_index].likelihood.mean, st->sum, n_new);
-}
-
-// inclusive 64-bit prefix sums of 32-bit counts, three passes: 1024 elements per block -> block totals -> totals scanned by ONE
-// block -> added back.  (Counts are <= N_new each, so 32 bits would overflow for peaked weights.)
-__device__ __forceinline__ unsigned long long block_scan_256(unsigned long long v, unsigned long long* s_wave, unsigned long long& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long o = __shfl_up(incl, off, 64);
-    if (lane >= static_cast<uint32_t>(off)) incl += o;
-  }
-  if (lane == 63u) s_wave[wave] = incl;
-  __syncthreads();
-  unsigned long long base = 0ull;
-  for (uint32_t w = 0; w < wave; ++w) base += s_wave[w];
-  total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-  __syncthreads();
-  return base + incl;
-}
-
-__global__ void __launch_bounds__(256) k_scan_blocks(const uint32_t* __restrict__ cnt, uint32_t n, unsigned long long* __restrict__ incl,
-                                                     unsigned long long* __restrict__ block_total) {
-  __shared__ unsigned long long s_wave[4];
-  const uint32_t base = blockIdx.x * 1024u + threadIdx.x * 4u;
-  unsigned long long c[4];
-#pragma unroll
-  for (uint32_t u = 0; u < 4u; ++u) c[u] = (base + u < n) ? cnt[base + u] : 0u;
-  const unsigned long long mine = (c[0] + c[1]) + (c[2] + c[3]);
-  unsigned long long total;
-  const unsigned long long end = block_scan_256(mine, s_wave, total);   // inclusive over the threads
-  unsigned long long run = end - mine;
-#pragma unroll
-  for (uint32_t u = 0; u < 4u; ++u) {
-    run += c[u];
-    if (base + u < n) incl[base + u] = run;
-  }
-  if (threadIdx.x == 0) block_total[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(256) k_scan_totals(unsigned long long* __restrict__ block_total, uint32_t nblocks) {
-  __shared__ unsigned long long s_wave[4];
-  unsigned long long carry = 0ull;
-  for (uint32_t b0 = 0; b0 < nblocks; b0 += 256u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const unsigned long long v = (b < nblocks) ? block_total[b] : 0ull;
-    unsigned long long total;
-    const unsigned long long inc = block_scan_256(v, s_wave, total);
-    if (b < nblocks) block_total[b] = carry + inc - v;   // exclusive: what precedes block b
-    carry += total;
-  }
-}
-
-__global__ void __launch_bounds__(256) k_scan_add(unsigned long long* __restrict__ incl, uint32_t n, const unsigned long long* __restrict__ block_excl) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) incl[i] += block_excl[i >> 10];
-}
-
-__global__ void __launch_bounds__(256) k_residual_fill(const xform* __restrict__ poses, const pattrs* __restrict__ attrs,
-                                                       const uint32_t* __restrict__ draw_idx, const unsigned long long* __restrict__ incl,
-                                                       uint32_t n_draws, xform* __restrict__ poses_new, pattrs* __restrict__ attrs_new,
-                                                       uint32_t n_new, uint32_t first, uint32_t count, GladiatorConfig cfg,
-                                                       ResidualStats* __restrict__ st, uint32_t key0, uint32_t key1, uint32_t step) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const uint32_t j = first + t;                 // global output slot
-  // the draw that fills slot j: the first k with incl[k] > j (the host launches this only when incl[n_draws - 1] >= n_new)
-  uint32_t lo = 0u, hi = n_draws - 1u;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (incl[mid] > static_cast<unsigned long long>(j)) hi = mid; else lo = mid + 1u;
-  }
-  const uint32_t k = lo;
-  if (j + 1u == n_new) st->n_draws = static_cast<unsigned long long>(k) + 1ull;   // the sequential loop stops after this draw
-  const uint32_t src = draw_idx[k];
-  const xform pose = poses[src];
-  pattrs an = attrs[src];
-  const double L_max_normed = static_cast<double>(an.likelihood.mean) / st->max;
-  uint32_t ra[4], rb[4];
-  philox4x32_10(j, step, 3u, 0u, key0, key1, ra);
-  philox4x32_10(j, step, 4u, 0u, key0, key1, rb);
-  float Nd_tx, Nd_ty, Nd_tz, Nd_rx, Nd_ry, Nd_rz;
-  box_muller(ra[0], ra[1], Nd_tx, Nd_ty);
-  box_muller(ra[2], ra[3], Nd_tz, Nd_rx);
-  box_muller(rb[0], rb[1], Nd_ry, Nd_rz);
-  const float noise_tx = static_cast<float>(static_cast<double>(cfg.min_noise_tx) / L_max_normed);
-  const float noise_ty = static_cast<float>(static_cast<double>(cfg.min_noise_ty) / L_max_normed);
-  const float noise_tz = static_cast<float>(static_cast<double>(cfg.min_noise_tz) / L_max_normed);
-  const float noise_roll = static_cast<float>(static_cast<double>(cfg.min_noise_roll) / L_max_normed);
-  const float noise_pitch = static_cast<float>(static_cast<double>(cfg.min_noise_pitch) / L_max_normed);
-  const float noise_yaw = static_cast<float>(static_cast<double>(cfg.min_noise_yaw) / L_max_normed);
-  xform pn = pose;
-  pn.t.x = pn.t.x + Nd_tx * noise_tx;
-  pn.t.y = pn.t.y + Nd_ty * noise_ty;
-  pn.t.z = pn.t.z + Nd_tz * noise_tz;
-  // EulerAngles <- Quaternion (textbook ZYX extraction, as in k_gladiator_resample)
-  const quat q = pn.R;
-  const float sinr_cosp = 2.0f * (q.w * q.x + q.y * q.z);
-  const float cosr_cosp = 1.0f - 2.0f * (q.x * q.x + q.y * q.y);
-  const float sinp = 2.0f * (q.w * q.y - q.z * q.x);
-  const float siny_cosp = 2.0f * (q.w * q.z + q.x * q.y);
-  const float cosy_cosp = 1.0f - 2.0f * (q.y * q.y + q.z * q.z);
-  float roll = static_cast<float>(atan2(static_cast<double>(sinr_cosp), static_cast<double>(cosr_cosp)));
-  float pitch = (fabsf(sinp) >= 1.0f) ? copysignf(static_cast<float>(3.14159265358979323846 / 2.0), sinp)
-                                      : static_cast<float>(asin(static_cast<double>(sinp)));
-  float yaw = static_cast<float>(atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp)));
-  roll = roll + Nd_rx * noise_roll;
-  pitch = pitch + Nd_ry * noise_pitch;
-  yaw = yaw + Nd_rz * noise_yaw;
-  pn.R = euler_to_quat(roll, pitch, yaw);
-  const xform diff = xmul(xinv(pose), pn);
-  const float trans_dist = (diff.t.x * diff.t.x + diff.t.y * diff.t.y) + diff.t.z * diff.t.z;   // l2normSquared (:164)
-  const float rot_dist = sqrtf(((diff.R.w * diff.R.w + diff.R.x * diff.R.x) + diff.R.y * diff.R.y) + diff.R.z * diff.R.z);
-  const float reduction_factor = static_cast<float>(pow(static_cast<double>(cfg.likelihood_forget_per_meter), static_cast<double>(trans_dist))) *
-                                 static_cast<float>(pow(static_cast<double>(cfg.likelihood_forget_per_radian), static_cast<double>(rot_dist)));
-  an.likelihood.n_meas = n_meas_scaled(an.likelihood.n_meas, reduction_factor);
-  poses_new[t] = pn;
-  attrs_new[t] = an;
-}
-
-// simple_stats_kernel (resampling.cu:41-81): {sum, max} of likelihood.mean; max seeded with 0 like the reference's
-// shared-memory init, sum accumulated in double.  Stage 1: <=256 blocks of grid-stride partials; stage 2: one wave.
-// likelihoods: `first` + i * stride floats -- the likelihood.mean members of an attribute array (stride 9) or a dense weight vector
-// (stride 1: what the sharded filter's all-gather leaves on every rank); the summation order depends on n alone, so both forms of the
-// same n values give the same bits
-__global__ void __launch_bounds__(256) k_likelihood_stats_partial(const float* __restrict__ first, uint32_t stride, uint32_t n,
-                                                                  double* __restrict__ psum, float* __restrict__ pmax) {
-  __shared__ double s_sum[4];
-  __shared__ float s_max[4];
-  double sum = 0.0;
-  float mx = 0.0f;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float L = first[static_cast<size_t>(i) * stride];
-    sum += static_cast<double>(L);
-    mx = (L > mx) ? L : mx;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off);
-    const float o = __shfl_down(mx, off);
-    mx = (o > mx) ? o : mx;
-  }
-  if ((threadIdx.x & 63u) == 0u) { s_sum[threadIdx.x >> 6] = sum; s_max[threadIdx.x >> 6] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    psum[blockIdx.x] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-    pmax[blockIdx.x] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-  }
-}
-
-__global__ void __launch_bounds__(64) k_likelihood_stats_final(const double* __restrict__ psum, const float* __restrict__ pmax,
-                                                               uint32_t nblocks, float* __restrict__ out) {
-  double sum = 0.0;
-  float mx = 0.0f;
-  for (uint32_t i = threadIdx.x; i < nblocks; i += 64u) {
-    sum += psum[i];
-    mx = fmaxf(mx, pmax[i]);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_down(sum, off);
-    mx = fmaxf(mx, __shfl_down(mx, off));
-  }
-  if (threadIdx.x == 0) { out[0] = static_cast<float>(sum); out[1] = mx; }
-}
-
 // ---------------------------------------------------------------------------------------------
 // pose estimate of the particle cloud (RmclNode::estimateStats, rmcl_ros/src/nodes/rmcl_localization.cpp:642-731) as
 // three linear moment passes, so that it shards: every GPU reduces its block of the particles to <= 24 doubles and the
@@ -2046,15 +1749,8 @@ __global__ void __launch_bounds__(256) k_pose_moments(const xform* __restrict__ 
     } else {
       const double w = L / L_sum;
       const xform Td = xmul(Tmb, T);
-      // EulerAngles <- Quaternion (textbook ZYX extraction, as in k_gladiator_resample)
-      const quat qd = Td.R;
-      const float sinr_cosp = 2.0f * (qd.w * qd.x + qd.y * qd.z), cosr_cosp = 1.0f - 2.0f * (qd.x * qd.x + qd.y * qd.y);
-      const float sinp = 2.0f * (qd.w * qd.y - qd.z * qd.x);
-      const float siny_cosp = 2.0f * (qd.w * qd.z + qd.x * qd.y), cosy_cosp = 1.0f - 2.0f * (qd.y * qd.y + qd.z * qd.z);
-      const double d[6] = {Td.t.x, Td.t.y, Td.t.z,
-                           atan2(static_cast<double>(sinr_cosp), static_cast<double>(cosr_cosp)),
-                           (fabsf(sinp) >= 1.0f) ? copysign(3.14159265358979323846 / 2.0, static_cast<double>(sinp)) : asin(static_cast<double>(sinp)),
-                           atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp))};
+      double d[6] = {Td.t.x, Td.t.y, Td.t.z, 0.0, 0.0, 0.0};
+      quat_to_euler_f64(Td.R, d[3], d[4], d[5]);   // the angles in double, not rounded to float (pf_random.hip.h)
       int k = 0;
 #pragma unroll
       for (int a = 0; a < 6; ++a)
@@ -2876,86 +2572,10 @@ hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* 
   return hipGetLastError();
 }
 
-hipError_t launch_pf_extract_weights(const void* attrs, uint32_t n, float* weights, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pf_extract_weights, dim3((n + 255u) / 256u), dim3(256), 0, s,
-                     reinterpret_cast<const pattrs*>(attrs), n, weights);
-  return hipGetLastError();
-}
-
-hipError_t launch_gladiator_resample(const xform* poses, const void* attrs, uint32_t n, xform* poses_new, void* attrs_new,
-                                     uint32_t first, uint32_t count, const float* cfg8, uint32_t trans_dist_metric,
-                                     uint64_t seed, uint32_t step, hipStream_t s) {
-  if (count == 0) return hipSuccess;
-  GladiatorConfig c{cfg8[0], cfg8[1], cfg8[2], cfg8[3], cfg8[4], cfg8[5], cfg8[6], cfg8[7], trans_dist_metric};
-  hipLaunchKernelGGL(k_gladiator_resample, dim3((count + 255u) / 256u), dim3(256), 0, s, poses,
-                     reinterpret_cast<const pattrs*>(attrs), n, poses_new, reinterpret_cast<pattrs*>(attrs_new), first,
-                     count, c, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), step);
-  return hipGetLastError();
-}
-
-// residual resampling, step 1: {sum, max} in double + the expected number of copies per draw (x n) -> *stats (device)
-hipError_t launch_residual_prepare(const void* attrs, uint32_t n, uint32_t n_new, double* psum, float* pmax, void* stats, hipStream_t s) {
-  uint32_t nblocks = (n + 1023u) / 1024u;
-  if (nblocks < 1u) nblocks = 1u;
-  if (nblocks > 256u) nblocks = 256u;
-  hipLaunchKernelGGL(k_likelihood_stats_partial, dim3(nblocks), dim3(256), 0, s, reinterpret_cast<const float*>(attrs), 9u, n, psum, pmax);
-  hipLaunchKernelGGL(k_residual_stats_final, dim3(1), dim3(64), 0, s, psum, pmax, nblocks, reinterpret_cast<ResidualStats*>(stats));
-  hipLaunchKernelGGL(k_residual_expect, dim3(nblocks), dim3(256), 0, s, reinterpret_cast<const pattrs*>(attrs), n, n_new,
-                     reinterpret_cast<ResidualStats*>(stats));
-  return hipGetLastError();
-}
-
-// step 2: the particle and the copy count of draws 0 .. n_draws-1 and the inclusive prefix sums of the counts
-hipError_t launch_residual_draws(const void* attrs, uint32_t n, uint32_t n_new, const void* stats, uint32_t n_draws, uint64_t seed,
-                                 uint32_t step, uint32_t* draw_idx, uint32_t* draw_cnt, unsigned long long* incl,
-                                 unsigned long long* block_tot, hipStream_t s) {
-  if (n_draws == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_residual_counts, dim3((n_draws + 255u) / 256u), dim3(256), 0, s, reinterpret_cast<const pattrs*>(attrs), n, n_new,
-                     reinterpret_cast<const ResidualStats*>(stats), n_draws, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
-                     step, draw_idx, draw_cnt);
-  const uint32_t nb = (n_draws + 1023u) / 1024u;
-  hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(256), 0, s, draw_cnt, n_draws, incl, block_tot);
-  hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(256), 0, s, block_tot, nb);
-  hipLaunchKernelGGL(k_scan_add, dim3((n_draws + 255u) / 256u), dim3(256), 0, s, incl, n_draws, block_tot);
-  return hipGetLastError();
-}
-
-// step 3: slots first .. first+count-1 of the new cloud -> poses_new / attrs_new [0 .. count)
-hipError_t launch_residual_fill(const xform* poses, const void* attrs, const uint32_t* draw_idx, const unsigned long long* incl,
-                                uint32_t n_draws, xform* poses_new, void* attrs_new, uint32_t n_new, uint32_t first, uint32_t count,
-                                const float* cfg8, void* stats, uint64_t seed, uint32_t step, hipStream_t s) {
-  if (count == 0) return hipSuccess;
-  GladiatorConfig c{cfg8[0], cfg8[1], cfg8[2], cfg8[3], cfg8[4], cfg8[5], cfg8[6], cfg8[7], 1u};
-  hipLaunchKernelGGL(k_residual_fill, dim3((count + 255u) / 256u), dim3(256), 0, s, poses, reinterpret_cast<const pattrs*>(attrs), draw_idx,
-                     incl, n_draws, poses_new, reinterpret_cast<pattrs*>(attrs_new), n_new, first, count, c,
-                     reinterpret_cast<ResidualStats*>(stats), static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), step);
-  return hipGetLastError();
-}
-
 hipError_t launch_build_cnodes16(const uint32_t* cnodes, uint32_t n_nodes, uint32_t* cnodes16, hipStream_t s) {
   if (n_nodes == 0u) return hipSuccess;
   const uint32_t nb = (n_nodes * 16u + 255u) / 256u;
   hipLaunchKernelGGL(k_build_cnodes16, dim3(nb), dim3(256), 0, s, reinterpret_cast<const uint4*>(cnodes), n_nodes, reinterpret_cast<uint4*>(cnodes16));
-  return hipGetLastError();
-}
-
-hipError_t launch_likelihood_stats(const void* attrs, uint32_t n, double* psum, float* pmax, float* out2, hipStream_t s) {
-  uint32_t nblocks = (n + 1023u) / 1024u;
-  if (nblocks < 1u) nblocks = 1u;
-  if (nblocks > 256u) nblocks = 256u;
-  static_assert(sizeof(pattrs) == 36 && offsetof(pattrs, likelihood) == 0, "likelihood.mean is the first float of a 9-float record");
-  hipLaunchKernelGGL(k_likelihood_stats_partial, dim3(nblocks), dim3(256), 0, s, reinterpret_cast<const float*>(attrs), 9u, n, psum, pmax);
-  hipLaunchKernelGGL(k_likelihood_stats_final, dim3(1), dim3(64), 0, s, psum, pmax, nblocks, out2);
-  return hipGetLastError();
-}
-
-hipError_t launch_likelihood_stats_dense(const float* weights, uint32_t n, double* psum, float* pmax, float* out2, hipStream_t s) {
-  uint32_t nblocks = (n + 1023u) / 1024u;   // the rule of launch_likelihood_stats: same blocks, same order, same bits
-  if (nblocks < 1u) nblocks = 1u;
-  if (nblocks > 256u) nblocks = 256u;
-  hipLaunchKernelGGL(k_likelihood_stats_partial, dim3(nblocks), dim3(256), 0, s, weights, 1u, n, psum, pmax);
-  hipLaunchKernelGGL(k_likelihood_stats_final, dim3(1), dim3(64), 0, s, psum, pmax, nblocks, out2);
   return hipGetLastError();
 }
 
@@ -2974,9 +2594,7 @@ hipError_t launch_pointcloud2_unpack(const uint8_t* data, uint32_t point_step, u
 
 hipError_t launch_pose_moments(const xform* poses, const void* attrs, uint32_t n, int pass, double L_sum, xform Tbm,
                                double* partials, double* out32, hipStream_t s, const uint32_t* labels, uint32_t want) {
-  uint32_t nblocks = (n + 1023u) / 1024u;
-  if (nblocks < 1u) nblocks = 1u;
-  if (nblocks > 256u) nblocks = 256u;
+  const uint32_t nblocks = partial_blocks(n);
   hipLaunchKernelGGL(k_pose_moments, dim3(nblocks), dim3(256), 0, s, poses, reinterpret_cast<const pattrs*>(attrs), n, pass, L_sum, Tbm,
                      partials, labels, want);
   hipLaunchKernelGGL(k_pose_moments_final, dim3(1), dim3(256), 0, s, partials, nblocks, out32);

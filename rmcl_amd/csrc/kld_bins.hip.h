@@ -1,5 +1,6 @@
 // kld_bins.hip.h -- the bin of a particle (include/rmclhip.h, BINS) as device code: ONE statement of the key rule for the kernel that
-// fills the table of occupied bins (adaptive.hip) and the kernels that read it back (hypotheses.hip).
+// fills the table of occupied bins (adaptive.hip) and the kernels that read it back (hypotheses.hip); pattr36, the particle
+// attributes as these files and the resamplers (resample.hip) read them.
 //   key   63 bits: x | y << 14 | z << 28 (14 bits each, index + 8192) | roll << 42 | pitch << 49 | yaw << 56 (7 bits each)
 //   table open addressing over 64-bit words, linear probing from mix64(key) & mask, kEmptySlot where nothing was stored
 #pragma once
@@ -50,7 +51,7 @@ __device__ __forceinline__ bool kld_particle_key(const xform& T, float L, const 
   return counted;
 }
 
-// the systematic resampler's integer weight
+// the systematic resampler's integer weight (resample.hip); a hypothesis weighs the sum of its particles' (hypotheses.hip)
 __device__ __forceinline__ unsigned long long sys_weight(float L, double max_l) {
   if (!finite_f(L) || !(L > 0.0f)) return 0ull;
   return static_cast<unsigned long long>(rint((static_cast<double>(L) / max_l) * 16777216.0));

@@ -1,5 +1,5 @@
 // pf_random.hip.h -- the counter-based random stream of the particle filter and the Euler -> quaternion step its draws end in, shared
-// by the resamplers (kernels.hip) and the cloud initialisation (particles.hip): ONE text, so that a particle drawn by either is the
+// by the resamplers (resample.hip) and the cloud initialisation (particles.hip): ONE text, so that a particle drawn by either is the
 // same function of (seed, counter) down to the bit.  Device code only.
 //
 // Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
@@ -46,25 +46,40 @@ __device__ __forceinline__ quat euler_to_quat(float roll, float pitch, float yaw
   return q;
 }
 
-// rmagine EulerAngles <- Quaternion (textbook ZYX extraction): float products, atan2 / asin in double, rounded to float -- the
-// statement k_gladiator_resample, k_residual_fill and the pose moments carry inline
+// rmagine EulerAngles <- Quaternion (textbook ZYX extraction): the float products ...
+struct euler_terms { float sinr_cosp, cosr_cosp, sinp, siny_cosp, cosy_cosp; };
+__device__ __forceinline__ euler_terms quat_euler_terms(quat q) {
+  euler_terms e;
+  e.sinr_cosp = 2.0f * (q.w * q.x + q.y * q.z);
+  e.cosr_cosp = 1.0f - 2.0f * (q.x * q.x + q.y * q.y);
+  e.sinp = 2.0f * (q.w * q.y - q.z * q.x);
+  e.siny_cosp = 2.0f * (q.w * q.z + q.x * q.y);
+  e.cosy_cosp = 1.0f - 2.0f * (q.y * q.y + q.z * q.z);
+  return e;
+}
+
+// ... and atan2 / asin of them in double, rounded to float
 __device__ __forceinline__ void quat_to_euler(quat q, float& roll, float& pitch, float& yaw) {
-  const float sinr_cosp = 2.0f * (q.w * q.x + q.y * q.z);
-  const float cosr_cosp = 1.0f - 2.0f * (q.x * q.x + q.y * q.y);
-  const float sinp = 2.0f * (q.w * q.y - q.z * q.x);
-  const float siny_cosp = 2.0f * (q.w * q.z + q.x * q.y);
-  const float cosy_cosp = 1.0f - 2.0f * (q.y * q.y + q.z * q.z);
-  roll = static_cast<float>(atan2(static_cast<double>(sinr_cosp), static_cast<double>(cosr_cosp)));
-  pitch = (fabsf(sinp) >= 1.0f) ? copysignf(static_cast<float>(3.14159265358979323846 / 2.0), sinp)
-                                : static_cast<float>(asin(static_cast<double>(sinp)));
-  yaw = static_cast<float>(atan2(static_cast<double>(siny_cosp), static_cast<double>(cosy_cosp)));
+  const euler_terms e = quat_euler_terms(q);
+  roll = static_cast<float>(atan2(static_cast<double>(e.sinr_cosp), static_cast<double>(e.cosr_cosp)));
+  pitch = (fabsf(e.sinp) >= 1.0f) ? copysignf(static_cast<float>(3.14159265358979323846 / 2.0), e.sinp)
+                                  : static_cast<float>(asin(static_cast<double>(e.sinp)));
+  yaw = static_cast<float>(atan2(static_cast<double>(e.siny_cosp), static_cast<double>(e.cosy_cosp)));
+}
+
+// the same angles NOT rounded to float: what the pose moments sum (kernels.hip: k_pose_moments)
+__device__ __forceinline__ void quat_to_euler_f64(quat q, double& roll, double& pitch, double& yaw) {
+  const euler_terms e = quat_euler_terms(q);
+  roll = atan2(static_cast<double>(e.sinr_cosp), static_cast<double>(e.cosr_cosp));
+  pitch = (fabsf(e.sinp) >= 1.0f) ? copysign(3.14159265358979323846 / 2.0, static_cast<double>(e.sinp)) : asin(static_cast<double>(e.sinp));
+  yaw = atan2(static_cast<double>(e.siny_cosp), static_cast<double>(e.cosy_cosp));
 }
 
 // n_meas after a resampler forgets: uint32(float(n_meas) * rate), the reference's statement (resampling.cu:188), with the
 // conversion written out -- C++ leaves a float -> uint32 conversion of NaN, of a negative value or of one >= 2^32 undefined, and
 // float(n_meas) IS 2^32 for every n_meas >= 2^32 - 128.  The rule (what the CUDA reference's conversion instruction does; its x86
 // CPU resamplers are undefined here): NaN or <= 0 -> 0; >= 2^32 -> 0xFFFFFFFF; otherwise truncate.  Used by k_gladiator_resample,
-// k_residual_fill (kernels.hip) and k_sys_fill (adaptive.hip); oracle/rmcl_oracle.c: orc_n_meas_scaled pins the same text.
+// k_residual_fill and k_sys_fill (resample.hip); oracle/rmcl_oracle.c: orc_n_meas_scaled pins the same text.
 __host__ __device__ __forceinline__ uint32_t n_meas_scaled(uint32_t n_meas, float rate) {
   const float v = static_cast<float>(n_meas) * rate;
   if (!(v > 0.0f)) return 0u;

@@ -1,5 +1,5 @@
-"""Host restatement (numpy only) of the adaptive particle count -- what rmcl_amd/csrc/adaptive.hip and rmclhip_kld_bound_host compute,
-operation by operation in their order (include/rmclhip.h states the rules):
+"""Host restatement (numpy only) of the adaptive particle count -- what rmcl_amd/csrc/adaptive.hip (the bins), resample.hip (the
+systematic resampler) and rmclhip_kld_bound_host compute, operation by operation in their order (include/rmclhip.h states the rules):
 
     quat_to_euler        the textbook ZYX extraction: float products, atan2 / asin in double, rounded to float
     likelihood_max       the maximum rmclhip_resampler_compute_stats returns (seeded with 0, NaN never taken)
@@ -199,7 +199,7 @@ def n_meas_scaled(n_meas, rate):
 
 
 def perturb(poses, attrs, slots, cfg, seed, step):
-    """the gladiator's winning enemy (kernels.hip: k_gladiator_resample) with the Gaussians of the GLOBAL slot indices `slots` from
+    """the gladiator's winning enemy (resample.hip: k_gladiator_resample) with the Gaussians of the GLOBAL slot indices `slots` from
     draws 6 and 7; poses / attrs: the sources, one per slot"""
     a, b = _words(slots, step, 6, seed), _words(slots, step, 7, seed)
     Nd_tx, Nd_ty = box_muller(a[:, 1], a[:, 2])

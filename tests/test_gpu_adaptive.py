@@ -1,4 +1,4 @@
-"""GPU tests of the adaptive particle count (rmcl_amd/csrc/adaptive.hip) against the numpy restatement tests/adaptive_ref.py:
+"""GPU tests of the adaptive particle count (rmcl_amd/csrc/adaptive.hip, resample.hip) against the numpy restatement tests/adaptive_ref.py:
 occupied bins (k and the counted particles exact), systematic resampling to any size (sources and attributes byte-identical,
 perturbed poses within the 1e-6 the other resamplers' tests allow), and the one call a Resampler plugin makes."""
 import math

@@ -293,7 +293,7 @@ def test_bad_configs_are_refused_by_every_resampler(ra, orc, ctx, meshes):
 
 
 def test_systematic_fill_uses_the_pinned_conversion(ra, ctx):
-    """the third site of the conversion (adaptive.hip: k_sys_fill) on the n_meas edges, against tests/adaptive_ref.py"""
+    """the third site of the conversion (resample.hip: k_sys_fill) on the n_meas edges, against tests/adaptive_ref.py"""
     import adaptive_ref as ar
     from rmcl_amd import types as T
     c = rc.tournament_case("n_meas_edges")
