@@ -45,7 +45,7 @@ rmclhip_status rmclhip_debug_surface_faces(rmclhip_pf* pf, uint32_t* faces_dev);
 rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* rcc, const rmclhip_transform* Tbm_est, uint32_t* out, size_t cap_dwords,
                                         uint32_t* n_waves_out);
 /* the moments the LAST moment-form attempt of rmclhip_rcc_correct_once worked from (rmclhip.h: rmclhip_rcc_set_micp_fast): the 96 sums
- * of its partial rows (82 used; layout in kernels.hip) and the number of correspondences it left undecided.  Works without the
+ * of its partial rows (82 used; layout in reduce_common.hip.h) and the number of correspondences it left undecided.  Works without the
  * experiments library. */
 rmclhip_status rmclhip_debug_micp_moments(rmclhip_rcc* rcc, double* totals96, uint32_t* n_rows_out, uint64_t* n_uncertain_out);
 /* tools/probe_find.py: one spherical find() through an instrumented copy of the one-lane-per-ray traversal that stamps

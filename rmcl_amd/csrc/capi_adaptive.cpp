@@ -1,7 +1,7 @@
 // capi_adaptive.cpp -- see capi_internal.h
 #include "capi_internal.h"
 
-// ---- a particle count that follows the posterior (include/rmclhip.h states the rules; adaptive.hip implements them) ----
+// ---- a particle count that follows the posterior (include/rmclhip.h states the rules; adaptive.hip and resample.hip implement them) ----
 void rmclhip_kld_params_default(rmclhip_kld_params* out) {
   if (!out) return;
   std::memset(out, 0, sizeof(*out));

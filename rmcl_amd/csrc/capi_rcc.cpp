@@ -749,8 +749,8 @@ RMCL_INTERNAL rmclhip_status reduce_enqueue(rmclhip_rcc* r, const xform& Tpre, c
   return RMCLHIP_OK;
 }
 
-// Wait for the completion tag the LAST kernel of a chain stores in host-mapped memory after its results (kernels.hip
-// publish_tag), instead of hipStreamSynchronize: the tag arrives ~9 us before the stream's completion signal has made its way
+// Wait for the completion tag the LAST kernel of a chain stores in host-mapped memory after its results
+// (reduce_common.hip.h publish_tag), instead of hipStreamSynchronize: the tag arrives ~9 us before the stream's completion signal has made its way
 // through the runtime (measured on the MICP loop: 84 -> 75 us per correction).
 // The tag carries {sequence number of the call, xor of every result word}: the result is accepted only when the sequence number is
 // this call's AND the words the host reads add up to the tag's sum; otherwise polling continues.  (Round 2 polled a flag of constant
@@ -809,7 +809,7 @@ static float adaptive_max_dist(const rmclhip_rcc* r, double p) {
                             static_cast<double>(r->adaptive_max_dist_min) * p);
 }
 
-// ---- the gate-stable moments on the host (micp_host.h; kernels.hip k_micp_publish) -----------------------------------------------
+// ---- the gate-stable moments on the host (micp_host.h; micp.hip k_micp_publish) -----------------------------------------------
 // The band of max_dist' values a speculating find classifies for: max_dist' = max_dist (1 - p) + adaptive_max_dist_min p moves with
 // the node's convergence_progress_ from one correction to the next (micp_localization.cpp:988-1007), the find does not know the
 // next value, so it takes +-8 % around the last one, clipped to what the two parameters allow.  A max_dist' outside the band
@@ -880,6 +880,32 @@ static inline void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau) {
   r->fast_info.tau_cap = r->fast_tau_cap;
 }
 
+// Arms the moment epilogue of the find `fp` of kind `fv` (23, 32 or 2): one partial row per workgroup (*nb of them) and *wpb mask words
+// per workgroup, the gate band and the caps the rows are good for, and -- allocated and zeroed once per handle -- the area through
+// which the workgroups of the fold hand their sums over (micp.hip fold_hand_over_row)
+static rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp, int fv, uint32_t nred, float lo, float hi, float rho_cap, float tau_cap,
+                                          uint32_t* nb_out, uint32_t* wpb_out) {
+  const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;
+  HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
+  HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
+  fp.mom_dataset_points = r->ds_pts;
+  fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
+  fp.mom_n = nred;
+  fp.mom_gate_lo = lo; fp.mom_gate_hi = hi; fp.mom_rho_cap = rho_cap; fp.mom_tau_cap = tau_cap;
+  fp.mom_partials = r->d_fast_partials.p;
+  fp.mom_unc_mask = r->d_fast_mask.p;
+  if (!r->d_fold_rows) {
+    const size_t bytes = kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), bytes));
+    HIPCHK(hipMemset(r->d_fold_rows, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
+  }
+  r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
+  *nb_out = nb; *wpb_out = wpb;
+  return RMCLHIP_OK;
+}
+
 // find + moment epilogue + publish on the handle's stream (kinds 23 / 2), or find + moment pass + publish (any other kind);
 // the caller waits with wait_moments(seq, ...)
 static rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap, uint32_t seq,
@@ -896,22 +922,8 @@ static rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm
   r->last_moment_find_kind = fv;
   r->last_moment_find_tiled = epilogue_allowed && (fv == 23 || fv == 32 || fv == 2);
   if (epilogue_allowed && (fv == 23 || fv == 32 || fv == 2)) {
-    const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;   // mask words per workgroup
-    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
-    HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
-    fp.mom_dataset_points = r->ds_pts;
-    fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-    fp.mom_n = nred;
-    fp.mom_gate_lo = lo; fp.mom_gate_hi = hi; fp.mom_rho_cap = rho_cap; fp.mom_tau_cap = tau_cap;
-    fp.mom_partials = r->d_fast_partials.p;
-    fp.mom_unc_mask = r->d_fast_mask.p;
-    if (!r->d_fold_rows) {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-      HIPCHK(hipMemset(r->d_fold_rows, 0, kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-      HIPCHK(hipDeviceSynchronize());
-      r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
-    }
-    r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
+    uint32_t nb, wpb;
+    if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, lo, hi, rho_cap, tau_cap, &nb, &wpb)) return st;
     HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
     HIPCHK(launch_micp_publish_tiled(r->ds_pts, r->d_points.p, r->d_normals.p, nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W,
                                      fp.tiles_x, fp.tile_w_log2, wpb, r->h_mom_dev, r->h_done_dev, seq, r->d_fold_rows, r->d_fold_flags,
@@ -1204,7 +1216,7 @@ static void micp_caps_after_fallback(rmclhip_rcc* r, const xform& Ts, bool overf
   r->fast_info.tau_cap = r->fast_tau_cap;
 }
 
-// Moment form (kernels.hip "gate-stable moment form"), fast modes 1, 3 and 4, launched directly with the per-call data BY VALUE -- no
+// Moment form (micp.hip "gate-stable moment form"), fast modes 1, 3 and 4, launched directly with the per-call data BY VALUE -- no
 // H2D copy node, no graph launch (a graph replay costs the host 10-16 us whatever it holds).  *out: code 0 = served, the correction
 // is in r->h_state; 1 / 2 = the caller runs the per-iteration form, which recomputes the correction from scratch.
 static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uint32_t n_iter, float maxd, uint32_t nred,
@@ -1238,10 +1250,10 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
         fs.max_tau = std::max(fs.max_tau, tau);
         if (!(rho <= r->mset.rho_cap) || !(tau <= r->mset.tau_cap)) { fs.code = 1u; fs.iter = it; break; }
         last = micp_statistics_from_set(r->mset, T_s, maxd);
-        T_s = xmul(T_s, umeyama(last));   // kernels.hip micp_advance_sensor
+        T_s = xmul(T_s, umeyama(last));   // micp.hip micp_advance_sensor
       }
       if (fs.code == 0u) {
-        // kernels.hip micp_close_sensor
+        // micp.hip micp_close_sensor
         fs.iter = n_iter;
         const xform Tso = xmul(Tbo, r->Tsb);
         r->h_state->T_snew_sold = T_s;
@@ -1272,22 +1284,8 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
     // (fast_mode 4, round 3's default) TWO kernels: the find forms the moments in its epilogue (find_kernel.hip.h: the 10 x 10 factor
     // products of its 64 correspondences per wave through f64 MFMA), one partial row per workgroup; the loop launch folds them and runs
     // every iteration on the device
-    const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;   // partial rows, mask words per workgroup
-    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
-    HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
-    fp.mom_dataset_points = r->ds_pts;
-    fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-    fp.mom_n = nred;
-    fp.mom_gate_lo = maxd; fp.mom_gate_hi = maxd; fp.mom_rho_cap = r->fast_rho_cap; fp.mom_tau_cap = r->fast_tau_cap;
-    fp.mom_partials = r->d_fast_partials.p;
-    fp.mom_unc_mask = r->d_fast_mask.p;
-    if (!r->d_fold_rows) {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-      HIPCHK(hipMemset(r->d_fold_rows, 0, kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t)));
-      HIPCHK(hipDeviceSynchronize());
-      r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
-    }
-    r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
+    uint32_t nb, wpb;
+    if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, &nb, &wpb)) return st;
     HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
     HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
                                        nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter,
@@ -1531,7 +1529,7 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
   MicpMultiCall* d_call = reinterpret_cast<MicpMultiCall*>(r0->d_multi_blob.p);
   MicpMultiState* d_state = reinterpret_cast<MicpMultiState*>(r0->d_multi_blob.p + sizeof(MicpMultiCall));
   hipError_t e = hipSuccess;
-  // ---- moment form first (kernels.hip k_micp_multi_fast_loop): every sensor's caps are the ones its own corrections learnt
+  // ---- moment form first (micp.hip k_micp_multi_fast_loop): every sensor's caps are the ones its own corrections learnt
   bool fast_eligible = n_iter >= 2u;
   for (uint32_t s = 0; s < n_sensors; ++s) fast_eligible = fast_eligible && sensors[s]->fast_mode != 0;
   bool fast_tried = false;

@@ -478,7 +478,7 @@ RM_HD xform umeyama(const cstats& s) {
 }
 
 
-// ---- gate-stable moment form of the MICP iterations (kernels.hip k_micp_moments, find_kernel.hip.h find_moments_wave, and the
+// ---- gate-stable moment form of the MICP iterations (micp.hip k_micp_moments, find_kernel.hip.h find_moments_wave, and the
 // host's evaluation in micp_host.h): classification of one correspondence at the identity pre-transform.  spd0 = (I - D) . N is
 // the reduction's own gate value, nd = |D|.  While the pre-transform stays within (rho_cap = |2 sin(theta/2)|, tau_cap = |t|) the
 // dataset point moves by at most rho_cap nd + tau_cap, and so does the gate value (|N| = 1; the 1e-4 (1 + nd) covers the f32

@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) k_tile_planes(const FindParams p, float* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// MICP moment epilogue of k_find (kMoments; launch_find_moments).  The gate-stable moment form (kernels.hip k_micp_moments) needs,
+// MICP moment epilogue of k_find (kMoments; launch_find_moments).  The gate-stable moment form (micp.hip k_micp_moments) needs,
 // per correspondence that is certainly gated in, the 82 sums  sum X_a Y_b  of the factor vectors
 //   X = (N0N0, N0N1, N0N2, N1N1, N1N2, N2N2 | 1 | sN0, sN1, sN2)      s = N . I
 //   Y = (1 | D0, D1, D2 | D0D0, D0D1, D0D2, D1D1, D1D2, D2D2)

@@ -1,4 +1,4 @@
-// kernels.h -- launch interface between the C ABI (capi_*.cpp) and the HIP kernels (kernels.hip).
+// kernels.h -- launch interface between the C ABI (capi_*.cpp) and the HIP kernels (kernels.hip, micp.hip and the other *.hip files).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,7 +65,7 @@ struct FindParams {
   uint32_t xcd_mapping;    // single scans: 0 = workgroup b computes tiles 4b.. (every XCD sees all of the image), 1 = an eighth of the image per XCD, 2 = a CU's two workgroups from the image's two halves (find_kernel.hip.h)   // workgroups of consecutive slots one XCD takes before the next XCD's turn (load balance across the XCDs)
   // diagnostics (nullable): per physical wave {s_memtime at entry, at exit (low 32 bits), s_memrealtime at entry, tile | xcc << 24}
   uint32_t* wave_clock;
-  // MICP moment epilogue (launch_find_moments, k_find<..., kMom = true>): the moments of the gate-stable form (kernels.hip) are
+  // MICP moment epilogue (launch_find_moments, k_find<..., kMom = true>): the moments of the gate-stable form (micp.hip) are
   // formed while the correspondences are still in registers -- classification as in k_micp_moments, the 10 x 10 products
   // X^T Y of the factor vectors through v_mfma_f64_16x16x4_f64 -- instead of a second pass over the find's outputs
   const float* mom_dataset_points;
@@ -165,7 +165,7 @@ struct MicpState {
   cstats stats_o;                // last merged statistics, odom frame
 };
 
-// moment form of the schedule-(R) loop (kernels.hip: "gate-stable moment form"): one streaming pass + one single-workgroup
+// moment form of the schedule-(R) loop (micp.hip: "gate-stable moment form"): one streaming pass + one single-workgroup
 // launch for all iterations.  status->code: 0 = done (state_out valid), 1 = a pre-transform left (rho_cap, tau_cap) at
 // iteration `iter`, 2 = more than 4096 uncertain correspondences; for 1 and 2 the caller runs the per-iteration form.
 struct MicpFastStatus { uint32_t code, iter, n_uncertain; float max_rho, max_tau; uint32_t pad[3]; };
@@ -241,7 +241,7 @@ struct MicpMultiFastParams {
   uint32_t n_iter;
   MicpMultiState* state_out;                              // may be host-mapped
   MicpMultiFastStatus* status;                            // may be host-mapped
-  unsigned long long* done;                               // host-mapped completion tag (see kernels.hip publish_tag)
+  unsigned long long* done;                               // host-mapped completion tag (see reduce_common.hip.h publish_tag)
   // sensors whose find + moment pass ran on ANOTHER stream (bit s of join_mask): the loop waits for join_flags[s] == seq before it
   // touches sensor s's rows -- an in-kernel wait of ~1 us where a cross-stream event takes ~10 us to reach the waiting queue
   const uint32_t* join_flags;
@@ -320,11 +320,11 @@ uint32_t reduce_num_blocks(uint32_t n, uint32_t nposes);
 hipError_t launch_reduce_partials(const ReduceParams& p, hipStream_t s);
 // finalize one pose's partials into CrossStatistics (writes to out, which may be host-mapped memory)
 // done (nullable, host-mapped, single pose only): completion tag {seq, xor of the 16 result words}, one 8-byte store after
-// `out` (kernels.hip publish_tag): the host polls the tag and VERIFIES the sum -- a flag alone is not enough, see capi_rcc.cpp wait_done
+// `out` (reduce_common.hip.h publish_tag): the host polls the tag and VERIFIES the sum -- a flag alone is not enough, see capi_rcc.cpp wait_done
 hipError_t launch_reduce_finalize(const double* partials, uint32_t nblocks, uint32_t nposes, cstats* out,
                                   unsigned long long* done, uint32_t seq, hipStream_t s);
 // closing launch of the launch_micp_iter chain: solve of the last iteration + T_onew_oold / stats_o (the chain itself works in
-// the sensor frame, kernels.hip micp_advance_sensor)
+// the sensor frame, micp.hip micp_advance_sensor)
 // done (nullable, host-mapped): completion tag {call->seq, xor of the state's words}, stored after the results
 hipError_t launch_micp_close(const double* partials, uint32_t nblocks, const MicpCall* call, const MicpState* state,
                              MicpState* state_out, unsigned long long* done, hipStream_t s);

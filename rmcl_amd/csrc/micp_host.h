@@ -5,12 +5,12 @@
 //   D' = R D + t;  dist = N . I - N . D';  M = D' + N dist;  keep iff |dist| < max_dist.
 // For the correspondences whose gate decision cannot change (devmath.h micp_gate_class == 1) the 16 raw sums of the reduction
 // (sum D', sum M, sum M D'^T, n) are polynomials in (R, t) whose coefficients are 82 moments of (D, N, s = N . I); the device
-// forms them once per find (find_kernel.hip.h find_moments_wave / kernels.hip k_micp_moments), folds them and hands them to the
+// forms them once per find (find_kernel.hip.h find_moments_wave / micp.hip k_micp_moments), folds them and hands them to the
 // host together with the few undecided correspondences (k_micp_publish).  An iteration is then O(1): ~1.5 k flops here instead of
 // a 131 072-element streaming reduce plus a launch and a completion wait (or, in the device loop of round 3, ~4.4 k cycles of
 // ONE lane's dependent f64 chain).
 //
-// Moment row layout (kernels.hip kMom):  n | D[3] | DD[6] | sN[3] | sND[9] | NN[6] | NND[18] | NNDD[36],  symmetric pairs in
+// Moment row layout (reduce_common.hip.h kMom):  n | D[3] | DD[6] | sN[3] | sND[9] | NN[6] | NND[18] | NNDD[36],  symmetric pairs in
 // the order 00 01 02 11 12 22.
 #pragma once
 #include <cstdint>
@@ -68,8 +68,8 @@ inline const double* mh_Q(const double* mom, int x) { return x < 6 ? mom + 46 + 
 inline const double* mh_P(const double* mom, int x) { return x < 6 ? mom + 28 + 3 * x : (x == 6 ? mom + 1 : mom + 13 + 3 * (x - 7)); }
 inline double mh_W(const double* mom, int x) { return x < 6 ? mom[22 + x] : (x == 6 ? mom[0] : mom[10 + (x - 7)]); }
 
-// linear map of qrot (q v q*) in double from the f32 components (as k_micp_fast_loop forms it)
-inline void micp_rotation_f64(const quat& q, double* R) {
+// linear map of qrot (q v q*) in double from the f32 components (micp.hip's loops form it with this text too)
+RM_HD void micp_rotation_f64(const quat& q, double* R) {
   const double x = q.x, y = q.y, z = q.z, w = q.w;
   const double ww = w * w, uu = (x * x + y * y) + z * z;
   R[0] = (ww - uu) + 2.0 * x * x; R[1] = 2.0 * (x * y - w * z);   R[2] = 2.0 * (x * z + w * y);
@@ -121,7 +121,7 @@ inline void micp_moment_sums(const double* mom, const double* R, const double* t
   out[15] = n;
 }
 
-// The undecided correspondences with the reduction's own f32 arithmetic (kernels.hip k_reduce_partials / k_micp_iter: xapply = the two
+// The undecided correspondences with the reduction's own f32 arithmetic (reduce_common.hip.h p2l_accumulate: xapply = the two
 // quaternion products of devmath.h qrot, rmagine's dot, the gate |dist| < max_dist), f64 sums.  Order of the sums: eight interleaved
 // partial sums (element e goes to lane e % 8), folded ((0+1)+(2+3))+((4+5)+(6+7)) at the end -- the shape of one AVX2 register, so the
 // same routine compiles to vector code where the CPU has it and to the identical arithmetic, lane by lane, where it has not: results
@@ -201,7 +201,7 @@ inline void micp_undecided_sums(const float (*unc)[kMicpUncPadded], uint32_t n_u
   micp_simd::body(unc, n_unc, Tpre, max_dist, acc);
 }
 
-// raw sums -> CrossStatistics (kernels.hip finalize_pose: IEEE divisions)
+// raw sums -> CrossStatistics (reduce_common.hip.h finalize_pose: IEEE divisions)
 inline cstats micp_stats_from_sums(const double* acc) {
   cstats s = cs_identity();
   const double n = acc[15];
@@ -221,8 +221,8 @@ inline cstats micp_stats_from_sums(const double* acc) {
   return s;
 }
 
-inline float micp_rho(const xform& T) { return 2.0f * sqrtf((T.R.x * T.R.x + T.R.y * T.R.y) + T.R.z * T.R.z); }
-inline float micp_tau(const xform& T) { return sqrtf(dot_plain(T.t, T.t)); }
+RM_HD float micp_rho(const xform& T) { return 2.0f * sqrtf((T.R.x * T.R.x + T.R.y * T.R.y) + T.R.z * T.R.z); }
+RM_HD float micp_tau(const xform& T) { return sqrtf(dot_plain(T.t, T.t)); }
 
 // is this set an exact summary for (pre-transform, max_dist)?
 inline bool micp_set_covers(const MicpMomentSet& ms, const xform& Tpre, float max_dist) {

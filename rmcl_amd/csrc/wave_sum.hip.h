@@ -1,5 +1,5 @@
 // wave_sum.hip.h -- wave64 sums of per-lane double accumulators through LDS, shared by the streaming reductions
-// (kernels.hip k_reduce_partials / k_micp_iter, pose_information.hip).
+// (kernels.hip k_reduce_partials, micp.hip k_micp_iter, pose_information.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

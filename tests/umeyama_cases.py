@@ -1,7 +1,7 @@
 """Inputs of the rotation solve (rm::umeyama_transform) where it can go wrong, shared by the CPU and the GPU tests, and its
 third, independent statement in float64 numpy.
 
-Three solvers serve the MICP correction: umeyama() of devmath.h (host and device), umeyama_fast() of kernels.hip (the moment-form
+Three solvers serve the MICP correction: umeyama() of devmath.h (host and device), umeyama_fast() of micp.hip (the moment-form
 loops) and the oracle's orc_umeyama_transform.  umeyama_ref() below is the definition they are all measured against:
 
     n_meas = 0                      identity transform
