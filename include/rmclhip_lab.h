@@ -59,7 +59,8 @@ rmclhip_status rmclhip_debug_probe_find(rmclhip_rcc* rcc, const rmclhip_transfor
  * frontier start with the descent's bookkeeping); bits 8..15 of max_levels, when not 0: kind 32's bound on the final leaves one ray may
  * enter before its wave starts at the root instead (default 24); bits 29..30, when not 0: 1 + the tile mapping of single scans (0 as
  * dealt, 1 an eighth of the image per XCD, 2 a CU's two workgroups from the image's halves; find_kernel.hip.h) instead of the tuned /
- * default one; bit 31 set: descend on the four-wide nodes even where the map carries the 16-wide twins (A/B).  Results do not depend on any of them.  Exported by librmclhip.so. */
+ * default one; bit 16 set: kind 32 keeps accepted candidates undivided through its cooperative leaf loop (rmclhip_rcc_autotune sets it
+ * where it measures faster; every call of this function sets or clears it); bit 31 set: descend on the four-wide nodes even where the map carries the 16-wide twins (A/B).  Results do not depend on any of them.  Exported by librmclhip.so. */
 rmclhip_status rmclhip_rcc_set_descent(rmclhip_rcc* rcc, uint32_t final_cap, uint32_t max_levels);
 
 /* A/B knob (round 6, VERDICT r5 #7b): pose batches in WORLD ORDER (the default; on = 0 restores the pose-major launch).  Every batch launch

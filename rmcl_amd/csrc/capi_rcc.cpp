@@ -445,7 +445,7 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
     // tree that leaves no room for even two starts every ray at the root.
     p.descent_final_cap = r->descent_final_cap;
     p.xcd_mapping = (r->xcd_mapping_override >= 0) ? static_cast<uint32_t>(r->xcd_mapping_override) : r->tuned_xcd_mapping;
-    p.descent_levels = (r->descent_levels & 0xFFu) | (r->descent_leaf_cap << 8);   // (traverse.hip.h frontier_descent_start: levels | most leaves per ray << 8)
+    p.descent_levels = (r->descent_levels & 0xFFu) | (r->descent_leaf_cap << 8) | (r->descent_carry ? 1u << 16 : 0u);   // (traverse.hip.h frontier_descent_start: levels | most leaves per ray << 8 | pending candidates << 16)
     p.frontier_max_preload = (need < 64u) ? 64u - need : 0u;
     if (p.frontier_max_preload < 2u) p.tile_planes = nullptr;
   }

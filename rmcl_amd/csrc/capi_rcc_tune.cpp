@@ -96,6 +96,19 @@ rmclhip_status rmclhip_rcc_autotune(rmclhip_rcc* r, const rmclhip_transform* Tbm
   }
   r->tuned_kind = best->kind; r->tuned_frontier = best->frontier;
   r->descent_final_cap = best->descent_cap != 0u ? best->descent_cap : saved_cap;
+  // ... kind 32: accepted candidates undivided through the cooperative leaf loop (traverse.hip.h TriPending) -- one division per ray
+  // instead of one per slot on maps whose rays have one hit (sphere-100k -2.4 %), a loss where candidates collide (room-100k +3 %)
+  r->descent_carry = false;
+  if (best->kind == 32) {
+    r->descent_carry = true;
+    float t[5];
+    for (float& x : t) {
+      if (rmclhip_status st = rmclhip_rcc_time_find(r, Tbm_est, 8, &x)) { r->descent_carry = false; return st; }
+    }
+    std::sort(t, t + 5);
+    if (t[2] < best_ms) best_ms = t[2];
+    else r->descent_carry = false;
+  }
   // ... then the tile shape of the winner (the rule: 16 wide x 4 tall; profiles/r03_find_tile_shapes.txt shows maps that prefer
   // 4 x 16 or 32 x 2): widths 4, 8, 32 where the image is tall enough, the plane table rebuilt for each
   if (r->tile_override == 0) {
@@ -283,6 +296,7 @@ rmclhip_status rmclhip_rcc_set_descent(rmclhip_rcc* r, uint32_t final_cap, uint3
   r->descent_final_cap = final_cap;
   r->descent_levels = max_levels & 0xFFu;
   if ((max_levels >> 8) & 0xFFu) r->descent_leaf_cap = (max_levels >> 8) & 0xFFu;   // bits 8..15 (A/B): kind 32's leaves-per-ray bound, 0 = keep
+  r->descent_carry = ((max_levels >> 16) & 1u) != 0u;   // bit 16 (A/B): kind 32 keeps accepted candidates undivided through its cooperative leaf loop
   r->xcd_mapping_override = static_cast<int>((max_levels >> 29) & 3u) - 1;   // bits 29..30 (A/B): 1 + FindParams::xcd_mapping, 0 = the tuned / default one
   r->descent_wide = (max_levels >> 31) == 0u;   // bit 31 (A/B): the four-wide nodes even where the map has the 16-wide twins
   r->graph_dirty = true;

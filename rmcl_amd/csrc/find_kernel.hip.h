@@ -236,8 +236,11 @@ __device__ __forceinline__ void find_moments_wave(const FindParams& p, uint32_t*
 
 // kClock: entry / traversal / store clocks of every wave go to p.wave_clock (tools/wave_timeline.py); the production
 // instantiations are built with kClock = false and contain no s_memtime
-template <uint32_t kModel, int kTrav, bool kClock = false, bool kMoments = false>
+// kCarry (kind 32): its cooperative leaf loop keeps accepted candidates undivided (traverse.hip.h TriPending); launch_find picks the
+// instantiation by bit 16 of p.descent_levels
+template <uint32_t kModel, int kTrav, bool kClock = false, bool kMoments = false, bool kCarry = false>
 __global__ void __launch_bounds__(256) k_find(const FindParams p) {
+  static_assert(!kCarry || kTrav == 32, "pending candidates belong to kind 32's cooperative leaf loop");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
   static_assert(!kMoments || ((kTrav == 23 || kTrav == 31 || kTrav == 32 || kTrav == 2) && !kClock), "the moment epilogue is built for kinds 23, 31, 32 and 2");
   __shared__ double s_mom_red[kMoments ? 4 : 1][kMoments ? kMomTile : 1];
@@ -384,7 +387,7 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
       if (p.tile_planes != nullptr) {     // (no table: the rays start at the root)
         const float* planes = p.tile_planes + static_cast<size_t>(__builtin_amdgcn_readfirstlane(tile)) * 16u;
         if (kTrav == 31 || kTrav == 32)
-          start = frontier_descent_start<kFindBfRows, 1, kTrav == 32>(p.frontier, p.n_frontier, p.cnodes, p.cnodes16, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar,
+          start = frontier_descent_start<kFindBfRows, 1, kTrav == 32, kCarry>(p.frontier, p.n_frontier, p.cnodes, p.cnodes16, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar,
                                                          org_m, dir_m, rs, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload,
                                                          lds_dyn + kFind31ListsAt + wave * kDescentWaveDwords, min(p.descent_final_cap, kDescentCap), p.descent_levels, kClock ? &clk_descent : nullptr,
                                                          kClock ? clk_stamps : nullptr, p.tris, &coop_seed);

@@ -920,7 +920,17 @@ hipError_t launch_find(const FindParams& p, ModelKind kind, int variant, hipStre
     RMCL_LAUNCH_FIND(23, lds)
   } else if (variant == 32) {  // the cooperative descent below the frontier, one bit per final leaf and ray: + the four waves' lists
     const size_t lds = static_cast<size_t>(kFind31LdsDwords) * sizeof(uint32_t);
-    RMCL_LAUNCH_FIND(32, lds)
+    if ((p.descent_levels >> 16) & 1u) {   // pending candidates in the cooperative leaf loop: a kernel of its own
+      switch (kind) {
+        case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, false, true>), grid, block, lds, s, p); break;
+        case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, false, true>), grid, block, lds, s, p); break;
+        case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 32, false, false, true>), grid, block, lds, s, p); break;
+        case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 32, false, false, true>), grid, block, lds, s, p); break;
+        default: return hipErrorInvalidValue;
+      }
+    } else {
+      RMCL_LAUNCH_FIND(32, lds)
+    }
   } else {                     // 24: one lane per ray on the 64-B quantised nodes: frontier start, leaf trigger, 16 LDS rows
     const size_t lds4 = 16u * 256u * sizeof(uint32_t);
     RMCL_LAUNCH_FIND(24, lds4)
@@ -953,6 +963,16 @@ hipError_t launch_find_moments(const FindParams& p, ModelKind kind, int variant,
   }
   if (variant == 32) {   // kind 23's epilogue behind the cooperative descent (+ the four waves' lists)
     const size_t lds31 = static_cast<size_t>(kFind31LdsDwords) * sizeof(uint32_t);
+    if ((p.descent_levels >> 16) & 1u) {   // pending candidates in the cooperative leaf loop
+      switch (kind) {
+        case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, true, true>), grid, block, lds31, s, p); break;
+        case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, true, true>), grid, block, lds31, s, p); break;
+        case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 32, false, true, true>), grid, block, lds31, s, p); break;
+        case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 32, false, true, true>), grid, block, lds31, s, p); break;
+        default: return hipErrorInvalidValue;
+      }
+      return hipGetLastError();
+    }
     switch (kind) {
       case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, true>), grid, block, lds31, s, p); break;
       case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, true>), grid, block, lds31, s, p); break;

@@ -190,6 +190,63 @@ __device__ __forceinline__ void tri_update(uint4 a, uint4 b, uint4 c, uint32_t r
   }
 }
 
+// ONE DIVISION PER RAY in kind 32's cooperative leaf loop.  tri_update's `if (ok)` block -- Tt / aden (eleven instructions as an IEEE
+// division), the depth tests, the tie branch -- runs for the whole wave as soon as ONE lane accepts, although a ray of a closed map has
+// one hit.  In that loop (frontier_descent_start, kCoop) nothing reads best_t between the rounds -- the leaves a ray tests are fixed
+// before it --, so a lane keeps its accepted candidate UNDIVIDED across them (TriPending: {Tt, aden, rec}; rec == kNone: none) and
+// resolves it -- tri_update's block, the same expressions in the same order -- once behind the loop.  A lane that accepts a second
+// candidate while it holds one resolves the first on the spot, under its own condition: the wave skips that unless some lane has collided.
+// It is a choice per launch between two kernels (k_find's kCarry; bit 16 of FindParams::descent_levels, set by rmclhip_rcc_autotune
+// where it measures faster): on maps whose rays cross several surfaces the candidates collide, nothing is saved and the bookkeeping is
+// added.  (A run-time branch between the two forms inside ONE kernel cost both of them 3 %: profiles/one_division_ab.txt.)
+// The leaf VISITS of the per-lane traversals keep tri_update: there the candidate would have to be resolved at the end of every visit
+// (the node steps cull with best_t), and that form measured 2 % slower on kind 23 (profiles/one_division_ab.txt).
+// Why (best_t, best_rec) are bit-identical to tri_update's:
+//  * the barycentric test is tri_accept's, and a candidate is taken iff ok && Tt > 0 -- the first term of tri_update's `acc`, decided
+//    without the quotient; a candidate with Tt <= 0 (or NaN) was rejected there and is rejected here;
+//  * every candidate taken is resolved by tri_update's expression: t = Tt / aden (IEEE), t <= ray_tfar, t < best_t, and on an exact tie
+//    the smaller original face id, "no hit" losing to a hit at t == tfar;
+//  * the running best is therefore the lexicographic minimum of (t, original face id) over the candidates that pass t <= tfar: that fold
+//    is commutative and idempotent, so neither the ORDER of resolution nor resolving a record twice (a short leaf re-tests its last
+//    record; it then replaces itself in the pending slot) can change the outcome.
+//    (Assumes what the builder guarantees: two DISTINCT records have distinct original face ids.  With equal ids the tie would go to
+//    whichever is resolved first, and the order of resolution here is not tri_update's order of tests.)
+struct TriPending {
+  float Tt, aden;
+  uint32_t rec;
+};
+
+// tri_update's accepted-hit block for an undivided candidate; ONLY for lanes that hold one (pd.rec != kNone: the tie branch forms the
+// record's address)
+__device__ __forceinline__ void tri_resolve(const TriPending& pd, const uint32_t* __restrict__ tris, float ray_tfar, float& best_t,
+                                            uint32_t& best_rec) {
+  const float t = pd.Tt / pd.aden;
+  const bool acc = t <= ray_tfar;   // (Tt > 0 was checked when the candidate was taken)
+  bool closer = acc && (t < best_t);
+  if (acc && (t == best_t) && (pd.rec != best_rec)) {
+    // exact tie: the smaller ORIGINAL face id wins; a first hit at exactly t == tfar wins against "no hit"
+    closer = (best_rec == kNone) || (tris[static_cast<size_t>(pd.rec) * 16u + 15u] < tris[static_cast<size_t>(best_rec) * 16u + 15u]);
+  }
+  best_t = closer ? t : best_t;
+  best_rec = closer ? pd.rec : best_rec;
+}
+
+// one triangle test that leaves its candidate pending (same record layout and arithmetic as tri_update)
+__device__ __forceinline__ void tri_offer(uint4 a, uint4 b, uint4 c, uint32_t rec, const uint32_t* __restrict__ tris, f3 O, f3 D,
+                                          float ray_tfar, float& best_t, uint32_t& best_rec, TriPending& pd) {
+  const f3 v0 = mk3(asf(a.x), asf(a.y), asf(a.z));
+  const f3 e1 = mk3(asf(a.w), asf(b.x), asf(b.y));
+  const f3 e2 = mk3(asf(b.z), asf(b.w), asf(c.x));
+  const f3 Ng = mk3(asf(c.y), asf(c.z), asf(c.w));
+  float Tt, aden;
+  const bool take = tri_accept(v0, e1, e2, Ng, O, D, Tt, aden) && (Tt > 0.0f);
+  // a collision: this lane already holds ANOTHER record (the same one, re-tested for a short leaf, just replaces itself)
+  if (take && (pd.rec != kNone) && (pd.rec != rec)) tri_resolve(pd, tris, ray_tfar, best_t, best_rec);
+  pd.Tt = take ? Tt : pd.Tt;
+  pd.aden = take ? aden : pd.aden;
+  pd.rec = take ? rec : pd.rec;
+}
+
 // A whole leaf (<= 4 records) in ONE memory round trip: the loop form waits for triangle i before it requests
 // triangle i+1 -- up to four dependent round trips per leaf visit, and the wave runs as many as its fullest leaf has
 // triangles.  Here the records of all four slots are requested together, unconditionally (a load under a wave-uniform
@@ -198,9 +255,11 @@ __device__ __forceinline__ void tri_update(uint4 a, uint4 b, uint4 c, uint32_t r
 // skip slots no lane of the wave fills: results identical to the loop.
 // `after_requests` runs between the record requests and the first test (kPipe: the lane's NEXT node is requested there, behind
 // the records, so the records' arrival is not held up by it and its latency is covered by the tests)
-template <class F>
-__device__ __forceinline__ void leaf_batch_then(const uint32_t* __restrict__ tris, uint32_t cur, f3 O, f3 D, float ray_tfar,
-                                                float& best_t, uint32_t& best_rec, F&& after_requests) {
+// kCarry (kind 32's cooperative leaf loop): the tests leave the lane's candidate pending in *pd across calls, the caller resolves it when
+// it needs (best_t, best_rec); otherwise every test ends resolved (tri_update)
+template <bool kCarry, class F>
+__device__ __forceinline__ void leaf_batch_tests(const uint32_t* __restrict__ tris, uint32_t cur, f3 O, f3 D, float ray_tfar,
+                                                 float& best_t, uint32_t& best_rec, TriPending* pd, F&& after_requests) {
   const uint32_t first = cur & 0x0FFFFFFFu;
   const uint32_t last = first + ((cur >> 28) & 7u);
   const bool w2 = __any(last > first), w3 = __any(last > first + 1u), w4 = __any(last > first + 2u);
@@ -214,10 +273,26 @@ __device__ __forceinline__ void leaf_batch_then(const uint32_t* __restrict__ tri
   const uint4 a2 = t2[0], b2 = t2[1], c2 = t2[2];
   const uint4 a3 = t3[0], b3 = t3[1], c3 = t3[2];
   after_requests();
-  tri_update(a0, b0, c0, first, tris, O, D, ray_tfar, best_t, best_rec);
-  if (w2) tri_update(a1, b1, c1, i1, tris, O, D, ray_tfar, best_t, best_rec);
-  if (w3) tri_update(a2, b2, c2, i2, tris, O, D, ray_tfar, best_t, best_rec);
-  if (w4) tri_update(a3, b3, c3, i3, tris, O, D, ray_tfar, best_t, best_rec);
+  if constexpr (kCarry) {
+    tri_offer(a0, b0, c0, first, tris, O, D, ray_tfar, best_t, best_rec, *pd);
+    if (w2) tri_offer(a1, b1, c1, i1, tris, O, D, ray_tfar, best_t, best_rec, *pd);
+    if (w3) tri_offer(a2, b2, c2, i2, tris, O, D, ray_tfar, best_t, best_rec, *pd);
+    if (w4) tri_offer(a3, b3, c3, i3, tris, O, D, ray_tfar, best_t, best_rec, *pd);
+  } else {
+    tri_update(a0, b0, c0, first, tris, O, D, ray_tfar, best_t, best_rec);
+    if (w2) tri_update(a1, b1, c1, i1, tris, O, D, ray_tfar, best_t, best_rec);
+    if (w3) tri_update(a2, b2, c2, i2, tris, O, D, ray_tfar, best_t, best_rec);
+    if (w4) tri_update(a3, b3, c3, i3, tris, O, D, ray_tfar, best_t, best_rec);
+  }
+}
+template <class F>
+__device__ __forceinline__ void leaf_batch_then(const uint32_t* __restrict__ tris, uint32_t cur, f3 O, f3 D, float ray_tfar,
+                                                float& best_t, uint32_t& best_rec, F&& after_requests) {
+  leaf_batch_tests<false>(tris, cur, O, D, ray_tfar, best_t, best_rec, nullptr, after_requests);
+}
+__device__ __forceinline__ void leaf_batch_carry(const uint32_t* __restrict__ tris, uint32_t cur, f3 O, f3 D, float ray_tfar,
+                                                 float& best_t, uint32_t& best_rec, TriPending& pd) {
+  leaf_batch_tests<true>(tris, cur, O, D, ray_tfar, best_t, best_rec, &pd, [] {});
 }
 __device__ __forceinline__ void leaf_batch(const uint32_t* __restrict__ tris, uint32_t cur, f3 O, f3 D, float ray_tfar,
                                            float& best_t, uint32_t& best_rec) {
@@ -1415,7 +1490,8 @@ constexpr uint32_t kDescentWaveDwords = (kDescentCap + 2u * kDescentInnerCap) * 
 
 // kCoop (kind 32): the per-ray part without the sorted hand-over -- see the comment at the final list below.  `seed` receives the closest hit
 // among the final LEAVES; the per-lane traversal that follows starts from it and only sees what the descent left unexpanded.
-template <int kRows, int kRow0, bool kCoop = false>
+// kCarry (kCoop only): accepted candidates stay undivided through the leaf loop (TriPending) -- a kernel of its own, chosen per launch
+template <int kRows, int kRow0, bool kCoop = false, bool kCarry = false>
 __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __restrict__ frontier, uint32_t n_frontier,
                                                              const uint32_t* __restrict__ cnodes, const uint32_t* __restrict__ cnodes16,
                                                              f3 scene_center, float scene_half_diag,
@@ -1631,8 +1707,13 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
         if (dbg_levels) { if (stamps != nullptr) stamps[13] = 1u; }   // diagnostics: this wave took the leaf-cap fallback
         return root;
       }
+      // The rounds below cull nothing with best_t (the bits are fixed), so with kCarry the lane's candidate stays pending ACROSS them
+      // (TriPending, above leaf_batch_tests) and is resolved once behind the loop: a ray of a closed map divides once, not once per slot
+      // and round.  Where rays cross several surfaces the candidates collide and the form loses (room-100k +3 %): the autotune measures
+      // both kernels and keeps this one only where it is faster; without it the loop is tri_update's
       float best_t = ray_tfar;
       uint32_t best_rec = kNone;
+      TriPending pd = {0.0f, 1.0f, kNone};
       const uint32_t* Fw = reinterpret_cast<const uint32_t*>(Fl);
       while (__any((m_lo | m_hi) != 0u)) {
         uint32_t ref = kDone;
@@ -1644,7 +1725,13 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
           m_hi = lo ? m_hi : (m_hi & (m_hi - 1u));
           ref = Fw[8u * (bit + (lo ? 0u : 32u)) + 6u];
         }
-        if (ref > kDone) leaf_batch(tris, ref, O, D, ray_tfar, best_t, best_rec);
+        if (ref > kDone) {
+          if constexpr (kCarry) leaf_batch_carry(tris, ref, O, D, ray_tfar, best_t, best_rec, pd);
+          else leaf_batch(tris, ref, O, D, ray_tfar, best_t, best_rec);
+        }
+      }
+      if constexpr (kCarry) {
+        if (pd.rec != kNone) tri_resolve(pd, tris, ray_tfar, best_t, best_rec);
       }
       seed->t = best_t;
       seed->rec = best_rec;
