@@ -963,6 +963,33 @@ class MapSegmentationHipNode_ {
 using ScanMapSegmentationHipNode = MapSegmentationHipNode_<SphericalModel>;
 using O1DnMapSegmentationHipNode = MapSegmentationHipNode_<O1DnModel>;
 
+// The motion of the sensor during one scan (include/rmclhip.h, MOTION-COMPENSATED INPUT): knots[k] = T_sref_s(times[k]), the sensor
+// frame at times[k] in the sensor frame at the reference time; 2 .. 64 knots, times in seconds, strictly increasing.  The device
+// interpolates between knots by nlerp: fromBasePoses subdivides by slerp, 16 knots per 0.3 rad keep nlerp below float resolution.
+struct ScanMotion {
+  std::vector<Transform> knots;
+  std::vector<double> times;
+  rmclhip_scan_motion c_motion() const {
+    if (knots.size() != times.size()) throw std::runtime_error("ScanMotion: one time per knot");
+    return rmclhip_scan_motion{knots.data(), times.data(), static_cast<uint32_t>(knots.size())};
+  }
+  // from base poses T_x_b (base in a fixed frame such as odom: two tf lookups, or more) at `stamps`; t_ref: the stamp the caller
+  // localises at; subdivide - 1 slerp knots are inserted per segment (rmclhip_scan_motion_from_base_poses_host)
+  static ScanMotion fromBasePoses(const Transform& Tsb, const std::vector<Transform>& T_x_b, const std::vector<double>& stamps, double t_ref,
+                                  uint32_t subdivide = 1u) {
+    if (T_x_b.size() != stamps.size()) throw std::runtime_error("ScanMotion: one stamp per base pose");
+    ScanMotion m;
+    m.knots.resize(64);
+    m.times.resize(64);
+    uint32_t n = 0;
+    check(rmclhip_scan_motion_from_base_poses_host(&Tsb, T_x_b.data(), stamps.data(), static_cast<uint32_t>(T_x_b.size()), t_ref, subdivide,
+                                                   m.knots.data(), m.times.data(), 64u, &n));
+    m.knots.resize(n);
+    m.times.resize(n);
+    return m;
+  }
+};
+
 // rmcl::RCCEmbree{Spherical, Pinhole, O1Dn, OnDn} (RCCEmbree.hpp:18-83): the correspondence operator + ModelSetter + -- protected --
 // the simulator of its model.  find() is the reference's `simulate(Tbm_est, model_buffers_)` (RCCEmbree.cpp:35) on the operator's own
 // buffers, which live behind the C handle (rmclhip_rcc_find); like Correspondences_::model_buffers_ they carry {points, normals, hits}
@@ -999,6 +1026,34 @@ class RCCHip_ : public CorrespondencesHIP, public ModelSetter<ModelT>, protected
     view.ptr = ranges;
     view.n = this->m_model->size();
     return view;
+  }
+  // RCCHipOnDn only.  A sensor_msgs/PointCloud2 taken while the sensor moved becomes this operator's OnDn model -- every ray from the
+  // pose the sensor had when it measured it -- AND its dataset in one device pass (rmclhip_rcc_set_input_pointcloud2_deskewed;
+  // include/rmclhip.h states the rules).  `time`: the per-point time field; filters: nullptr = keep every row / column; out_width /
+  // out_height (nullable): the model's size after the filters.  m_model then holds the size and range only: origins and directions
+  // live on the device (rmclhip_rcc_input_views).
+  template <typename M = ModelT>
+  rmclhip_deskew_stats setInputPointCloud2Deskewed(const uint8_t* data, size_t nbytes, const rmclhip_pointcloud2_layout& layout,
+                                                   const rmclhip_pointcloud2_time& time, const ScanMotion& motion, Interval range,
+                                                   const rmclhip_filter1d* filter_height = nullptr, const rmclhip_filter1d* filter_width = nullptr,
+                                                   bool src_is_device = false, uint32_t* out_width = nullptr, uint32_t* out_height = nullptr) {
+    static_assert(std::is_same<M, OnDnModel>::value && std::is_same<M, ModelT>::value,
+                  "setInputPointCloud2Deskewed casts every ray from its own origin: RCCHipOnDn only");
+    const rmclhip_scan_motion mo = motion.c_motion();
+    rmclhip_deskew_stats stats{};
+    uint32_t w = 0, h = 0;
+    check(rmclhip_rcc_set_input_pointcloud2_deskewed(h_, data, nbytes, &layout, &time, filter_height, filter_width, range, src_is_device ? 1 : 0,
+                                                     &mo, &w, &h, &stats));
+    auto m = std::make_shared<OnDnModel>();
+    m->width = w;
+    m->height = h;
+    m->range = range;
+    this->m_model = m;
+    if (out_width) *out_width = w;
+    if (out_height) *out_height = h;
+    bound_points_ = bound_mask_ = ~0ull;   // the library's own dataset is current until the `dataset` member is written again
+    outdated = true;
+    return stats;
   }
 };
 using RCCHipSpherical = RCCHip_<SphericalModel>;
@@ -1040,6 +1095,42 @@ class Pc2ToScanHip {
   Transform T_ = identity();
   bool has_T_ = false;
   rmclhip_pc2scan_stats stats_{};
+};
+
+// The cloud form of the motion compensation (rmclhip_pointcloud2_deskew) as a converter beside Pc2ToScanHip: the message's bytes, its
+// per-point time field and the scan's motion in, the cloud in the sensor frame of the reference time out -- 12-byte xyz records in
+// device memory owned by this object until the next convert(), NaN where a point is out of range_ or has no time.  What
+// RCCHipSpherical::setInputPointCloud2 (src_is_device, point_step 12; neglects the parallax of the ray origins) and a CPCHip dataset
+// view (exact) accept.
+class Pc2DeskewHip {
+ public:
+  rmclhip_pointcloud2_time time_{0u, 7u, 1.0, 0.0};   // the time field: offset, PointField datatype (6 / 7 / 8), t = offset_s + scale * raw
+  Interval range_{0.f, 1e30f};
+
+  explicit Pc2DeskewHip(ContextPtr ctx) : ctx_(std::move(ctx)), points_(ctx_) {
+    if (!ctx_) throw std::runtime_error("NO CONTEXT");
+  }
+  DeviceView<const float> convert(const uint8_t* data, size_t nbytes, const rmclhip_pointcloud2_layout& layout, const ScanMotion& motion,
+                                  bool src_is_device = false) {
+    const size_t n = static_cast<size_t>(layout.width) * layout.height;
+    points_.resize(3 * n);
+    const rmclhip_scan_motion mo = motion.c_motion();
+    check(rmclhip_pointcloud2_deskew(ctx_->handle(), data, nbytes, &layout, &time_, src_is_device ? 1 : 0, &mo, range_, points_.raw(), &stats_));
+    DeviceView<const float> view;
+    view.ptr = points_.raw();
+    view.n = 3 * n;
+    return view;
+  }
+  // the layout of convert()'s records for the calls that take PointCloud2 bytes
+  static rmclhip_pointcloud2_layout layoutOf(size_t n_points) {
+    return rmclhip_pointcloud2_layout{static_cast<uint32_t>(n_points), 1u, 12u, static_cast<uint32_t>(12u * n_points), 0u, 4u, 8u, 7u};
+  }
+  const rmclhip_deskew_stats& stats() const { return stats_; }   // of the last convert()
+
+ private:
+  ContextPtr ctx_;
+  Memory<float, VRAM_HIP> points_;
+  rmclhip_deskew_stats stats_{};
 };
 
 // rmcl::CPCEmbree (rmcl/include/rmcl/registration/CPCEmbree.hpp): closest-point correspondences

@@ -358,6 +358,83 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2_scan(rmclhip_rcc* rcc, const ui
                                                       const rmclhip_pointcloud2_layout* layout, int src_is_device,
                                                       const rmclhip_transform* T_sensor_cloud, uint32_t flags,
                                                       const float** ranges_dev_out, rmclhip_pc2scan_stats* stats);
+
+/* ---- MOTION-COMPENSATED INPUT: a PointCloud2 taken while the sensor moved, every point from its own pose ----
+ * A spinning LiDAR takes 50-100 ms per revolution; the drivers stamp every point.  The calls above treat a scan as taken from one
+ * pose.  These take the cloud's per-point time field and the sensor's motion during the scan and cast every ray from the pose the
+ * sensor had when it measured it: an OnDn model (one origin per ray) plus the dataset, in one device pass.
+ *
+ * Motion of a scan: K knots, 2 <= K <= 64.  times[k]: doubles, seconds, strictly increasing.  knots[k] = T_sref_s(t_k): the sensor
+ * frame at t_k expressed in the sensor frame at the REFERENCE time -- the stamp the caller localises at; the knot at that time is the
+ * identity.  (stamp of a knot is ignored.)
+ * Time of a point: t = offset_s + scale * raw, in double; raw is the time field at byte `offset` of the record: PointField UINT32
+ * (6: Ouster t, ns -> scale 1e-9), FLOAT32 (7: Velodyne time) or FLOAT64 (8); any other datatype: RMCLHIP_ERR_UNSUPPORTED.
+ * Pose of a point:
+ *   k = the largest index with times[k] <= t, limited to [0, K - 2]
+ *   s = (float)((t - times[k]) / (times[k+1] - times[k])), the quotient in double; s < 0 or s > 1 is clamped to that end -- the point
+ *       takes the end knot and is counted in n_time_clamped
+ *   float from here on, every step one IEEE operation:  a = 1.0f - s;  q' = -q_{k+1} if ((qx qx' + qy qy') + qz qz') + qw qw' < 0
+ *   (the shorter arc), else q_{k+1};  q = a * q_k + s * q' per component, each divided by sqrtf(((x*x + y*y) + z*z) + w*w);
+ *   tr = a * t_k + s * t_{k+1} per component.
+ *   This is nlerp, not slerp, on purpose: no transcendental on the device, so a float32 restatement on the host (tests/deskew_ref.py)
+ *   reproduces the bytes.  Over a segment that turns by theta, nlerp stays on slerp's arc and is off along it by at most
+ *   theta^3 / (144 sqrt 3) ~ theta^3 / 249 to leading order in theta (the next term adds theta^2 / 80 of that; attained at s = 0.21
+ *   and 0.79, zero at both ends and in the middle): 1.1e-4 rad for a 0.3 rad scan
+ *   in ONE segment, 2.6e-8 rad -- below 2^-24, the resolution of a float quaternion -- in 16.  The caller makes the knots that
+ *   dense; rmclhip_scan_motion_from_base_poses_host subdivides by true slerp in double.
+ *   A non-finite t takes knots[0], is counted in n_time_nonfinite (not in n_time_clamped) and has mask 0.
+ * Outputs per point, i = ti * out_w + tj over the rows / columns the filters keep (as rmclhip_rcc_set_input_pointcloud2):
+ *   x, y, z as there (FLOAT64 cast to float); one of them non-finite: range = 0, dir_local = 0; else
+ *   range = sqrtf((x*x + y*y) + z*z), dir_local = (x, y, z) / range
+ *   orig_i = tr;  dir_i = q * dir_local (the Hamilton product q (d, 0) q^-1 of rmclhip_transform);  point_i = dir_i * range + orig_i
+ *   mask_i = range within `range` and t finite
+ * With identity knots every output is, bit for bit, what rmclhip_rcc_set_input_pointcloud2 writes for the same bytes, all origins
+ * +0 (but for the sign of a coordinate that is -0 in the cloud).
+ * stats (nullable): n_points = out_w * out_h, n_finite (x, y, z finite), n_valid (mask 1), n_time_clamped, n_time_nonfinite.
+ * RMCLHIP_ERR_INVALID, before anything is launched, outputs and the operator's state untouched: a null layout; null data / time /
+ * motion / knots / times with points to read; data shorter than the last byte a kept point's x / y / z / time field reaches;
+ * K outside [2, 64]; non-finite or non-increasing knot times; a non-finite knot, or a quaternion whose norm is off 1 by more than
+ * 1e-3; a non-finite scale or offset_s; bad filters; more than 2^31 points.  An empty cloud is no error. */
+typedef struct { uint32_t offset, datatype; double scale, offset_s; } rmclhip_pointcloud2_time;
+typedef struct { const rmclhip_transform* knots; const double* times; uint32_t n_knots; } rmclhip_scan_motion;
+typedef struct { uint32_t n_points, n_finite, n_valid, n_time_clamped, n_time_nonfinite; } rmclhip_deskew_stats;
+/* The operator form: the operator becomes OnDn (out_w x out_h rays, as rmclhip_rcc_set_model_ondn leaves it: tuned kinds reset, no
+ * frontier start) with the dataset set, as set_model_ondn + set_dataset of the arrays above would leave it -- without the host loop
+ * and the two uploads.  `data` may be a host or a device pointer; buffers are grow-only, a repeated call allocates nothing. */
+rmclhip_status rmclhip_rcc_set_input_pointcloud2_deskewed(rmclhip_rcc* rcc, const uint8_t* data, size_t nbytes,
+                                                          const rmclhip_pointcloud2_layout* layout,
+                                                          const rmclhip_pointcloud2_time* time,
+                                                          const rmclhip_filter1d* filter_height, const rmclhip_filter1d* filter_width,
+                                                          rmclhip_interval range, int src_is_device, const rmclhip_scan_motion* motion,
+                                                          uint32_t* out_width, uint32_t* out_height, rmclhip_deskew_stats* stats);
+/* The cloud form, a free function on the context's PointCloud2 stream (calls on one context serialise; synchronous): every point of
+ * the layout (no filters) as one 12-byte xyz float record in points_out_dev (device memory, width * height records), in the sensor
+ * frame of the reference time; NaN where the mask would be 0.  The records are byte-equal to the operator form's points.  They are a
+ * valid src_is_device input of rmclhip_rcc_set_input_pointcloud2_scan (point_step 12, offsets 0 / 4 / 8, FLOAT32): the spherical fast
+ * path -- points moved, rays cast from the reference pose.  That NEGLECTS THE PARALLAX of the ray origins (up to the distance the
+ * sensor moved, seen from the surface's range); the operator form does not.  They are also valid for rmclhip_rcc_set_dataset_view +
+ * rmclhip_rcc_find_cpc: closest-point correspondences need no rays, so that path is exact. */
+rmclhip_status rmclhip_pointcloud2_deskew(rmclhip_ctx* ctx, const uint8_t* data, size_t nbytes,
+                                          const rmclhip_pointcloud2_layout* layout, const rmclhip_pointcloud2_time* time,
+                                          int src_is_device, const rmclhip_scan_motion* motion, rmclhip_interval range,
+                                          float* points_out_dev, rmclhip_deskew_stats* stats);
+/* HOST function, in double: the motion of a scan from n >= 2 base poses T_x_b[i] (base in any fixed frame x: odometry) at strictly
+ * increasing times[i].  The base pose at t_ref (within [times[0], times[n-1]]) is interpolated by slerp + lerp; knot k is
+ * ~Tsb * ~T_x_b(t_ref) * T_x_b(t_k) * Tsb.  Every segment gets subdivide - 1 >= 0 further knots by slerp + lerp, evenly in time:
+ * (n - 1) * subdivide + 1 knots in all, written to knots_out / times_out (capacity entries each); *n_out: their number.
+ * RMCLHIP_ERR_INVALID: null arguments, n < 2, subdivide == 0, non-finite or non-increasing times, t_ref outside them, a non-finite
+ * pose or a zero quaternion, a result beyond capacity or beyond 64 knots (nothing is written then). */
+rmclhip_status rmclhip_scan_motion_from_base_poses_host(const rmclhip_transform* Tsb, const rmclhip_transform* T_x_b,
+                                                        const double* times, uint32_t n, double t_ref, uint32_t subdivide,
+                                                        rmclhip_transform* knots_out, double* times_out, uint32_t capacity,
+                                                        uint32_t* n_out);
+/* The operator's inputs in device memory, borrowed -- valid until the next set_model_* / set_dataset* / set_input_* call of this
+ * operator: the sensor model's table (spherical: cos phi | sin phi | cos theta | sin theta; O1Dn: width * height directions; OnDn:
+ * width * height origins, then as many directions; pinhole or no model: NULL), the model's size, the dataset's points and mask
+ * (NULL: none) and its size -- what a caller reads the compensated points of rmclhip_rcc_set_input_pointcloud2_deskewed from.
+ * Every out pointer is nullable.  Waits for the operator's stream. */
+rmclhip_status rmclhip_rcc_input_views(rmclhip_rcc* rcc, const float** model_table_dev, uint32_t* width, uint32_t* height,
+                                       const float** dataset_points_dev, const uint8_t** dataset_mask_dev, uint32_t* n_dataset);
 /* rmcl::CPCEmbree::find (rmcl/src/rmcl/registration/CPCEmbree.cpp:18-44), closest-point correspondences (`type: CP`):
  * for every dataset point Pm = Tsm * d_i the nearest surface point of the map; model buffers (sized like the
  * dataset) receive hits = (distance <= params.max_dist), points = Tms * p_closest, normals = Tms.R * n_face
@@ -763,6 +840,15 @@ rmclhip_status rmclhip_pf_set_schedule(rmclhip_pf* pf, uint32_t refill_idle_lane
 rmclhip_status rmclhip_pf_sample_beams_pointcloud2(const uint8_t* data, size_t nbytes, const rmclhip_pointcloud2_layout* layout,
                                                    uint32_t samples, uint64_t seed, rmclhip_range_measurement* beams_out,
                                                    uint32_t* n_out);
+/* The same sampler for a scan taken in motion (HOST function; MOTION-COMPENSATED INPUT above states the pose rule): the same
+ * mt19937 draws, retries and index rule, so an identity motion returns the bytes of rmclhip_pf_sample_beams_pointcloud2.  Each beam
+ * gets orig = tr_i and dir = q_i * dir of its point's own pose and keeps its range.  Refusals as above, plus those of the time field
+ * and the motion. */
+rmclhip_status rmclhip_pf_sample_beams_pointcloud2_deskewed(const uint8_t* data, size_t nbytes,
+                                                            const rmclhip_pointcloud2_layout* layout,
+                                                            const rmclhip_pointcloud2_time* time, const rmclhip_scan_motion* motion,
+                                                            uint32_t samples, uint64_t seed, rmclhip_range_measurement* beams_out,
+                                                            uint32_t* n_out);
 
 
 /* ---- resampling: rmcl::GladiatorResamplerGPU (GladiatorResamplerGPU.cpp:46-81, resampling.cu:41-219) ----

@@ -150,6 +150,25 @@ class Pc2ScanStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PointCloud2Time(C.Structure):
+    """rmclhip_pointcloud2_time: the per-point time field, t = offset_s + scale * raw"""
+    _fields_ = [("offset", C.c_uint32), ("datatype", C.c_uint32), ("scale", C.c_double), ("offset_s", C.c_double)]
+
+
+class ScanMotion(C.Structure):
+    """rmclhip_scan_motion: K knots T_sref_s(t_k) (TRANSFORM records) and their times (doubles), host memory"""
+    _fields_ = [("knots", C.c_void_p), ("times", C.c_void_p), ("n_knots", C.c_uint32)]
+
+
+class DeskewStats(C.Structure):
+    """rmclhip_deskew_stats"""
+    _fields_ = [("n_points", C.c_uint32), ("n_finite", C.c_uint32), ("n_valid", C.c_uint32), ("n_time_clamped", C.c_uint32),
+                ("n_time_nonfinite", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 PC2SCAN_TRUE_ELEVATION, PC2SCAN_FLOOR, PC2SCAN_WRAP_THETA, PC2SCAN_NEAREST = 1, 2, 4, 8
 SEG_PINT_WITH_ORIGIN = 1
 SEG_NONE, SEG_INLIER, SEG_OUTLIER_SCAN, SEG_OUTLIER_MAP = 0, 1, 2, 3
@@ -210,6 +229,16 @@ SIGNATURES = {
                                             _vp, _i32, C.POINTER(Pc2ScanStats)]),
     "rmclhip_rcc_set_input_pointcloud2_scan": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), _i32, _vp, _u32, _pp,
                                                        C.POINTER(Pc2ScanStats)]),
+    "rmclhip_rcc_set_input_pointcloud2_deskewed": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), C.POINTER(PointCloud2Time),
+                                                           C.POINTER(Filter1D), C.POINTER(Filter1D), Interval, _i32,
+                                                           C.POINTER(ScanMotion), C.POINTER(_u32), C.POINTER(_u32),
+                                                           C.POINTER(DeskewStats)]),
+    "rmclhip_pointcloud2_deskew": (_i32, [_vp, _vp, _sz, C.POINTER(PointCloud2Layout), C.POINTER(PointCloud2Time), _i32,
+                                           C.POINTER(ScanMotion), Interval, _vp, C.POINTER(DeskewStats)]),
+    "rmclhip_scan_motion_from_base_poses_host": (_i32, [_vp, _vp, _vp, _u32, _dbl, _u32, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "rmclhip_pf_sample_beams_pointcloud2_deskewed": (_i32, [_vp, _sz, C.POINTER(PointCloud2Layout), C.POINTER(PointCloud2Time),
+                                                             C.POINTER(ScanMotion), _u32, C.c_uint64, _vp, C.POINTER(_u32)]),
+    "rmclhip_rcc_input_views": (_i32, [_vp, _pp, C.POINTER(_u32), C.POINTER(_u32), _pp, _pp, C.POINTER(_u32)]),
     "rmclhip_rcc_compute_cross_statistics": (_i32, [_vp, _vp, _dbl, _vp]),
     "rmclhip_rcc_download": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rmclhip_rcc_device_views": (_i32, [_vp, _pp, _pp, _pp, _pp, _pp, C.POINTER(_u32)]),

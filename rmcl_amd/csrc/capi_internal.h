@@ -5,6 +5,7 @@
 //   capi_rcc_tune.cpp  tuning knobs, autotune, measurement aids (include/rmclhip_bench.h) and diagnostics (include/rmclhip_lab.h) of that operator
 //   capi_segment.cpp   map segmentation of that operator: trace into its own scratch, labels, compacted outlier clouds (kernels: segment.hip)
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
+//   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
@@ -164,6 +165,7 @@ struct rmclhip_ctx {
   hipStream_t pc2_stream = nullptr;
   Pc2ScanScratch pc2;
   DevBuf<uint8_t> pc2_raw;              // staged host bytes
+  DevBuf<uint8_t> deskew_aux;           // rmclhip_pointcloud2_deskew (capi_deskew.cpp), same stream and mutex: the four counters
   // rmclhip_particles_* (capi_particles.cpp): their stream and the visualisation pack's device staging, created by the first call
   // under the mutex, which also serialises the calls of one context
   std::mutex part_mtx;
@@ -334,6 +336,7 @@ struct rmclhip_rcc {
   // not give the bins back), the range image the dataset was made of and the keys, grow-only; host bytes are staged in d_raw
   rmclhip_spherical_model sph_model{{0.f, 0.f, 0u}, {0.f, 0.f, 0u}, {0.f, 0.f}};
   Pc2ScanScratch pc2;
+  DevBuf<uint8_t> d_deskew_aux;    // rmclhip_rcc_set_input_pointcloud2_deskewed (capi_deskew.cpp): the four counters
   bool capturing = false;          // inside hipStreamBeginCapture: no synchronisation allowed
   int variant = 15;       // traversal kind: 0 wave-packet, 1 one lane per ray (while-while), 2 four lanes per ray
                           // (quad-cooperative), 15 automatic: quad while the launch is bound by the slowest ray's

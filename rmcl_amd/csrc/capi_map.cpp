@@ -55,7 +55,7 @@ rmclhip_ctx::~rmclhip_ctx() {
   if (pc2_stream != nullptr) {
     (void)hipSetDevice(device);
     (void)hipStreamSynchronize(pc2_stream);
-    pc2.release(); pc2_raw.release();
+    pc2.release(); pc2_raw.release(); deskew_aux.release();
     (void)hipStreamDestroy(pc2_stream);
   }
   if (p2l_stream == nullptr) return;

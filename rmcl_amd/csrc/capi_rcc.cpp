@@ -75,7 +75,7 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
   r->d_multi_blob.release();
   r->d_seg_ranges.release(); r->d_seg_normals.release(); r->d_seg_real.release(); r->d_seg_labels.release(); r->d_seg_block_counts.release();
   if (r->h_seg_counts) DBG_STEP(hipHostFree(r->h_seg_counts));
-  r->pc2.release();
+  r->pc2.release(); r->d_deskew_aux.release();
   if (r->h_multi_state) DBG_STEP(hipHostFree(r->h_multi_state));
   if (r->h_multi_status) DBG_STEP(hipHostFree(r->h_multi_status));
   if (r->h_call) DBG_STEP(hipHostFree(r->h_call));
@@ -331,6 +331,22 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2(rmclhip_rcc* r, const uint8_t* 
   HIPCHK(hipMemcpyAsync(&nv, r->d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
   if (n_valid_out) *n_valid_out = nv;
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_rcc_input_views(rmclhip_rcc* r, const float** model_table_dev, uint32_t* width, uint32_t* height,
+                                       const float** dataset_points_dev, const uint8_t** dataset_mask_dev, uint32_t* n_dataset) {
+  ApiGuard guard_("rmclhip_rcc_input_views");
+  if (!r) return fail(RMCLHIP_ERR_INVALID, "rcc_input_views: null");
+  HIPCHK(hipSetDevice(r->ctx->device));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  const bool has_table = (r->kind == kModelSpherical || r->kind == kModelO1Dn || r->kind == kModelOnDn) && r->W != 0u && r->H != 0u;
+  if (model_table_dev) *model_table_dev = has_table ? r->d_model_tab.p : nullptr;
+  if (width) *width = r->W;
+  if (height) *height = r->H;
+  if (dataset_points_dev) *dataset_points_dev = r->n_dataset ? r->ds_pts : nullptr;
+  if (dataset_mask_dev) *dataset_mask_dev = (r->n_dataset && r->ds_has_mask) ? r->ds_msk : nullptr;
+  if (n_dataset) *n_dataset = r->n_dataset;
   return RMCLHIP_OK;
 }
 

@@ -395,6 +395,27 @@ inline uint32_t pc2scan_blocks(size_t n) { return static_cast<uint32_t>((n + kPc
 // the keys' memset + k_pc2scan_bin + k_pc2scan_resolve + k_pc2scan_publish ({finite, in image, in range, cells filled} to the
 // host-mapped counters_host), all on s
 hipError_t launch_pc2scan(const Pc2ScanParams& p, uint32_t* counters_host, hipStream_t s);
+// PointCloud2 bytes + per-point times + the scan's motion -> every point from its own pose (deskew.hip; the rules: include/rmclhip.h,
+// MOTION-COMPENSATED INPUT).  The knots travel BY VALUE in the launch parameters (2.3 of the 4 KB a launch may carry), so they need
+// no copy of their own on the stream; every workgroup stages them in LDS.
+constexpr uint32_t kDeskewBlock = 256;
+struct DeskewKnots { double times[64]; quat q[64]; f3 t[64]; };   // 2 304 B
+constexpr uint32_t kDeskewValid = 0u, kDeskewFinite = 1u, kDeskewClamped = 2u, kDeskewTimeNonFinite = 3u, kDeskewCounters = 4u;
+constexpr uint32_t kDeskewCounterStride = 32u;   // words between two counters: a 128-byte line each
+struct DeskewParams {
+  const uint8_t* data;           // device; output point (ti, tj) reads row ti * h_inc + h_skip, column tj * w_inc + w_skip
+  uint32_t point_step, row_step, off_x, off_y, off_z, is_f64;
+  uint32_t off_t, t_type;        // the time field and its PointField datatype (6 UINT32, 7 FLOAT32, 8 FLOAT64)
+  double t_scale, t_offset;      // t = t_offset + t_scale * raw
+  uint32_t h_skip, h_inc, w_skip, w_inc, out_w, out_h;
+  float range_min, range_max;
+  DeskewKnots knots;
+  uint32_t n_knots;              // in [2, 64]
+  float* origs; float* dirs;     // the operator form: the OnDn model table's two halves, 3 n floats each ...
+  float* points; uint8_t* mask;  // ... and the dataset.  The cloud form: points = n records of 12 bytes, NaN where the mask would be 0
+  uint32_t* counters;            // counter c at word c * kDeskewCounterStride, zeroed by the caller
+};
+hipError_t launch_deskew(const DeskewParams& p, bool cloud_form, hipStream_t s);
 hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s);
 hipError_t launch_pf_extract_weights(const void* attrs, uint32_t n, float* weights, hipStream_t s);
 // rmclhip_surface_params as the kernels take it (surface.hip.h)

@@ -14,6 +14,7 @@
 // (lab_hooks.h), and report kLabMissing (kernels.h) otherwise.
 #include "find_kernel.hip.h"
 #include "lab_hooks.h"
+#include "pc2_load.hip.h"
 #include "pf_common.hip.h"
 #include "pf_random.hip.h"
 #include "reduce_common.hip.h"
@@ -159,11 +160,6 @@ struct Pc2Params {
   uint8_t* mask;
   uint32_t* n_valid;
 };
-
-__device__ __forceinline__ float pc2_load(const uint8_t* p, bool f64) {
-  if (f64) { double d; __builtin_memcpy(&d, p, 8); return static_cast<float>(d); }
-  float f; __builtin_memcpy(&f, p, 4); return f;
-}
 
 __global__ void __launch_bounds__(256) k_pointcloud2_unpack(const Pc2Params p) {
   const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // wave_sum.hip.h -- wave64 sums of per-lane double accumulators through LDS, shared by the streaming reductions
-// (kernels.hip k_reduce_partials, micp.hip k_micp_iter, pose_information.hip).
+// (kernels.hip k_reduce_partials, micp.hip k_micp_iter, pose_information.hip), and the wave64 count of a per-lane flag (deskew.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,5 +25,8 @@ __device__ __forceinline__ double wave_sum16_lds(const double (&v)[16], double* 
   t += __shfl_xor(t, 32, 64);
   return t;
 }
+
+// wave64 sum of a per-lane flag: one ballot.  Every lane of the wave calls it (exited lanes count as 0); all lanes get the total.
+__device__ __forceinline__ uint32_t wave_count(bool b) { return static_cast<uint32_t>(__popcll(__ballot(b))); }
 
 }  // namespace rmclhip

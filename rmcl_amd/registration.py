@@ -120,6 +120,25 @@ def _cloud_bytes(data, device, nbytes):
     return _ptr(buf), buf.size, buf
 
 
+def _motion_arg(motion):
+    """rmclhip_scan_motion of (knots, times): TRANSFORM[K] and float64[K] (wire.scan_motion returns such a pair); the second value
+    keeps the arrays alive over the call"""
+    knots, times = motion
+    k = np.ascontiguousarray(knots, dtype=TRANSFORM).reshape(-1)
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    if len(k) != len(t):
+        raise ValueError("a scan motion holds one time per knot")
+    return _capi.ScanMotion(k.ctypes.data, t.ctypes.data, len(k)), (k, t)
+
+
+def _time_arg(time_field):
+    """rmclhip_pointcloud2_time of (offset, datatype[, scale[, offset_s]]): t = offset_s + scale * raw"""
+    off, dt = int(time_field[0]), int(time_field[1])
+    scale = float(time_field[2]) if len(time_field) > 2 else 1.0
+    offset_s = float(time_field[3]) if len(time_field) > 3 else 0.0
+    return _capi.PointCloud2Time(off, dt, scale, offset_s)
+
+
 class HipMap:
     """Immutable triangle mesh + BVH on the device (rm::EmbreeMap / rm::OptixMap analogue)."""
 
@@ -503,6 +522,30 @@ class CorrespondencesHIP:
             _capi.check(_capi.lib().rmclhip_rcc_set_dataset(self._h, _ptr(p), _ptr(m), len(p), 0))
         self.outdated = True
 
+    _TABLE_FLOATS_PER_RAY = 0   # of the model table inputView() reads back: 3 for O1Dn (directions), 6 for OnDn (origins | directions)
+
+    def inputView(self):
+        """host copy of the operator's inputs (rmclhip_rcc_input_views): the dataset's {points [n, 3], mask [n] or None} and, for
+        O1Dn / OnDn models, {dirs [W * H, 3]} (+ {origs} for OnDn) -- e.g. the compensated points, origins and directions
+        setInputPointCloud2Deskewed wrote"""
+        tab, pts, msk = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        w, h, n = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_rcc_input_views(self._h, C.byref(tab), C.byref(w), C.byref(h), C.byref(pts), C.byref(msk),
+                                                        C.byref(n)))
+        out = {"width": w.value, "height": h.value, "points": np.zeros((n.value, 3), np.float32), "mask": None}
+        if n.value and pts.value:
+            out["points"] = DeviceView(self.ctx, np.float32, 3 * n.value, pts.value).download().reshape(-1, 3)
+        if n.value and msk.value:
+            out["mask"] = DeviceView(self.ctx, np.uint8, n.value, msk.value).download()
+        rays, per = w.value * h.value, self._TABLE_FLOATS_PER_RAY
+        if per and rays and tab.value:
+            t = DeviceView(self.ctx, np.float32, per * rays, tab.value).download()
+            if per == 6:
+                out["origs"], out["dirs"] = t[:3 * rays].reshape(-1, 3), t[3 * rays:].reshape(-1, 3)
+            else:
+                out["dirs"] = t.reshape(-1, 3)
+        return out
+
     def set_dataset_from_ranges(self, ranges):
         """unpackMessage mirror: points = dir*range (+orig), mask = range within model.range"""
         r = np.ascontiguousarray(ranges, dtype=np.float32).reshape(-1)
@@ -829,6 +872,7 @@ class RCCHipSpherical(CorrespondencesHIP):
 
 class RCCHipO1Dn(CorrespondencesHIP):
     """rmcl::RCCEmbreeO1Dn / RCCOptixO1Dn on gfx950 (RCCEmbree.cpp:71-99)."""
+    _TABLE_FLOATS_PER_RAY = 3
 
     def setModel(self, width, height, range_min, range_max, orig, dirs):
         d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
@@ -878,6 +922,7 @@ class RCCHipPinhole(CorrespondencesHIP):
 
 class RCCHipOnDn(CorrespondencesHIP):
     """rmcl::RCCEmbreeOnDn / RCCOptixOnDn on gfx950 (RCCEmbree.cpp:102-130): N origins, N directions."""
+    _TABLE_FLOATS_PER_RAY = 6
 
     def setModel(self, width, height, range_min, range_max, origs, dirs):
         o = np.ascontiguousarray(origs, dtype=np.float32).reshape(-1, 3)
@@ -887,6 +932,30 @@ class RCCHipOnDn(CorrespondencesHIP):
         rng = _capi.Interval(range_min, range_max)
         _capi.check(_capi.lib().rmclhip_rcc_set_model_ondn(self._h, int(width), int(height), rng, _ptr(o), _ptr(d)))
         self._model_shape = (int(height), int(width))
+
+    def setInputPointCloud2Deskewed(self, data, width, height, point_step, row_step, offset_x, offset_y, offset_z, time_field, motion,
+                                    datatype=7, range_min=0.0, range_max=1e30, filter_height=None, filter_width=None,
+                                    device=False, nbytes=None):
+        """A sensor_msgs/PointCloud2 taken while the sensor moved (bytes / uint8 array, or a device pointer with device=True and
+        nbytes) becomes the OnDn model -- every ray from the pose the sensor had when it measured it -- and the dataset in one device
+        pass (rmclhip_rcc_set_input_pointcloud2_deskewed; include/rmclhip.h states the rules).  time_field: (offset, datatype[, scale[,
+        offset_s]]) of the per-point time, t = offset_s + scale * raw; motion: (knots, times) as wire.scan_motion returns them;
+        filter_*: (skip_begin, skip_end, increment) or None.  Returns (width, height, stats dict) after filtering."""
+        L = _capi.PointCloud2Layout(int(width), int(height), int(point_step), int(row_step), int(offset_x),
+                                    int(offset_y), int(offset_z), int(datatype))
+        fh = _capi.Filter1D(*filter_height) if filter_height is not None else None
+        fw = _capi.Filter1D(*filter_width) if filter_width is not None else None
+        ptr, nb, _keep = _cloud_bytes(data, device, nbytes)
+        tf = _time_arg(time_field)
+        mo, _keep_motion = _motion_arg(motion)
+        ow, oh, st = C.c_uint32(0), C.c_uint32(0), _capi.DeskewStats()
+        _capi.check(_capi.lib().rmclhip_rcc_set_input_pointcloud2_deskewed(
+            self._h, ptr, nb, C.byref(L), C.byref(tf), C.byref(fh) if fh is not None else None,
+            C.byref(fw) if fw is not None else None, _capi.Interval(range_min, range_max), int(bool(device)), C.byref(mo),
+            C.byref(ow), C.byref(oh), C.byref(st)))
+        self._model_shape = (oh.value, ow.value)
+        self.outdated = True
+        return ow.value, oh.value, st.as_dict()
 
 
 class CPCHip(CorrespondencesHIP):

@@ -15,6 +15,7 @@ from . import _capi
 from .pf import beams_from_points
 
 FLOAT32, FLOAT64 = 7, 8   # sensor_msgs/PointField datatypes
+UINT32 = 6                # ... of a per-point time field (Ouster t, ns); FLOAT32 (Velodyne time) and FLOAT64 are the others
 
 
 def spherical_from_scan_info(info):
@@ -90,3 +91,62 @@ def pointcloud2_to_scan(ctx, data, width, height, point_step, row_step, offset_x
     _capi.check(_capi.lib().rmclhip_pointcloud2_to_scan(ctx.handle, ptr, nb, C.byref(L), int(bool(device)), Tp, C.byref(model),
                                                         int(flags), optr, 0 if into is None else 1, C.byref(st)))
     return (out, st.as_dict()) if into is None else st.as_dict()
+
+
+def scan_motion(Tsb, base_poses, times, t_ref, subdivide=1, capacity=64):
+    """The motion of a scan from base poses T_x_b (TRANSFORM[n], base in a fixed frame such as odometry) at strictly increasing
+    `times` (seconds): knots T_sref_s(t_k) = ~Tsb * ~T_x_b(t_ref) * T_x_b(t_k) * Tsb with `subdivide` - 1 slerp knots inserted per
+    segment, in double on the host (rmclhip_scan_motion_from_base_poses_host).  Returns (knots TRANSFORM[K], times float64[K]): what
+    the deskewing calls take as `motion`.  The device interpolates between knots by nlerp; 16 knots per 0.3 rad keep that below
+    float resolution (include/rmclhip.h)."""
+    from .types import TRANSFORM, _ptr
+    sb = np.ascontiguousarray(Tsb, dtype=TRANSFORM).reshape(1)
+    P = np.ascontiguousarray(base_poses, dtype=TRANSFORM).reshape(-1)
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    if len(P) != len(t):
+        raise ValueError("one time per base pose")
+    knots, kt, n = np.zeros(int(capacity), TRANSFORM), np.zeros(int(capacity), np.float64), C.c_uint32(0)
+    _capi.check(_capi.lib().rmclhip_scan_motion_from_base_poses_host(_ptr(sb), _ptr(P), _ptr(t), len(P), float(t_ref), int(subdivide),
+                                                                     _ptr(knots), _ptr(kt), int(capacity), C.byref(n)))
+    return knots[:n.value].copy(), kt[:n.value].copy()
+
+
+def pointcloud2_deskew(ctx, data, width, height, point_step, row_step, offset_x, offset_y, offset_z, time_field, motion,
+                       datatype=FLOAT32, range_min=0.0, range_max=1e30, device=False, nbytes=None, into=None):
+    """A cloud taken in motion -> the cloud in the sensor frame of the reference time, on the device, without an operator
+    (rmclhip_pointcloud2_deskew): width * height xyz float32 records, NaN where the point is out of range or has no time.
+    time_field: (offset, datatype[, scale[, offset_s]]); motion: (knots, times) as scan_motion returns them.  into=None: returns
+    (a DeviceArray of 3 * n floats, stats dict); into=device memory of that size: fills it and returns the stats dict.  The records
+    are what RCCHipSpherical.setInputPointCloud2(device=True, point_step=12) and CPCHip.set_dataset(device=True) accept."""
+    from .registration import DeviceArray, _as_ptr, _cloud_bytes, _motion_arg, _time_arg
+    L = _capi.PointCloud2Layout(int(width), int(height), int(point_step), int(row_step), int(offset_x), int(offset_y),
+                                int(offset_z), int(datatype))
+    ptr, nb, _keep = _cloud_bytes(data, device, nbytes)
+    tf = _time_arg(time_field)
+    mo, _keep_motion = _motion_arg(motion)
+    st = _capi.DeskewStats()
+    n = int(width) * int(height)
+    out = DeviceArray(ctx, np.float32, max(3 * n, 1)) if into is None else None
+    optr = C.c_void_p(out.ptr) if into is None else _as_ptr(into)
+    _capi.check(_capi.lib().rmclhip_pointcloud2_deskew(ctx.handle, ptr, nb, C.byref(L), C.byref(tf), int(bool(device)), C.byref(mo),
+                                                       _capi.Interval(range_min, range_max), optr, C.byref(st)))
+    return (out, st.as_dict()) if into is None else st.as_dict()
+
+
+def sample_beams_pointcloud2_deskewed(data, width, height, point_step, row_step, offset_x, offset_y, offset_z, time_field, motion,
+                                      samples, seed, datatype=FLOAT32):
+    """pf.sample_beams_pointcloud2 for a scan taken in motion (rmclhip_pf_sample_beams_pointcloud2_deskewed, a host function): the
+    same draws, every beam with the origin and rotated direction of its point's own pose; an identity motion returns the plain
+    sampler's bytes."""
+    from .registration import _cloud_bytes, _motion_arg, _time_arg
+    from .types import RANGE_MEASUREMENT, _ptr
+    ptr, nb, _keep = _cloud_bytes(data, False, None)
+    L = _capi.PointCloud2Layout(int(width), int(height), int(point_step), int(row_step), int(offset_x), int(offset_y),
+                                int(offset_z), int(datatype))
+    tf = _time_arg(time_field)
+    mo, _keep_motion = _motion_arg(motion)
+    out = np.zeros(int(samples), dtype=RANGE_MEASUREMENT)
+    n = C.c_uint32(0)
+    _capi.check(_capi.lib().rmclhip_pf_sample_beams_pointcloud2_deskewed(ptr, nb, C.byref(L), C.byref(tf), C.byref(mo), int(samples),
+                                                                         int(seed), _ptr(out), C.byref(n)))
+    return out[: n.value].copy()
