@@ -246,6 +246,15 @@ rmclhip_status rmclhip_bvh_build_host(const float* vertices_xyz, uint32_t n_vert
  * Node4 array of rmclhip_bvh_build_host): what the incoherent traversals (particle filter, pose batches) read */
 rmclhip_status rmclhip_bvh_build_host_quantised(const float* vertices_xyz, uint32_t n_vertices, const uint32_t* faces_ijk,
                                                 uint32_t n_faces, uint32_t* qnodes_out, size_t qnodes_capacity_dwords);
+/* the frontier table of the map's tree (pf_tree = 0) or of the particle filter's (1) -- the <= 256 child references at depth 4 where
+ * a scan's rays start, 8 dwords each {lo.xyz hi.x | hi.yz ref pad} -- and its 16 group boxes in the same format: group g = the union
+ * of the stored boxes of table entries 16 g ... 16 g + 15, ref = how many entries it covers, the far point where it covers none.  A
+ * wave tests the groups first and skips the blocks of the table whose groups lie outside its tile's pyramid.  Either buffer may be
+ * null; *n_table / *n_groups receive the entry counts (n_groups is 16, or 0 for an empty table). */
+rmclhip_status rmclhip_bvh_build_host_frontier(const float* vertices_xyz, uint32_t n_vertices, const uint32_t* faces_ijk,
+                                               uint32_t n_faces, int pf_tree, uint32_t* table_out, size_t table_capacity_dwords,
+                                               uint32_t* n_table, uint32_t* groups_out, size_t groups_capacity_dwords,
+                                               uint32_t* n_groups);
 
 /* the particle filter's own tree of the same map: the builder splits ONE BVH2 down to leaves of <= 2 triangles; the map's
  * tree (leaves <= 4, rmclhip_bvh_build_host) and this one are two cuts through it and share the leaf-ordered record

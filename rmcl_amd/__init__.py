@@ -11,7 +11,7 @@ from .pf import (AdaptiveResamplerHip, GladiatorResamplerHip, PCDSensorUpdaterHi
                  TFMotionUpdaterHip, beams_from_points, chol6, combined_forget_rate, constrain_to_surface, init_particles_pose,
                  init_particles_uniform, kld_bound, kld_params, pack_visualization, sample_beams)
 from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, HipMap, MapMap, RCCHipO1Dn,  # noqa: F401
-                           RCCHipOnDn, RCCHipPinhole, RCCHipSpherical, ShardedCorrectorHip, build_bvh_host, build_bvh_host_pf, build_bvh_host_quantised,
+                           RCCHipOnDn, RCCHipPinhole, RCCHipSpherical, ShardedCorrectorHip, build_bvh_host, build_bvh_host_frontier, build_bvh_host_pf, build_bvh_host_quantised,
                            flatten_scene_host, import_hip_map, import_hip_scene, pose_information_p2l, statistics_p2l)
 
 from ._capi import load_lab  # noqa: F401  (experiments library; tools/ and the `lab` tests only)

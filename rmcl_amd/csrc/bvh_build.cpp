@@ -1078,6 +1078,28 @@ void quantise(const std::vector<Node4>& nodes, std::vector<Node4Q>& qnodes, int 
 
 }  // namespace
 
+void frontier_groups_of(const std::vector<Node4C::Child>& table, std::vector<Node4C::Child>& groups) {
+  groups.clear();
+  if (table.empty()) return;
+  Node4C::Child far;
+  far.lo[0] = kFarPoint[0]; far.lo[1] = kFarPoint[1]; far.lo[2] = kFarPoint[2];
+  far.hix = kFarPoint[0]; far.hiy = kFarPoint[1]; far.hiz = kFarPoint[2];
+  far.ref = 0; far.pad = 0;
+  groups.assign(kFrontierGroups, far);
+  for (size_t i = 0; i < table.size() && i < static_cast<size_t>(kFrontierGroups) * kFrontierGroupSize; ++i) {
+    const Node4C::Child& e = table[i];
+    Node4C::Child& g = groups[i / kFrontierGroupSize];
+    if (g.ref == 0) {
+      g = e;
+      g.ref = 1; g.pad = 0;
+      continue;
+    }
+    for (int a = 0; a < 3; ++a) g.lo[a] = std::min(g.lo[a], e.lo[a]);
+    g.hix = std::max(g.hix, e.hix); g.hiy = std::max(g.hiy, e.hiy); g.hiz = std::max(g.hiz, e.hiz);
+    ++g.ref;
+  }
+}
+
 static std::string build_bvh_impl(const float* verts, uint32_t nv, const uint32_t* faces, uint32_t nf, BvhHost& out, uint32_t max_leaf);
 
 // the boundary of the builder: an allocation that fails on a 10 M-face build, or a thread the system refuses, becomes an error string
@@ -1280,6 +1302,8 @@ static std::string build_bvh_impl(const float* verts, uint32_t nv, const uint32_
   // ... and of the filter's tree: the batch traversal of find (kind 24) walks that tree (round 3: its two-triangle leaves make the
   // per-lane triangle loop 6-10 % cheaper for pose batches), whose node indices differ from the map tree's below the top levels
   frontier_of(out.nodes_pf, out.frontier_pf);
+  frontier_groups_of(out.frontier, out.frontier_groups);
+  frontier_groups_of(out.frontier_pf, out.frontier_groups_pf);
 
   out.cnodes.resize(out.nodes.size());
   parallel_chunks(out.nodes.size(), nt, [&](int, size_t lo_i, size_t hi_i) {

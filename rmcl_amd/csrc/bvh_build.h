@@ -32,9 +32,19 @@ struct BvhHost {
   std::vector<Node4Q> qnodes_pf;  // ... and its quantised form, what k_pf_update_* reads
   std::vector<Node4C::Child> frontier;  // <= 4^kFrontierDepth entries {box, ref}: where a scan's rays can start (layout.h)
   std::vector<Node4C::Child> frontier_pf;   // the same for the filter's tree (nodes_pf / qnodes_pf)
+  // group boxes of the two tables (frontier_groups_of): kFrontierGroups entries each, or none for an empty table
+  std::vector<Node4C::Child> frontier_groups, frontier_groups_pf;
   std::vector<TriRec> tris;  // leaf order (shared by both trees)
   BvhInfo info;
 };
+
+// Group boxes of a frontier table: entry g = the union of the STORED boxes of table entries 16 g ... 16 g + 15 (the table lists a
+// depth-2 subtree's entries consecutively, so a tile's few survivors sit in one or two groups).  Always kFrontierGroups entries for a
+// non-empty table: the last group of a table that is no multiple of 16 is short, a group past the table's end is the far point
+// (layout.h: never inside a scene).  A union of stored (already padded) boxes needs no padding of its own: whatever lies outside it
+// lies outside each of them.  ref = the number of entries in the group.
+constexpr uint32_t kFrontierGroupSize = 16, kFrontierGroups = 16;
+void frontier_groups_of(const std::vector<Node4C::Child>& table, std::vector<Node4C::Child>& groups);
 
 // returns empty string on success, else an error message
 // max_leaf: largest leaf of the map's tree (1..kMaxLeafTris)

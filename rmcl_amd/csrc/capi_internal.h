@@ -192,6 +192,9 @@ struct rmclhip_map {
   uint32_t n_frontier = 0;
   uint32_t* d_frontier_pf = nullptr;   // ... of the filter's tree (find kind 24 walks d_qnodes_pf)
   uint32_t n_frontier_pf = 0;
+  // group boxes of the two tables (bvh_build.h frontier_groups_of): 16 x 8 dwords behind each table in ITS allocation, null for a table of <= 64 entries
+  const uint32_t* d_frontier_groups = nullptr;
+  const uint32_t* d_frontier_groups_pf = nullptr;
   uint32_t* d_qnodes_pf = nullptr;  // Node4Q array of the particle filter's own tree (leaves <= kPfLeafTris, same records)
   uint32_t* d_cnodes = nullptr;  // Node4C twins
   uint32_t* d_cnodes16 = nullptr;  // Node16C twins (maps of up to kMaxNodes16 nodes; find kind 32 descends two levels per pass on them), else null

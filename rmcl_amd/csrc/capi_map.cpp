@@ -144,6 +144,30 @@ rmclhip_status rmclhip_bvh_build_host_pf(const float* v, uint32_t nv, const uint
   return RMCLHIP_OK;
 }
 
+rmclhip_status rmclhip_bvh_build_host_frontier(const float* v, uint32_t nv, const uint32_t* f, uint32_t nf, int pf_tree,
+                                              uint32_t* table_out, size_t table_cap, uint32_t* n_table,
+                                              uint32_t* groups_out, size_t groups_cap, uint32_t* n_groups) {
+  ApiGuard guard_("rmclhip_bvh_build_host_frontier");
+  if (!n_table || !n_groups) return fail(RMCLHIP_ERR_INVALID, "bvh_build_host_frontier: null");
+  BvhHost bvh;
+  const std::string err = build_bvh(v, nv, f, nf, bvh);
+  if (!err.empty()) return fail(RMCLHIP_ERR_INVALID, "bvh_build_host_frontier: " + err);
+  const std::vector<Node4C::Child>& table = pf_tree ? bvh.frontier_pf : bvh.frontier;
+  const std::vector<Node4C::Child>& groups = pf_tree ? bvh.frontier_groups_pf : bvh.frontier_groups;
+  const size_t td = table.size() * 8, gd = groups.size() * 8;
+  *n_table = static_cast<uint32_t>(table.size());
+  *n_groups = static_cast<uint32_t>(groups.size());
+  if (table_out) {
+    if (table_cap < td) return fail(RMCLHIP_ERR_INVALID, "bvh_build_host_frontier: table buffer too small");
+    if (td) std::memcpy(table_out, table.data(), td * 4);
+  }
+  if (groups_out) {
+    if (groups_cap < gd) return fail(RMCLHIP_ERR_INVALID, "bvh_build_host_frontier: groups buffer too small");
+    if (gd) std::memcpy(groups_out, groups.data(), gd * 4);
+  }
+  return RMCLHIP_OK;
+}
+
 rmclhip_status rmclhip_bvh_build_host_quantised(const float* v, uint32_t nv, const uint32_t* f, uint32_t nf,
                                                 uint32_t* qnodes_out, size_t qnodes_cap) {
   ApiGuard guard_("rmclhip_bvh_build_host_quantised");
@@ -194,13 +218,21 @@ RMCL_INTERNAL rmclhip_status map_upload(rmclhip_ctx* ctx, const BvhHost& bvh, rm
   const size_t qpb = bvh.qnodes_pf.size() * sizeof(Node4Q);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_qnodes_pf), qpb);
   if (e == hipSuccess) e = hipMemcpy(m->d_qnodes_pf, bvh.qnodes_pf.data(), qpb, hipMemcpyHostToDevice);
-  const size_t fb = bvh.frontier.size() * sizeof(Node4C::Child);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_frontier), std::max<size_t>(fb, 32));
-  if (e == hipSuccess && fb) e = hipMemcpy(m->d_frontier, bvh.frontier.data(), fb, hipMemcpyHostToDevice);
+  // the two frontier tables, each with its group boxes (bvh_build.h frontier_groups_of) behind it in the same allocation; a table of
+  // <= 64 entries is one block of the cull: nothing to skip, the kernels get no group pointer
+  auto upload_frontier = [&](const std::vector<Node4C::Child>& table, const std::vector<Node4C::Child>& groups, uint32_t** d_table,
+                             const uint32_t** d_groups, size_t* bytes) {
+    const size_t fb = table.size() * sizeof(Node4C::Child), gb = groups.size() * sizeof(Node4C::Child);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(d_table), std::max<size_t>(fb + gb, 32));
+    if (e == hipSuccess && fb) e = hipMemcpy(*d_table, table.data(), fb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && gb) e = hipMemcpy(reinterpret_cast<char*>(*d_table) + fb, groups.data(), gb, hipMemcpyHostToDevice);
+    *d_groups = (table.size() > 64 && groups.size() == kFrontierGroups) ? *d_table + fb / 4 : nullptr;
+    *bytes = fb + gb;
+  };
+  size_t fb = 0, fpb = 0;
+  upload_frontier(bvh.frontier, bvh.frontier_groups, &m->d_frontier, &m->d_frontier_groups, &fb);
   m->n_frontier = static_cast<uint32_t>(bvh.frontier.size());
-  const size_t fpb = bvh.frontier_pf.size() * sizeof(Node4C::Child);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_frontier_pf), std::max<size_t>(fpb, 32));
-  if (e == hipSuccess && fpb) e = hipMemcpy(m->d_frontier_pf, bvh.frontier_pf.data(), fpb, hipMemcpyHostToDevice);
+  upload_frontier(bvh.frontier_pf, bvh.frontier_groups_pf, &m->d_frontier_pf, &m->d_frontier_groups_pf, &fpb);
   m->n_frontier_pf = static_cast<uint32_t>(bvh.frontier_pf.size());
   const size_t cb = bvh.cnodes.size() * sizeof(Node4C);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_cnodes), cb);

@@ -420,6 +420,7 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
   p.n_nodes = r->map->info.n_nodes;
   p.frontier = r->map->d_frontier;
   p.n_frontier = r->map->n_frontier;
+  p.frontier_groups = r->map->d_frontier_groups;
   {
     const BvhInfo& bi = r->map->info;
     p.scene_center = mk3(0.5f * (bi.bbox_min[0] + bi.bbox_max[0]), 0.5f * (bi.bbox_min[1] + bi.bbox_max[1]), 0.5f * (bi.bbox_min[2] + bi.bbox_max[2]));
@@ -453,6 +454,7 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
       p.qnodes = r->map->d_qnodes_pf;
       p.frontier = r->map->d_frontier_pf;
       p.n_frontier = r->map->n_frontier_pf;
+      p.frontier_groups = r->map->d_frontier_groups_pf;
       need = r->map->info.stack_need_pf;
     }
     // The frontier start pre-loads a lane's stack (up to 19 entries for kind 23, 12 for kind 24, more for the quad kind); map_upload's

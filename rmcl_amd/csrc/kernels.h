@@ -74,6 +74,9 @@ struct FindParams {
   float mom_gate_lo, mom_gate_hi, mom_rho_cap, mom_tau_cap;   // devmath.h micp_gate_class
   double* mom_partials;                // [gridDim.x][kMicpFastMoments]
   unsigned long long* mom_unc_mask;    // [4 * gridDim.x]: bit l of word t = lane l of (virtual) tile t holds an undecided correspondence
+  // kind 32: the group boxes of `frontier` (bvh_build.h frontier_groups_of), 16 x 8 dwords in the table's format: entry g = the union of
+  // table entries 16 g ... 16 g + 15; null when n_frontier <= 64.  (Last: the kernels of the other kinds keep their argument offsets.)
+  const uint32_t* frontier_groups;
 };
 
 // what follows the reduction launch (capi_internal.h ReduceTail): nothing, the finalize launch or the batch solve launch

@@ -1364,6 +1364,25 @@ __device__ __forceinline__ bool box_in_pyramid(const WavePyramid& w, f3 O2, f3 l
   return ok;
 }
 
+// The scalar-plane form (kPairs = false) as a WAVE MASK: bit l = lane l's box is not outside the pyramid.  The same four values from the
+// same expressions in the same order, compared as in the bool form (NaN keeps) -- but each compare goes straight to a scalar pair
+// and the four are combined by three scalar ANDs, where the compiler packs the bool form's four results through 16-bit VALU ops
+// (17 VALU and four s_nop per box).  The descent wants the ballots anyway; a lane gets its own bit back at no VALU cost with
+// __builtin_amdgcn_inverse_ballot_w64.  Every lane of the wave must be active.
+__device__ __forceinline__ uint64_t box_in_pyramid_mask(const WavePyramid& w, f3 O2, f3 lo, f3 hi) {
+  const f3 c2 = mk3((lo.x + hi.x) - O2.x, (lo.y + hi.y) - O2.y, (lo.z + hi.z) - O2.z);
+  const f3 h2 = mk3(hi.x - lo.x, hi.y - lo.y, hi.z - lo.z);
+  uint64_t m = ~0ull;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float nx = (q & 1) ? w.nx[q >> 1].y : w.nx[q >> 1].x, ny = (q & 1) ? w.ny[q >> 1].y : w.ny[q >> 1].x;
+    const float nz = (q & 1) ? w.nz[q >> 1].y : w.nz[q >> 1].x, o2 = (q & 1) ? w.off2[q >> 1].y : w.off2[q >> 1].x;
+    const float v = fmaf(fabsf(nz), h2.z, fmaf(fabsf(ny), h2.y, fmaf(fabsf(nx), h2.x, fmaf(nz, c2.z, fmaf(ny, c2.y, nx * c2.x)))));
+    m &= __ballot(!(v < o2));
+  }
+  return m;
+}
+
 // Frontier start: instead of walking the top levels of the tree, the wave culls the map's frontier table (the <= 256 child
 // references of BFS depth kFrontierDepth with their boxes) against the pyramid of its tile, then every lane tests the few
 // survivors against its own ray and starts with the accepted ones on its stack, the two nearest on top.
@@ -1493,7 +1512,8 @@ constexpr uint32_t kDescentWaveDwords = (kDescentCap + 2u * kDescentInnerCap) * 
 // kCarry (kCoop only): accepted candidates stay undivided through the leaf loop (TriPending) -- a kernel of its own, chosen per launch
 template <int kRows, int kRow0, bool kCoop = false, bool kCarry = false>
 __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __restrict__ frontier, uint32_t n_frontier,
-                                                             const uint32_t* __restrict__ cnodes, const uint32_t* __restrict__ cnodes16,
+                                                             const uint32_t* __restrict__ groups, const uint32_t* __restrict__ cnodes,
+                                                             const uint32_t* __restrict__ cnodes16,
                                                              f3 scene_center, float scene_half_diag,
                                                              const float* __restrict__ planes, quat Rsm, float tfar, f3 O, f3 D,
                                                              const RaySlab& rs, float ray_tfar, uint32_t lane, uint32_t* __restrict__ lds_col,
@@ -1507,7 +1527,7 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
   // everything in flight has arrived -- 0 entry, 1 frontier + planes here, 2 culled, 3 lists written, 4 + 2 L nodes of level L here,
   // 5 + 2 L level L compacted (L < 3), 10 final list lane-resident, 11 every ray has seen every entry; 12 levels descended; 13 / 14 (flags, not
   // clocks, with dbg_levels): the wave started at the root after all -- a ray entered more final leaves than the leaf cap / a lane's stack
-  // was left without room
+  // was left without room; 15 (flags): bits 0..3 the blocks of the cull that ran
 #define RMCL_STAMP(i) { if (stamps != nullptr) { uint64_t t_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : : "memory"); stamps[i] = static_cast<uint32_t>(t_); } }
   RMCL_STAMP(0)
   if constexpr (kCoop) { seed->t = ray_tfar; seed->rec = kNone; }
@@ -1517,6 +1537,15 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
   root.cur = active ? 0u : kDone;
   root.sp = static_cast<uint32_t>(kRow0);
   if (n_frontier == 0u) return root;
+  // the table's group boxes (bvh_build.h frontier_groups_of; null for a table of one block): lane l takes group l & 15.  Requested with
+  // the entries and ahead of them -- no round trip of its own, and the first to arrive
+  const bool grouped = groups != nullptr;   // (wave-uniform)
+  uint4 ga = uint4{0u, 0u, 0u, 0u}, gb = uint4{0u, 0u, 0u, 0u};
+  if (grouped) {
+    const uint4* Gt = reinterpret_cast<const uint4*>(groups);
+    ga = Gt[2u * (lane & 15u)];
+    gb = Gt[2u * (lane & 15u) + 1u];
+  }
   const uint4* Ft = reinterpret_cast<const uint4*>(frontier);
   uint4 ea[4], eb[4];
 #pragma unroll
@@ -1532,12 +1561,26 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
   RMCL_STAMP(1)
   const f3 O2 = mk3(2.0f * O.x, 2.0f * O.y, 2.0f * O.z);
   // a box {a.xyz = lo, a.w b.x b.y = hi} against the pyramid
-  auto in_pyramid = [&](const uint4& a, const uint4& b) -> bool {
-    return box_in_pyramid<false>(pyr, O2, mk3(asf(a.x), asf(a.y), asf(a.z)), mk3(asf(a.w), asf(b.x), asf(b.y)));
+  auto in_pyramid = [&](const uint4& a, const uint4& b) -> uint64_t {
+    return box_in_pyramid_mask(pyr, O2, mk3(asf(a.x), asf(a.y), asf(a.z)), mk3(asf(a.w), asf(b.x), asf(b.y)));
   };
-  bool acc[4];
+  // The cull by groups.  A narrow pyramid keeps 2 - 3 of the 256 entries, and the table lists a depth-2 subtree's 16 entries side by
+  // side: they sit in one or two groups.  Bit g of gmask: group g's box -- the union of the stored boxes of entries 16 g ... 16 g + 15 --
+  // is not outside the pyramid (the same conservative test; a group past the table's end holds the far point, whose entries the index
+  // test below drops anyway).  Block k of the cull holds groups 4 k ... 4 k + 3 (lane l: entry l + 64 k); a block none of whose groups
+  // is kept is not tested: every entry in it lies inside a box outside the pyramid, so no ray of the wave can reach it.
+  uint32_t gmask = 0xFFFFu;
+  if (grouped) gmask = static_cast<uint32_t>(in_pyramid(ga, gb)) & 0xFFFFu;
+  // which entries survive, which of them are inner nodes (wave masks; lane l's own bit of block k: inverse_ballot(m_all[k]))
+  uint64_t m_all[4] = {0ull, 0ull, 0ull, 0ull}, m_in[4] = {0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-  for (uint32_t k = 0; k < 4u; ++k) acc[k] = ((lane + 64u * k) < n_frontier) && in_pyramid(ea[k], eb[k]);
+  for (uint32_t k = 0; k < 4u; ++k) {
+    if ((gmask & (0xFu << (4u * k))) != 0u) {   // wave-uniform
+      m_all[k] = __ballot((lane + 64u * k) < n_frontier) & in_pyramid(ea[k], eb[k]);
+      m_in[k] = m_all[k] & __ballot(!(eb[k].z & kLeafBit));
+      if (stamps != nullptr) stamps[15] |= 1u << k;
+    }
+  }
 
   uint32_t first_ref = kDone, first_key = 0xFFFFFFFFu, second_ref = kDone, second_key = 0xFFFFFFFFu, sp = static_cast<uint32_t>(kRow0);
   // one entry {box, ref} (wave-uniform values) against this lane's ray: the traversal's own slab test; the two nearest accepted entries
@@ -1563,13 +1606,9 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
     }
   };
 
-  // how many entries survive, how many of them are inner nodes (wave-uniform)
-  uint64_t m_all[4], m_in[4];
   uint32_t n_surv = 0, n_inner = 0;
 #pragma unroll
   for (uint32_t k = 0; k < 4u; ++k) {
-    m_all[k] = __ballot(acc[k]);
-    m_in[k] = __ballot(acc[k] && !(eb[k].z & kLeafBit));
     n_surv += static_cast<uint32_t>(__popcll(m_all[k]));
     n_inner += static_cast<uint32_t>(__popcll(m_in[k]));
   }
@@ -1585,8 +1624,9 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
     uint32_t nF = 0, nA = 0;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
+      if (m_all[k] == 0ull) continue;   // wave-uniform: a block without survivors (skipped by its groups, or culled entry by entry)
       const uint64_t m_lf = m_all[k] & ~m_in[k];
-      if (acc[k]) {
+      if (__builtin_amdgcn_inverse_ballot_w64(m_all[k])) {
         const bool inner = !(eb[k].z & kLeafBit);
         const uint32_t idx = inner ? nA + static_cast<uint32_t>(__popcll(m_in[k] & lt)) : nF + static_cast<uint32_t>(__popcll(m_lf & lt));
         uint4* dst = inner ? Acur : Fl;
@@ -1625,10 +1665,11 @@ __device__ __forceinline__ TraceStart frontier_descent_start(const uint32_t* __r
         const uint4 ca = cn[0], cb = cn[1];
         if (base == 0u) { if (levels == 0u) RMCL_STAMP(4) else if (levels == 1u) RMCL_STAMP(6) else if (levels == 2u) RMCL_STAMP(8) }
         // (an unused child slot holds the far point, layout.h: never inside a scene -- but possibly inside an unbounded pyramid)
-        const bool ok = have && (asf(ca.x) < 1.0e29f) && in_pyramid(ca, cb);
+        const uint64_t okm = __ballot(have && (asf(ca.x) < 1.0e29f)) & in_pyramid(ca, cb);
         const bool inner = !(cb.z & kLeafBit);
-        const uint64_t mi = __ballot(ok && inner), ml = __ballot(ok && !inner);
-        if (ok) {
+        const uint64_t innerm = __ballot(inner);
+        const uint64_t mi = okm & innerm, ml = okm & ~innerm;
+        if (__builtin_amdgcn_inverse_ballot_w64(okm)) {
           const uint32_t idx = inner ? nAn + static_cast<uint32_t>(__popcll(mi & lt)) : nFn + static_cast<uint32_t>(__popcll(ml & lt));
           if (idx < (inner ? kDescentInnerCap : kDescentCap)) {
             uint4* dst = inner ? Anext : Fl;

@@ -287,6 +287,19 @@ def build_bvh_host_quantised(vertices, faces, n_nodes):
     return q
 
 
+def build_bvh_host_frontier(vertices, faces, pf_tree=False):
+    """the frontier table of the map's tree (or of the filter's) and its group boxes (host only): (table[n, 8] u32, groups[16, 8] u32),
+    both rows {lo.xyz hi.x | hi.yz ref pad}; a group's ref is the number of table entries 16 g ... 16 g + 15 it covers."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    table = np.zeros((256, 8), dtype=np.uint32)
+    groups = np.zeros((16, 8), dtype=np.uint32)
+    nt, ng = C.c_uint32(0), C.c_uint32(0)
+    _capi.check(_capi.lib().rmclhip_bvh_build_host_frontier(_ptr(v), len(v), _ptr(f), len(f), 1 if pf_tree else 0, _ptr(table), table.size,
+                                                            C.byref(nt), _ptr(groups), groups.size, C.byref(ng)))
+    return table[:nt.value].copy(), groups[:ng.value].copy()
+
+
 # the five bundle attributes in the C ABI's argument order (rmclhip_rcc_download, rmclhip_bundle_views)
 _ATTRS = ("hits", "ranges", "points", "normals", "face_ids")
 _ATTR_BIT = dict(hits=_capi.OUT_HITS, ranges=_capi.OUT_RANGES, points=_capi.OUT_POINTS, normals=_capi.OUT_NORMALS, face_ids=_capi.OUT_FACE_IDS)
