@@ -71,6 +71,15 @@ rmclhip_status rmclhip_rcc_set_descent(rmclhip_rcc* rcc, uint32_t final_cap, uin
  * default, 64), so that what runs on an XCD at a time -- one L2 -- sees one region of the map instead of one pose's whole scan.
  * Results do not depend on it.  Exported by librmclhip.so. */
 rmclhip_status rmclhip_rcc_set_batch_order(rmclhip_rcc* rcc, int on);
+/* TEST read-back of the order of the LAST batch launch this operator enqueued (find_batch, correct_batch, simulate with several poses;
+ * tests/test_gpu_pose_batch.py): *n_out = its number of order entries, nposes x *ngroups_out (nullable; the workgroups of one pose) --
+ * 0 when that launch went pose-major (world order off, fewer than two poses, more than 65 535 workgroups per pose).  keys_out[pose *
+ * ngroups + g] = the sort key (cell 0 .. 4095) of workgroup g of that pose; order_out[s] = pose << 16 | g of the s-th workgroup of the
+ * sorted list.  Host buffers of `cap` words each, filled after a stream synchronisation; either may be null, both null only queries n;
+ * cap < n: RMCLHIP_ERR_INVALID.  The values live in the operator's scratch until its next batch launch.  Changes nothing; works
+ * without the experiments library. */
+rmclhip_status rmclhip_debug_batch_order(rmclhip_rcc* rcc, uint32_t* keys_out, uint32_t* order_out, size_t cap, uint32_t* n_out,
+                                         uint32_t* ngroups_out);
 
 /* TEST knob of the loopback communicator (rmclhip_comm_create_loopback): its all-reduce adds the ranks' contributions starting at
  * `first_rank` instead of rank 0 -- the freedom a real collective library has.  Whatever must not depend on the library's order of

@@ -247,6 +247,7 @@ struct rmclhip_rcc {
   uint32_t tuned_xcd_mapping = 0;  // rmclhip_rcc_autotune's choice among 0 / 1 / 2 (FindParams::xcd_mapping); 0 = the default
   uint32_t batch_order = 64;   // 0 = pose-major; else the granule (workgroups per XCD turn)
   DevBuf<uint32_t> d_ord_scratch, d_ord_vals;
+  uint32_t last_order_n = 0, last_order_ngroups = 0;   // entries / workgroups per pose of the last batch launch's order, 0 = it went pose-major (rmclhip_debug_batch_order)
   bool descent_carry = false;   // kind 32: accepted candidates stay undivided through the cooperative leaf loop (traverse.hip.h TriPending); set by the autotune where it measures faster, or by rmclhip_rcc_set_descent's bit 16
   uint32_t descent_leaf_cap = 24;   // kind 32: a wave one of whose rays enters more final leaves than this starts at the root (lab: rmclhip_rcc_set_descent)
   uint32_t out_mask = RMCLHIP_OUT_ALL;   // rmclhip_rcc_set_outputs: which model buffers find / find_batch write

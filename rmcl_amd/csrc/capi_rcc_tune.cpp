@@ -452,6 +452,7 @@ rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* r, const rmclhip_transform*
 // all included (profiles/r06_batch_order_ab.txt).  On by default; rmclhip_rcc_set_batch_order(rcc, 0) restores the pose-major launch (A/B).
 RMCL_INTERNAL rmclhip_status batch_order_enqueue(rmclhip_rcc* r, FindParams& p, int variant) {
   const uint32_t ntiles = p.tiles_x * p.tiles_y, group = (variant == 2) ? 1u : 4u, ngroups = (ntiles + group - 1u) / group;
+  r->last_order_n = 0; r->last_order_ngroups = 0;   // (what rmclhip_debug_batch_order reports of a pose-major launch)
   if (r->batch_order == 0u || p.nposes < 2u || ngroups > 65535u || p.nposes > 32768u || p.Tsm_arr == nullptr) return RMCLHIP_OK;
   const uint32_t n = ngroups * p.nposes;
   HIPCHK(r->d_ord_scratch.reserve(batch_order_scratch_dwords(n))); HIPCHK(r->d_ord_vals.reserve(n));
@@ -461,6 +462,26 @@ RMCL_INTERNAL rmclhip_status batch_order_enqueue(rmclhip_rcc* r, FindParams& p, 
   p.tile_order = r->d_ord_vals.p;
   p.n_tile_order = n;
   p.tile_order_granule = r->batch_order;
+  r->last_order_n = n; r->last_order_ngroups = ngroups;
+  return RMCLHIP_OK;
+}
+
+// TEST read-back of that order (include/rmclhip_lab.h): the keys and the sorted list of the last batch launch, as they lie in the
+// operator's scratch -- the next batch launch overwrites them
+rmclhip_status rmclhip_debug_batch_order(rmclhip_rcc* r, uint32_t* keys_out, uint32_t* order_out, size_t cap, uint32_t* n_out,
+                                         uint32_t* ngroups_out) {
+  ApiGuard guard_("rmclhip_debug_batch_order");
+  if (!r || !n_out) return fail(RMCLHIP_ERR_INVALID, "debug_batch_order: null");
+  const uint32_t n = r->last_order_n;
+  *n_out = n;
+  if (ngroups_out) *ngroups_out = r->last_order_ngroups;
+  if (!keys_out && !order_out) return RMCLHIP_OK;   // (a query of n)
+  if (cap < n) return fail(RMCLHIP_ERR_INVALID, "debug_batch_order: buffer too small");
+  if (n == 0u) return RMCLHIP_OK;
+  HIPCHK(hipSetDevice(r->ctx->device));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  if (keys_out) HIPCHK(hipMemcpy(keys_out, r->d_ord_scratch.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  if (order_out) HIPCHK(hipMemcpy(order_out, r->d_ord_vals.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
   return RMCLHIP_OK;
 }
 

@@ -752,6 +752,22 @@ class CorrespondencesHIP:
         _capi.check(_capi.lib().rmclhip_debug_micp_moments(self._h, _ptr(tot), C.byref(rows), C.byref(unc)))
         return tot, rows.value, unc.value
 
+    def set_batch_order(self, on):
+        """pose batches in world order (rmclhip_rcc_set_batch_order, include/rmclhip_lab.h): 0 = the pose-major launch, 1 = the default
+        granule (64 workgroups per XCD turn), any other value = that granule"""
+        _capi.check(_capi.lib().rmclhip_rcc_set_batch_order(self._h, int(on)))
+
+    def debug_batch_order(self):
+        """diagnostics: (keys, order, ngroups) of the last batch launch (rmclhip_debug_batch_order): keys[pose * ngroups + g] = the sort
+        cell of workgroup g of that pose, order[s] = pose << 16 | g of the s-th workgroup launched; empty arrays when the launch went
+        pose-major"""
+        n, ng = C.c_uint32(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_debug_batch_order(self._h, None, None, 0, C.byref(n), C.byref(ng)))
+        keys, order = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            _capi.check(_capi.lib().rmclhip_debug_batch_order(self._h, _ptr(keys), _ptr(order), n.value, C.byref(n), C.byref(ng)))
+        return keys, order, ng.value
+
     def debug_probe_find(self, Tbm_est, mode=0):
         """diagnostics: per-wave step timeline of one spherical scan -> uint32 array [n_tiles, 256, 2]"""
         T = np.ascontiguousarray(Tbm_est, dtype=TRANSFORM).reshape(1)

@@ -112,13 +112,16 @@ def correct_once_multi(mesh, sensors, Tom, n_iter, convergence_progress=0.0, wan
 
 def correct_batch(mesh, model, Tsb, Tbm, ds_points, ds_mask, max_dist, nthreads=1):
     """v1 SphereCorrector::correct: per pose raycast + reduce (Tpre = I) + Umeyama;
-    Tdelta_b = Tsb * T_s * ~Tsb."""
+    Tdelta_b = Tsb * T_s * ~Tsb.  `model`: a SphericalModel, or any model simulate_model takes."""
     Tbm = np.asarray(Tbm, dtype=orc.TRANSFORM).reshape(-1)
     out = np.zeros(len(Tbm), dtype=orc.TRANSFORM)
     stats = np.zeros(len(Tbm), dtype=orc.CROSS_STATISTICS)
     ident = orc.transform()
     for i in range(len(Tbm)):
-        sim = mesh.simulate_spherical(model, Tsb, Tbm[i], bvh=True, nthreads=nthreads)
+        if isinstance(model, dict):
+            sim = simulate_model(mesh, model, Tsb, Tbm[i])
+        else:
+            sim = mesh.simulate_spherical(model, Tsb, Tbm[i], bvh=True, nthreads=nthreads)
         s = orc.statistics_p2l_exact(ident, ds_points, ds_mask, sim["points"], sim["normals"], sim["hits"], max_dist)
         Ts = orc.umeyama(s)
         out[i] = orc.tmult(orc.tmult(Tsb, Ts), orc.tinv(Tsb))

@@ -551,10 +551,13 @@ def test_pose_batch_in_world_order_equals_the_pose_major_launch_and_the_oracle(r
     rcc.setTsb(syn.tsb_offset())
     rcc.setModel(model)
     rcc.set_traversal(variant)
+    far = np.array([T.transform_from_rpy((500.0, 20.0, 3.0), (0.0, 0.0, 1.0))] * 37, dtype=T.TRANSFORM)   # beyond the range limit: every ray misses
     out = {}
     for on in (0, 1, 3):     # pose-major, the default granule, three workgroups per XCD turn
         _capi.check(_capi.lib().rmclhip_rcc_set_batch_order(rcc._h, on))
         for P in (poses, poses[:2]):
+            rcc.find_batch(far[:len(P)])   # what a slot that the measured launch never computes would keep: misses, not the call before's right answer
+            assert not rcc.modelView(("hits",))["hits"].any()
             rcc.find_batch(P)
             mv = rcc.modelView()
             out[(on, len(P))] = {k: np.array(mv[k]) for k in ("hits", "ranges", "points", "normals", "face_ids")}
