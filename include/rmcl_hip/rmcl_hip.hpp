@@ -1202,6 +1202,64 @@ struct ParticleUpdater<VRAM_HIP> {
                                        const ParticleUpdateConfig& config = {}) = 0;
 };
 
+// The distance field of a map (include/rmclhip.h, DISTANCE FIELD): a lattice of distances to the closest triangle, built on the
+// device once.  Shared via shared_ptr; an updater it is set on (PCDSensorUpdaterHip::setField) keeps the device memory alive too.
+struct FieldParams : rmclhip_field_params {
+  FieldParams() { rmclhip_field_params_default(this); }
+  FieldParams(float cell_, float margin_) { rmclhip_field_params_default(this); cell = cell_; margin = margin_; }
+};
+using FieldInfo = rmclhip_field_info;
+class DistanceFieldHip {
+ public:
+  explicit DistanceFieldHip(HipMapPtr map, const FieldParams& params = FieldParams()) : map_(std::move(map)) {
+    if (!map_) throw std::runtime_error("NO MAP");
+    check(rmclhip_field_create(map_->context()->handle(), map_->handle(), &params, &h_));
+  }
+  ~DistanceFieldHip() { rmclhip_field_destroy(h_); }
+  DistanceFieldHip(const DistanceFieldHip&) = delete;
+  DistanceFieldHip& operator=(const DistanceFieldHip&) = delete;
+  // the geometry a field over this box gets: no device needed
+  static FieldInfo layout(const float (&bbox_min)[3], const float (&bbox_max)[3], const FieldParams& params = FieldParams()) {
+    FieldInfo i{};
+    check(rmclhip_field_layout_host(bbox_min, bbox_max, &params, &i));
+    return i;
+  }
+  FieldInfo info() const {
+    FieldInfo i{};
+    check(rmclhip_field_get_info(h_, &i));
+    return i;
+  }
+  // the node values, x fastest, then y, then z
+  std::vector<float> download() const {
+    std::vector<float> out(static_cast<size_t>(info().n_nodes));
+    check(rmclhip_field_download(h_, out.data(), out.size()));
+    return out;
+  }
+  // the lookup at points in map coordinates: host memory in, host memory out
+  std::vector<float> query(const std::vector<Vector>& points) const {
+    std::vector<float> out(points.size());
+    check(rmclhip_field_query(h_, points.empty() ? nullptr : &points[0].x, points.size(), 0, out.data()));
+    return out;
+  }
+  // ... and on device memory of the field's context
+  void query(DeviceView<const Vector> points, DeviceView<float> distances) const {
+    if (distances.size() < points.size()) throw std::runtime_error("DistanceFieldHip::query: distances.size() < points.size()");
+    check(rmclhip_field_query(h_, points.size() ? &points.raw()->x : nullptr, points.size(), 1, distances.raw()));
+  }
+  DeviceView<const float> lattice() const {
+    const float* p = nullptr;
+    check(rmclhip_field_device_view(h_, &p));
+    return DeviceView<const float>{p, static_cast<size_t>(info().n_nodes)};
+  }
+  rmclhip_field* handle() const { return h_; }
+  const HipMapPtr& map() const { return map_; }
+
+ private:
+  HipMapPtr map_;
+  rmclhip_field* h_ = nullptr;
+};
+using DistanceFieldHipPtr = std::shared_ptr<DistanceFieldHip>;
+
 // rmcl::PCDSensorUpdaterOptix on gfx950.  setInput() takes the already sampled measurements (sensor frame)
 // and Tsb; sampling from a PointCloud2 and the TF lookup stay with the ROS-side caller
 // (PCDSensorUpdaterEmbree.cpp:249-327).
@@ -1241,11 +1299,24 @@ class PCDSensorUpdaterHip : public SensorUpdaterBase, public ParticleUpdater<VRA
                             static_cast<uint32_t>(beams_.size()), &Tsb_));
     return {};
   }
+  // config_.correspondence_type 1 answered from a distance field of this updater's map (nullptr: off, the tree query); the updater
+  // shares the field's ownership
+  void setField(DistanceFieldHipPtr field) {
+    init();
+    check(rmclhip_pf_set_field(h_, field ? field->handle() : nullptr));
+    field_ = std::move(field);
+  }
+  // the per-beam errors of the next updates land here ([n_particles * n_beams] floats of device memory; nullptr: off)
+  void setErrorOutput(float* errors_dev) {
+    init();
+    check(rmclhip_pf_set_error_output(h_, errors_dev));
+  }
   rmclhip_pf* handle() const { return h_; }
 
  private:
   HipMapPtr map_;
   rmclhip_pf* h_ = nullptr;
+  DistanceFieldHipPtr field_;
   std::vector<RangeMeasurement> beams_;
   Transform Tsb_ = identity();
 };
@@ -1444,6 +1515,8 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
   // the surface constraint of motionUpdate and step on every device's block (nullopt: off), and the standalone pass on the sharded
   // cloud; the devices' counts are summed on the host
   void setSurface(const std::optional<SurfaceParams>& params) { check(rmclhip_pf_sharded_set_surface(h_, params ? &*params : nullptr)); }
+  // config_.correspondence_type 1 answered by lookup: every device builds the distance field of its copy of the map (nullopt: off)
+  void setField(const std::optional<FieldParams>& params) { check(rmclhip_pf_sharded_set_field(h_, params ? &*params : nullptr)); }
   SurfaceStats constrainToSurface(const SurfaceParams& params) {
     SurfaceStats st{};
     check(rmclhip_pf_sharded_set_params(h_, &config_));

@@ -166,6 +166,7 @@ typedef struct rmclhip_resampler rmclhip_resampler;
 typedef struct rmclhip_comm rmclhip_comm;              /* RCCL communicators of one process driving several devices */
 typedef struct rmclhip_pf_sharded rmclhip_pf_sharded;  /* a particle cloud block-partitioned over those devices */
 typedef struct rmclhip_rcc_sharded rmclhip_rcc_sharded; /* one correspondence operator per device: pose batches block-partitioned */
+typedef struct rmclhip_field rmclhip_field;            /* the distance field of a map: a lattice of distances to the closest triangle */
 
 /* ---- library ------------------------------------------------------------------ */
 const char* rmclhip_last_error(void);
@@ -1214,6 +1215,84 @@ void rmclhip_pose_covariance_params_default(rmclhip_pose_covariance_params* out)
  * n_meas == 0 with sigma > 0: every direction is degenerate. */
 rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
                                             rmclhip_pose_covariance* out);
+
+/* ---- DISTANCE FIELD: the closest-point sensor update by lookup ----------------------------------------------------
+ * sensor_update.correspondence_type 1 (evaluate_cpc) scores a beam by the distance of its end point to the surface: the likelihood
+ * is smooth in the pose, without the grazing-ray cliffs of ray casting -- what AMCL users know as the likelihood-field model, and the
+ * mode a global localisation wants.  The map is immutable, so that distance can be tabulated once: a distance field is a regular
+ * lattice of float32 distances to the closest triangle, built on the device from a map.  With a field attached (rmclhip_pf_set_field)
+ * the sensor update answers correspondence_type 1 from the lattice -- eight loads and a trilinear blend per beam, no tree.  A handle
+ * without a field returns the bytes it returned before this interface existed.
+ *
+ * THE GEOMETRY.  Every operation is in float32 unless it says double; the library is built without contraction
+ * (tests/field_ref.py restates this in numpy).
+ *   - Per axis k: ext_k = (bbox_max_k - bbox_min_k) + 2 * margin and origin_k = bbox_min_k - margin.
+ *   - Automatic cell (params.cell == 0): cell = float(cbrt(max(ext_x, 1e-3) * max(ext_y, 1e-3) * max(ext_z, 1e-3) / 2e6)), in double.
+ *     This is the near grid's size rule.
+ *   - n_k = max(2, uint(ceil(ext_k / cell)) + 1) nodes.
+ *   - inv_cell = 1.0f / cell.
+ *   - Node (i, j, k) lies at origin + (float(i) * cell, float(j) * cell, float(k) * cell), product first, then sum.
+ *   - Node value: the distance the library's own closest-point query reports for that point: sqrtf(d2) of the query of
+ *     rmclhip_rcc_find_cpc / correspondence_type 1 (smallest d2, then smallest face id).  A node whose query finds nothing stores NaN.
+ *   The build runs coarse to fine: every 16th node per axis first, then every 4th, then all, each level's queries starting from the
+ *   triangle the level before found for the nearest node -- an actual candidate, so the values are those of unseeded queries, and the
+ *   same map and parameters give the same bytes on every device.
+ *
+ * THE LOOKUP at a point P (map coordinates).
+ *   - If any component of P fails |P_k| <= FLT_MAX, the result is NaN.
+ *   - u_k = (P_k - origin_k) * inv_cell.
+ *   - c_k = min(max(u_k, 0), float(n_k - 1)).
+ *   - i_k = min(int(floor(c_k)), n_k - 2).
+ *   - f_k = c_k - float(i_k).
+ *   - lerp(a, b, f) = a + f * (b - a).  Lerp four times along x, twice along y, once along z.  Call the result d.
+ *   - Axis k is clamped when u_k < 0 or u_k > float(n_k - 1).  o_k = P_k - (origin_k + c_k * cell) on clamped axes, and 0 on the others.
+ *     If any axis is clamped, the result is d + sqrtf((o_x^2 + o_y^2) + o_z^2).  Otherwise it is d.
+ *
+ * WHAT THIS GUARANTEES.  The distance d(P) to the surface is 1-Lipschitz, and the blend's weights w_c over the cell's corners c
+ * satisfy sum_c w_c |c - P| <= sqrt(sum_k cell^2 f_k (1 - f_k)) <= (sqrt(3) / 2) cell.
+ *   - Inside the lattice, |lookup - d(P)| <= (sqrt(3) / 2) * cell plus rounding.
+ *   - Outside, the lookup never reports less than d(P) - (sqrt(3) / 2) * cell.  It may report up to twice the distance to the box more. */
+typedef struct {
+  float cell;          /* node spacing in metres; 0 (the default): automatic */
+  float margin;        /* the lattice extends this far beyond the map's box on every side; default 0 */
+  uint64_t max_nodes;  /* a lattice of more nodes is refused; default 2^26 (256 MiB) */
+} rmclhip_field_params;
+void rmclhip_field_params_default(rmclhip_field_params* out);
+typedef struct {
+  uint32_t n[3];       /* nodes per axis */
+  float origin[3];     /* node (0, 0, 0) */
+  float cell, inv_cell;
+  uint64_t n_nodes, bytes;
+} rmclhip_field_info;
+/* host only, no device needed: the geometry rmclhip_field_create will use for a map with this box.  RMCLHIP_ERR_INVALID: cell or margin
+ * negative or not finite, a box that is not finite or has min > max, a lattice of more than max_nodes nodes.  params NULL: the defaults */
+rmclhip_status rmclhip_field_layout_host(const float bbox_min[3], const float bbox_max[3], const rmclhip_field_params* params,
+                                         rmclhip_field_info* info_out);
+/* builds the field of `map` on its device and waits for it.  The field retains the map and is immutable; its bytes are added to the
+ * map's device_bytes (rmclhip_map_get_info) while it lives.  Refused with RMCLHIP_ERR_INVALID before anything is launched: what
+ * rmclhip_field_layout_host refuses, and a map with no faces.  rmclhip_field_destroy drops the creator's reference: a filter handle
+ * the field is set on keeps it alive */
+rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_params* params, rmclhip_field** out);
+void rmclhip_field_destroy(rmclhip_field* field);
+rmclhip_status rmclhip_field_get_info(const rmclhip_field* field, rmclhip_field_info* out);
+/* the node values to host memory, x fastest, then y, then z; capacity: floats `out` has room for (>= n_nodes) */
+rmclhip_status rmclhip_field_download(rmclhip_field* field, float* out, size_t capacity);
+/* the lattice in device memory, in rmclhip_field_download's order; valid while the field lives, read only */
+rmclhip_status rmclhip_field_device_view(const rmclhip_field* field, const float** lattice_dev);
+/* the lookup alone for n points (xyz triples, map coordinates).  points_on_device != 0: points_xyz and distances_out are device
+ * memory of the field's device; else host memory.  n == 0: RMCLHIP_OK, nothing is touched; null pointers with n > 0: RMCLHIP_ERR_INVALID */
+rmclhip_status rmclhip_field_query(rmclhip_field* field, const float* points_xyz, size_t n, int points_on_device, float* distances_out);
+/* later rmclhip_pf_update[_async] calls on this handle answer correspondence_type 1 from the field: per (particle, beam) the end point
+ * Tsm * orig + (Tsm.R * dir) * range exactly as without a field, the error is the lookup there (a NaN error poisons the particle, as it
+ * does without a field), evaluated and merged in beam order as correspondence_type 1 is -- the in-order chain, bit for bit for the
+ * same errors; n_meas is exact.  rmclhip_pf_set_error_output works as in every other mode; rmclhip_pf_set_mapping / _set_variant are
+ * not read (one dealing, results do not depend on it).  NULL switches it off; a fresh handle has it off.  The handle keeps a reference
+ * to the field.  RMCLHIP_ERR_INVALID if the field is of another map.  While a field is set and correspondence_type != 1,
+ * rmclhip_pf_update[_async] return RMCLHIP_ERR_INVALID and touch nothing */
+rmclhip_status rmclhip_pf_set_field(rmclhip_pf* pf, rmclhip_field* field);
+/* every replica builds its own field from its own copy of the map (the build is deterministic: all replicas hold the same bytes) and
+ * sets it on its filter handle, replacing an earlier one; NULL switches it off */
+rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* pf, const rmclhip_field_params* params);
 
 /* ---- device memory helpers for hosts without their own allocator ---------------------- */
 rmclhip_status rmclhip_malloc(rmclhip_ctx* ctx, size_t bytes, void** out_dev);

@@ -14,6 +14,9 @@ from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, Hip
                            RCCHipOnDn, RCCHipPinhole, RCCHipSpherical, ShardedCorrectorHip, build_bvh_host, build_bvh_host_frontier, build_bvh_host_pf, build_bvh_host_quantised,
                            flatten_scene_host, import_hip_map, import_hip_scene, pose_information_p2l, statistics_p2l)
 
+from . import field  # noqa: F401
+from .field import DistanceFieldHip, field_layout, field_params  # noqa: F401
+
 from ._capi import load_lab  # noqa: F401  (experiments library; tools/ and the `lab` tests only)
 
 __version__ = "0.1.0"

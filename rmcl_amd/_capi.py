@@ -169,6 +169,21 @@ class DeskewStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class FieldParams(C.Structure):
+    """rmclhip_field_params (the distance field's lattice: cell 0 = automatic)"""
+    _fields_ = [("cell", C.c_float), ("margin", C.c_float), ("max_nodes", C.c_uint64)]
+
+
+class FieldInfo(C.Structure):
+    """rmclhip_field_info"""
+    _fields_ = [("n", C.c_uint32 * 3), ("origin", C.c_float * 3), ("cell", C.c_float), ("inv_cell", C.c_float),
+                ("n_nodes", C.c_uint64), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {"n": tuple(int(x) for x in self.n), "origin": tuple(float(x) for x in self.origin), "cell": float(self.cell),
+                "inv_cell": float(self.inv_cell), "n_nodes": int(self.n_nodes), "bytes": int(self.bytes)}
+
+
 PC2SCAN_TRUE_ELEVATION, PC2SCAN_FLOOR, PC2SCAN_WRAP_THETA, PC2SCAN_NEAREST = 1, 2, 4, 8
 SEG_PINT_WITH_ORIGIN = 1
 SEG_NONE, SEG_INLIER, SEG_OUTLIER_SCAN, SEG_OUTLIER_MAP = 0, 1, 2, 3
@@ -374,6 +389,16 @@ SIGNATURES = {
     "rmclhip_pose_information_solve_host": (_i32, [_vp, _dbl, _vp]),
     "rmclhip_pose_covariance_params_default": (None, [C.POINTER(PoseCovarianceParams)]),
     "rmclhip_pose_covariance_host": (_i32, [_vp, C.POINTER(PoseCovarianceParams), _vp]),
+    "rmclhip_field_params_default": (None, [C.POINTER(FieldParams)]),
+    "rmclhip_field_layout_host": (_i32, [_vp, _vp, C.POINTER(FieldParams), C.POINTER(FieldInfo)]),
+    "rmclhip_field_create": (_i32, [_vp, _vp, C.POINTER(FieldParams), _pp]),
+    "rmclhip_field_destroy": (None, [_vp]),
+    "rmclhip_field_get_info": (_i32, [_vp, C.POINTER(FieldInfo)]),
+    "rmclhip_field_download": (_i32, [_vp, _vp, _sz]),
+    "rmclhip_field_device_view": (_i32, [_vp, _pp]),
+    "rmclhip_field_query": (_i32, [_vp, _vp, _sz, _i32, _vp]),
+    "rmclhip_pf_set_field": (_i32, [_vp, _vp]),
+    "rmclhip_pf_sharded_set_field": (_i32, [_vp, C.POINTER(FieldParams)]),
     "rmclhip_malloc": (_i32, [_vp, _sz, _pp]),
     "rmclhip_free": (_i32, [_vp, _vp]),
     "rmclhip_memcpy_h2d": (_i32, [_vp, _vp, _vp, _sz]),

@@ -1,0 +1,253 @@
+// capi_field.cpp -- see capi_internal.h
+#include "capi_internal.h"
+
+// ---- the map's distance field (include/rmclhip.h, DISTANCE FIELD, states the geometry and the lookup; kernels: field.hip) ----
+void rmclhip_field_params_default(rmclhip_field_params* out) {
+  if (!out) return;
+  out->cell = 0.0f;
+  out->margin = 0.0f;
+  out->max_nodes = 1ull << 26;
+}
+
+// the geometry of a field over [bmin, bmax], in the header's operation order
+static rmclhip_status field_layout(const std::string& who, const float* bmin, const float* bmax, const rmclhip_field_params* params,
+                                   rmclhip_field_info* out) {
+  rmclhip_field_params p;
+  rmclhip_field_params_default(&p);
+  if (params) p = *params;
+  if (!std::isfinite(p.cell) || p.cell < 0.0f) return fail(RMCLHIP_ERR_INVALID, who + ": cell must be finite and >= 0 (0: automatic)");
+  if (!std::isfinite(p.margin) || p.margin < 0.0f) return fail(RMCLHIP_ERR_INVALID, who + ": margin must be finite and >= 0");
+  float ext[3];
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(bmin[k]) || !std::isfinite(bmax[k]) || bmin[k] > bmax[k]) return fail(RMCLHIP_ERR_INVALID, who + ": the box is not finite or has min > max");
+    ext[k] = (bmax[k] - bmin[k]) + 2.0f * p.margin;
+    out->origin[k] = bmin[k] - p.margin;
+    if (!std::isfinite(ext[k]) || !std::isfinite(out->origin[k])) return fail(RMCLHIP_ERR_INVALID, who + ": the box plus its margin overflows float32");
+  }
+  float cell = p.cell;
+  if (cell == 0.0f) {
+    const double vol = std::max(static_cast<double>(ext[0]), 1e-3) * std::max(static_cast<double>(ext[1]), 1e-3) * std::max(static_cast<double>(ext[2]), 1e-3);
+    cell = static_cast<float>(std::cbrt(vol / 2.0e6));
+  }
+  if (!(cell > 0.0f) || !std::isfinite(cell) || !std::isfinite(1.0f / cell)) return fail(RMCLHIP_ERR_INVALID, who + ": the cell size is not a positive float32");
+  const std::string too_many = who + ": the lattice has more than max_nodes nodes (a larger cell, a smaller margin, or a larger max_nodes)";
+  uint64_t total = 1;
+  for (int k = 0; k < 3; ++k) {
+    const float steps = std::ceil(ext[k] / cell);
+    if (!(steps < 2147483648.0f)) return fail(RMCLHIP_ERR_INVALID, too_many);
+    out->n[k] = std::max(2u, static_cast<uint32_t>(steps) + 1u);
+    if (out->n[k] > p.max_nodes / total) return fail(RMCLHIP_ERR_INVALID, too_many);   // total * n_k > max_nodes, without the overflow
+    total *= out->n[k];
+  }
+  out->cell = cell;
+  out->inv_cell = 1.0f / cell;
+  out->n_nodes = total;
+  out->bytes = total * sizeof(float);
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_field_layout_host(const float* bbox_min, const float* bbox_max, const rmclhip_field_params* params, rmclhip_field_info* info_out) {
+  ApiGuard guard_("rmclhip_field_layout_host");
+  if (!bbox_min || !bbox_max || !info_out) return fail(RMCLHIP_ERR_INVALID, "field_layout_host: null");
+  std::memset(info_out, 0, sizeof(*info_out));
+  rmclhip_field_info info{};
+  if (rmclhip_status st = field_layout("field_layout_host", bbox_min, bbox_max, params, &info)) return st;
+  *info_out = info;
+  return RMCLHIP_OK;
+}
+
+static FieldView field_view(const rmclhip_field* fd) {
+  FieldView v;
+  v.lat = fd->d_lat;
+  for (int k = 0; k < 3; ++k) { v.n[k] = fd->info.n[k]; v.origin[k] = fd->info.origin[k]; }
+  v.cell = fd->info.cell;
+  v.inv_cell = fd->info.inv_cell;
+  return v;
+}
+
+RMCL_INTERNAL void field_release(rmclhip_field* fd) {
+  if (!fd || fd->refs.fetch_sub(1) != 1) return;
+  (void)hipSetDevice(fd->ctx->device);
+  if (fd->stream) (void)hipStreamSynchronize(fd->stream);
+  fd->d_q_points.release(); fd->d_q_out.release();
+  if (fd->d_lat) {
+    (void)hipFree(fd->d_lat);
+    std::lock_guard<std::mutex> lock(fd->map->grid_mtx);
+    fd->map->bytes -= fd->info.bytes;
+  }
+  if (fd->stream) (void)hipStreamDestroy(fd->stream);
+  rmclhip_map_release(fd->map);
+  ctx_release(fd->ctx);
+  delete fd;
+}
+
+// Coarse to fine, as ensure_near_grid builds the near grid: the nodes far from any surface are the expensive, unbounded queries, and
+// there are 4096 x fewer of them at every 16th node per axis than in the lattice.  Each level leaves the record it found per node;
+// the next starts every query from the record of the previous level's nearest node.
+static rmclhip_status field_build(rmclhip_field* fd) {
+  const rmclhip_map* m = fd->map;
+  FieldBuildParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.nodes = m->d_nodes;
+  p.tris = m->d_tris;
+  p.n_tris = m->info.n_records;
+  p.fv = field_view(fd);
+  const uint32_t n_max = std::max(fd->info.n[0], std::max(fd->info.n[1], fd->info.n[2]));
+  uint32_t* d_prev = nullptr;
+  uint32_t* d_rec = nullptr;
+  hipError_t e = hipSuccess;
+  for (uint32_t stride = 16u; stride >= 1u && e == hipSuccess; stride >>= 2) {
+    if (stride > 1u && n_max <= 2u * stride) continue;   // a level of two nodes per axis prunes nothing
+    p.stride = stride;
+    size_t total = 1;
+    for (int k = 0; k < 3; ++k) { p.cn[k] = (fd->info.n[k] - 1u) / stride + 1u; total *= p.cn[k]; }
+    p.seed_rec = d_prev;
+    d_rec = nullptr;
+    if (stride > 1u) e = hipMalloc(reinterpret_cast<void**>(&d_rec), total * sizeof(uint32_t));
+    p.rec_out = d_rec;
+    p.dist_out = (stride == 1u) ? fd->d_lat : nullptr;
+    if (e == hipSuccess) e = launch_field_build(p, fd->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(fd->stream);
+    if (d_prev) (void)hipFree(d_prev);
+    d_prev = d_rec;
+    p.pstride = stride;
+    for (int k = 0; k < 3; ++k) p.pn[k] = p.cn[k];
+  }
+  if (d_prev) (void)hipFree(d_prev);
+  if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("field_create: ") + hipGetErrorString(e));
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_params* params, rmclhip_field** out) {
+  ApiGuard guard_("rmclhip_field_create");
+  if (!out) return fail(RMCLHIP_ERR_INVALID, "field_create: out is null");
+  *out = nullptr;
+  if (!ctx || !map) return fail(RMCLHIP_ERR_INVALID, "field_create: NO MAP");
+  if (map->ctx != ctx) return fail(RMCLHIP_ERR_INVALID, "field_create: the map belongs to another context");
+  rmclhip_field_info info{};
+  if (rmclhip_status st = field_layout("field_create", map->info.bbox_min, map->info.bbox_max, params, &info)) return st;
+  if (map->info.n_faces == 0u || map->info.n_records == 0u) return fail(RMCLHIP_ERR_INVALID, "field_create: the map has no faces");
+  HIPCHK(hipSetDevice(ctx->device));
+  rmclhip_field* fd = new rmclhip_field();
+  fd->ctx = ctx;
+  ctx_retain(ctx);
+  fd->map = map;
+  rmclhip_map_retain(map);
+  fd->info = info;
+  hipError_t e = hipStreamCreateWithFlags(&fd->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) {
+    e = hipMalloc(reinterpret_cast<void**>(&fd->d_lat), info.bytes);
+    if (e == hipSuccess) {
+      std::lock_guard<std::mutex> lock(map->grid_mtx);
+      map->bytes += info.bytes;
+    } else {
+      fd->d_lat = nullptr;
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    field_release(fd);
+    return fail(e == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string("field_create: ") + hipGetErrorString(e));
+  }
+  if (rmclhip_status st = field_build(fd)) {
+    field_release(fd);
+    return st;
+  }
+  *out = fd;
+  return RMCLHIP_OK;
+}
+
+void rmclhip_field_destroy(rmclhip_field* field) {
+  ApiGuard guard_("rmclhip_field_destroy");
+  field_release(field);
+}
+
+rmclhip_status rmclhip_field_get_info(const rmclhip_field* field, rmclhip_field_info* out) {
+  ApiGuard guard_("rmclhip_field_get_info");
+  if (!field || !out) return fail(RMCLHIP_ERR_INVALID, "field_get_info: null");
+  *out = field->info;
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_field_download(rmclhip_field* field, float* out, size_t capacity) {
+  ApiGuard guard_("rmclhip_field_download");
+  if (!field || !out) return fail(RMCLHIP_ERR_INVALID, "field_download: null");
+  if (capacity < field->info.n_nodes) return fail(RMCLHIP_ERR_INVALID, "field_download: capacity is smaller than n_nodes");
+  HIPCHK(hipSetDevice(field->ctx->device));
+  std::lock_guard<std::mutex> lock(field->mtx);
+  HIPCHK(upload_on(field->stream, out, field->d_lat, field->info.bytes, hipMemcpyDeviceToHost));
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_field_device_view(const rmclhip_field* field, const float** lattice_dev) {
+  ApiGuard guard_("rmclhip_field_device_view");
+  if (!field || !lattice_dev) return fail(RMCLHIP_ERR_INVALID, "field_device_view: null");
+  *lattice_dev = field->d_lat;
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_field_query(rmclhip_field* field, const float* points_xyz, size_t n, int points_on_device, float* distances_out) {
+  ApiGuard guard_("rmclhip_field_query");
+  if (!field) return fail(RMCLHIP_ERR_INVALID, "field_query: null");
+  if (n == 0) return RMCLHIP_OK;
+  if (!points_xyz || !distances_out) return fail(RMCLHIP_ERR_INVALID, "field_query: null buffers");
+  HIPCHK(hipSetDevice(field->ctx->device));
+  std::lock_guard<std::mutex> lock(field->mtx);
+  const FieldView fv = field_view(field);
+  if (points_on_device) {
+    HIPCHK(launch_field_query(fv, points_xyz, n, distances_out, field->stream));
+    HIPCHK(hipStreamSynchronize(field->stream));
+    return RMCLHIP_OK;
+  }
+  HIPCHK(field->d_q_points.reserve(3u * n));
+  HIPCHK(field->d_q_out.reserve(n));
+  HIPCHK(upload_on(field->stream, field->d_q_points.p, points_xyz, 3u * n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(launch_field_query(fv, field->d_q_points.p, n, field->d_q_out.p, field->stream));
+  HIPCHK(upload_on(field->stream, distances_out, field->d_q_out.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_pf_set_field(rmclhip_pf* f, rmclhip_field* field) {
+  ApiGuard guard_("rmclhip_pf_set_field");
+  if (!f) return fail(RMCLHIP_ERR_INVALID, "pf_set_field: null");
+  if (field && field->map != f->map) return fail(RMCLHIP_ERR_INVALID, "pf_set_field: the field is of another map");
+  if (field == f->field) return RMCLHIP_OK;
+  // an update in flight on the handle's stream may still read the old lattice
+  if (f->field) {
+    HIPCHK(hipSetDevice(f->ctx->device));
+    HIPCHK(hipStreamSynchronize(f->stream));
+  }
+  if (field) field->refs.fetch_add(1);
+  field_release(f->field);
+  f->field = field;
+  return RMCLHIP_OK;
+}
+
+// rmclhip_pf_update[_async] with a field set (capi_pf.cpp pf_enqueue): the beams are on the device already
+RMCL_INTERNAL rmclhip_status pf_field_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, rmclhip_particle_attributes* attrs, uint32_t n, uint32_t n_beams,
+                                              const rmclhip_transform* Tsb) {
+  if (f->params.correspondence_type != 1u)
+    return fail(RMCLHIP_ERR_INVALID, "pf_update: a distance field is set (rmclhip_pf_set_field), which answers correspondence_type 1 only");
+  if (n_beams > 8192u) return fail(RMCLHIP_ERR_UNSUPPORTED, "pf_update: more than 8192 beams");
+  PfFieldParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.fv = field_view(f->field);
+  p.poses = reinterpret_cast<const xform*>(poses);
+  p.attrs = attrs;
+  p.n_particles = n;
+  p.beams = f->d_beams.p;
+  p.n_beams = n_beams;
+  p.Tsb = to_x(Tsb);
+  p.dist_sigma = f->params.dist_sigma;
+  p.max_n_meas = f->params.max_n_meas;
+  p.errors = f->errors_dev;
+  // particles per workgroup as pf_enqueue deals them: ~2048 beams per workgroup, at most 64 particles; small clouds take fewer until
+  // the launch has ~4 workgroups per CU, but never less than one beam per lane
+  uint32_t pb = 2048u / n_beams;
+  if (pb < 1u) pb = 1u;
+  if (pb > 64u) pb = 64u;
+  while (pb > 1u && n / pb < 1024u && static_cast<uint64_t>(pb >> 1) * n_beams >= 256u) pb >>= 1;
+  p.particles_per_block = pb;
+  HIPCHK(launch_pf_update_field(p, f->stream));
+  return RMCLHIP_OK;
+}

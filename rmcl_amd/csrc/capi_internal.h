@@ -7,6 +7,7 @@
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
 //   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
+//   capi_field.cpp     the map's distance field: layout, coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field.hip)
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
 //   capi_pose_information.cpp the point-to-plane information matrix of a find's correspondences and its host algebra: covariance, degeneracy (kernels: pose_information.hip)
@@ -208,6 +209,19 @@ struct rmclhip_map {
   struct GridSlot { bool ready = false, failed = false; NearGrid g = {}; };
   GridSlot grid_slot[2];
   std::vector<uint32_t> scene_first_face;  // map_create_scene: first global face id of every instance, + the total (else empty)
+};
+
+// the distance field of a map (capi_field.cpp): the lattice, immutable once built; handles that read it (rmclhip_pf_set_field) hold a
+// reference.  `stream` and the two staging buffers serve rmclhip_field_query / _download alone, one call at a time (mtx).
+struct rmclhip_field {
+  rmclhip_ctx* ctx = nullptr;
+  rmclhip_map* map = nullptr;
+  std::atomic<int> refs{1};
+  rmclhip_field_info info{};
+  float* d_lat = nullptr;
+  std::mutex mtx;
+  hipStream_t stream = nullptr;
+  DevBuf<float> d_q_points, d_q_out;
 };
 
 struct rmclhip_rcc {
@@ -449,6 +463,7 @@ struct rmclhip_pf {
   uint32_t* d_surf = nullptr;
   uint32_t* h_surf = nullptr;
   uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: borrowed device memory, one word per particle of the next constrained launches
+  rmclhip_field* field = nullptr;  // rmclhip_pf_set_field (capi_field.cpp): correspondence_type 1 is answered from this lattice; the handle holds a reference
 };
 
 // GladiatorResamplerGPU analogue: owns a stream and the scratch of the {sum, max} reduction
@@ -562,4 +577,8 @@ RMCL_INTERNAL rmclhip_status pose_hypotheses_run(const char* who, rmclhip_resamp
 // capi_rcc.cpp: the stream and host-mapped scratch of the free functions on caller-owned views (rmclhip_statistics_p2l,
 // rmclhip_pose_information_p2l), created by the first call; the caller holds ctx->p2l_mtx
 RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx);
+// capi_field.cpp: a reference less on a field (the last one frees it; null: nothing), and the sensor update answered from f->field
+RMCL_INTERNAL void field_release(rmclhip_field* fd);
+RMCL_INTERNAL rmclhip_status pf_field_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, rmclhip_particle_attributes* attrs, uint32_t n, uint32_t n_beams,
+                                              const rmclhip_transform* Tsb);
 //@@DECLS@@

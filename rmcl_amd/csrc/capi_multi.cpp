@@ -706,6 +706,27 @@ rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* h, const rmclh
   return RMCLHIP_OK;
 }
 
+// ---- the distance field on the sharded cloud (capi_field.cpp has the single-device entry points) ----
+// every replica builds its own field from its own copy of the map; its filter handle keeps the only reference
+rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip_field_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_field");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_field: null");
+  if (params) {   // refuse before any replica is touched
+    rmclhip_field_info info;
+    for (PfRank& R : h->ranks)
+      if (rmclhip_status st = rmclhip_field_layout_host(R.map->info.bbox_min, R.map->info.bbox_max, params, &info)) return st;
+  }
+  for (PfRank& R : h->ranks) {
+    rmclhip_field* fd = nullptr;
+    if (params)
+      if (rmclhip_status st = rmclhip_field_create(R.ctx, R.map, params, &fd)) return st;
+    const rmclhip_status st = rmclhip_pf_set_field(R.pf, fd);
+    rmclhip_field_destroy(fd);
+    if (st) return st;
+  }
+  return RMCLHIP_OK;
+}
+
 // the sum of every device's last counts (ranks without particles launched nothing: their block is skipped)
 static void pf_sharded_sum_surface_stats(rmclhip_pf_sharded* h, rmclhip_surface_stats* out) {
   std::memset(out, 0, sizeof(*out));

@@ -33,6 +33,7 @@ void rmclhip_pf_destroy(rmclhip_pf* f) {
   if (f->stream) (void)hipStreamSynchronize(f->stream);
   f->d_beams.release(); f->d_evals.release(); f->d_gpow.release(); f->d_order.release(); f->tag.destroy();
   pf_surface_release(f);
+  field_release(f->field);
   if (f->h_beams) (void)hipHostFree(f->h_beams);
   if (f->ev0) (void)hipEventDestroy(f->ev0);
   if (f->ev1) (void)hipEventDestroy(f->ev1);
@@ -94,6 +95,7 @@ static rmclhip_status pf_upload_beams(rmclhip_pf* f, const rmclhip_range_measure
 
 static rmclhip_status pf_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, rmclhip_particle_attributes* attrs,
                                  uint32_t n, uint32_t n_beams, const rmclhip_transform* Tsb) {
+  if (f->field) return pf_field_enqueue(f, poses, attrs, n, n_beams, Tsb);   // rmclhip_pf_set_field: no tree is touched
   PfParams p;
   std::memset(&p, 0, sizeof(p));
   p.nodes = f->map->d_nodes;
@@ -198,6 +200,8 @@ rmclhip_status rmclhip_pf_update_async(rmclhip_pf* f, const rmclhip_transform* p
   if (!f || !Tsb) return fail(RMCLHIP_ERR_INVALID, "pf_update: null");
   if (n == 0 || n_beams == 0) return RMCLHIP_OK;
   if (!poses || !attrs || !beams) return fail(RMCLHIP_ERR_INVALID, "pf_update: null buffers");
+  if (f->field && f->params.correspondence_type != 1u)
+    return fail(RMCLHIP_ERR_INVALID, "pf_update: a distance field is set (rmclhip_pf_set_field), which answers correspondence_type 1 only");
   HIPCHK(hipSetDevice(f->ctx->device));
   if (rmclhip_status st = pf_upload_beams(f, beams, n_beams)) return st;
   return pf_enqueue(f, poses, attrs, n, n_beams, Tsb);

@@ -1,0 +1,160 @@
+// field.hip -- the map's distance field (include/rmclhip.h, DISTANCE FIELD, states the geometry and the lookup).
+//
+//   k_field_build     one lane per node of one level of the coarse-to-fine build: the library's closest-point query
+//                     (nearest_lane_ww, min d2 then min face id) at the node, started from the record the previous level found for
+//                     the node nearest to it -- an actual candidate, so the result is the unseeded query's
+//   k_field_query     the lookup alone, one lane per point
+//   k_pf_update_field the sensor update of correspondence_type 1 answered from the lattice: k_pf_update<64, 3> (pf_common.hip.h) with
+//                     the tree query replaced by the lookup -- same Tsm, same end point, same evaluation, same in-order merge.  No
+//                     traversal, no stack: LDS holds the workgroup's Tsm and its beam evaluations only.
+//
+// The lookup is eight dependent gathers and seven lerps in a stated float order (the library is built without contraction).  Rays are
+// dealt beam-minor: the lanes of a wave hold consecutive beams of one particle, Tsm is a wave-uniform LDS read, and the end points of
+// neighbouring beams fall into neighbouring cells.
+#include "pf_common.hip.h"
+
+namespace rmclhip {
+namespace {
+
+__device__ __forceinline__ float field_lerp(float a, float b, float f) { return a + f * (b - a); }
+
+// include/rmclhip.h, "the lookup at a point P", line by line
+__device__ __forceinline__ float field_lookup(const FieldView& fv, f3 P) {
+  const float pk[3] = {P.x, P.y, P.z};
+  if (!((fabsf(pk[0]) <= 3.402823466e38f) && (fabsf(pk[1]) <= 3.402823466e38f) && (fabsf(pk[2]) <= 3.402823466e38f)))
+    return __uint_as_float(0x7FC00000u);
+  uint32_t i[3];
+  float f[3], o[3];
+  bool clamped = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float top = static_cast<float>(fv.n[k] - 1u);
+    const float u = (pk[k] - fv.origin[k]) * fv.inv_cell;
+    const float c = fminf(fmaxf(u, 0.0f), top);
+    i[k] = min(static_cast<uint32_t>(static_cast<int>(floorf(c))), fv.n[k] - 2u);
+    f[k] = c - static_cast<float>(i[k]);
+    const bool out = (u < 0.0f) || (u > top);
+    o[k] = out ? pk[k] - (fv.origin[k] + c * fv.cell) : 0.0f;
+    clamped = clamped || out;
+  }
+  const size_t nx = fv.n[0], nxy = nx * fv.n[1];
+  const float* c0 = fv.lat + (static_cast<size_t>(i[2]) * nxy + static_cast<size_t>(i[1]) * nx + i[0]);
+  // the two x-neighbours of a corner pair are adjacent in memory
+  const float v000 = c0[0], v100 = c0[1], v010 = c0[nx], v110 = c0[nx + 1u];
+  const float v001 = c0[nxy], v101 = c0[nxy + 1u], v011 = c0[nxy + nx], v111 = c0[nxy + nx + 1u];
+  const float x00 = field_lerp(v000, v100, f[0]), x10 = field_lerp(v010, v110, f[0]);
+  const float x01 = field_lerp(v001, v101, f[0]), x11 = field_lerp(v011, v111, f[0]);
+  const float y0 = field_lerp(x00, x10, f[1]), y1 = field_lerp(x01, x11, f[1]);
+  const float d = field_lerp(y0, y1, f[2]);
+  return clamped ? d + sqrtf((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) : d;
+}
+
+__global__ void __launch_bounds__(256) k_field_build(const FieldBuildParams p) {
+  extern __shared__ uint32_t lds_dyn[];
+  const size_t total = static_cast<size_t>(p.cn[0]) * p.cn[1] * p.cn[2];
+  const size_t id = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
+  const bool live = id < total;
+  const size_t ii = live ? id : 0u;
+  const uint32_t cx = static_cast<uint32_t>(ii % p.cn[0]);
+  const size_t cyz = ii / p.cn[0];
+  const uint32_t cy = static_cast<uint32_t>(cyz % p.cn[1]), cz = static_cast<uint32_t>(cyz / p.cn[1]);
+  const uint32_t ix = cx * p.stride, iy = cy * p.stride, iz = cz * p.stride;   // < n: cn = (n - 1) / stride + 1
+  // node (i, j, k): origin + (float(i) cell, float(j) cell, float(k) cell), product first, then sum
+  const f3 P = mk3(p.fv.origin[0] + static_cast<float>(ix) * p.fv.cell, p.fv.origin[1] + static_cast<float>(iy) * p.fv.cell,
+                   p.fv.origin[2] + static_cast<float>(iz) * p.fv.cell);
+  const bool ok = live && (P.x == P.x) && (P.y == P.y) && (P.z == P.z);
+  uint32_t sr = kNone;
+  if (p.seed_rec != nullptr && ok) {
+    const uint32_t px = min((ix + p.pstride / 2u) / p.pstride, p.pn[0] - 1u), py = min((iy + p.pstride / 2u) / p.pstride, p.pn[1] - 1u),
+                   pz = min((iz + p.pstride / 2u) / p.pstride, p.pn[2] - 1u);
+    sr = p.seed_rec[(static_cast<size_t>(pz) * p.pn[1] + py) * p.pn[0] + px];
+  }
+  NearHit seed = near_seed_from_record(p.tris, sr, p.n_tris, P, ok);
+  // a record whose distance overflows to NaN is no bound (k_pf_update<64, 3>: its bound check)
+  if (!(seed.d2 <= 3.0e38f)) { seed.d2 = 3.0e38f; seed.face = kInvalidFace; seed.rec = 0; seed.p = mk3(0.f, 0.f, 0.f); }
+  NearHit nh;
+  nearest_lane_ww<16>(p.nodes, p.tris, P, ok, lds_dyn + threadIdx.x, 256u, nh, &seed);
+  if (!live) return;
+  const bool found = nh.face != kInvalidFace;
+  if (p.rec_out != nullptr) p.rec_out[id] = found ? nh.rec : kNone;
+  if (p.dist_out != nullptr) p.dist_out[id] = found ? sqrtf(nh.d2) : __uint_as_float(0x7FC00000u);
+}
+
+__global__ void __launch_bounds__(256) k_field_query(const FieldView fv, const float* __restrict__ points, size_t n, float* __restrict__ out) {
+  const size_t id = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
+  if (id >= n) return;
+  const float* pp = points + 3u * id;
+  out[id] = field_lookup(fv, mk3(pp[0], pp[1], pp[2]));
+}
+
+__global__ void __launch_bounds__(256) k_pf_update_field(const PfFieldParams p) {
+  // LDS: [ Tsm (PB xforms) | evals (PB * n_beams floats) ]
+  extern __shared__ uint32_t lds_dyn[];
+  xform* s_Tsm = reinterpret_cast<xform*>(lds_dyn);
+  float* s_eval = reinterpret_cast<float*>(s_Tsm + p.particles_per_block);
+
+  const uint32_t PB = p.particles_per_block;
+  const uint32_t p0 = blockIdx.x * PB;
+  if (p0 >= p.n_particles) return;
+  const uint32_t np = min(PB, p.n_particles - p0);
+  if (threadIdx.x < np) s_Tsm[threadIdx.x] = xmul(p.poses[p0 + threadIdx.x], p.Tsb);
+  __syncthreads();
+
+  const float sq = p.dist_sigma * p.dist_sigma;
+  const uint32_t nrays = np * p.n_beams;
+  for (uint32_t r = threadIdx.x; r < nrays; r += 256u) {
+    const uint32_t pi = r / p.n_beams, b = r - pi * p.n_beams;
+    const xform Tsm = s_Tsm[pi];
+    const float* bm = p.beams + 16u * b;
+    // meas_m = Tsm * meas_s; evaluate_cpc: the distance of meas_m.mean() = orig + dir * range to the surface (k_pf_update<64, 3>)
+    const f3 dir = qrot(Tsm.R, mk3(bm[3], bm[4], bm[5]));
+    const f3 org = xapply(Tsm, mk3(bm[0], bm[1], bm[2]));
+    const f3 mean = add3(org, scale3(dir, bm[6]));
+    const float error = field_lookup(p.fv, mean);
+    if (p.errors) p.errors[static_cast<size_t>(p0 + pi) * p.n_beams + b] = error;
+    const float arg = -(error * error) / sq / 2;
+    s_eval[r] = static_cast<float>(exp(static_cast<double>(arg)) / sqrt(static_cast<double>(2 * sq) * 3.14159265358979323846));
+  }
+  __syncthreads();
+  // in-order merge, one lane per particle (sequential semantics of sensorUpdate)
+  if (threadIdx.x < np) {
+    pattrs* A = reinterpret_cast<pattrs*>(p.attrs) + (p0 + threadIdx.x);
+    g1d L = A->likelihood;
+    const float* ev = s_eval + threadIdx.x * p.n_beams;
+    for (uint32_t b = 0; b < p.n_beams; ++b) {
+      g1d m; m.mean = ev[b]; m.sigma = 0.0f; m.n_meas = 1;
+      L = g1d_add(L, m);
+      L.n_meas = min(L.n_meas, p.max_n_meas);
+    }
+    A->likelihood = L;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_field_build(const FieldBuildParams& p, hipStream_t s) {
+  const size_t total = static_cast<size_t>(p.cn[0]) * p.cn[1] * p.cn[2];
+  if (total == 0u) return hipSuccess;
+  const size_t blocks = (total + 255u) / 256u;
+  if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_field_build, dim3(static_cast<uint32_t>(blocks)), dim3(256), 16u * 256u * sizeof(uint32_t), s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_field_query(const FieldView& fv, const float* points, size_t n, float* out, hipStream_t s) {
+  if (n == 0u) return hipSuccess;
+  const size_t blocks = (n + 255u) / 256u;
+  if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_field_query, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, fv, points, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s) {
+  const uint32_t nblocks = (p.n_particles + p.particles_per_block - 1u) / p.particles_per_block;
+  const size_t lds = sizeof(xform) * p.particles_per_block + sizeof(float) * static_cast<size_t>(p.particles_per_block) * p.n_beams;
+  if (lds > 65536u) return hipErrorInvalidValue;   // the caller deals at most 8192 beams to a workgroup
+  hipLaunchKernelGGL(k_pf_update_field, dim3(nblocks), dim3(256), lds, s, p);
+  return hipGetLastError();
+}
+
+}  // namespace rmclhip

@@ -490,4 +490,45 @@ hipError_t launch_hypotheses(const xform* poses, const void* attrs, uint32_t n, 
 constexpr uint32_t kPoseInfoRow = 32u;
 hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s);
 
+// field.hip: the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
+struct FieldView {
+  const float* lat;
+  uint32_t n[3];
+  float origin[3];
+  float cell, inv_cell;
+};
+// one level of the coarse-to-fine build: the nodes (ci * stride, cj * stride, ck * stride), ci < cn[0] ..., of `fv`'s lattice.
+// seed_rec (nullable): the records the previous level left, pn[0] * pn[1] * pn[2] of them at stride pstride -- a node starts from the
+// record of the previous level's node nearest to it; rec_out (nullable): cn[0] * cn[1] * cn[2] records, x fastest; dist_out
+// (nullable, stride 1 only): the lattice itself
+struct FieldBuildParams {
+  const uint32_t* nodes;
+  const uint32_t* tris;
+  uint32_t n_tris;
+  FieldView fv;
+  uint32_t stride, cn[3];
+  const uint32_t* seed_rec;
+  uint32_t pstride, pn[3];
+  uint32_t* rec_out;
+  float* dist_out;
+};
+hipError_t launch_field_build(const FieldBuildParams& p, hipStream_t s);
+// the lookup alone: n points (xyz, map coordinates) -> n distances
+hipError_t launch_field_query(const FieldView& fv, const float* points, size_t n, float* out, hipStream_t s);
+// the sensor update of correspondence_type 1 answered from the field: k_pf_update<64, 3>'s end points, evaluation and in-order merge
+struct PfFieldParams {
+  FieldView fv;
+  const xform* poses;
+  void* attrs;
+  uint32_t n_particles;
+  const float* beams;
+  uint32_t n_beams;
+  xform Tsb;
+  float dist_sigma;
+  uint32_t max_n_meas;
+  float* errors;                 // nullable [n_particles * n_beams]
+  uint32_t particles_per_block;
+};
+hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s);
+
 }  // namespace rmclhip

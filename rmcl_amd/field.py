@@ -1,0 +1,80 @@
+"""The map's distance field over the C ABI (include/rmclhip.h, DISTANCE FIELD): a lattice of float32 distances to the closest
+triangle, built on the device.  Set on a PCDSensorUpdaterHip, it answers sensor_update.correspondence_type 1 by lookup.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .registration import _as_ptr
+from .types import _ptr
+
+DEFAULT_MAX_NODES = 1 << 26
+
+
+def field_params(cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX_NODES):
+    """rmclhip_field_params: cell 0 = automatic (the near grid's size rule)"""
+    p = _capi.FieldParams()
+    _capi.lib().rmclhip_field_params_default(C.byref(p))
+    p.cell, p.margin, p.max_nodes = float(cell), float(margin), int(max_nodes)
+    return p
+
+
+def field_layout(bbox_min, bbox_max, cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX_NODES):
+    """rmclhip_field_layout_host (no device needed): the geometry a field over this box gets, as FieldInfo.as_dict()"""
+    lo = np.ascontiguousarray(bbox_min, dtype=np.float32).reshape(3)
+    hi = np.ascontiguousarray(bbox_max, dtype=np.float32).reshape(3)
+    info = _capi.FieldInfo()
+    p = field_params(cell, margin, max_nodes)
+    _capi.check(_capi.lib().rmclhip_field_layout_host(_ptr(lo), _ptr(hi), C.byref(p), C.byref(info)))
+    return info.as_dict()
+
+
+class DistanceFieldHip:
+    """rmclhip_field: built once from a HipMap, immutable.  An updater it is set on keeps it alive past close()."""
+
+    def __init__(self, hip_map, cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX_NODES):
+        if hip_map is None:
+            raise RuntimeError("NO MAP")
+        self.map, self.ctx = hip_map, hip_map.ctx
+        self._h = C.c_void_p()
+        p = field_params(cell, margin, max_nodes)
+        _capi.check(_capi.lib().rmclhip_field_create(self.ctx.handle, hip_map.handle, C.byref(p), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        fi = _capi.FieldInfo()
+        _capi.check(_capi.lib().rmclhip_field_get_info(self._h, C.byref(fi)))
+        return fi.as_dict()
+
+    def download(self):
+        """the node values as a float32 array [n_z, n_y, n_x] (x fastest)"""
+        i = self.info()
+        out = np.zeros(i["n_nodes"], dtype=np.float32)
+        _capi.check(_capi.lib().rmclhip_field_download(self._h, _ptr(out), out.size))
+        return out.reshape(i["n"][2], i["n"][1], i["n"][0])
+
+    def query(self, points, out_dev=None, n=None):
+        """the lookup at points in map coordinates: an [n, 3] array on the host -> float32 array of n; or device memory of 3 n floats
+        together with out_dev (n floats on the device), which then receives the distances"""
+        if out_dev is not None:
+            _capi.check(_capi.lib().rmclhip_field_query(self._h, _as_ptr(points), int(n), 1, _as_ptr(out_dev)))
+            return None
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), dtype=np.float32)
+        _capi.check(_capi.lib().rmclhip_field_query(self._h, _ptr(p), len(p), 0, _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            _capi.lib().rmclhip_field_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

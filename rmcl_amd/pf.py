@@ -233,6 +233,13 @@ class PCDSensorUpdaterHip:
             self.init()
         _capi.check(_capi.lib().rmclhip_pf_set_error_output(self._h, _as_ptr(errors_dev)))
 
+    def set_field(self, field):
+        """answer correspondence_type 1 from a DistanceFieldHip of this updater's map (rmclhip_pf_set_field); None: off.  The handle
+        keeps the field alive: the field object may be closed afterwards."""
+        if not self._h:
+            self.init()
+        _capi.check(_capi.lib().rmclhip_pf_set_field(self._h, None if field is None else field.handle))
+
     def extract_weights(self, particle_attrs, n_particles, weights_dev):
         _capi.check(_capi.lib().rmclhip_pf_extract_weights(self._h, _as_ptr(particle_attrs), int(n_particles),
                                                            _as_ptr(weights_dev)))
@@ -576,6 +583,15 @@ class ShardedParticleFilterHip:
     def set_surface(self, params):
         """the surface constraint of motion_update and step on every device's block (rmclhip_pf_sharded_set_surface); None: off"""
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_surface(self._h, None if params is None else C.byref(params)))
+
+    def set_field(self, cell=0.0, margin=0.0, max_nodes=1 << 26):
+        """every device builds the distance field of its copy of the map and answers correspondence_type 1 from it
+        (rmclhip_pf_sharded_set_field); set_field(None): off"""
+        if cell is None:
+            _capi.check(_capi.lib().rmclhip_pf_sharded_set_field(self._h, None))
+            return
+        p = _capi.FieldParams(float(cell), float(margin), int(max_nodes))
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_field(self._h, C.byref(p)))
 
     def constrain_to_surface(self, params):
         """the standalone surface pass on every device's own block, no collective; returns the counts summed over the devices"""
