@@ -1209,6 +1209,13 @@ struct FieldParams : rmclhip_field_params {
   FieldParams(float cell_, float margin_) { rmclhip_field_params_default(this); cell = cell_; margin = margin_; }
 };
 using FieldInfo = rmclhip_field_info;
+// the damped Gauss-Newton refinement of particles on a field (include/rmclhip.h, REFINE ON THE FIELD): poses move towards the map,
+// likelihood attributes are not touched -- a sensor update follows
+struct RefineParams : rmclhip_refine_params {
+  RefineParams() { rmclhip_refine_params_default(this); }
+};
+using RefineResult = rmclhip_refine_result;
+using RefineStats = rmclhip_refine_stats;
 class DistanceFieldHip {
  public:
   explicit DistanceFieldHip(HipMapPtr map, const FieldParams& params = FieldParams()) : map_(std::move(map)) {
@@ -1250,6 +1257,15 @@ class DistanceFieldHip {
     const float* p = nullptr;
     check(rmclhip_field_device_view(h_, &p));
     return DeviceView<const float>{p, static_cast<size_t>(info().n_nodes)};
+  }
+  // refines the poses in place (MemoryView<Transform, VRAM_HIP> is a DeviceView); results (optional): one row per particle
+  RefineStats refine(DeviceView<Transform> poses, const std::vector<RangeMeasurement>& beams, const Transform& Tsb,
+                     const RefineParams& params = RefineParams(), DeviceView<RefineResult> results = DeviceView<RefineResult>{nullptr, 0}) const {
+    if (results.raw() && results.size() < poses.size()) throw std::runtime_error("DistanceFieldHip::refine: results.size() < poses.size()");
+    RefineStats st{};
+    check(rmclhip_field_refine(h_, poses.raw(), static_cast<uint32_t>(poses.size()), beams.data(), static_cast<uint32_t>(beams.size()), &Tsb, &params,
+                               results.raw(), &st));
+    return st;
   }
   rmclhip_field* handle() const { return h_; }
   const HipMapPtr& map() const { return map_; }
@@ -1305,6 +1321,17 @@ class PCDSensorUpdaterHip : public SensorUpdaterBase, public ParticleUpdater<VRA
     init();
     check(rmclhip_pf_set_field(h_, field ? field->handle() : nullptr));
     field_ = std::move(field);
+  }
+  // refines the poses in place on the field of setField with the beams and Tsb of setInput (rmclhip_pf_refine); attributes are not
+  // touched: update() follows
+  RefineStats refine(DeviceView<Transform> poses, const RefineParams& params = RefineParams(),
+                     DeviceView<RefineResult> results = DeviceView<RefineResult>{nullptr, 0}) {
+    init();
+    if (results.raw() && results.size() < poses.size()) throw std::runtime_error("PCDSensorUpdaterHip::refine: results.size() < poses.size()");
+    RefineStats st{};
+    check(rmclhip_pf_refine(h_, poses.raw(), static_cast<uint32_t>(poses.size()), beams_.data(), static_cast<uint32_t>(beams_.size()), &Tsb_, &params,
+                            results.raw(), &st));
+    return st;
   }
   // the per-beam errors of the next updates land here ([n_particles * n_beams] floats of device memory; nullptr: off)
   void setErrorOutput(float* errors_dev) {
@@ -1517,6 +1544,12 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
   void setSurface(const std::optional<SurfaceParams>& params) { check(rmclhip_pf_sharded_set_surface(h_, params ? &*params : nullptr)); }
   // config_.correspondence_type 1 answered by lookup: every device builds the distance field of its copy of the map (nullopt: off)
   void setField(const std::optional<FieldParams>& params) { check(rmclhip_pf_sharded_set_field(h_, params ? &*params : nullptr)); }
+  // every device refines its own block on its own field (setField first), no collective; the counts are summed over the devices
+  RefineStats refine(const std::vector<RangeMeasurement>& beams, const Transform& Tsb, const RefineParams& params = RefineParams()) {
+    RefineStats st{};
+    check(rmclhip_pf_sharded_refine(h_, beams.data(), static_cast<uint32_t>(beams.size()), &Tsb, &params, &st));
+    return st;
+  }
   SurfaceStats constrainToSurface(const SurfaceParams& params) {
     SurfaceStats st{};
     check(rmclhip_pf_sharded_set_params(h_, &config_));

@@ -1294,6 +1294,86 @@ rmclhip_status rmclhip_pf_set_field(rmclhip_pf* pf, rmclhip_field* field);
  * sets it on its filter handle, replacing an earlier one; NULL switches it off */
 rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* pf, const rmclhip_field_params* params);
 
+/* ---- REFINE ON THE FIELD: damped Gauss-Newton of every particle by lookup -------------------------------------------
+ * The eight lattice values that give the distance at a beam's end point also give its gradient, so a particle can be moved towards the
+ * map, not only weighed against it: a per-particle Levenberg-Marquardt refinement of the cost sum_b min(d_b, max_dist)^2, all
+ * iterations inside one launch, no tree, no stack.  Likelihood attributes are NEVER touched: a refined pose has not been scored, the
+ * caller follows with a sensor update.  (This is the gradient half of a Stein variational step; the repulsion between particles is not
+ * part of this interface.)
+ *
+ * THE ARITHMETIC.  Everything is float32 unless it says double; the library is built without contraction and the device evaluates no
+ * transcendental (tests/refine_ref.py restates this in numpy; the device matches it byte for byte).
+ *   Per beam b of a particle with pose (R, t):  Tsm = pose * Tsb, the end point M = Tsm * orig + (Tsm.R * dir) * range exactly as the
+ *   field's sensor update forms it, and the lever L = M - t, componentwise.
+ *   Lookup with gradient at M: index, fraction and clamping are THE LOOKUP's; d is its value, bit for bit.  With the eight corner
+ *   values v_xyz of the cell, (fx, fy, fz) its fractions and lerp(a, b, f) = a + f * (b - a):
+ *     gx = lerp(lerp(v100 - v000, v110 - v010, fy), lerp(v101 - v001, v111 - v011, fy), fz) * inv_cell
+ *     gy = lerp(lerp(v010 - v000, v110 - v100, fx), lerp(v011 - v001, v111 - v101, fx), fz) * inv_cell
+ *     gz = lerp(lerp(v001 - v000, v101 - v100, fx), lerp(v011 - v010, v111 - v110, fx), fy) * inv_cell
+ *   The gradient is not normalised.  A beam is VALID when every component of M passes |M_k| <= FLT_MAX, no axis is clamped (M lies
+ *   inside the lattice) and d, gx, gy, gz are finite (no NaN corner).  A beam is USED when it is valid and d < max_dist.
+ *   Cost of a pose: C = sum_b rho_b in double, rho_b = double(m) * double(m) with m = d for a used beam and max_dist for any other
+ *   (that is min(d, max_dist)^2 for a valid beam).
+ *   Normal equations over the used beams, for the perturbation M' ~ M + v + omega x L (a translation v and a world-axes rotation omega
+ *   about the particle's own position): J = (gx, gy, gz, Ly*gz - Lz*gy, Lz*gx - Lx*gz, Lx*gy - Ly*gx) in float, unfused; r = d.  In
+ *   double: the 21 entries A_ij += double(J_i) * double(J_j) (i <= j), the 6 entries b_i += double(J_i) * double(r), and the count n_used.
+ *   Summation order (C, A, b alike): 64 partial sums; partial l takes the beams l, l + 64, l + 128, ... in increasing order, starting
+ *   from +0; then six rounds s = 32, 16, 8, 4, 2, 1 in which every partial l becomes partial_l + partial_(l xor s); the total is
+ *   partial 0.  It does not depend on the launch, on the number of particles or on sharding.
+ *   Step, in double: a degree of freedom k whose bit in dof_mask is clear (bits 0..5: x, y, z, rotation about world x, y, z) gets row
+ *   and column k of A set to 0, A_kk = 1, b_k = 0.  H = A with H_kk = (A_kk + lambda * A_kk) + 1e-9.  H = G G^T by Cholesky without
+ *   pivoting, column by column: s = H_jj - G_j0^2 - ... - G_j,j-1^2 (subtracted one by one), G_jj = sqrt(s), G_ij = (H_ij - G_i0 G_j0 -
+ *   ... ) / G_jj; a pivot s that is not > 0 REJECTS the step.  G y = b forwards, G^T x = y backwards (terms subtracted in increasing
+ *   index, then one division), delta = -x, and 0 for a locked k.  |v| = sqrt((v_x^2 + v_y^2) + v_z^2), |omega| alike; the whole delta is
+ *   multiplied by the smallest of 1, max_step_trans / |v| (if |v| > 0) and max_step_rot / |omega| (if |omega| > 0).
+ *   Candidate pose: t'_k = t_k + float(v_k) on the free translation axes (a locked one is copied); if any rotation is free,
+ *   q' = normalise((float(0.5 * omega), w = 1) * R) with the quaternion product and the four-division normalise of the surface
+ *   constraint (else R is copied).  First order, which suffices: the fixed point is delta = 0.
+ *   Loop: one pass computes (C, A, b, n_used) at a pose.  The start pose is evaluated; then `iterations` times: solve; if not rejected
+ *   evaluate the candidate; if C_cand < C_cur the candidate becomes the current pose with its A, b and n_used and
+ *   lambda = max(lambda / 3, 1e-6); otherwise (rejected, or no smaller cost) lambda = lambda * 10.  lambda starts at double(lambda0).
+ *   By construction cost_after <= cost_before for every particle.
+ *   Untouched, bit for bit: iterations == 0, dof_mask == 0, n_used == 0 at the start, a pose with a component that is not finite, and
+ *   every particle that accepted no step.  A result row is written in each of these cases too. */
+typedef struct {
+  uint32_t iterations;     /* default 8, at most 64 */
+  uint32_t dof_mask;       /* default 0x3F; bits 0..5: x, y, z, rotation about world x, y, z; at most 0x3F */
+  float max_dist;          /* default 0.5, must be > 0: a beam farther from the surface is not used and costs max_dist^2 */
+  float max_step_trans;    /* default 0.5 (metres per iteration), must be > 0 */
+  float max_step_rot;      /* default 0.25 (radians per iteration), must be > 0 */
+  float lambda0;           /* default 1e-3, must be > 0 */
+} rmclhip_refine_params;
+void rmclhip_refine_params_default(rmclhip_refine_params* out);
+typedef struct {
+  float cost_before, cost_after;   /* float(C) at the start pose and at the final pose */
+  uint32_t n_used;                 /* at the final pose */
+  uint32_t accepted;               /* steps */
+} rmclhip_refine_result;
+typedef struct {
+  uint32_t n_particles;
+  uint32_t n_moved;        /* accepted at least one step */
+  uint32_t n_no_beams;     /* finite pose, n_used == 0 at the start */
+  uint32_t n_not_finite;   /* a pose component is not finite */
+  double cost_before_sum, cost_after_sum;   /* the rows' costs summed in double in particle order */
+} rmclhip_refine_stats;
+/* refines n_particles poses (device memory of the field's device) in place and waits for it.  beams: host memory, n_beams records, at
+ * most 8192 (the field sensor update's bound); Tsb as in rmclhip_pf_update; params NULL: the defaults.  results_dev (nullable): device
+ * memory for one row per particle; stats_out (nullable).  n_particles == 0: RMCLHIP_OK, nothing is touched.  RMCLHIP_ERR_INVALID before
+ * anything is launched: a parameter that is not finite or outside its range, null poses / beams / Tsb with n_particles > 0, n_beams 0
+ * or above 8192 */
+rmclhip_status rmclhip_field_refine(rmclhip_field* field, rmclhip_transform* poses_dev, uint32_t n_particles,
+                                    const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
+                                    const rmclhip_refine_params* params, rmclhip_refine_result* results_dev, rmclhip_refine_stats* stats_out);
+/* the same on the field set with rmclhip_pf_set_field, on the handle's stream (behind whatever was enqueued on it); the same bytes.
+ * RMCLHIP_ERR_INVALID when no field is set */
+rmclhip_status rmclhip_pf_refine(rmclhip_pf* pf, rmclhip_transform* poses_dev, uint32_t n_particles, const rmclhip_range_measurement* beams,
+                                 uint32_t n_beams, const rmclhip_transform* Tsb, const rmclhip_refine_params* params,
+                                 rmclhip_refine_result* results_dev, rmclhip_refine_stats* stats_out);
+/* every replica refines its own block on its own field (rmclhip_pf_sharded_set_field), no collective: particles are independent, so
+ * the poses equal the unsharded call's bit for bit.  stats_out: the replicas' counts and sums added in rank order */
+rmclhip_status rmclhip_pf_sharded_refine(rmclhip_pf_sharded* pf, const rmclhip_range_measurement* beams, uint32_t n_beams,
+                                         const rmclhip_transform* Tsb, const rmclhip_refine_params* params, rmclhip_refine_stats* stats_out);
+
 /* ---- device memory helpers for hosts without their own allocator ---------------------- */
 rmclhip_status rmclhip_malloc(rmclhip_ctx* ctx, size_t bytes, void** out_dev);
 rmclhip_status rmclhip_free(rmclhip_ctx* ctx, void* ptr_dev);

@@ -184,6 +184,21 @@ class FieldInfo(C.Structure):
                 "inv_cell": float(self.inv_cell), "n_nodes": int(self.n_nodes), "bytes": int(self.bytes)}
 
 
+class RefineParams(C.Structure):
+    """rmclhip_refine_params (the damped Gauss-Newton refinement on the distance field)"""
+    _fields_ = [("iterations", C.c_uint32), ("dof_mask", C.c_uint32), ("max_dist", C.c_float), ("max_step_trans", C.c_float),
+                ("max_step_rot", C.c_float), ("lambda0", C.c_float)]
+
+
+class RefineStats(C.Structure):
+    """rmclhip_refine_stats"""
+    _fields_ = [("n_particles", C.c_uint32), ("n_moved", C.c_uint32), ("n_no_beams", C.c_uint32), ("n_not_finite", C.c_uint32),
+                ("cost_before_sum", C.c_double), ("cost_after_sum", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if k.startswith("cost") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
 PC2SCAN_TRUE_ELEVATION, PC2SCAN_FLOOR, PC2SCAN_WRAP_THETA, PC2SCAN_NEAREST = 1, 2, 4, 8
 SEG_PINT_WITH_ORIGIN = 1
 SEG_NONE, SEG_INLIER, SEG_OUTLIER_SCAN, SEG_OUTLIER_MAP = 0, 1, 2, 3
@@ -399,6 +414,10 @@ SIGNATURES = {
     "rmclhip_field_query": (_i32, [_vp, _vp, _sz, _i32, _vp]),
     "rmclhip_pf_set_field": (_i32, [_vp, _vp]),
     "rmclhip_pf_sharded_set_field": (_i32, [_vp, C.POINTER(FieldParams)]),
+    "rmclhip_refine_params_default": (None, [C.POINTER(RefineParams)]),
+    "rmclhip_field_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),
+    "rmclhip_pf_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),
+    "rmclhip_pf_sharded_refine": (_i32, [_vp, _vp, _u32, _vp, C.POINTER(RefineParams), C.POINTER(RefineStats)]),
     "rmclhip_malloc": (_i32, [_vp, _sz, _pp]),
     "rmclhip_free": (_i32, [_vp, _vp]),
     "rmclhip_memcpy_h2d": (_i32, [_vp, _vp, _vp, _sz]),

@@ -56,7 +56,7 @@ rmclhip_status rmclhip_field_layout_host(const float* bbox_min, const float* bbo
   return RMCLHIP_OK;
 }
 
-static FieldView field_view(const rmclhip_field* fd) {
+RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd) {
   FieldView v;
   v.lat = fd->d_lat;
   for (int k = 0; k < 3; ++k) { v.n[k] = fd->info.n[k]; v.origin[k] = fd->info.origin[k]; }
@@ -69,7 +69,7 @@ RMCL_INTERNAL void field_release(rmclhip_field* fd) {
   if (!fd || fd->refs.fetch_sub(1) != 1) return;
   (void)hipSetDevice(fd->ctx->device);
   if (fd->stream) (void)hipStreamSynchronize(fd->stream);
-  fd->d_q_points.release(); fd->d_q_out.release();
+  fd->d_q_points.release(); fd->d_q_out.release(); fd->refine.release();
   if (fd->d_lat) {
     (void)hipFree(fd->d_lat);
     std::lock_guard<std::mutex> lock(fd->map->grid_mtx);

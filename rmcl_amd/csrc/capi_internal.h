@@ -8,6 +8,7 @@
 //   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_field.cpp     the map's distance field: layout, coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field.hip)
+//   capi_refine.cpp    the damped Gauss-Newton refinement of particles on a distance field: parameters, launch, counts (kernel: refine.hip)
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
 //   capi_pose_information.cpp the point-to-plane information matrix of a find's correspondences and its host algebra: covariance, degeneracy (kernels: pose_information.hip)
@@ -211,6 +212,15 @@ struct rmclhip_map {
   std::vector<uint32_t> scene_first_face;  // map_create_scene: first global face id of every instance, + the total (else empty)
 };
 
+// rmclhip_field_refine / rmclhip_pf_refine (capi_refine.cpp): grow-only scratch of one owner -- the beams' device records, the result
+// rows when the caller gives none but asks for the counts, the three counters -- and what the call in flight needs to finish
+struct RefineScratch {
+  DevBuf<float> beams;
+  DevBuf<uint32_t> rows, counters;
+  const uint32_t* rows_src = nullptr;   // where the rows of the call in flight land (device memory); null: none were asked for
+  void release() { beams.release(); rows.release(); counters.release(); }
+};
+
 // the distance field of a map (capi_field.cpp): the lattice, immutable once built; handles that read it (rmclhip_pf_set_field) hold a
 // reference.  `stream` and the two staging buffers serve rmclhip_field_query / _download alone, one call at a time (mtx).
 struct rmclhip_field {
@@ -222,6 +232,7 @@ struct rmclhip_field {
   std::mutex mtx;
   hipStream_t stream = nullptr;
   DevBuf<float> d_q_points, d_q_out;
+  RefineScratch refine;            // rmclhip_field_refine, under mtx
 };
 
 struct rmclhip_rcc {
@@ -463,6 +474,7 @@ struct rmclhip_pf {
   uint32_t* d_surf = nullptr;
   uint32_t* h_surf = nullptr;
   uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: borrowed device memory, one word per particle of the next constrained launches
+  RefineScratch refine;            // rmclhip_pf_refine (capi_refine.cpp)
   rmclhip_field* field = nullptr;  // rmclhip_pf_set_field (capi_field.cpp): correspondence_type 1 is answered from this lattice; the handle holds a reference
 };
 
@@ -581,4 +593,15 @@ RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx);
 RMCL_INTERNAL void field_release(rmclhip_field* fd);
 RMCL_INTERNAL rmclhip_status pf_field_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, rmclhip_particle_attributes* attrs, uint32_t n, uint32_t n_beams,
                                               const rmclhip_transform* Tsb);
+// capi_field.cpp: the kernels' view of a field
+RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd);
+// capi_refine.cpp: the refinement in two halves, so that the sharded filter has every device's launch in flight before it waits for any.
+// refine_check refuses what the header lists (params null: the defaults are written to *out); refine_enqueue uploads the beams and
+// launches on `stream`; refine_finish waits for the stream and ADDS this call's counts to *stats (nullable)
+RMCL_INTERNAL rmclhip_status refine_check(const std::string& who, const void* poses_dev, uint32_t n, const rmclhip_range_measurement* beams, uint32_t n_beams,
+                                          const rmclhip_transform* Tsb, const rmclhip_refine_params* params, rmclhip_refine_params* out);
+RMCL_INTERNAL rmclhip_status refine_enqueue(const rmclhip_field* field, hipStream_t stream, RefineScratch& sc, rmclhip_transform* poses_dev, uint32_t n,
+                                            const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
+                                            const rmclhip_refine_params& params, rmclhip_refine_result* results_dev, bool want_stats);
+RMCL_INTERNAL rmclhip_status refine_finish(hipStream_t stream, RefineScratch& sc, uint32_t n, rmclhip_refine_stats* stats);
 //@@DECLS@@

@@ -727,6 +727,32 @@ rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip
   return RMCLHIP_OK;
 }
 
+// every replica refines its own block on its own field (capi_refine.cpp); no collective, attributes and weights are not touched
+rmclhip_status rmclhip_pf_sharded_refine(rmclhip_pf_sharded* h, const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
+                                         const rmclhip_refine_params* params, rmclhip_refine_stats* stats_out) {
+  ApiGuard guard_("rmclhip_pf_sharded_refine");
+  if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_refine: null");
+  for (PfRank& R : h->ranks)
+    if (!R.pf->field) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_refine: no distance field is set (rmclhip_pf_sharded_set_field)");
+  rmclhip_refine_params p;
+  if (rmclhip_status st = refine_check("pf_sharded_refine", h, h->n_total, beams, n_beams, Tsb, params, &p)) return st;
+  if (h->n_total == 0) return RMCLHIP_OK;
+  for (PfRank& R : h->ranks) {   // every rank's launch is in flight before the host waits for any
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    if (rmclhip_status st = refine_enqueue(R.pf->field, R.pf->stream, R.pf->refine, reinterpret_cast<rmclhip_transform*>(R.d_poses), R.hi - R.lo, beams,
+                                           n_beams, Tsb, p, nullptr, stats_out != nullptr))
+      return st;
+  }
+  for (PfRank& R : h->ranks) {
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    if (rmclhip_status st = refine_finish(R.pf->stream, R.pf->refine, R.hi - R.lo, stats_out)) return st;
+  }
+  return RMCLHIP_OK;
+}
+
 // the sum of every device's last counts (ranks without particles launched nothing: their block is skipped)
 static void pf_sharded_sum_surface_stats(rmclhip_pf_sharded* h, rmclhip_surface_stats* out) {
   std::memset(out, 0, sizeof(*out));

@@ -8,46 +8,13 @@
 //                     the tree query replaced by the lookup -- same Tsm, same end point, same evaluation, same in-order merge.  No
 //                     traversal, no stack: LDS holds the workgroup's Tsm and its beam evaluations only.
 //
-// The lookup is eight dependent gathers and seven lerps in a stated float order (the library is built without contraction).  Rays are
+// The lookup (field_lookup.hip.h, shared with refine.hip) is eight dependent gathers and seven lerps in a stated float order.  Rays are
 // dealt beam-minor: the lanes of a wave hold consecutive beams of one particle, Tsm is a wave-uniform LDS read, and the end points of
 // neighbouring beams fall into neighbouring cells.
-#include "pf_common.hip.h"
+#include "field_lookup.hip.h"
 
 namespace rmclhip {
 namespace {
-
-__device__ __forceinline__ float field_lerp(float a, float b, float f) { return a + f * (b - a); }
-
-// include/rmclhip.h, "the lookup at a point P", line by line
-__device__ __forceinline__ float field_lookup(const FieldView& fv, f3 P) {
-  const float pk[3] = {P.x, P.y, P.z};
-  if (!((fabsf(pk[0]) <= 3.402823466e38f) && (fabsf(pk[1]) <= 3.402823466e38f) && (fabsf(pk[2]) <= 3.402823466e38f)))
-    return __uint_as_float(0x7FC00000u);
-  uint32_t i[3];
-  float f[3], o[3];
-  bool clamped = false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float top = static_cast<float>(fv.n[k] - 1u);
-    const float u = (pk[k] - fv.origin[k]) * fv.inv_cell;
-    const float c = fminf(fmaxf(u, 0.0f), top);
-    i[k] = min(static_cast<uint32_t>(static_cast<int>(floorf(c))), fv.n[k] - 2u);
-    f[k] = c - static_cast<float>(i[k]);
-    const bool out = (u < 0.0f) || (u > top);
-    o[k] = out ? pk[k] - (fv.origin[k] + c * fv.cell) : 0.0f;
-    clamped = clamped || out;
-  }
-  const size_t nx = fv.n[0], nxy = nx * fv.n[1];
-  const float* c0 = fv.lat + (static_cast<size_t>(i[2]) * nxy + static_cast<size_t>(i[1]) * nx + i[0]);
-  // the two x-neighbours of a corner pair are adjacent in memory
-  const float v000 = c0[0], v100 = c0[1], v010 = c0[nx], v110 = c0[nx + 1u];
-  const float v001 = c0[nxy], v101 = c0[nxy + 1u], v011 = c0[nxy + nx], v111 = c0[nxy + nx + 1u];
-  const float x00 = field_lerp(v000, v100, f[0]), x10 = field_lerp(v010, v110, f[0]);
-  const float x01 = field_lerp(v001, v101, f[0]), x11 = field_lerp(v011, v111, f[0]);
-  const float y0 = field_lerp(x00, x10, f[1]), y1 = field_lerp(x01, x11, f[1]);
-  const float d = field_lerp(y0, y1, f[2]);
-  return clamped ? d + sqrtf((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) : d;
-}
 
 __global__ void __launch_bounds__(256) k_field_build(const FieldBuildParams p) {
   extern __shared__ uint32_t lds_dyn[];

@@ -531,4 +531,23 @@ struct PfFieldParams {
 };
 hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s);
 
+// refine.hip: the damped Gauss-Newton refinement of every particle on the field (include/rmclhip.h, REFINE ON THE FIELD), all
+// iterations in one launch.  poses are rewritten in place for particles that accepted a step; rows (nullable): n_particles
+// rmclhip_refine_result; counters (nullable): {n_moved, n_no_beams, n_not_finite}, added to, so zeroed by the caller.
+constexpr uint32_t kRefineMaxBeams = 8192u;
+constexpr uint32_t kRefineMaxIterations = 64u;
+struct RefineKernelParams {
+  FieldView fv;
+  xform* poses;
+  uint32_t n_particles;
+  const float* beams;            // n_beams records of 16 floats, as the sensor update reads them
+  uint32_t n_beams;
+  xform Tsb;
+  uint32_t iterations, dof_mask;
+  float max_dist, max_step_trans, max_step_rot, lambda0;
+  uint32_t* rows;
+  uint32_t* counters;
+};
+hipError_t launch_field_refine(const RefineKernelParams& p, hipStream_t s);
+
 }  // namespace rmclhip

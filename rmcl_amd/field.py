@@ -30,6 +30,38 @@ def field_layout(bbox_min, bbox_max, cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX
     return info.as_dict()
 
 
+REFINE_RESULT = np.dtype([("cost_before", np.float32), ("cost_after", np.float32), ("n_used", np.uint32), ("accepted", np.uint32)])
+
+
+def refine_params(iterations=None, dof_mask=None, max_dist=None, max_step_trans=None, max_step_rot=None, lambda0=None):
+    """rmclhip_refine_params: the library's defaults (rmclhip_refine_params_default), overridden by the keywords that are given"""
+    p = _capi.RefineParams()
+    _capi.lib().rmclhip_refine_params_default(C.byref(p))
+    for k, v in (("iterations", iterations), ("dof_mask", dof_mask)):
+        if v is not None:
+            setattr(p, k, int(v))
+    for k, v in (("max_dist", max_dist), ("max_step_trans", max_step_trans), ("max_step_rot", max_step_rot), ("lambda0", lambda0)):
+        if v is not None:
+            setattr(p, k, float(v))
+    return p
+
+
+def _refine_call(fn, handle, poses_dev, n_particles, beams, Tsb, params, results_dev, kwargs):
+    """the argument handling DistanceFieldHip.refine and PCDSensorUpdaterHip.refine share: returns the counts as a dict"""
+    from .types import RANGE_MEASUREMENT, TRANSFORM
+    if params is None:
+        params = refine_params(**kwargs)
+    elif kwargs:
+        raise TypeError("refine: give params or keywords, not both")
+    if n_particles is None:
+        n_particles = poses_dev.count if hasattr(poses_dev, "count") else poses_dev.shape[0]
+    b = np.ascontiguousarray(beams, dtype=RANGE_MEASUREMENT).reshape(-1)
+    T = np.ascontiguousarray(Tsb, dtype=TRANSFORM).reshape(1)
+    st = _capi.RefineStats()
+    _capi.check(fn(handle, _as_ptr(poses_dev), int(n_particles), _ptr(b), len(b), _ptr(T), C.byref(params), _as_ptr(results_dev), C.byref(st)))
+    return st.as_dict()
+
+
 class DistanceFieldHip:
     """rmclhip_field: built once from a HipMap, immutable.  An updater it is set on keeps it alive past close()."""
 
@@ -67,6 +99,12 @@ class DistanceFieldHip:
         out = np.zeros(len(p), dtype=np.float32)
         _capi.check(_capi.lib().rmclhip_field_query(self._h, _ptr(p), len(p), 0, _ptr(out)))
         return out
+
+    def refine(self, poses_dev, beams, Tsb, n_particles=None, params=None, results_dev=None, **kwargs):
+        """rmclhip_field_refine: damped Gauss-Newton of every pose (device memory, in place) on this field; likelihood attributes are
+        not touched -- follow with a sensor update.  params: a refine_params(), or its keywords directly; results_dev: device memory for
+        one REFINE_RESULT row per particle (optional).  Returns the counts (rmclhip_refine_stats) as a dict."""
+        return _refine_call(_capi.lib().rmclhip_field_refine, self._h, poses_dev, n_particles, beams, Tsb, params, results_dev, kwargs)
 
     def close(self):
         if self._h:

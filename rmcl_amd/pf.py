@@ -240,6 +240,16 @@ class PCDSensorUpdaterHip:
             self.init()
         _capi.check(_capi.lib().rmclhip_pf_set_field(self._h, None if field is None else field.handle))
 
+    def refine(self, particle_poses, n_particles=None, params=None, results_dev=None, **kwargs):
+        """rmclhip_pf_refine: damped Gauss-Newton of every pose (device memory, in place) on the field set with set_field, with the
+        beams and Tsb of setInput.  Attributes are not touched: follow with update().  Returns the counts as a dict."""
+        from .field import _refine_call
+        if not self._h:
+            self.init()
+        if self._beams is None:
+            raise RuntimeError("setInput() first")
+        return _refine_call(_capi.lib().rmclhip_pf_refine, self._h, particle_poses, n_particles, self._beams, self._Tsb, params, results_dev, kwargs)
+
     def extract_weights(self, particle_attrs, n_particles, weights_dev):
         _capi.check(_capi.lib().rmclhip_pf_extract_weights(self._h, _as_ptr(particle_attrs), int(n_particles),
                                                            _as_ptr(weights_dev)))
@@ -592,6 +602,20 @@ class ShardedParticleFilterHip:
             return
         p = _capi.FieldParams(float(cell), float(margin), int(max_nodes))
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_field(self._h, C.byref(p)))
+
+    def refine(self, beams, Tsb, params=None, **kwargs):
+        """every device refines its own block on its own field (rmclhip_pf_sharded_refine; set_field first), no collective; attributes
+        and weights are not touched.  Returns the counts summed over the devices."""
+        from .field import refine_params
+        if params is None:
+            params = refine_params(**kwargs)
+        elif kwargs:
+            raise TypeError("refine: give params or keywords, not both")
+        b = np.ascontiguousarray(beams, dtype=RANGE_MEASUREMENT).reshape(-1)
+        T = np.ascontiguousarray(Tsb, dtype=TRANSFORM).reshape(1)
+        st = _capi.RefineStats()
+        _capi.check(_capi.lib().rmclhip_pf_sharded_refine(self._h, _ptr(b), len(b), _ptr(T), C.byref(params), C.byref(st)))
+        return st.as_dict()
 
     def constrain_to_surface(self, params):
         """the standalone surface pass on every device's own block, no collective; returns the counts summed over the devices"""
