@@ -1,7 +1,8 @@
 // capi_internal.h -- what the translation units of the C ABI (include/rmclhip.h) share: the handle structs, the error plumbing and the
 // internal functions one file defines and another calls.  Round 5 split the former capi.cpp (4 300 lines) by handle type:
 //   capi_map.cpp       context, map / scene upload, host-side algebra, device memory helpers
-//   capi_rcc.cpp       the correspondence operator: models, datasets, find, reduction, the MICP corrections (one and N sensors), pose batches
+//   capi_rcc.cpp       the correspondence operator: models, datasets, find, reduction, the moments' hand-over to the host, pose batches
+//   capi_micp.cpp      the MICP corrections of that operator, one sensor and N, each a dispatcher over its loop forms (kernels: micp.hip)
 //   capi_rcc_tune.cpp  tuning knobs, autotune, measurement aids (include/rmclhip_bench.h) and diagnostics (include/rmclhip_lab.h) of that operator
 //   capi_segment.cpp   map segmentation of that operator: trace into its own scratch, labels, compacted outlier clouds (kernels: segment.hip)
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
@@ -431,6 +432,22 @@ static inline void drop_moment_set(rmclhip_rcc* r) {
   r->mset_passes = 0;
 }
 
+// what a reduction over the operator's correspondences covers: the dataset or the last find's model buffers, whichever is shorter
+inline uint32_t nred_of(const rmclhip_rcc* r) { return std::min(r->n_dataset, r->n_model); }
+
+// the streaming reduction's parameter block over `n` correspondences of ONE scan of the operator, pre-transform the identity, into its
+// own partial rows; the caller sets what differs (nposes, Tpre, Tpre_dev)
+inline ReduceParams reduce_params(const rmclhip_rcc* r, uint32_t n, float max_dist, uint32_t nblocks) {
+  ReduceParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.dataset_points = r->ds_pts; p.dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
+  p.model_points = r->d_points.p; p.model_normals = r->d_normals.p; p.model_mask = r->d_hits.p;
+  p.n = n; p.nposes = 1; p.max_dist = max_dist;
+  p.Tpre = xidentity();
+  p.partials = r->d_partials.p; p.nblocks = nblocks;
+  return p;
+}
+
 struct rmclhip_pf {
   rmclhip_ctx* ctx = nullptr;
   rmclhip_map* map = nullptr;
@@ -545,6 +562,17 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
 RMCL_INTERNAL rmclhip_status ensure_model_buffers(rmclhip_rcc* r, size_t n_total);
 RMCL_INTERNAL rmclhip_status find_enqueue(rmclhip_rcc* r, const xform& Tbm, bool* speculate = nullptr);
 RMCL_INTERNAL rmclhip_status reduce_enqueue(rmclhip_rcc* r, const xform& Tpre, const xform* Tpre_dev, float max_dist, uint32_t nposes, const ReduceTail& tail);
+// capi_rcc.cpp, shared by find / computeCrossStatistics and the corrections (capi_micp.cpp): sequence numbers and completion tags, the
+// gate and its band, the moment epilogue of a find and the host's verified copy of what it publishes, the caps a served loop leaves
+RMCL_INTERNAL uint32_t next_seq(rmclhip_rcc* r);
+RMCL_INTERNAL hipError_t wait_done(const rmclhip_ctx* ctx, volatile const unsigned long long* tag, uint32_t seq, const DoneCheck& chk, hipStream_t stream);
+RMCL_INTERNAL hipError_t wait_chain_end(rmclhip_rcc* r);
+RMCL_INTERNAL float adaptive_max_dist(const rmclhip_rcc* r, double p);
+RMCL_INTERNAL void gate_band(const rmclhip_rcc* r, float centre, float* lo, float* hi);
+RMCL_INTERNAL hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, float hi, float rho_cap, float tau_cap);
+RMCL_INTERNAL void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau);
+RMCL_INTERNAL rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp, int fv, uint32_t nred, float lo, float hi, float rho_cap, float tau_cap, uint32_t* nb_out, uint32_t* wpb_out);
+RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap, uint32_t seq, bool epilogue_allowed);
 RMCL_INTERNAL rmclhip_status find_batch_enqueue(rmclhip_rcc* r, const rmclhip_transform* Tbm, uint32_t nposes);
 RMCL_INTERNAL rmclhip_status batch_order_enqueue(rmclhip_rcc* r, FindParams& p, int variant);   // pose batches in world order (capi_rcc_tune.cpp)
 RMCL_INTERNAL rmclhip_status ensure_near_grid(rmclhip_map* m, hipStream_t stream, bool full, const NearGrid** out);

@@ -489,12 +489,201 @@ RMCL_INTERNAL rmclhip_status rebuild_tile_planes(rmclhip_rcc* r, bool keep_tunin
   return RMCLHIP_OK;
 }
 
-static rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap, uint32_t seq,
-                                                bool epilogue_allowed);
-static inline void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau);
-static inline void gate_band(const rmclhip_rcc* r, float centre, float* lo, float* hi);
-static inline uint32_t next_seq(rmclhip_rcc* r);
-static hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, float hi, float rho_cap, float tau_cap);
+// ---- completion tags, the gate, the moments' hand-over to the host: shared with the corrections (capi_micp.cpp) --------------------
+// Wait for the completion tag the LAST kernel of a chain stores in host-mapped memory after its results
+// (reduce_common.hip.h publish_tag), instead of hipStreamSynchronize: the tag arrives ~9 us before the stream's completion signal has made its way
+// through the runtime (measured on the MICP loop: 84 -> 75 us per correction).
+// The tag carries {sequence number of the call, xor of every result word}: the result is accepted only when the sequence number is
+// this call's AND the words the host reads add up to the tag's sum; otherwise polling continues.  (Round 2 polled a flag of constant
+// value that the host cleared before each launch and read a stale result 1 call in ~10^4; the per-call sequence number is what cured
+// it -- the checksum has not rejected a block since, profiles/r05_tag_handoff.txt -- and the xor remains as a belt.)  20 ms without an
+// acceptable tag, or wait mode "block" (rmclhip_ctx_set_wait_mode), falls back to the stream.
+static inline uint32_t xor_host(const void* p, size_t bytes) {
+  const volatile uint32_t* w = static_cast<const volatile uint32_t*>(p);
+  uint32_t x = 0;
+  for (size_t i = 0; i < bytes / 4; ++i) x ^= w[i];
+  return x;
+}
+// how often a poller saw ITS sequence number in the tag while the result words did not (yet) add up to the tag's sum: the event the
+// checksum exists for (rmclhip_debug_tag_retries; profiles/r05_tag_handoff.txt)
+RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries{0};
+
+RMCL_INTERNAL uint32_t next_seq(rmclhip_rcc* r) {
+  if (++r->done_seq == 0u) r->done_seq = 1u;
+  return r->done_seq;
+}
+static inline uint32_t done_sum(const DoneCheck& c) {
+  uint32_t x = xor_host(c.base, c.base_bytes);
+  if (c.code == nullptr || *c.code == 0u)
+    for (int k = 0; k < 3; ++k) if (c.extra[k]) x ^= xor_host(c.extra[k], c.extra_bytes[k]);
+  return x;
+}
+RMCL_INTERNAL hipError_t wait_done(const rmclhip_ctx* ctx, volatile const unsigned long long* tag, uint32_t seq, const DoneCheck& chk,
+                                   hipStream_t stream) {
+  if (ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(stream);
+  const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
+  for (uint32_t spins = 0;; ++spins) {
+    const unsigned long long t = *tag;
+    if (static_cast<uint32_t>(t) == seq) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      if (done_sum(chk) == static_cast<uint32_t>(t >> 32)) return hipSuccess;
+      g_tag_sum_retries.fetch_add(1, std::memory_order_relaxed);   // this call's tag, but the words read do not add up to it (yet)
+    }
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#endif
+    if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) return hipStreamSynchronize(stream);
+  }
+}
+
+// Wait for the end of what the handle's stream holds.  SPIN mode: a one-thread launch behind the chain stores a completion tag in pinned
+// memory, which the host sees ~7 us before the stream's own completion signal (a synchronous 128x1024 find: 31.6 -> 24.5 us, round 4);
+// the chain has ended -- kernel boundary -- when that launch runs, so its results are complete.  BLOCK mode: hipStreamSynchronize.
+RMCL_INTERNAL hipError_t wait_chain_end(rmclhip_rcc* r) {
+  if (r->ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(r->stream);
+  const uint32_t seq = next_seq(r);
+  if (const hipError_t e = launch_host_tag(r->h_done_dev, seq, r->stream)) return e;
+  DoneCheck none;
+  return wait_done(r->ctx, r->h_done, seq, none, r->stream);
+}
+
+RMCL_INTERNAL float adaptive_max_dist(const rmclhip_rcc* r, double p) {
+  // CorrespondencesCPU.cpp:21-23 (float operands, double arithmetic, float store)
+  return static_cast<float>(static_cast<double>(r->max_dist) * (1.0 - p) +
+                            static_cast<double>(r->adaptive_max_dist_min) * p);
+}
+
+// ---- the gate-stable moments on the host (micp_host.h; micp.hip k_micp_publish) -----------------------------------------------
+// The band of max_dist' values a speculating find classifies for: max_dist' = max_dist (1 - p) + adaptive_max_dist_min p moves with
+// the node's convergence_progress_ from one correction to the next (micp_localization.cpp:988-1007), the find does not know the
+// next value, so it takes +-8 % around the last one, clipped to what the two parameters allow.  A max_dist' outside the band
+// costs the first computeCrossStatistics of that correction one moment pass of its own (what every call cost before round 4).
+RMCL_INTERNAL void gate_band(const rmclhip_rcc* r, float centre, float* lo, float* hi) {
+  const float a = std::min(r->max_dist, r->adaptive_max_dist_min), b = std::max(r->max_dist, r->adaptive_max_dist_min);
+  *lo = std::max(a, 0.92f * centre);
+  *hi = std::min(b, 1.08f * centre);
+  if (!(*lo <= centre)) *lo = centre;   // (centre outside [a, b]: parameters changed since; also NaN-safe)
+  if (!(*hi >= centre)) *hi = centre;
+}
+
+// wait for the tag of a publish launch and take a verified copy of the block (see wait_done for why the sum is checked)
+RMCL_INTERNAL hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, float hi, float rho_cap, float tau_cap) {
+  const MicpHostBlock* hb = r->h_mom;
+  auto block_sum = [hb]() -> uint32_t {
+    uint32_t x = xor_host(hb->mom, sizeof(hb->mom));
+    const uint32_t code = *reinterpret_cast<const volatile uint32_t*>(&hb->code);
+    const uint32_t n = *reinterpret_cast<const volatile uint32_t*>(&hb->n_uncertain);
+    x ^= code ^ n;
+    if (n <= kMicpHostMaxUnc) x ^= xor_host(hb->unc, static_cast<size_t>(n) * 9u * sizeof(float));   // (written whenever they fit)
+    return x;
+  };
+  hipError_t e = hipSuccess;
+  bool unverified = false;
+  if (r->ctx->wait_block.load(std::memory_order_relaxed)) e = hipStreamSynchronize(r->stream);
+  else {
+    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
+    volatile const unsigned long long* tag = r->h_done;
+    for (uint32_t spins = 0;; ++spins) {
+      const unsigned long long t = *tag;
+      if (static_cast<uint32_t>(t) == seq) {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (block_sum() == static_cast<uint32_t>(t >> 32)) break;
+        g_tag_sum_retries.fetch_add(1, std::memory_order_relaxed);
+      }
+#if defined(__x86_64__) || defined(__i386__)
+      __builtin_ia32_pause();
+#endif
+      if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) {
+        // 20 ms without this sequence number: either the device is that slow, or a later launch of this handle has already
+        // replaced the tag (h_done is shared by every tagged launch).  Drain the stream, then accept the block only if the tag
+        // still is this publish's and its sum matches; otherwise the caller takes the streaming reduction (ADVICE r4)
+        e = hipStreamSynchronize(r->stream);
+        const unsigned long long t2 = *tag;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        unverified = !(static_cast<uint32_t>(t2) == seq && block_sum() == static_cast<uint32_t>(t2 >> 32));
+        break;
+      }
+    }
+  }
+  r->mset_pending = false;
+  if (e != hipSuccess || unverified) { r->mset.valid = false; return e; }
+  MicpMomentSet& ms = r->mset;
+  std::memcpy(ms.mom, hb->mom, sizeof(ms.mom));
+  ms.gate_lo = lo; ms.gate_hi = hi; ms.rho_cap = rho_cap; ms.tau_cap = tau_cap;
+  ms.n_unc = hb->n_uncertain;
+  ms.valid = (hb->code == 0u && ms.n_unc <= kMicpHostMaxUnc);
+  if (ms.valid) ms.set_undecided(hb->unc, ms.n_unc);   // (component-major copy, padded for the eight-lane sums)
+  return hipSuccess;
+}
+
+// caps of the next moment set from the pre-transforms the last loop met (as rmclhip_rcc_correct_once learns them)
+RMCL_INTERNAL void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau) {
+  r->fast_rho_cap = std::max(0.002f, std::max(2.0f * max_rho, 0.9f * r->fast_rho_cap));
+  r->fast_tau_cap = std::max(0.005f, std::max(2.0f * max_tau, 0.9f * r->fast_tau_cap));
+  r->fast_info.rho_cap = r->fast_rho_cap;
+  r->fast_info.tau_cap = r->fast_tau_cap;
+}
+
+// Arms the moment epilogue of the find `fp` of kind `fv` (23, 32 or 2): one partial row per workgroup (*nb of them) and *wpb mask words
+// per workgroup, the gate band and the caps the rows are good for, and -- allocated and zeroed once per handle -- the area through
+// which the workgroups of the fold hand their sums over (micp.hip fold_hand_over_row)
+RMCL_INTERNAL rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp, int fv, uint32_t nred, float lo, float hi, float rho_cap,
+                                                 float tau_cap, uint32_t* nb_out, uint32_t* wpb_out) {
+  const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;
+  HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
+  HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
+  fp.mom_dataset_points = r->ds_pts;
+  fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
+  fp.mom_n = nred;
+  fp.mom_gate_lo = lo; fp.mom_gate_hi = hi; fp.mom_rho_cap = rho_cap; fp.mom_tau_cap = tau_cap;
+  fp.mom_partials = r->d_fast_partials.p;
+  fp.mom_unc_mask = r->d_fast_mask.p;
+  if (!r->d_fold_rows) {
+    const size_t bytes = kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), bytes));
+    HIPCHK(hipMemset(r->d_fold_rows, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
+  }
+  r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
+  *nb_out = nb; *wpb_out = wpb;
+  return RMCLHIP_OK;
+}
+
+// find + moment epilogue + publish on the handle's stream (kinds 23 / 2), or find + moment pass + publish (any other kind);
+// the caller waits with wait_moments(seq, ...)
+RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap,
+                                                       uint32_t seq, bool epilogue_allowed) {
+  const uint32_t nred = nred_of(r);
+  int fv = find_variant(r, 1);
+  // scans above 262 144 rays would take kind 24, which has no moment epilogue: the separate moment pass over half a million
+  // correspondences costs more (~40 us) than kind 23 loses against kind 24 there (~3 us) -- a correction of a 256 x 2048 scan 93 -> 6x us
+  if (epilogue_allowed && fv == 24 && r->variant == 15) fv = 23;
+  FindParams fp;
+  fill_find_params(r, fp, 1, fv);   // the tree and tables of the kind that RUNS
+  fp.Tsm = Tsm;
+  fp.Tms = xinv(Tsm);
+  r->last_moment_find_kind = fv;
+  r->last_moment_find_tiled = epilogue_allowed && (fv == 23 || fv == 32 || fv == 2);
+  if (epilogue_allowed && (fv == 23 || fv == 32 || fv == 2)) {
+    uint32_t nb, wpb;
+    if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, lo, hi, rho_cap, tau_cap, &nb, &wpb)) return st;
+    HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
+    HIPCHK(launch_micp_publish_tiled(r->ds_pts, r->d_points.p, r->d_normals.p, nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W,
+                                     fp.tiles_x, fp.tile_w_log2, wpb, r->h_mom_dev, r->h_done_dev, seq, r->d_fold_rows, r->d_fold_flags,
+                                     r->stream));
+  } else {
+    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
+    HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
+    r->last_fast_rows = micp_fast_blocks(nred); r->last_fast_words = (nred + 63u) / 64u;
+    MicpCallLite cl{};
+    cl.gate_lo = lo; cl.gate_hi = hi; cl.max_dist = hi; cl.rho_cap = rho_cap; cl.tau_cap = tau_cap; cl.seq = seq;
+    HIPCHK(launch_find(fp, r->kind, fv, r->stream));
+    HIPCHK(launch_micp_moments_publish(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
+                                       r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom_dev, r->h_done_dev, r->stream));
+  }
+  return RMCLHIP_OK;
+}
 
 // `speculate` (out, nullable): set when the find was enqueued WITH the moment epilogue + publish for the computeCrossStatistics calls
 // that will follow it (r->mset_pending, r->mset_seq, r->pend_*): the reference's caller loop (micp_localization.cpp:900-964)
@@ -562,11 +751,6 @@ static hipError_t stream_wait(const rmclhip_ctx* ctx, hipStream_t stream) {
   }
   return hipStreamSynchronize(stream);
 }
-
-// Wait for the end of what the handle's stream holds.  SPIN mode: a one-thread launch behind the chain stores a completion tag in pinned
-// memory, which the host sees ~7 us before the stream's own completion signal (a synchronous 128x1024 find: 31.6 -> 24.5 us, round 4);
-// the chain has ended -- kernel boundary -- when that launch runs, so its results are complete.  BLOCK mode: hipStreamSynchronize.
-static hipError_t wait_chain_end(rmclhip_rcc* r);
 
 rmclhip_status rmclhip_rcc_find(rmclhip_rcc* r, const rmclhip_transform* Tbm_est) {
   ApiGuard guard_("rmclhip_rcc_find");
@@ -742,220 +926,18 @@ rmclhip_status rmclhip_rcc_sync(rmclhip_rcc* r) {
 RMCL_INTERNAL rmclhip_status reduce_enqueue(rmclhip_rcc* r, const xform& Tpre, const xform* Tpre_dev, float max_dist,
                                      uint32_t nposes, const ReduceTail& tail) {
   if (!micp_outputs_selected(r)) return fail(RMCLHIP_ERR_INVALID, kNeedMicpOutputs);
-  const uint32_t n = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
+  const uint32_t n = nred_of(r);
   if (n == 0) return fail(RMCLHIP_ERR_INVALID, "computeCrossStatistics: empty dataset or model (call find first)");
   if (r->n_model != n && nposes > 1) return fail(RMCLHIP_ERR_INVALID, "batch reduction needs dataset size == model size");
   const uint32_t nb = reduce_num_blocks(n, nposes);
   HIPCHK(r->d_partials.reserve(static_cast<size_t>(nposes) * nb * 16));
-  ReduceParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.dataset_points = r->ds_pts;
-  p.dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-  p.model_points = r->d_points.p;
-  p.model_normals = r->d_normals.p;
-  p.model_mask = r->d_hits.p;
-  p.n = n;
+  ReduceParams p = reduce_params(r, n, max_dist, nb);
   p.nposes = nposes;
-  p.max_dist = max_dist;
   p.Tpre = Tpre;
   p.Tpre_dev = Tpre_dev;
-  p.partials = r->d_partials.p;
-  p.nblocks = nb;
   HIPCHK(launch_reduce_partials(p, r->stream));
   if (tail.mode == kTailStats) HIPCHK(launch_reduce_finalize(r->d_partials.p, nb, nposes, tail.stats_out, tail.done, tail.seq, r->stream));
   else if (tail.mode == kTailBatchSolve) HIPCHK(launch_batch_solve(r->d_partials.p, nb, nposes, r->Tsb, tail.Tdelta_out, tail.stats_out, r->stream));
-  return RMCLHIP_OK;
-}
-
-// Wait for the completion tag the LAST kernel of a chain stores in host-mapped memory after its results
-// (reduce_common.hip.h publish_tag), instead of hipStreamSynchronize: the tag arrives ~9 us before the stream's completion signal has made its way
-// through the runtime (measured on the MICP loop: 84 -> 75 us per correction).
-// The tag carries {sequence number of the call, xor of every result word}: the result is accepted only when the sequence number is
-// this call's AND the words the host reads add up to the tag's sum; otherwise polling continues.  (Round 2 polled a flag of constant
-// value that the host cleared before each launch and read a stale result 1 call in ~10^4; the per-call sequence number is what cured
-// it -- the checksum has not rejected a block since, profiles/r05_tag_handoff.txt -- and the xor remains as a belt.)  20 ms without an
-// acceptable tag, or wait mode "block" (rmclhip_ctx_set_wait_mode), falls back to the stream.
-static inline uint32_t xor_host(const void* p, size_t bytes) {
-  const volatile uint32_t* w = static_cast<const volatile uint32_t*>(p);
-  uint32_t x = 0;
-  for (size_t i = 0; i < bytes / 4; ++i) x ^= w[i];
-  return x;
-}
-// how often a poller saw ITS sequence number in the tag while the result words did not (yet) add up to the tag's sum: the event the
-// checksum exists for (rmclhip_debug_tag_retries; profiles/r05_tag_handoff.txt)
-RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries{0};
-
-static inline uint32_t next_seq(rmclhip_rcc* r) {
-  if (++r->done_seq == 0u) r->done_seq = 1u;
-  return r->done_seq;
-}
-static inline uint32_t done_sum(const DoneCheck& c) {
-  uint32_t x = xor_host(c.base, c.base_bytes);
-  if (c.code == nullptr || *c.code == 0u)
-    for (int k = 0; k < 3; ++k) if (c.extra[k]) x ^= xor_host(c.extra[k], c.extra_bytes[k]);
-  return x;
-}
-static hipError_t wait_done(const rmclhip_ctx* ctx, volatile const unsigned long long* tag, uint32_t seq, const DoneCheck& chk,
-                            hipStream_t stream) {
-  if (ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(stream);
-  const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-  for (uint32_t spins = 0;; ++spins) {
-    const unsigned long long t = *tag;
-    if (static_cast<uint32_t>(t) == seq) {
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (done_sum(chk) == static_cast<uint32_t>(t >> 32)) return hipSuccess;
-      g_tag_sum_retries.fetch_add(1, std::memory_order_relaxed);   // this call's tag, but the words read do not add up to it (yet)
-    }
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#endif
-    if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) return hipStreamSynchronize(stream);
-  }
-}
-
-static hipError_t wait_chain_end(rmclhip_rcc* r) {
-  if (r->ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(r->stream);
-  const uint32_t seq = next_seq(r);
-  if (const hipError_t e = launch_host_tag(r->h_done_dev, seq, r->stream)) return e;
-  DoneCheck none;
-  return wait_done(r->ctx, r->h_done, seq, none, r->stream);
-}
-
-static float adaptive_max_dist(const rmclhip_rcc* r, double p) {
-  // CorrespondencesCPU.cpp:21-23 (float operands, double arithmetic, float store)
-  return static_cast<float>(static_cast<double>(r->max_dist) * (1.0 - p) +
-                            static_cast<double>(r->adaptive_max_dist_min) * p);
-}
-
-// ---- the gate-stable moments on the host (micp_host.h; micp.hip k_micp_publish) -----------------------------------------------
-// The band of max_dist' values a speculating find classifies for: max_dist' = max_dist (1 - p) + adaptive_max_dist_min p moves with
-// the node's convergence_progress_ from one correction to the next (micp_localization.cpp:988-1007), the find does not know the
-// next value, so it takes +-8 % around the last one, clipped to what the two parameters allow.  A max_dist' outside the band
-// costs the first computeCrossStatistics of that correction one moment pass of its own (what every call cost before round 4).
-static inline void gate_band(const rmclhip_rcc* r, float centre, float* lo, float* hi) {
-  const float a = std::min(r->max_dist, r->adaptive_max_dist_min), b = std::max(r->max_dist, r->adaptive_max_dist_min);
-  *lo = std::max(a, 0.92f * centre);
-  *hi = std::min(b, 1.08f * centre);
-  if (!(*lo <= centre)) *lo = centre;   // (centre outside [a, b]: parameters changed since; also NaN-safe)
-  if (!(*hi >= centre)) *hi = centre;
-}
-
-// wait for the tag of a publish launch and take a verified copy of the block (see wait_done for why the sum is checked)
-static hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, float hi, float rho_cap, float tau_cap) {
-  const MicpHostBlock* hb = r->h_mom;
-  auto block_sum = [hb]() -> uint32_t {
-    uint32_t x = xor_host(hb->mom, sizeof(hb->mom));
-    const uint32_t code = *reinterpret_cast<const volatile uint32_t*>(&hb->code);
-    const uint32_t n = *reinterpret_cast<const volatile uint32_t*>(&hb->n_uncertain);
-    x ^= code ^ n;
-    if (n <= kMicpHostMaxUnc) x ^= xor_host(hb->unc, static_cast<size_t>(n) * 9u * sizeof(float));   // (written whenever they fit)
-    return x;
-  };
-  hipError_t e = hipSuccess;
-  bool unverified = false;
-  if (r->ctx->wait_block.load(std::memory_order_relaxed)) e = hipStreamSynchronize(r->stream);
-  else {
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-    volatile const unsigned long long* tag = r->h_done;
-    for (uint32_t spins = 0;; ++spins) {
-      const unsigned long long t = *tag;
-      if (static_cast<uint32_t>(t) == seq) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (block_sum() == static_cast<uint32_t>(t >> 32)) break;
-        g_tag_sum_retries.fetch_add(1, std::memory_order_relaxed);
-      }
-#if defined(__x86_64__) || defined(__i386__)
-      __builtin_ia32_pause();
-#endif
-      if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) {
-        // 20 ms without this sequence number: either the device is that slow, or a later launch of this handle has already
-        // replaced the tag (h_done is shared by every tagged launch).  Drain the stream, then accept the block only if the tag
-        // still is this publish's and its sum matches; otherwise the caller takes the streaming reduction (ADVICE r4)
-        e = hipStreamSynchronize(r->stream);
-        const unsigned long long t2 = *tag;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        unverified = !(static_cast<uint32_t>(t2) == seq && block_sum() == static_cast<uint32_t>(t2 >> 32));
-        break;
-      }
-    }
-  }
-  r->mset_pending = false;
-  if (e != hipSuccess || unverified) { r->mset.valid = false; return e; }
-  MicpMomentSet& ms = r->mset;
-  std::memcpy(ms.mom, hb->mom, sizeof(ms.mom));
-  ms.gate_lo = lo; ms.gate_hi = hi; ms.rho_cap = rho_cap; ms.tau_cap = tau_cap;
-  ms.n_unc = hb->n_uncertain;
-  ms.valid = (hb->code == 0u && ms.n_unc <= kMicpHostMaxUnc);
-  if (ms.valid) ms.set_undecided(hb->unc, ms.n_unc);   // (component-major copy, padded for the eight-lane sums)
-  return hipSuccess;
-}
-
-// caps of the next moment set from the pre-transforms the last loop met (as rmclhip_rcc_correct_once learns them)
-static inline void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau) {
-  r->fast_rho_cap = std::max(0.002f, std::max(2.0f * max_rho, 0.9f * r->fast_rho_cap));
-  r->fast_tau_cap = std::max(0.005f, std::max(2.0f * max_tau, 0.9f * r->fast_tau_cap));
-  r->fast_info.rho_cap = r->fast_rho_cap;
-  r->fast_info.tau_cap = r->fast_tau_cap;
-}
-
-// Arms the moment epilogue of the find `fp` of kind `fv` (23, 32 or 2): one partial row per workgroup (*nb of them) and *wpb mask words
-// per workgroup, the gate band and the caps the rows are good for, and -- allocated and zeroed once per handle -- the area through
-// which the workgroups of the fold hand their sums over (micp.hip fold_hand_over_row)
-static rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp, int fv, uint32_t nred, float lo, float hi, float rho_cap, float tau_cap,
-                                          uint32_t* nb_out, uint32_t* wpb_out) {
-  const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;
-  HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
-  HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
-  fp.mom_dataset_points = r->ds_pts;
-  fp.mom_dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-  fp.mom_n = nred;
-  fp.mom_gate_lo = lo; fp.mom_gate_hi = hi; fp.mom_rho_cap = rho_cap; fp.mom_tau_cap = tau_cap;
-  fp.mom_partials = r->d_fast_partials.p;
-  fp.mom_unc_mask = r->d_fast_mask.p;
-  if (!r->d_fold_rows) {
-    const size_t bytes = kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), bytes));
-    HIPCHK(hipMemset(r->d_fold_rows, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
-    r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
-  }
-  r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
-  *nb_out = nb; *wpb_out = wpb;
-  return RMCLHIP_OK;
-}
-
-// find + moment epilogue + publish on the handle's stream (kinds 23 / 2), or find + moment pass + publish (any other kind);
-// the caller waits with wait_moments(seq, ...)
-static rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap, uint32_t seq,
-                                                bool epilogue_allowed) {
-  const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-  int fv = find_variant(r, 1);
-  // scans above 262 144 rays would take kind 24, which has no moment epilogue: the separate moment pass over half a million
-  // correspondences costs more (~40 us) than kind 23 loses against kind 24 there (~3 us) -- a correction of a 256 x 2048 scan 93 -> 6x us
-  if (epilogue_allowed && fv == 24 && r->variant == 15) fv = 23;
-  FindParams fp;
-  fill_find_params(r, fp, 1, fv);   // the tree and tables of the kind that RUNS
-  fp.Tsm = Tsm;
-  fp.Tms = xinv(Tsm);
-  r->last_moment_find_kind = fv;
-  r->last_moment_find_tiled = epilogue_allowed && (fv == 23 || fv == 32 || fv == 2);
-  if (epilogue_allowed && (fv == 23 || fv == 32 || fv == 2)) {
-    uint32_t nb, wpb;
-    if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, lo, hi, rho_cap, tau_cap, &nb, &wpb)) return st;
-    HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
-    HIPCHK(launch_micp_publish_tiled(r->ds_pts, r->d_points.p, r->d_normals.p, nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W,
-                                     fp.tiles_x, fp.tile_w_log2, wpb, r->h_mom_dev, r->h_done_dev, seq, r->d_fold_rows, r->d_fold_flags,
-                                     r->stream));
-  } else {
-    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
-    HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
-    r->last_fast_rows = micp_fast_blocks(nred); r->last_fast_words = (nred + 63u) / 64u;
-    MicpCallLite cl{};
-    cl.gate_lo = lo; cl.gate_hi = hi; cl.max_dist = hi; cl.rho_cap = rho_cap; cl.tau_cap = tau_cap; cl.seq = seq;
-    HIPCHK(launch_find(fp, r->kind, fv, r->stream));
-    HIPCHK(launch_micp_moments_publish(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                       r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom_dev, r->h_done_dev, r->stream));
-  }
   return RMCLHIP_OK;
 }
 
@@ -976,7 +958,7 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
     r->ccs_last_maxd = maxd;
     r->ccs_max_rho = std::max(r->ccs_max_rho, rho);
     r->ccs_max_tau = std::max(r->ccs_max_tau, tau);
-    const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
+    const uint32_t nred = nred_of(r);
     if (r->fast_mode != 0 && nred != 0 && maxd == maxd) {
       ++r->ccs_info.calls;
       if (r->mset_pending) HIPCHK(wait_moments(r, r->mset_seq, r->pend_lo, r->pend_hi, r->pend_rho, r->pend_tau));
@@ -1193,558 +1175,6 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
   DoneCheck chk; chk.base = ctx->p2l_h_stats; chk.base_bytes = sizeof(cstats);
   HIPCHK(wait_done(ctx, ctx->p2l_h_done, ctx->p2l_seq, chk, ctx->p2l_stream));
   from_cs(*ctx->p2l_h_stats, out);
-  return RMCLHIP_OK;
-}
-
-// ---- schedule (R) of rmclhip_rcc_correct_once, micp_localization.cpp:900-964: 1 find, n_iter x (reduce + solve) -----------------
-
-// the outcome of one moment-form attempt in the handle's fast_info (code 0 done: the caps follow what it met; 1 a pre-transform left
-// the caps; 2 too many undecided correspondences)
-static void micp_record_attempt(rmclhip_rcc* r, uint32_t code, uint32_t n_uncertain, float max_rho, float max_tau) {
-  rmclhip_micp_fast_info& fi = r->fast_info;
-  fi.attempts++;
-  fi.last_code = code;
-  fi.last_uncertain = n_uncertain;
-  fi.last_rho = max_rho;
-  fi.last_tau = max_tau;
-  if (code == 0u) {
-    fi.done++;
-    learn_caps(r, max_rho, max_tau);
-  } else if (code == 1u) {
-    fi.cap_exits++;
-  } else if (code == 2u) {
-    fi.overflows++;
-  }
-}
-
-// caps of the next attempt after one the per-iteration form had to finish: the pre-transform the correction ended with (sensor frame,
-// Ts) bounds the next attempt (iterates approach it monotonically in the usual case; an attempt that still leaves the caps costs one
-// more fallback and doubles them).  After an overflow (too many undecided correspondences) the caps tighten instead.
-static void micp_caps_after_fallback(rmclhip_rcc* r, const xform& Ts, bool overflow, float prev_max_rho, float prev_max_tau) {
-  const float rho = 2.0f * std::sqrt(Ts.R.x * Ts.R.x + Ts.R.y * Ts.R.y + Ts.R.z * Ts.R.z);
-  const float tau = std::sqrt(Ts.t.x * Ts.t.x + Ts.t.y * Ts.t.y + Ts.t.z * Ts.t.z);
-  if (overflow) {
-    r->fast_rho_cap = std::max(0.002f, 1.25f * rho);
-    r->fast_tau_cap = std::max(0.005f, 1.25f * tau);
-  } else {
-    r->fast_rho_cap = std::max(0.002f, std::max(2.0f * rho, 2.0f * prev_max_rho));
-    r->fast_tau_cap = std::max(0.005f, std::max(2.0f * tau, 2.0f * prev_max_tau));
-  }
-  r->fast_info.rho_cap = r->fast_rho_cap;
-  r->fast_info.tau_cap = r->fast_tau_cap;
-}
-
-// Moment form (micp.hip "gate-stable moment form"), fast modes 1, 3 and 4, launched directly with the per-call data BY VALUE -- no
-// H2D copy node, no graph launch (a graph replay costs the host 10-16 us whatever it holds).  *out: code 0 = served, the correction
-// is in r->h_state; 1 / 2 = the caller runs the per-iteration form, which recomputes the correction from scratch.
-static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uint32_t n_iter, float maxd, uint32_t nred,
-                                           MicpFastStatus* out) {
-  HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
-  HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
-  MicpFastStatus fs{};
-  bool fs_ready = false;     // the host ran the iterations: `fs` (and r->h_state) are final, nothing to wait for
-  FindParams fp;
-  fill_find_params(r, fp, 1);
-  fp.Tsm = r->h_call->Tsm;
-  fp.Tms = r->h_call->Tms;
-  MicpCallLite cl;
-  cl.Tsb = r->Tsb; cl.Tbo = Tbo; cl.max_dist = maxd; cl.rho_cap = r->fast_rho_cap; cl.tau_cap = r->fast_tau_cap;
-  cl.gate_lo = maxd; cl.gate_hi = maxd;
-  cl.seq = r->h_call->seq;
-  const int fv = find_variant(r, 1);
-  const bool tiled = r->fast_mode != 3 && (fv == 23 || fv == 32 || fv == 2);   // the find forms the moments in its epilogue
-  if (r->fast_mode == 1) {
-    // ---- round 4 default: TWO launches (find with the moment epilogue; fold + publish), the iterations on the HOST from the 82
-    // moments + the undecided correspondences (micp_host.h): ~0.5 us per iteration instead of ~2.7 us of one lane's f64 chain
-    if (rmclhip_status st = enqueue_find_with_moments(r, r->h_call->Tsm, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, cl.seq, true)) return st;
-    HIPCHK(wait_moments(r, cl.seq, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap));
-    if (r->mset.valid) {
-      xform T_s = xidentity();
-      cstats last = cs_identity();
-      fs.code = 0u; fs.n_uncertain = r->mset.n_unc;
-      for (uint32_t it = 0; it < n_iter; ++it) {
-        const float rho = micp_rho(T_s), tau = micp_tau(T_s);
-        fs.max_rho = std::max(fs.max_rho, rho);
-        fs.max_tau = std::max(fs.max_tau, tau);
-        if (!(rho <= r->mset.rho_cap) || !(tau <= r->mset.tau_cap)) { fs.code = 1u; fs.iter = it; break; }
-        last = micp_statistics_from_set(r->mset, T_s, maxd);
-        T_s = xmul(T_s, umeyama(last));   // micp.hip micp_advance_sensor
-      }
-      if (fs.code == 0u) {
-        // micp.hip micp_close_sensor
-        fs.iter = n_iter;
-        const xform Tso = xmul(Tbo, r->Tsb);
-        r->h_state->T_snew_sold = T_s;
-        r->h_state->T_onew_oold = xmul(xmul(Tso, T_s), xinv(Tso));
-        r->h_state->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(r->Tsb, last)));
-      }
-      fs_ready = true;
-    } else {
-      // more undecided correspondences than the host takes: the device loop on the rows the find left (a sequence number of its own:
-      // the publish launch used this one for its hand-over flags and its tag)
-      cl.seq = r->h_call->seq = next_seq(r);
-      // kind and row layout are the ones enqueue_find_with_moments actually ran (it replaces kind 24 by 23 to get the epilogue):
-      // the loop folds THOSE rows instead of paying a moment pass of its own
-      const int ufv = r->last_moment_find_kind;
-      FindParams ufp;
-      fill_find_params(r, ufp, 1, ufv);
-      const uint32_t unb = find_moments_blocks(ufp, ufv), uwpb = (ufv == 2) ? 1u : 4u;
-      if (r->last_moment_find_tiled)
-        HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
-                                           nred, unb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, ufp.tiles_x, ufp.tile_w_log2, uwpb, n_iter,
-                                           r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
-      else
-        HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
-                                r->h_done_dev, r->stream, &cl));
-    }
-  } else if (tiled) {
-    // (fast_mode 4, round 3's default) TWO kernels: the find forms the moments in its epilogue (find_kernel.hip.h: the 10 x 10 factor
-    // products of its 64 correspondences per wave through f64 MFMA), one partial row per workgroup; the loop launch folds them and runs
-    // every iteration on the device
-    uint32_t nb, wpb;
-    if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, &nb, &wpb)) return st;
-    HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
-    HIPCHK(launch_micp_fast_loop_tiled(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p,
-                                       nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter,
-                                       r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags));
-  } else {
-    r->last_fast_rows = micp_fast_blocks(nred); r->last_fast_words = (nred + 63u) / 64u;
-    HIPCHK(launch_find(fp, r->kind, fv, r->stream));
-    HIPCHK(launch_micp_fast(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                            nullptr, r->d_fast_partials.p, r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev,
-                            r->h_done_dev, r->stream, &cl));
-  }
-  if (!fs_ready) {
-    // sum of the tag: the status block, plus the state block when the loop ran to its end (code 0)
-    DoneCheck chk; chk.base = r->h_fast_status; chk.base_bytes = sizeof(MicpFastStatus); chk.code = &r->h_fast_status->code;
-    chk.extra[0] = r->h_state; chk.extra_bytes[0] = sizeof(MicpState);
-    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
-    fs = *r->h_fast_status;
-  } else {
-    ++r->fast_info.host_loops;
-  }
-  r->last_fast = fs;
-  micp_record_attempt(r, fs.code, fs.n_uncertain, fs.max_rho, fs.max_tau);
-  r->fast_info.last_setup_clocks = fs.code == 0u ? fs.pad[0] : 0u;
-  r->fast_info.last_loop_clocks = fs.code == 0u ? fs.pad[1] : 0u;
-  if (fs.code > 2u) return fail(RMCLHIP_ERR_HIP, "correct_once: the moment-form loop did not report a status");
-  if (fs.code == 0u) r->fast_overflows = 0;
-  *out = fs;
-  return RMCLHIP_OK;
-}
-
-// the per-iteration chain on the handle's stream: the call block (H2D), the find, then ONE launch per iteration (k_micp_iter solves
-// the previous iteration in its prologue) + one closing solve -- n_iter + 1 launches instead of 2 * n_iter.  k_micp_close writes the
-// result straight into host-mapped memory (no copy node).  Without iterations: k_micp_init + a copy of that state.
-static rmclhip_status enqueue_micp_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
-  HIPCHK(hipMemcpyAsync(r->d_call, r->h_call, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream));
-  FindParams p;
-  fill_find_params(r, p, 1);
-  p.Tsm_arr = &r->d_call->Tsm;
-  p.Tms_arr = &r->d_call->Tms;
-  HIPCHK(launch_find(p, r->kind, find_variant(r, p.nposes), r->stream));
-  if (n_iter == 0) {
-    HIPCHK(launch_micp_init(r->d_state, r->stream));
-    HIPCHK(hipMemcpyAsync(r->h_state, r->d_state, sizeof(MicpState), hipMemcpyDeviceToHost, r->stream));
-    return RMCLHIP_OK;
-  }
-  const uint8_t* dmask = r->ds_has_mask ? r->ds_msk : nullptr;
-  const uint32_t nb = reduce_num_blocks(nred, 1);
-  double* part[2] = {r->d_partials.p, r->d_partials.p + static_cast<size_t>(nb) * 16};
-  for (uint32_t i = 0; i < n_iter; ++i)
-    HIPCHK(launch_micp_iter(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_call,
-                            part[(i + 1u) & 1u], part[i & 1u], r->d_state + (i & 1u), r->d_state + ((i + 1u) & 1u),
-                            i == 0, r->stream));
-  HIPCHK(launch_micp_close(part[(n_iter - 1u) & 1u], nb, r->d_call, r->d_state + (n_iter & 1u), r->h_state_dev,
-                           r->h_done_dev, r->stream));
-  return RMCLHIP_OK;
-}
-
-// The per-iteration form, captured ONCE into a hipGraph (the kernels read the per-call pose / frames / max_dist from d_call,
-// refreshed by the graph's first node), so that a correction costs one graph launch instead of 2 + n_iter host launches (~5 us each,
-// which left the GPU idle between these tiny kernels); set_variant bit 9 enqueues it directly.  Leaves the result in r->h_state.
-static rmclhip_status micp_per_iteration_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
-  // k_micp_close publishes a completion tag the host polls (a fresh sequence number: a moment-form attempt may have published one
-  // for this call already)
-  r->h_call->seq = next_seq(r);
-  if (r->use_graph) {
-    rmclhip_rcc::MicpKey key;
-    std::memset(&key, 0, sizeof(key));
-    key.n_iter = n_iter; key.W = r->W; key.H = r->H; key.n_dataset = r->n_dataset;
-    key.kind = static_cast<int>(r->kind); key.variant = r->variant; key.tile = r->tile_override;
-    key.has_mask = r->ds_has_mask ? 1 : 0;
-    key.ptrs[0] = r->d_points.p; key.ptrs[1] = r->ds_pts; key.ptrs[2] = r->d_partials.p;
-    key.ptrs[3] = r->d_model_tab.p; key.ptrs[4] = r->ds_msk; key.ptrs[5] = r->d_hits.p;
-    if (!r->micp_exec || r->graph_dirty || !(key == r->micp_key)) {
-      // the previous call returned on its completion tag, which precedes the stream's own completion: let the last node
-      // retire before its executable graph is destroyed
-      HIPCHK(hipStreamSynchronize(r->stream));
-      if (r->micp_exec) { (void)hipGraphExecDestroy(r->micp_exec); r->micp_exec = nullptr; }
-      if (r->micp_graph) { (void)hipGraphDestroy(r->micp_graph); r->micp_graph = nullptr; }
-      HIPCHK(hipStreamBeginCapture(r->stream, hipStreamCaptureModeThreadLocal));
-      r->capturing = true;
-      const rmclhip_status cst = enqueue_micp_chain(r, n_iter, nred);
-      r->capturing = false;
-      hipGraph_t g = nullptr;
-      const hipError_t ce = hipStreamEndCapture(r->stream, &g);
-      if (cst != RMCLHIP_OK) { if (g) (void)hipGraphDestroy(g); return cst; }
-      if (ce != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-      r->micp_graph = g;
-      HIPCHK(hipGraphInstantiate(&r->micp_exec, g, nullptr, nullptr, 0));
-      r->micp_key = key;
-      r->graph_dirty = false;
-    }
-    HIPCHK(hipGraphLaunch(r->micp_exec, r->stream));
-  } else if (rmclhip_status st = enqueue_micp_chain(r, n_iter, nred)) {
-    return st;
-  }
-  if (n_iter == 0) {
-    HIPCHK(hipStreamSynchronize(r->stream));
-  } else {
-    DoneCheck chk; chk.base = r->h_state; chk.base_bytes = sizeof(MicpState);
-    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
-  }
-  return RMCLHIP_OK;
-}
-
-rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform* Tom_, const rmclhip_transform* Tbo_,
-                                        uint32_t n_iter, double convergence_progress, int refind_each_iteration,
-                                        rmclhip_transform* T_out, rmclhip_cross_statistics* stats_out) {
-  ApiGuard guard_("rmclhip_rcc_correct_once");
-  if (!r || !Tom_ || !Tbo_ || !T_out) return fail(RMCLHIP_ERR_INVALID, "correct_once: null");
-  if (r->kind == kModelNone || r->W == 0 || r->H == 0) return fail(RMCLHIP_ERR_INVALID, "correct_once: no sensor model");
-  if (!micp_outputs_selected(r)) return fail(RMCLHIP_ERR_INVALID, kNeedMicpOutputs);
-  HIPCHK(hipSetDevice(r->ctx->device));
-  const xform Tom = to_x(Tom_), Tbo = to_x(Tbo_);
-  const float maxd = adaptive_max_dist(r, convergence_progress);
-  if (!refind_each_iteration) {
-    // schedule (R): nothing returns to the host until the end -- the pre-transform of iteration i+1 is produced on the device
-    // (or, in the moment form of mode 1, on the host from the moments the find published)
-    const size_t n = static_cast<size_t>(r->W) * r->H;
-    r->n_model = static_cast<uint32_t>(n);
-    r->nposes_last = 1;
-    if (rmclhip_status st = ensure_model_buffers(r, n)) return st;
-    const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-    if (nred == 0) return fail(RMCLHIP_ERR_INVALID, "correct_once: empty dataset");
-    HIPCHK(r->d_partials.reserve(std::max<size_t>(static_cast<size_t>(reduce_num_blocks(nred, 1)) * 32, 2u * 256u * 16u)));
-    r->h_call->Tsm = xmul(xmul(Tom, Tbo), r->Tsb);
-    r->h_call->Tms = xinv(r->h_call->Tsm);
-    r->h_call->Tsb = r->Tsb;
-    r->h_call->Tbo = Tbo;
-    r->h_call->max_dist = maxd;
-    r->h_call->gate_lo = maxd; r->h_call->gate_hi = maxd;
-    r->h_call->rho_cap = r->fast_rho_cap;
-    r->h_call->tau_cap = r->fast_tau_cap;
-    r->h_call->seq = next_seq(r);
-    // moment form first; any outcome other than "done" falls through to the per-iteration form (the device loops need >= 2
-    // iterations to pay for their moment pass; the host form -- two launches, no reduction launch at all -- serves 1 as well)
-    const bool fast_eligible = r->fast_mode != 0 && n_iter >= ((r->fast_mode == 1) ? 1u : 2u);
-    bool fast_tried = false;
-    if (fast_eligible && r->fast_holdoff > 0u) --r->fast_holdoff;
-    else if (fast_eligible) {
-      fast_tried = true;
-      MicpFastStatus fs;
-      if (rmclhip_status st = micp_try_moment_form(r, Tbo, n_iter, maxd, nred, &fs)) return st;
-      if (fs.code == 0u) {
-        from_x(r->h_state->T_onew_oold, T_out);
-        if (stats_out) from_cs(r->h_state->stats_o, stats_out);
-        return RMCLHIP_OK;
-      }
-    }
-    if (rmclhip_status st = micp_per_iteration_chain(r, n_iter, nred)) return st;
-    if (fast_tried) {
-      const xform Tb = xmul(xmul(xinv(Tbo), r->h_state->T_onew_oold), Tbo);
-      const bool overflow = r->last_fast.code == 2u;
-      micp_caps_after_fallback(r, xmul(xmul(xinv(r->Tsb), Tb), r->Tsb), overflow, r->last_fast.max_rho, r->last_fast.max_tau);
-      // too many uncertain correspondences twice in a row: stop trying for a while
-      if (overflow && ++r->fast_overflows >= 2u) { r->fast_holdoff = 32u; r->fast_overflows = 0; }
-    }
-    from_x(r->h_state->T_onew_oold, T_out);
-    if (stats_out) from_cs(r->h_state->stats_o, stats_out);
-    return RMCLHIP_OK;
-  }
-  // schedule (B), lidar_corrector_embree_benchmark.cpp:127-135: re-raycast from the corrected pose every iteration
-  xform T_onew_oold = xidentity();
-  cstats last = cs_identity();
-  for (uint32_t i = 0; i < n_iter; ++i) {
-    const xform Tom_cur = xmul(Tom, T_onew_oold);
-    if (rmclhip_status st = find_enqueue(r, xmul(Tom_cur, Tbo))) return st;
-    ReduceTail tail;
-    tail.mode = kTailStats;
-    tail.stats_out = r->h_stats_dev;
-    tail.done = r->h_done_dev;
-    tail.seq = next_seq(r);
-    if (rmclhip_status st = reduce_enqueue(r, xidentity(), nullptr, maxd, 1, tail)) return st;
-    DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
-    HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
-    const cstats Cs_o = cs_transform(Tbo, cs_transform(r->Tsb, r->h_stats[0]));
-    last = cs_merge(cs_identity(), Cs_o);
-    T_onew_oold = xmul(T_onew_oold, umeyama(last));
-  }
-  from_x(T_onew_oold, T_out);
-  if (stats_out) from_cs(last, stats_out);
-  return RMCLHIP_OK;
-}
-
-
-// MICPLocalizationNode::correctOnce inner loop for N sensors on one device (micp_localization.cpp:900-964): one find per
-// sensor, then per iteration one reduction per sensor and ONE step launch that merges, solves and hands out the next
-// pre-transforms; nothing returns to the host until the loop is over (the host form costs one synchronisation per sensor
-// and iteration).
-rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n_sensors, const rmclhip_transform* Tom_,
-                                         const rmclhip_transform* Tbo_, const double* merge_weight_multiplier, uint32_t n_iter,
-                                         double convergence_progress, rmclhip_transform* T_out,
-                                         rmclhip_cross_statistics* merged_out) {
-  ApiGuard guard_("rmclhip_micp_correct_once");
-  if (!sensors || !Tom_ || !Tbo_ || !T_out || n_sensors == 0) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: null");
-  if (n_sensors > kMaxMicpSensors) return fail(RMCLHIP_ERR_UNSUPPORTED, "micp_correct_once: at most 8 sensors");
-  rmclhip_rcc* r0 = sensors[0];
-  for (uint32_t s = 0; s < n_sensors; ++s) {
-    rmclhip_rcc* r = sensors[s];
-    if (!r) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: null sensor");
-    if (r->ctx->device != r0->ctx->device) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: sensors live on different devices");
-    if (r->kind == kModelNone || r->W == 0 || r->H == 0) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: sensor without a model");
-    if (r->n_dataset == 0) return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: sensor without a dataset");
-    if (!micp_outputs_selected(r)) return fail(RMCLHIP_ERR_INVALID, kNeedMicpOutputs);
-    // n_meas * weight is converted to uint32 on the host in one loop form and on the device in the other two: a negative or
-    // non-finite product has no defined conversion, and the forms would part
-    if (merge_weight_multiplier && !(std::isfinite(merge_weight_multiplier[s]) && merge_weight_multiplier[s] >= 0.0))
-      return fail(RMCLHIP_ERR_INVALID, "micp_correct_once: merge_weight_multiplier of sensor " + std::to_string(s) + " is negative or not finite");
-  }
-  HIPCHK(hipSetDevice(r0->ctx->device));
-  hipStream_t st = r0->stream;
-  static thread_local MicpMultiCall h_call;
-  std::memset(&h_call, 0, sizeof(h_call));
-  const xform Tom = to_x(Tom_);
-  for (uint32_t s = 0; s < n_sensors; ++s) {
-    rmclhip_rcc* r = sensors[s];
-    // (no synchronisation with the sensor's own stream: its find is enqueued ON that stream, behind whatever it still holds, and the
-    // loop touches the sensor only behind that find -- flag or event; a hipStreamSynchronize per sensor cost ~9 us each here)
-    const size_t n = static_cast<size_t>(r->W) * r->H;
-    r->n_model = static_cast<uint32_t>(n);
-    r->nposes_last = 1;
-    if (rmclhip_status e = ensure_model_buffers(r, n)) return e;
-    const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-    const uint32_t nb = reduce_num_blocks(nred, 1);
-    HIPCHK(r->d_partials.reserve(std::max<size_t>(static_cast<size_t>(nb) * 32, 2u * 256u * 16u)));
-    h_call.Tsb[s] = r->Tsb;
-    h_call.Tbo[s] = to_x(Tbo_ + s);
-    h_call.weight[s] = merge_weight_multiplier ? merge_weight_multiplier[s] : 1.0;
-    h_call.partials[s] = r->d_partials.p;
-    h_call.nblocks[s] = nb;
-  }
-  h_call.n_sensors = n_sensors;
-  h_call.seq = next_seq(r0);
-  // call + state live with the first sensor and persist between calls (an allocation per call cost more than the loop)
-  HIPCHK(r0->d_multi_blob.reserve(sizeof(MicpMultiCall) + sizeof(MicpMultiState)));
-  if (!r0->h_multi_state) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r0->h_multi_state), sizeof(MicpMultiState), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r0->h_multi_state_dev), r0->h_multi_state, 0));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r0->h_multi_status), sizeof(MicpMultiFastStatus), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r0->h_multi_status_dev), r0->h_multi_status, 0));
-  }
-  MicpMultiCall* d_call = reinterpret_cast<MicpMultiCall*>(r0->d_multi_blob.p);
-  MicpMultiState* d_state = reinterpret_cast<MicpMultiState*>(r0->d_multi_blob.p + sizeof(MicpMultiCall));
-  hipError_t e = hipSuccess;
-  // ---- moment form first (micp.hip k_micp_multi_fast_loop): every sensor's caps are the ones its own corrections learnt
-  bool fast_eligible = n_iter >= 2u;
-  for (uint32_t s = 0; s < n_sensors; ++s) fast_eligible = fast_eligible && sensors[s]->fast_mode != 0;
-  bool fast_tried = false;
-  if (fast_eligible && r0->multi_holdoff > 0u) --r0->multi_holdoff;
-  else if (fast_eligible) fast_tried = true;
-  // ---- round 4: every sensor's find forms its moments and publishes them to the host (its own stream, its own block and tag), the
-  // host merges and solves (micp_host.h; same frame-by-frame order as k_micp_multi_step).  Any sensor with too many undecided
-  // correspondences or a pre-transform outside its caps: the device forms below, from scratch.
-  bool device_fast = fast_tried;   // the device's moment loop is tried (after the host form, when that is on and did not finish)
-  bool host_form = fast_tried;
-  for (uint32_t s = 0; s < n_sensors; ++s) host_form = host_form && sensors[s]->fast_mode == 1;
-  if (host_form) {
-    float maxd[kMaxMicpSensors];
-    uint32_t seqs[kMaxMicpSensors];
-    for (uint32_t s = 0; s < n_sensors; ++s) {
-      rmclhip_rcc* r = sensors[s];
-      maxd[s] = adaptive_max_dist(r, convergence_progress);
-      seqs[s] = (s == 0u) ? h_call.seq : next_seq(r);
-      if (rmclhip_status e2 = enqueue_find_with_moments(r, xmul(xmul(Tom, h_call.Tbo[s]), r->Tsb), maxd[s], maxd[s], r->fast_rho_cap, r->fast_tau_cap,
-                                                        seqs[s], true))
-        return e2;
-    }
-    bool all_valid = true;
-    for (uint32_t s = 0; s < n_sensors; ++s) {
-      rmclhip_rcc* r = sensors[s];
-      HIPCHK(wait_moments(r, seqs[s], maxd[s], maxd[s], r->fast_rho_cap, r->fast_tau_cap));
-      all_valid = all_valid && r->mset.valid;
-    }
-    MicpMultiFastStatus hs;
-    std::memset(&hs, 0, sizeof(hs));
-    hs.code = all_valid ? 0u : 2u;
-    xform T_onew_oold = xidentity(), T_s[kMaxMicpSensors];
-    cstats merged = cs_identity(), merged_w = cs_identity();
-    for (uint32_t s = 0; s < n_sensors; ++s) { T_s[s] = xidentity(); hs.n_uncertain += sensors[s]->mset.n_unc; }
-    for (uint32_t it = 0; it < n_iter && hs.code == 0u; ++it) {
-      merged = cs_identity(); merged_w = cs_identity();
-      for (uint32_t s = 0; s < n_sensors; ++s) {
-        const rmclhip_rcc* r = sensors[s];
-        const float rho = micp_rho(T_s[s]), tau = micp_tau(T_s[s]);
-        hs.max_rho[s] = std::max(hs.max_rho[s], rho);
-        hs.max_tau[s] = std::max(hs.max_tau[s], tau);
-        if (!(rho <= r->mset.rho_cap) || !(tau <= r->mset.tau_cap)) { hs.code = 1u; hs.iter = it; hs.sensor = s; break; }
-        // micp_localization.cpp:926-937 with MICPSensor.hpp:178-182
-        const cstats stats_s = micp_statistics_from_set(r->mset, T_s[s], maxd[s]);
-        const cstats Cs_o = cs_transform(h_call.Tbo[s], cs_transform(r->Tsb, stats_s));
-        cstats Cs_w = Cs_o;
-        Cs_w.n_meas = static_cast<uint32_t>(static_cast<double>(Cs_w.n_meas) * h_call.weight[s]);
-        merged = cs_merge(merged, Cs_o);
-        merged_w = cs_merge(merged_w, Cs_w);
-      }
-      if (hs.code != 0u) break;
-      T_onew_oold = xmul(T_onew_oold, umeyama(merged_w));   // :952-963
-      for (uint32_t s = 0; s < n_sensors; ++s) {
-        const xform T_bnew_bold = xmul(xmul(xinv(h_call.Tbo[s]), T_onew_oold), h_call.Tbo[s]);
-        T_s[s] = xmul(xmul(xinv(sensors[s]->Tsb), T_bnew_bold), sensors[s]->Tsb);
-      }
-    }
-    for (uint32_t s = 0; s < n_sensors && hs.code != 2u; ++s) {   // (code 2: the device loop below is this call's attempt)
-      rmclhip_rcc* r = sensors[s];
-      micp_record_attempt(r, hs.code, hs.n_uncertain, hs.max_rho[s], hs.max_tau[s]);
-      r->fast_info.last_setup_clocks = r->fast_info.last_loop_clocks = 0u;
-      if (hs.code == 0u) r->fast_info.host_loops++;
-    }
-    if (hs.code == 0u) {
-      r0->multi_overflows = 0;
-      from_x(T_onew_oold, T_out);
-      if (merged_out) from_cs(merged, merged_out);
-      return RMCLHIP_OK;
-    }
-    // not served on the host: the device forms take over, from scratch (the moment sets belong to finds that are about to be redone).
-    // A pre-transform that left its caps would leave them in the device's moment loop as well: straight to the per-iteration form,
-    // whose end learns the caps from this status; too many undecided correspondences for the host (> kMicpHostMaxUnc = 1024 in a sensor): the device's
-    // moment loop takes up to 4096.
-    if (hs.code == 1u) {
-      device_fast = false;
-      *r0->h_multi_status = hs;
-    }
-    for (uint32_t s = 0; s < n_sensors; ++s) drop_moment_set(sensors[s]);
-    h_call.seq = next_seq(r0);
-  }
-  // sensor->setTom(Tom); sensor->findCorrespondences()  (:900-909): Tbm = Tom * Tbo.  The sensors' finds (and moment passes) do not
-  // depend on each other: sensor 0's go to the stream the loop runs on, every other sensor's to ITS OWN stream, joined by an event
-  // before the loop -- one scan leaves the chip partly idle (bench.py extras.find_two_operators_in_flight_*), a second sensor's scan
-  // fills it (round 3: everything sat on one stream)
-  MicpMultiFastParams fp;
-  std::memset(&fp, 0, sizeof(fp));
-  // A cross-stream EVENT takes ~10 us to reach the waiting queue (measured: the loop started 10-12 us after its last input), so in the
-  // moment form the join is a flag: a one-lane kernel behind the sensor's moment pass stores the call's sequence number, the loop
-  // kernel -- launched without waiting -- polls it before it touches that sensor's rows.  The per-iteration form (fallback) records
-  // an event on every other sensor's stream and waits for it.
-  if (n_sensors > 1u && !r0->d_join_flags) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r0->d_join_flags), kMaxMicpSensors * sizeof(uint32_t)));
-    HIPCHK(hipMemset(r0->d_join_flags, 0, kMaxMicpSensors * sizeof(uint32_t)));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  // every find first (the host needs ~4 us per launch: the second sensor's scan should not wait behind the first sensor's moment pass
-  // being enqueued), then the moment passes and the flags
-  for (uint32_t s = 0; s < n_sensors && e == hipSuccess; ++s) {
-    rmclhip_rcc* r = sensors[s];
-    FindParams p;
-    fill_find_params(r, p, 1);
-    p.Tsm = xmul(xmul(Tom, h_call.Tbo[s]), r->Tsb);
-    p.Tms = xinv(p.Tsm);
-    e = launch_find(p, r->kind, find_variant(r, 1), (s == 0u) ? st : r->stream);
-  }
-  for (uint32_t s = 0; s < n_sensors && e == hipSuccess && device_fast; ++s) {
-    rmclhip_rcc* r = sensors[s];
-    hipStream_t fs = (s == 0u) ? st : r->stream;
-    const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-    HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
-    HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
-    // per-call data by value: no H2D copy node per sensor (4.4 us each in the kernel trace of round 2's chain)
-    MicpCallLite cl;
-    cl.Tsb = r->Tsb; cl.Tbo = h_call.Tbo[s]; cl.max_dist = adaptive_max_dist(r, convergence_progress);
-    cl.gate_lo = cl.max_dist; cl.gate_hi = cl.max_dist;
-    cl.rho_cap = r->fast_rho_cap; cl.tau_cap = r->fast_tau_cap; cl.seq = h_call.seq;
-    HIPCHK(launch_micp_moments(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                               nullptr, r->d_fast_partials.p, r->d_fast_mask.p, fs, &cl));
-    fp.dataset_points[s] = r->ds_pts; fp.model_points[s] = r->d_points.p; fp.model_normals[s] = r->d_normals.p;
-    fp.partials[s] = r->d_fast_partials.p; fp.unc_mask[s] = r->d_fast_mask.p;
-    fp.n[s] = nred; fp.nblocks[s] = micp_fast_blocks(nred);
-    fp.Tsb[s] = cl.Tsb; fp.Tbo[s] = cl.Tbo; fp.weight[s] = h_call.weight[s];
-    fp.max_dist[s] = cl.max_dist; fp.rho_cap[s] = cl.rho_cap; fp.tau_cap[s] = cl.tau_cap;
-    if (s != 0u) {
-      HIPCHK(launch_signal_flag(r0->d_join_flags + s, h_call.seq, fs));
-      fp.join_mask |= 1u << s;
-    }
-  }
-  fp.join_flags = r0->d_join_flags;
-  if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("micp_correct_once: ") + hipGetErrorString(e));
-  if (device_fast) {
-    fp.n_sensors = n_sensors;
-    fp.seq = h_call.seq;
-    fp.n_iter = n_iter;
-    fp.state_out = r0->h_multi_state_dev;
-    fp.status = r0->h_multi_status_dev;
-    fp.done = r0->h_done_dev + 1;
-    HIPCHK(launch_micp_multi_fast_loop(fp, st));
-    {
-      DoneCheck chk; chk.base = r0->h_multi_status; chk.base_bytes = sizeof(MicpMultiFastStatus); chk.code = &r0->h_multi_status->code;
-      chk.extra[0] = &r0->h_multi_state->T_onew_oold; chk.extra_bytes[0] = sizeof(xform);
-      chk.extra[1] = &r0->h_multi_state->merged_o; chk.extra_bytes[1] = sizeof(cstats);
-      chk.extra[2] = &r0->h_multi_state->merged_weighted_o; chk.extra_bytes[2] = sizeof(cstats);
-      HIPCHK(wait_done(r0->ctx, r0->h_done + 1, h_call.seq, chk, st));
-    }
-    const MicpMultiFastStatus fs = *r0->h_multi_status;
-    for (uint32_t s = 0; s < n_sensors; ++s) micp_record_attempt(sensors[s], fs.code, fs.n_uncertain, fs.max_rho[s], fs.max_tau[s]);
-    if (fs.code == 0u) {
-      r0->multi_overflows = 0;
-      from_x(r0->h_multi_state->T_onew_oold, T_out);
-      if (merged_out) from_cs(r0->h_multi_state->merged_o, merged_out);
-      return RMCLHIP_OK;
-    }
-    if (fs.code != 1u && fs.code != 2u) return fail(RMCLHIP_ERR_HIP, "micp_correct_once: the moment-form loop did not report a status");
-  }
-  // per-iteration form (fallback, or the moment form is off): the call block goes to the device.  The other sensors' finds ran on
-  // their own streams: this stream waits for their events first.
-  for (uint32_t s = 1; s < n_sensors; ++s) {
-    rmclhip_rcc* r = sensors[s];
-    if (!r->ev_join) HIPCHK(hipEventCreateWithFlags(&r->ev_join, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(r->ev_join, r->stream));   // (recorded here, not per call: the moment form never needs it)
-    HIPCHK(hipStreamWaitEvent(st, r->ev_join, 0));
-  }
-  e = hipMemcpyAsync(d_call, &h_call, sizeof(h_call), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_micp_multi_init(d_call, d_state, st);
-  for (uint32_t it = 0; it < n_iter && e == hipSuccess; ++it) {
-    for (uint32_t s = 0; s < n_sensors && e == hipSuccess; ++s) {
-      rmclhip_rcc* r = sensors[s];
-      const uint32_t nred = (r->n_dataset < r->n_model) ? r->n_dataset : r->n_model;
-      ReduceParams rp;
-      std::memset(&rp, 0, sizeof(rp));
-      rp.dataset_points = r->ds_pts;
-      rp.dataset_mask = r->ds_has_mask ? r->ds_msk : nullptr;
-      rp.model_points = r->d_points.p; rp.model_normals = r->d_normals.p; rp.model_mask = r->d_hits.p;
-      rp.n = nred; rp.nposes = 1;
-      rp.max_dist = adaptive_max_dist(r, convergence_progress);
-      rp.Tpre = xidentity();
-      rp.Tpre_dev = &d_state->T_snew_sold[s];
-      rp.partials = r->d_partials.p;
-      rp.nblocks = h_call.nblocks[s];
-      e = launch_reduce_partials(rp, st);
-    }
-    if (e == hipSuccess) e = launch_micp_multi_step(d_call, d_state, st);
-  }
-  MicpMultiState h_state;
-  if (e == hipSuccess) e = hipMemcpyAsync(&h_state, d_state, sizeof(h_state), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("micp_correct_once: ") + hipGetErrorString(e));
-  if (fast_tried) {
-    // caps for the next attempt from the pre-transforms this correction ended with (see rmclhip_rcc_correct_once)
-    const bool overflow = r0->h_multi_status->code == 2u;
-    for (uint32_t s = 0; s < n_sensors; ++s)
-      micp_caps_after_fallback(sensors[s], h_state.T_snew_sold[s], overflow, r0->h_multi_status->max_rho[s], r0->h_multi_status->max_tau[s]);
-    if (overflow && ++r0->multi_overflows >= 2u) { r0->multi_holdoff = 32u; r0->multi_overflows = 0; }
-  }
-  from_x(h_state.T_onew_oold, T_out);
-  if (merged_out) from_cs(h_state.merged_o, merged_out);
   return RMCLHIP_OK;
 }
 

@@ -2,7 +2,7 @@
 and at its edges, against the oracle's loop (tests/oracle_micp.py::correct_once_multi).  The rigs: tests/micp_multi_cases.py;
 tests/test_micp_multi_cases_cpu.py shows that they are what they claim and that no correspondence sits on a gate.
 
-One answer, three pieces of code (rmcl_amd/csrc/capi_rcc.cpp):
+One answer, three pieces of code (rmcl_amd/csrc/capi_micp.cpp):
     host            set_micp_fast(1) on every sensor: moments + at most 1024 undecided correspondences per sensor, iterations on the host
     device          k_micp_multi_fast_loop: modes 3 / 4, or the hand-over when the host form reports code 2; at most 4096 undecided
     per-iteration   k_micp_multi_init / k_micp_multi_step: mode 0 on any sensor, n_iter < 2, or both moment forms gave up
@@ -216,14 +216,24 @@ def test_cap_exit_after_the_caps_were_learnt_small(ra, ctx, maps):
     met.  Under small caps few correspondences are undecided even at far's pose (some 600 against more than 4096
     under fresh caps), so the moment form starts there -- and the second iteration's pre-transform leaves the caps: code 1, and
     the per-iteration form serves the call"""
+    cap_exit_after_small_caps(ra, maps, 1, "host")
+
+
+def test_cap_exit_in_the_device_loop(ra, ctx, maps):
+    """the same calls with every sensor in mode 4: the caps are learnt by the device's moment loop, and it is that loop which
+    reports code 1 at far's pose; the per-iteration form serves the call and learns the caps from the loop's status"""
+    cap_exit_after_small_caps(ra, maps, 4, "device")
+
+
+def cap_exit_after_small_caps(ra, maps, mode, form):
     near, far = mc.cases()["near"], mc.cases()["far"]
     tiny = near.with_state(Tom=mc.orc.tmult(near.truth, mc.bracket_pert(mc.TINY_SCALE)))
-    loc = mc.make_localization(ra, maps(near.mesh_name), near, 1)
+    loc = mc.make_localization(ra, maps(near.mesh_name), near, mode)
     for _ in range(2):
         mc.call(loc, near)
-    proven_call(loc, near, "host")
+    proven_call(loc, near, form)
     for _ in range(30):
-        proven_call(loc, tiny, "host")
+        proven_call(loc, tiny, form)
     caps = [(a["rho_cap"], a["tau_cap"]) for a in mc.infos(loc)]
     assert all(r < 0.005 and t < 0.03 for r, t in caps), caps
     T, merged, after = proven_call(loc, far, "cap-exit")
@@ -286,9 +296,10 @@ def test_orders_and_subsets_of_one_set_of_operators(ra, ctx, maps):
 
 
 # ---- n_iter, convergence_progress ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", [1, 4])
+@pytest.mark.parametrize("mode", [0, 1, 4])
 def test_zero_and_one_iteration(ra, ctx, maps, mode):
-    """n_iter < 2 is not eligible for the moment forms: 0 gives the identity and empty statistics, 1 one oracle iteration"""
+    """n_iter < 2 is not eligible for the moment forms, in mode 0 nothing is: 0 gives the identity and empty statistics, 1 one
+    oracle iteration"""
     base = mc.cases()["mixed4"]
     loc = mc.make_localization(ra, maps(base.mesh_name), base, mode)
     zero = base.with_state(n_iter=0)
