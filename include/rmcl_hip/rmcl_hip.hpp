@@ -1216,6 +1216,13 @@ struct RefineParams : rmclhip_refine_params {
 };
 using RefineResult = rmclhip_refine_result;
 using RefineStats = rmclhip_refine_stats;
+// the Stein variational step of a cloud on an updater's field (include/rmclhip.h, STEIN STEP ON THE FIELD): every particle moves by the
+// kernel-weighted average of its neighbours' Gauss-Newton steps and away from its neighbours
+struct SteinParams : rmclhip_stein_params {
+  SteinParams() { rmclhip_stein_params_default(this); }
+};
+using SteinResult = rmclhip_stein_result;
+using SteinStats = rmclhip_stein_stats;
 class DistanceFieldHip {
  public:
   explicit DistanceFieldHip(HipMapPtr map, const FieldParams& params = FieldParams()) : map_(std::move(map)) {
@@ -1331,6 +1338,17 @@ class PCDSensorUpdaterHip : public SensorUpdaterBase, public ParticleUpdater<VRA
     RefineStats st{};
     check(rmclhip_pf_refine(h_, poses.raw(), static_cast<uint32_t>(poses.size()), beams_.data(), static_cast<uint32_t>(beams_.size()), &Tsb_, &params,
                             results.raw(), &st));
+    return st;
+  }
+  // params.iterations Stein variational steps of the cloud in place on the field of setField with the beams and Tsb of setInput
+  // (rmclhip_pf_stein_step); attributes are not touched: update() follows
+  SteinStats steinStep(DeviceView<Transform> poses, const SteinParams& params = SteinParams(),
+                       DeviceView<SteinResult> results = DeviceView<SteinResult>{nullptr, 0}) {
+    init();
+    if (results.raw() && results.size() < poses.size()) throw std::runtime_error("PCDSensorUpdaterHip::steinStep: results.size() < poses.size()");
+    SteinStats st{};
+    check(rmclhip_pf_stein_step(h_, poses.raw(), static_cast<uint32_t>(poses.size()), beams_.data(), static_cast<uint32_t>(beams_.size()), &Tsb_,
+                                &params, results.raw(), &st));
     return st;
   }
   // the per-beam errors of the next updates land here ([n_particles * n_beams] floats of device memory; nullptr: off)

@@ -1298,8 +1298,8 @@ rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* pf, const rmclhi
  * The eight lattice values that give the distance at a beam's end point also give its gradient, so a particle can be moved towards the
  * map, not only weighed against it: a per-particle Levenberg-Marquardt refinement of the cost sum_b min(d_b, max_dist)^2, all
  * iterations inside one launch, no tree, no stack.  Likelihood attributes are NEVER touched: a refined pose has not been scored, the
- * caller follows with a sensor update.  (This is the gradient half of a Stein variational step; the repulsion between particles is not
- * part of this interface.)
+ * caller follows with a sensor update.  (This is the gradient half of a Stein variational step; the neighbours' average and the
+ * repulsion between particles are STEIN STEP ON THE FIELD, below.)
  *
  * THE ARITHMETIC.  Everything is float32 unless it says double; the library is built without contraction and the device evaluates no
  * transcendental (tests/refine_ref.py restates this in numpy; the device matches it byte for byte).
@@ -1373,6 +1373,82 @@ rmclhip_status rmclhip_pf_refine(rmclhip_pf* pf, rmclhip_transform* poses_dev, u
  * the poses equal the unsharded call's bit for bit.  stats_out: the replicas' counts and sums added in rank order */
 rmclhip_status rmclhip_pf_sharded_refine(rmclhip_pf_sharded* pf, const rmclhip_range_measurement* beams, uint32_t n_beams,
                                          const rmclhip_transform* Tsb, const rmclhip_refine_params* params, rmclhip_refine_stats* stats_out);
+
+/* ---- STEIN STEP ON THE FIELD: neighbour-averaged moves and repulsion ---------------------------------------------------
+ * REFINE ON THE FIELD moves every particle on its own, and eight iterations put every particle of a basin on one point.  A Stein
+ * variational step moves particle i by the kernel-weighted average of its neighbours' moves and pushes it away from them, so the cloud
+ * goes down the cost and keeps a width.  One call runs `iterations` such steps on the handle's stream, with no host round trip between
+ * their phases.  Likelihood attributes are NEVER touched: the caller follows with a sensor update.
+ *
+ * THE ARITHMETIC (tests/stein_ref.py restates it in numpy; the device matches it byte for byte).  float32 and unfused unless it says
+ * double.  Iteration `it` = 0 .. iterations - 1; every neighbour term is computed from the poses as they were at the iteration's start.
+ *   1. Drive.  For a particle j with a finite pose: one pass of REFINE ON THE FIELD at its pose (C, A, b, n_used) and one solve at
+ *      lambda = double(lambda0), the step limits included: refine's first candidate step delta.  drive_j[k] = float(delta_k); the drive
+ *      is zero when n_used == 0, when the solve is rejected and on locked degrees of freedom.  A particle with a pose component that is
+ *      not finite is untouched, has no drive and is nobody's neighbour.
+ *   2. Cell list over the FREE translation axes.  width = 1.001f * h_trans; the bin of t_k on a free axis is the translation bin of BINS
+ *      (floor(t_k / width) clamped to -8192 .. 8191), a locked axis is ignored; rotations are not binned.  count_B = the finite-pose
+ *      particles of bin B.  Every particle of a bin with count_B <= max_per_bin is LISTED; in a fuller bin particle j is listed iff
+ *      uint64(r_j) * count_B < uint64(max_per_bin) << 32, r_j = word 0 of draw 8 of the resamplers' random stream, counter
+ *      (j, step + it, 8, 0) under the key `seed`.  w_B = float(count_B) / float(listed_B); a bin with listed_B == 0 gives nothing.  The
+ *      listed set is a function of indices and counts, never of an arrival order.
+ *   3. Pair sums of a particle i with a finite pose.  Candidates: the listed particles j != i of the 3^d bins around i's bin, d = the
+ *      number of free translation axes; a bin index beyond the clamp's range does not exist (no wrap).  Since width > h_trans, these
+ *      bins hold every j inside the kernel's support.  Per candidate:
+ *        e_k = (t_j - t_i)_k / h_trans on the free translation axes;
+ *        on the free rotation axes e_k = rho_k / h_rot, rho = 2 * vec(q_j * conj(q_i)) (the Hamilton product of the transform algebra,
+ *        conj negates x, y, z), negated if the product's w < 0: world axes, first order -- the convention of refine's omega;
+ *        s = the sum of e_k * e_k over the free degrees of freedom in bit order, from +0;
+ *        the pair COUNTS iff s < 1; then u = 1 - s, kk = u * u, a = w_B * kk.
+ *      The kernel is (1 - s)^2 for s < 1 and 0 beyond: compact support, so the adjacent bins are all of it, and no transcendental.  (It
+ *      is chosen for support and exactness, not for positive definiteness.)  With Q(x) = int64(rint(double(x) * 2^32)):
+ *        W += Q(a);   D_k += Q(a * drive_j[k]);   R_k += Q((w_B * u) * e_k)   on the free degrees of freedom k;
+ *        the self term: W += 2^32, D_k += Q(drive_i[k]).
+ *      The sums are 64-bit integers: exact in any order, so the result does not depend on the order inside a bin, on the launch or on
+ *      the schedule.  (sum of a <= n_particles <= 2^26, |drive| <= 16, |e_k| < 1: every |sum| < 2^63.)
+ *   4. Move, in double: phi_k = (double(D_k) - ((double(repulsion) * 4) * double(h_k)) * double(R_k)) / double(W), h_k = h_trans for
+ *      k < 3 and h_rot else; 0 on a locked degree of freedom.  (-4 u e_k / h_k is the kernel's gradient with respect to x_j; scaled by
+ *      repulsion * h_k^2 both terms are lengths.)  phi is limited in length as refine limits delta and applied by refine's candidate
+ *      rule.  There is NO accept test: repulsion is meant to raise a particle's own cost.
+ * Not built: the sharded filter (it would need an all-gather of poses and drives). */
+typedef struct {
+  uint32_t iterations;     /* default 1, at most 64 */
+  uint32_t dof_mask;       /* default 0x3F: refine's bits */
+  float max_dist;          /* default 0.5, must be > 0: as in refine */
+  float max_step_trans;    /* default 0.5, must be > 0 and <= 16 */
+  float max_step_rot;      /* default 0.25, must be > 0 and <= 16 */
+  float lambda0;           /* default 1e-3, must be > 0 */
+  float h_trans;           /* default 0.25 (metres): the kernel's bandwidth in translation, must be > 0 */
+  float h_rot;             /* default 0.2 (radians): ... in rotation, must be > 0 */
+  float repulsion;         /* default 0.25, must be >= 0 and finite; 0: the kernel-weighted average alone */
+  uint32_t max_per_bin;    /* default 256, must be >= 1: fuller bins are thinned to about this many listed particles */
+  uint64_t seed;           /* default 0: the key of the thinning's random stream */
+  uint32_t step;           /* default 0: its step; iteration `it` uses step + it */
+} rmclhip_stein_params;
+void rmclhip_stein_params_default(rmclhip_stein_params* out);
+typedef struct {
+  float cost;              /* float(C) at the pose the LAST iteration started from */
+  uint32_t n_used;         /* at that pose */
+  uint32_t n_neighbours;   /* the pairs with s < 1 in the last iteration */
+  float kernel_weight;     /* float(double(W) * 2^-32) of the last iteration; 0 for a pose that is not finite */
+} rmclhip_stein_result;
+typedef struct {
+  uint32_t n_particles;
+  uint32_t n_not_finite;   /* a pose component is not finite */
+  uint32_t n_no_beams;     /* finite pose, n_used == 0 */
+  uint32_t n_bins;         /* occupied bins of the cell list */
+  uint32_t n_thinned_bins; /* bins with count_B > max_per_bin; all four from the last iteration */
+  uint32_t reserved;
+  double cost_sum;         /* the rows' costs summed in double in particle order */
+} rmclhip_stein_stats;
+/* runs `iterations` Stein steps on n_particles poses (device memory) in place, on the field set with rmclhip_pf_set_field, on the
+ * handle's stream, and waits for them.  beams, n_beams, Tsb, params NULL, results_dev, stats_out: as in rmclhip_pf_refine.  The scratch
+ * belongs to the handle: it only grows and is freed with it.  n_particles == 0: RMCLHIP_OK, nothing is touched; iterations == 0:
+ * RMCLHIP_OK, nothing is launched and no row is written.  RMCLHIP_ERR_INVALID before anything is launched: a parameter outside its
+ * rule, n_particles > 2^26, no field set, and everything rmclhip_pf_refine refuses */
+rmclhip_status rmclhip_pf_stein_step(rmclhip_pf* pf, rmclhip_transform* poses_dev, uint32_t n_particles, const rmclhip_range_measurement* beams,
+                                     uint32_t n_beams, const rmclhip_transform* Tsb, const rmclhip_stein_params* params,
+                                     rmclhip_stein_result* results_dev, rmclhip_stein_stats* stats_out);
 
 /* ---- device memory helpers for hosts without their own allocator ---------------------- */
 rmclhip_status rmclhip_malloc(rmclhip_ctx* ctx, size_t bytes, void** out_dev);

@@ -99,6 +99,11 @@ rmclhip_status rmclhip_debug_tag_retries(unsigned long long* retries_out);
  * receives the bracket of the last such call made while it was on (0 before any).  Off by default: two event records per call.
  * Works without the experiments library. */
 rmclhip_status rmclhip_debug_particles_timing(rmclhip_ctx* ctx, int on, float* last_ms);
+/* MEASUREMENT aid of rmclhip_pf_stein_step (tools/stein_time.py): on != 0 puts four HIP events at the borders of the LAST iteration's
+ * three phases -- the drive | the cell list (clears, insert, decision, scan, scatter) | the pair sums and the move; last_ms3 (nullable,
+ * three floats) receives the phases of the last call made while it was on (0 before any).  Off by default.  Works without the
+ * experiments library. */
+rmclhip_status rmclhip_debug_stein_timing(rmclhip_pf* pf, int on, float* last_ms3);
 
 /* TEST hook of the rotation solve (tests/test_gpu_umeyama.py): out_host[i] = the solve of stats_host[i] by solver 0 = umeyama() on the
  * host (what rmclhip_umeyama_transform calls; ctx may be null), 1 = umeyama() on the device, 2 = umeyama_fast() on the device (the

@@ -190,6 +190,22 @@ class RefineParams(C.Structure):
                 ("max_step_rot", C.c_float), ("lambda0", C.c_float)]
 
 
+class SteinParams(C.Structure):
+    """rmclhip_stein_params (the Stein variational step on a filter handle's field)"""
+    _fields_ = [("iterations", C.c_uint32), ("dof_mask", C.c_uint32), ("max_dist", C.c_float), ("max_step_trans", C.c_float),
+                ("max_step_rot", C.c_float), ("lambda0", C.c_float), ("h_trans", C.c_float), ("h_rot", C.c_float), ("repulsion", C.c_float),
+                ("max_per_bin", C.c_uint32), ("seed", C.c_uint64), ("step", C.c_uint32)]
+
+
+class SteinStats(C.Structure):
+    """rmclhip_stein_stats"""
+    _fields_ = [("n_particles", C.c_uint32), ("n_not_finite", C.c_uint32), ("n_no_beams", C.c_uint32), ("n_bins", C.c_uint32),
+                ("n_thinned_bins", C.c_uint32), ("reserved", C.c_uint32), ("cost_sum", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if k.startswith("cost") else int)(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 class RefineStats(C.Structure):
     """rmclhip_refine_stats"""
     _fields_ = [("n_particles", C.c_uint32), ("n_moved", C.c_uint32), ("n_no_beams", C.c_uint32), ("n_not_finite", C.c_uint32),
@@ -366,6 +382,7 @@ SIGNATURES = {
     "rmclhip_debug_tag_retries": (_i32, [C.POINTER(C.c_ulonglong)]),
     "rmclhip_debug_trace": (_i32, [_i32, _vp, _sz]),
     "rmclhip_debug_particles_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
+    "rmclhip_debug_stein_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
     "rmclhip_debug_solve": (_i32, [_vp, _vp, _u32, _i32, _vp]),
     "rmclhip_comm_destroy": (None, [_vp]),
     "rmclhip_comm_size": (_u32, [_vp]),
@@ -418,6 +435,8 @@ SIGNATURES = {
     "rmclhip_field_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),
     "rmclhip_pf_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),
     "rmclhip_pf_sharded_refine": (_i32, [_vp, _vp, _u32, _vp, C.POINTER(RefineParams), C.POINTER(RefineStats)]),
+    "rmclhip_stein_params_default": (None, [C.POINTER(SteinParams)]),
+    "rmclhip_pf_stein_step": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(SteinParams), _vp, C.POINTER(SteinStats)]),
     "rmclhip_malloc": (_i32, [_vp, _sz, _pp]),
     "rmclhip_free": (_i32, [_vp, _vp]),
     "rmclhip_memcpy_h2d": (_i32, [_vp, _vp, _vp, _sz]),

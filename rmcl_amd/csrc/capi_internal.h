@@ -9,6 +9,7 @@
 //   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_field.cpp     the map's distance field: layout, coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field.hip)
+//   capi_stein.cpp     the Stein variational step of a cloud on a filter handle's field: parameters, scratch, the iterations' launches, counts (kernels: stein.hip)
 //   capi_refine.cpp    the damped Gauss-Newton refinement of particles on a distance field: parameters, launch, counts (kernel: refine.hip)
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
@@ -220,6 +221,23 @@ struct RefineScratch {
   DevBuf<uint32_t> rows, counters;
   const uint32_t* rows_src = nullptr;   // where the rows of the call in flight land (device memory); null: none were asked for
   void release() { beams.release(); rows.release(); counters.release(); }
+};
+
+// rmclhip_pf_stein_step (capi_stein.cpp): grow-only scratch of a filter handle, freed with it -- the cell list (table, counts, prefix
+// sums, every particle's word), the drives, the bins' records, the counters and the result rows when the caller gives none but asks
+// for the counts.  The beams use RefineScratch's buffer.  events: rmclhip_debug_stein_timing (include/rmclhip_lab.h)
+struct SteinScratch {
+  DevBuf<unsigned long long> table, incl, block_tot;
+  DevBuf<uint32_t> words3, slot_of, records, counters, rows;   // words3: count | listed | cursor
+  DevBuf<float> drive;
+  bool timing = false;
+  hipEvent_t events[kSteinEvents] = {nullptr, nullptr, nullptr, nullptr};
+  float last_ms[kSteinEvents - 1u] = {0.f, 0.f, 0.f};
+  void release() {
+    table.release(); incl.release(); block_tot.release(); words3.release(); slot_of.release(); records.release(); counters.release();
+    rows.release(); drive.release();
+    for (hipEvent_t& e : events) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  }
 };
 
 // the distance field of a map (capi_field.cpp): the lattice, immutable once built; handles that read it (rmclhip_pf_set_field) hold a
@@ -492,6 +510,7 @@ struct rmclhip_pf {
   uint32_t* h_surf = nullptr;
   uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: borrowed device memory, one word per particle of the next constrained launches
   RefineScratch refine;            // rmclhip_pf_refine (capi_refine.cpp)
+  SteinScratch stein;              // rmclhip_pf_stein_step (capi_stein.cpp)
   rmclhip_field* field = nullptr;  // rmclhip_pf_set_field (capi_field.cpp): correspondence_type 1 is answered from this lattice; the handle holds a reference
 };
 

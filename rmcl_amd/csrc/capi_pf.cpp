@@ -34,6 +34,7 @@ void rmclhip_pf_destroy(rmclhip_pf* f) {
   f->d_beams.release(); f->d_evals.release(); f->d_gpow.release(); f->d_order.release(); f->tag.destroy();
   pf_surface_release(f);
   f->refine.release();
+  f->stein.release();
   field_release(f->field);
   if (f->h_beams) (void)hipHostFree(f->h_beams);
   if (f->ev0) (void)hipEventDestroy(f->ev0);

@@ -550,4 +550,40 @@ struct RefineKernelParams {
 };
 hipError_t launch_field_refine(const RefineKernelParams& p, hipStream_t s);
 
+// resample.hip: the inclusive 64-bit prefix sums of n 32-bit counts, by the three scan kernels of the resamplers (incl: n words,
+// block_tot: ceil(n / 1024) words)
+hipError_t launch_scan_counts(const uint32_t* counts, uint32_t n, unsigned long long* incl, unsigned long long* block_tot, hipStream_t s);
+
+// stein.hip: one iteration of the Stein variational step (include/rmclhip.h, STEIN STEP ON THE FIELD): the drive of every particle, the
+// cell list over the free translation axes, the pair sums and the move, all enqueued on s; nothing waits.  r carries the field, the
+// poses, the beams, Tsb, dof_mask, max_dist, the step limits and lambda0 (its iterations, rows and counters are not read).  Scratch,
+// all the caller's: table / incl: table_words words of 64 bits (a power of two >= 2 n), block_tot: ceil(table_words / 1024) words,
+// count / listed / cursor: table_words words of 32 bits each, slot_of: n words, drive: kSteinDriveStride * n floats, records:
+// kSteinRecordWords * n words, counters: kSteinCounters words.  rows (nullable): n rmclhip_stein_result.
+constexpr uint32_t kSteinMaxParticles = 1u << 26;
+constexpr uint32_t kSteinDriveStride = 8u;     // six floats of drive, two of padding: one particle's drive is two 16-B loads
+constexpr uint32_t kSteinRecordWords = 16u;    // {t.x t.y t.z index | R.x R.y R.z R.w | drive 0..3 | drive 4 5, two words of padding}
+constexpr uint32_t kSteinCounters = 4u;        // {n_not_finite, n_no_beams, n_bins, n_thinned_bins}
+constexpr uint32_t kSteinEvents = 4u;          // the borders of drive | cell list | pair sums and move
+struct SteinKernelParams {
+  RefineKernelParams r;
+  float h_trans, h_rot, repulsion;
+  uint32_t max_per_bin;
+  uint32_t key0, key1, step;     // the Philox key (the seed's halves) and step + iteration
+  unsigned long long* table;
+  uint64_t table_words;
+  unsigned long long* incl;
+  unsigned long long* block_tot;
+  uint32_t* count;
+  uint32_t* listed;
+  uint32_t* cursor;
+  uint32_t* slot_of;
+  float* drive;
+  uint32_t* records;
+  uint32_t* counters;
+  uint32_t* rows;
+};
+// events (nullable): kSteinEvents events recorded on s before the drive, before the cell list, before the pair kernel and after it
+hipError_t launch_stein_iteration(const SteinKernelParams& p, hipStream_t s, hipEvent_t* events);
+
 }  // namespace rmclhip

@@ -3,7 +3,8 @@
 // same function of (seed, counter) down to the bit.  Device code only.
 //
 // Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
-//   stream 0: the resamplers   (champion or slot index, step, draw 0..7: gladiator 0 1, residual 2 3 4, systematic 5 6 7)
+//   stream 0: the resamplers   (champion or slot index, step, draw 0..7: gladiator 0 1, residual 2 3 4, systematic 5 6 7;
+//                               particle index, step + iteration, draw 8: the Stein step's thinning of full bins, stein.hip)
 //   stream 1: the initialisers (global particle index, epoch, draw 0..1)
 // reproducible, independent of the launch shape and of how the particle range is sharded across GPUs.  Transcendentals are evaluated in
 // double and rounded to float (see oracle).

@@ -483,6 +483,13 @@ hipError_t launch_sys_scan(const void* attrs, uint32_t n, double max_l, unsigned
   return hipGetLastError();
 }
 
+// the same three kernels over plain counts (stein.hip: the listed particles of every word of the cell list's table)
+hipError_t launch_scan_counts(const uint32_t* counts, uint32_t n, unsigned long long* incl, unsigned long long* block_tot, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  launch_scan(ScanCounts{counts}, n, incl, block_tot, true, s);
+  return hipGetLastError();
+}
+
 hipError_t launch_sys_fill(const xform* poses, const void* attrs, const unsigned long long* incl, uint32_t n, xform* poses_new, void* attrs_new,
                            uint32_t n_new, uint32_t first, uint32_t count, const float* cfg8, uint32_t trans_dist_metric, uint64_t seed,
                            uint32_t step, hipStream_t s) {

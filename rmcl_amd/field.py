@@ -62,6 +62,24 @@ def _refine_call(fn, handle, poses_dev, n_particles, beams, Tsb, params, results
     return st.as_dict()
 
 
+STEIN_RESULT = np.dtype([("cost", np.float32), ("n_used", np.uint32), ("n_neighbours", np.uint32), ("kernel_weight", np.float32)])
+
+
+def stein_params(iterations=None, dof_mask=None, max_dist=None, max_step_trans=None, max_step_rot=None, lambda0=None, h_trans=None, h_rot=None,
+                 repulsion=None, max_per_bin=None, seed=None, step=None):
+    """rmclhip_stein_params: the library's defaults (rmclhip_stein_params_default), overridden by the keywords that are given"""
+    p = _capi.SteinParams()
+    _capi.lib().rmclhip_stein_params_default(C.byref(p))
+    for k, v in (("iterations", iterations), ("dof_mask", dof_mask), ("max_per_bin", max_per_bin), ("seed", seed), ("step", step)):
+        if v is not None:
+            setattr(p, k, int(v))
+    for k, v in (("max_dist", max_dist), ("max_step_trans", max_step_trans), ("max_step_rot", max_step_rot), ("lambda0", lambda0),
+                 ("h_trans", h_trans), ("h_rot", h_rot), ("repulsion", repulsion)):
+        if v is not None:
+            setattr(p, k, float(v))
+    return p
+
+
 class DistanceFieldHip:
     """rmclhip_field: built once from a HipMap, immutable.  An updater it is set on keeps it alive past close()."""
 

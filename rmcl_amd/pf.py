@@ -250,6 +250,27 @@ class PCDSensorUpdaterHip:
             raise RuntimeError("setInput() first")
         return _refine_call(_capi.lib().rmclhip_pf_refine, self._h, particle_poses, n_particles, self._beams, self._Tsb, params, results_dev, kwargs)
 
+    def stein_step(self, particle_poses, n_particles=None, params=None, results_dev=None, **kwargs):
+        """rmclhip_pf_stein_step: Stein variational steps of the cloud (device memory, in place) on the field set with set_field, with
+        the beams and Tsb of setInput -- every particle moves by the kernel-weighted average of its neighbours' Gauss-Newton steps and
+        away from its neighbours.  Attributes are not touched: follow with update().  params: a stein_params(), or its keywords
+        directly; results_dev: device memory for one STEIN_RESULT row per particle (optional).  Returns the counts as a dict."""
+        from .field import stein_params
+        if not self._h:
+            self.init()
+        if self._beams is None:
+            raise RuntimeError("setInput() first")
+        if params is None:
+            params = stein_params(**kwargs)
+        elif kwargs:
+            raise TypeError("stein_step: give params or keywords, not both")
+        if n_particles is None:
+            n_particles = particle_poses.count if hasattr(particle_poses, "count") else particle_poses.shape[0]
+        st = _capi.SteinStats()
+        _capi.check(_capi.lib().rmclhip_pf_stein_step(self._h, _as_ptr(particle_poses), int(n_particles), _ptr(self._beams), len(self._beams),
+                                                      _ptr(self._Tsb), C.byref(params), _as_ptr(results_dev), C.byref(st)))
+        return st.as_dict()
+
     def extract_weights(self, particle_attrs, n_particles, weights_dev):
         _capi.check(_capi.lib().rmclhip_pf_extract_weights(self._h, _as_ptr(particle_attrs), int(n_particles),
                                                            _as_ptr(weights_dev)))
