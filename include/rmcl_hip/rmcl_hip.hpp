@@ -1209,6 +1209,14 @@ struct FieldParams : rmclhip_field_params {
   FieldParams(float cell_, float margin_) { rmclhip_field_params_default(this); cell = cell_; margin = margin_; }
 };
 using FieldInfo = rmclhip_field_info;
+// a banded field (include/rmclhip.h, BANDED DISTANCE FIELD): the same logical lattice, fine nodes stored only in bricks within `band`
+// of the surface, the rest answered from a coarse lattice -- fine cells on maps whose dense lattice is refused.  max_nodes counts the
+// stored nodes
+struct BandFieldParams : rmclhip_band_field_params {
+  BandFieldParams() { rmclhip_band_field_params_default(this); }
+  BandFieldParams(float cell_, float margin_, float band_) { rmclhip_band_field_params_default(this); cell = cell_; margin = margin_; band = band_; }
+};
+using BandFieldInfo = rmclhip_band_field_info;
 // the damped Gauss-Newton refinement of particles on a field (include/rmclhip.h, REFINE ON THE FIELD): poses move towards the map,
 // likelihood attributes are not touched -- a sensor update follows
 struct RefineParams : rmclhip_refine_params {
@@ -1229,6 +1237,14 @@ class DistanceFieldHip {
     if (!map_) throw std::runtime_error("NO MAP");
     check(rmclhip_field_create(map_->context()->handle(), map_->handle(), &params, &h_));
   }
+  // a banded field of the map: query, refine and PCDSensorUpdaterHip::setField work as on a dense one (refine and the Stein step
+  // refuse max_dist > band); download() and lattice() throw (rmclhip_field_download_banded has the three arrays)
+  static std::shared_ptr<DistanceFieldHip> banded(HipMapPtr map, const BandFieldParams& params = BandFieldParams()) {
+    if (!map) throw std::runtime_error("NO MAP");
+    rmclhip_field* h = nullptr;
+    check(rmclhip_field_create_banded(map->context()->handle(), map->handle(), &params, &h));
+    return std::shared_ptr<DistanceFieldHip>(new DistanceFieldHip(std::move(map), h));
+  }
   ~DistanceFieldHip() { rmclhip_field_destroy(h_); }
   DistanceFieldHip(const DistanceFieldHip&) = delete;
   DistanceFieldHip& operator=(const DistanceFieldHip&) = delete;
@@ -1241,6 +1257,12 @@ class DistanceFieldHip {
   FieldInfo info() const {
     FieldInfo i{};
     check(rmclhip_field_get_info(h_, &i));
+    return i;
+  }
+  // of a banded field (a dense one throws)
+  BandFieldInfo bandInfo() const {
+    BandFieldInfo i{};
+    check(rmclhip_field_get_band_info(h_, &i));
     return i;
   }
   // the node values, x fastest, then y, then z
@@ -1278,6 +1300,7 @@ class DistanceFieldHip {
   const HipMapPtr& map() const { return map_; }
 
  private:
+  DistanceFieldHip(HipMapPtr map, rmclhip_field* h) : map_(std::move(map)), h_(h) {}
   HipMapPtr map_;
   rmclhip_field* h_ = nullptr;
 };

@@ -1294,6 +1294,81 @@ rmclhip_status rmclhip_pf_set_field(rmclhip_pf* pf, rmclhip_field* field);
  * sets it on its filter handle, replacing an earlier one; NULL switches it off */
 rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* pf, const rmclhip_field_params* params);
 
+/* ---- BANDED DISTANCE FIELD: fine cells on large maps, stored near the surface ----------------------------------------
+ * A dense lattice at a fine cell does not fit a large map, and most of it is never needed at full resolution: beyond a few sigma the
+ * sensor update's exp(-d^2 / 2 sigma^2) is 0 whatever d's third digit is, and REFINE / STEIN ignore a beam with d >= max_dist.  A
+ * banded field keeps the dense field's geometry and lookup rule, stores fine nodes only in bricks near the surface, and answers the
+ * rest from a coarse lattice.  The handle is an rmclhip_field: rmclhip_field_query, rmclhip_pf_set_field, rmclhip_pf_update[_async],
+ * rmclhip_field_refine, rmclhip_pf_refine, rmclhip_pf_stein_step, rmclhip_field_get_info (the logical geometry, the actual bytes) and
+ * the map's device_bytes work on it unchanged.  rmclhip_field_download and rmclhip_field_device_view return RMCLHIP_ERR_INVALID on it.
+ *
+ * THE LAYOUT (tests/band_field_ref.py restates this in numpy).
+ *   - Logical lattice: exactly the dense field's origin, cell, inv_cell and n_k (THE GEOMETRY above; an automatic cell is the dense
+ *     rule), without the cap on the node count.  n_k - 1 <= 2^20 on every axis.
+ *   - Bricks: a brick is 8 cells per axis, nb_k = ceil((n_k - 1) / 8).  Brick (bx, by, bz) owns the logical nodes 8 b_k ... 8 b_k + 8 on
+ *     each axis: 9^3 = 729 floats, the shared faces duplicated, so the eight corners of any cell come from one brick.  In-brick order
+ *     is x fastest: node (lx, ly, lz) at (lz * 9 + ly) * 9 + lx.  Nodes of a ragged last brick beyond n_k - 1 hold NaN and are never
+ *     read (i_k <= n_k - 2).
+ *   - Coarse lattice: dense, nb_k + 1 nodes per axis, x fastest.  Coarse node c_k holds the field's value at logical node
+ *     min(8 c_k, n_k - 1): the dense node value, i.e. the library's own closest-point query there.
+ *   - Classification: reach = band + 6.9282032f * cell in float (band + 4 sqrt(3) cell: no point of a brick is farther than
+ *     4 sqrt(3) cell from its nearest corner).  A brick is STORED iff the minimum of its eight coarse corner values is <= reach, or a
+ *     corner is NaN.  Otherwise it is FAR.
+ *   - Stored bricks are numbered by an exact prefix scan in brick order (x fastest): stored index = the number of stored bricks before
+ *     it.  The numbering never follows an arrival order, so every device builds the same bytes.  A uint32 table, one word per brick
+ *     in brick order, holds the stored index or 0xFFFFFFFF (FAR).
+ *   - Fine nodes of stored bricks hold the dense field's node values (a build seed is only a candidate; the value is the unseeded
+ *     query's).
+ *
+ * THE LOOKUP.  The finite check, u_k, c_k, i_k, f_k, the clamped axes and o_k are THE LOOKUP's above.  The cell's brick is b_k = i_k >> 3.
+ *   - STORED brick: the eight corners are read from the brick at local index i_k & 7; the blend and the clamp term are unchanged.  The
+ *     result is the dense field's, to the bit.
+ *   - FAR brick: the cell is the brick.  The eight corners are the brick's coarse corners and the fractions are
+ *     F_k = (c_k - float(8 b_k)) / float(e_k) with e_k = min(8, (n_k - 1) - 8 b_k); the same blend, the same clamp term.  Every corner
+ *     exceeds reach, so the result exceeds band -- and, d being 1-Lipschitz, so does the true distance.  The error is bounded by
+ *     (sqrt(3) / 2) * 8 * cell plus rounding.
+ *   - The value-with-gradient lookup of REFINE ON THE FIELD: a beam whose cell lies in a FAR brick is NOT VALID, the rule a clamped
+ *     axis already follows.
+ *
+ * CONSEQUENCES.  With max_dist <= band, rmclhip_field_refine, rmclhip_pf_refine, rmclhip_pf_sharded_refine and rmclhip_pf_stein_step on
+ * a banded field give the dense field's bytes: a beam in a FAR brick has d > band >= max_dist on the dense field, and is not used
+ * there either (an unused beam adds max_dist^2 to the cost whether or not it is valid).  max_dist > band on a banded field is refused
+ * with RMCLHIP_ERR_INVALID before anything is launched. */
+typedef struct {
+  float cell;          /* node spacing in metres; 0 (the default): automatic, the dense field's rule */
+  float margin;        /* as rmclhip_field_params; default 0 */
+  uint64_t max_nodes;  /* counts STORED nodes: 729 * n_stored + n_coarse beyond it is refused; default 2^26 (256 MiB) */
+  float band;          /* fine values are kept wherever the distance may be <= band; default 0.5, > 0 and finite */
+  uint32_t reserved;   /* 0 */
+} rmclhip_band_field_params;
+void rmclhip_band_field_params_default(rmclhip_band_field_params* out);
+typedef struct {
+  uint32_t nb[3];      /* bricks per axis */
+  uint32_t brick_edge; /* 8 */
+  uint64_t n_bricks, n_stored, n_coarse;
+  float band, reach;
+  uint64_t bytes;      /* table + coarse lattice + stored bricks, as held on the device */
+} rmclhip_band_field_info;
+/* host only, no device needed: the logical geometry and the bricks rmclhip_field_create_banded will use for a map with this box;
+ * n_stored and both bytes are 0 (they depend on the map).  RMCLHIP_ERR_INVALID: what rmclhip_field_layout_host refuses except the node
+ * count, band not positive and finite, more than 2^20 cells on an axis, a coarse lattice of more than max_nodes nodes */
+rmclhip_status rmclhip_band_field_layout_host(const float bbox_min[3], const float bbox_max[3], const rmclhip_band_field_params* params,
+                                              rmclhip_field_info* logical_out, rmclhip_band_field_info* info_out);
+/* builds the banded field of `map` on its device and waits for it: the coarse lattice by seeded queries (every 16th logical node, then
+ * every 8th), the classification, the exact scan, one count read back, then the stored bricks.  Refused with RMCLHIP_ERR_INVALID: what
+ * rmclhip_band_field_layout_host refuses and a map with no faces before anything is launched; 729 * n_stored + n_coarse > max_nodes
+ * once the count is known -- everything allocated is freed and the map's device_bytes is what it was.  Lifetime and accounting are
+ * rmclhip_field_create's */
+rmclhip_status rmclhip_field_create_banded(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_band_field_params* params, rmclhip_field** out);
+/* RMCLHIP_ERR_INVALID on a dense field */
+rmclhip_status rmclhip_field_get_band_info(const rmclhip_field* field, rmclhip_band_field_info* out);
+/* the three arrays to host memory: table (n_bricks words), coarse (n_coarse floats), bricks (729 * n_stored floats, in stored order).
+ * Each pointer may be NULL (that array is skipped); each capacity counts elements.  RMCLHIP_ERR_INVALID on a dense field */
+rmclhip_status rmclhip_field_download_banded(rmclhip_field* field, uint32_t* table, size_t table_capacity, float* coarse, size_t coarse_capacity,
+                                             float* bricks, size_t bricks_capacity);
+/* rmclhip_pf_sharded_set_field with a banded field on every replica (same bytes on all); NULL switches the field off */
+rmclhip_status rmclhip_pf_sharded_set_field_banded(rmclhip_pf_sharded* pf, const rmclhip_band_field_params* params);
+
 /* ---- REFINE ON THE FIELD: damped Gauss-Newton of every particle by lookup -------------------------------------------
  * The eight lattice values that give the distance at a beam's end point also give its gradient, so a particle can be moved towards the
  * map, not only weighed against it: a per-particle Levenberg-Marquardt refinement of the cost sum_b min(d_b, max_dist)^2, all

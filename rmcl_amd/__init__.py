@@ -15,7 +15,7 @@ from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, Hip
                            flatten_scene_host, import_hip_map, import_hip_scene, pose_information_p2l, statistics_p2l)
 
 from . import field  # noqa: F401
-from .field import DistanceFieldHip, field_layout, field_params, refine_params, stein_params  # noqa: F401
+from .field import DistanceFieldHip, band_field_layout, band_field_params, field_layout, field_params, refine_params, stein_params  # noqa: F401
 
 from ._capi import load_lab  # noqa: F401  (experiments library; tools/ and the `lab` tests only)
 

@@ -184,6 +184,22 @@ class FieldInfo(C.Structure):
                 "inv_cell": float(self.inv_cell), "n_nodes": int(self.n_nodes), "bytes": int(self.bytes)}
 
 
+class BandFieldParams(C.Structure):
+    """rmclhip_band_field_params (a banded distance field: fine nodes within `band` of the surface; max_nodes counts stored nodes)"""
+    _fields_ = [("cell", C.c_float), ("margin", C.c_float), ("max_nodes", C.c_uint64), ("band", C.c_float), ("reserved", C.c_uint32)]
+
+
+class BandFieldInfo(C.Structure):
+    """rmclhip_band_field_info"""
+    _fields_ = [("nb", C.c_uint32 * 3), ("brick_edge", C.c_uint32), ("n_bricks", C.c_uint64), ("n_stored", C.c_uint64),
+                ("n_coarse", C.c_uint64), ("band", C.c_float), ("reach", C.c_float), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {"nb": tuple(int(x) for x in self.nb), "brick_edge": int(self.brick_edge), "n_bricks": int(self.n_bricks),
+                "n_stored": int(self.n_stored), "n_coarse": int(self.n_coarse), "band": float(self.band), "reach": float(self.reach),
+                "bytes": int(self.bytes)}
+
+
 class RefineParams(C.Structure):
     """rmclhip_refine_params (the damped Gauss-Newton refinement on the distance field)"""
     _fields_ = [("iterations", C.c_uint32), ("dof_mask", C.c_uint32), ("max_dist", C.c_float), ("max_step_trans", C.c_float),
@@ -431,6 +447,12 @@ SIGNATURES = {
     "rmclhip_field_query": (_i32, [_vp, _vp, _sz, _i32, _vp]),
     "rmclhip_pf_set_field": (_i32, [_vp, _vp]),
     "rmclhip_pf_sharded_set_field": (_i32, [_vp, C.POINTER(FieldParams)]),
+    "rmclhip_band_field_params_default": (None, [C.POINTER(BandFieldParams)]),
+    "rmclhip_band_field_layout_host": (_i32, [_vp, _vp, C.POINTER(BandFieldParams), C.POINTER(FieldInfo), C.POINTER(BandFieldInfo)]),
+    "rmclhip_field_create_banded": (_i32, [_vp, _vp, C.POINTER(BandFieldParams), _pp]),
+    "rmclhip_field_get_band_info": (_i32, [_vp, C.POINTER(BandFieldInfo)]),
+    "rmclhip_field_download_banded": (_i32, [_vp, _vp, _sz, _vp, _sz, _vp, _sz]),
+    "rmclhip_pf_sharded_set_field_banded": (_i32, [_vp, C.POINTER(BandFieldParams)]),
     "rmclhip_refine_params_default": (None, [C.POINTER(RefineParams)]),
     "rmclhip_field_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),
     "rmclhip_pf_refine": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineStats)]),

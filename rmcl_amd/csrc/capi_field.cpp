@@ -9,9 +9,10 @@ void rmclhip_field_params_default(rmclhip_field_params* out) {
   out->max_nodes = 1ull << 26;
 }
 
-// the geometry of a field over [bmin, bmax], in the header's operation order
-static rmclhip_status field_layout(const std::string& who, const float* bmin, const float* bmax, const rmclhip_field_params* params,
-                                   rmclhip_field_info* out) {
+// the geometry of a field over [bmin, bmax], in the header's operation order.  banded: the logical lattice of a banded field
+// (capi_band_field.cpp) -- no cap on the nodes, at most 2^20 cells per axis; bytes is left 0
+RMCL_INTERNAL rmclhip_status field_layout(const std::string& who, const float* bmin, const float* bmax, const rmclhip_field_params* params,
+                                          rmclhip_field_info* out, bool banded) {
   rmclhip_field_params p;
   rmclhip_field_params_default(&p);
   if (params) p = *params;
@@ -36,13 +37,15 @@ static rmclhip_status field_layout(const std::string& who, const float* bmin, co
     const float steps = std::ceil(ext[k] / cell);
     if (!(steps < 2147483648.0f)) return fail(RMCLHIP_ERR_INVALID, too_many);
     out->n[k] = std::max(2u, static_cast<uint32_t>(steps) + 1u);
-    if (out->n[k] > p.max_nodes / total) return fail(RMCLHIP_ERR_INVALID, too_many);   // total * n_k > max_nodes, without the overflow
+    if (banded) {
+      if (out->n[k] - 1u > (1u << 20)) return fail(RMCLHIP_ERR_INVALID, who + ": more than 2^20 cells on an axis (a larger cell or a smaller margin)");
+    } else if (out->n[k] > p.max_nodes / total) return fail(RMCLHIP_ERR_INVALID, too_many);   // total * n_k > max_nodes, without the overflow
     total *= out->n[k];
   }
   out->cell = cell;
   out->inv_cell = 1.0f / cell;
   out->n_nodes = total;
-  out->bytes = total * sizeof(float);
+  out->bytes = banded ? 0u : total * sizeof(float);
   return RMCLHIP_OK;
 }
 
@@ -51,7 +54,7 @@ rmclhip_status rmclhip_field_layout_host(const float* bbox_min, const float* bbo
   if (!bbox_min || !bbox_max || !info_out) return fail(RMCLHIP_ERR_INVALID, "field_layout_host: null");
   std::memset(info_out, 0, sizeof(*info_out));
   rmclhip_field_info info{};
-  if (rmclhip_status st = field_layout("field_layout_host", bbox_min, bbox_max, params, &info)) return st;
+  if (rmclhip_status st = field_layout("field_layout_host", bbox_min, bbox_max, params, &info, false)) return st;
   *info_out = info;
   return RMCLHIP_OK;
 }
@@ -62,6 +65,11 @@ RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd) {
   for (int k = 0; k < 3; ++k) { v.n[k] = fd->info.n[k]; v.origin[k] = fd->info.origin[k]; }
   v.cell = fd->info.cell;
   v.inv_cell = fd->info.inv_cell;
+  // a banded field (capi_band_field.cpp): lat is null
+  v.table = fd->d_table;
+  v.coarse = fd->d_coarse;
+  v.bricks = fd->d_bricks;
+  for (int k = 0; k < 3; ++k) v.nb[k] = fd->band.nb[k];
   return v;
 }
 
@@ -70,10 +78,13 @@ RMCL_INTERNAL void field_release(rmclhip_field* fd) {
   (void)hipSetDevice(fd->ctx->device);
   if (fd->stream) (void)hipStreamSynchronize(fd->stream);
   fd->d_q_points.release(); fd->d_q_out.release(); fd->refine.release();
-  if (fd->d_lat) {
-    (void)hipFree(fd->d_lat);
+  if (fd->d_lat) (void)hipFree(fd->d_lat);
+  if (fd->d_table) (void)hipFree(fd->d_table);
+  if (fd->d_coarse) (void)hipFree(fd->d_coarse);
+  if (fd->d_bricks) (void)hipFree(fd->d_bricks);
+  if (fd->accounted) {
     std::lock_guard<std::mutex> lock(fd->map->grid_mtx);
-    fd->map->bytes -= fd->info.bytes;
+    fd->map->bytes -= fd->accounted;
   }
   if (fd->stream) (void)hipStreamDestroy(fd->stream);
   rmclhip_map_release(fd->map);
@@ -125,7 +136,7 @@ rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rm
   if (!ctx || !map) return fail(RMCLHIP_ERR_INVALID, "field_create: NO MAP");
   if (map->ctx != ctx) return fail(RMCLHIP_ERR_INVALID, "field_create: the map belongs to another context");
   rmclhip_field_info info{};
-  if (rmclhip_status st = field_layout("field_create", map->info.bbox_min, map->info.bbox_max, params, &info)) return st;
+  if (rmclhip_status st = field_layout("field_create", map->info.bbox_min, map->info.bbox_max, params, &info, false)) return st;
   if (map->info.n_faces == 0u || map->info.n_records == 0u) return fail(RMCLHIP_ERR_INVALID, "field_create: the map has no faces");
   HIPCHK(hipSetDevice(ctx->device));
   rmclhip_field* fd = new rmclhip_field();
@@ -140,6 +151,7 @@ rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rm
     if (e == hipSuccess) {
       std::lock_guard<std::mutex> lock(map->grid_mtx);
       map->bytes += info.bytes;
+      fd->accounted = info.bytes;
     } else {
       fd->d_lat = nullptr;
     }
@@ -172,6 +184,7 @@ rmclhip_status rmclhip_field_get_info(const rmclhip_field* field, rmclhip_field_
 rmclhip_status rmclhip_field_download(rmclhip_field* field, float* out, size_t capacity) {
   ApiGuard guard_("rmclhip_field_download");
   if (!field || !out) return fail(RMCLHIP_ERR_INVALID, "field_download: null");
+  if (field->banded) return fail(RMCLHIP_ERR_INVALID, "field_download: the field is banded (rmclhip_field_download_banded)");
   if (capacity < field->info.n_nodes) return fail(RMCLHIP_ERR_INVALID, "field_download: capacity is smaller than n_nodes");
   HIPCHK(hipSetDevice(field->ctx->device));
   std::lock_guard<std::mutex> lock(field->mtx);
@@ -182,6 +195,8 @@ rmclhip_status rmclhip_field_download(rmclhip_field* field, float* out, size_t c
 rmclhip_status rmclhip_field_device_view(const rmclhip_field* field, const float** lattice_dev) {
   ApiGuard guard_("rmclhip_field_device_view");
   if (!field || !lattice_dev) return fail(RMCLHIP_ERR_INVALID, "field_device_view: null");
+  *lattice_dev = nullptr;
+  if (field->banded) return fail(RMCLHIP_ERR_INVALID, "field_device_view: the field is banded, it has no dense lattice");
   *lattice_dev = field->d_lat;
   return RMCLHIP_OK;
 }

@@ -9,6 +9,7 @@
 //   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
 //   capi_field.cpp     the map's distance field: layout, coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field.hip)
+//   capi_band_field.cpp the banded distance field: layout, the coarse build, classification, the bricks' fill, download (kernels: band_field.hip; the lookups are field.hip's)
 //   capi_stein.cpp     the Stein variational step of a cloud on a filter handle's field: parameters, scratch, the iterations' launches, counts (kernels: stein.hip)
 //   capi_refine.cpp    the damped Gauss-Newton refinement of particles on a distance field: parameters, launch, counts (kernel: refine.hip)
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
@@ -248,6 +249,14 @@ struct rmclhip_field {
   std::atomic<int> refs{1};
   rmclhip_field_info info{};
   float* d_lat = nullptr;
+  // a banded field (capi_band_field.cpp): d_lat is null, the three arrays of BANDED DISTANCE FIELD instead; info is the logical
+  // geometry with the actual bytes
+  bool banded = false;
+  rmclhip_band_field_info band{};
+  uint32_t* d_table = nullptr;
+  float* d_coarse = nullptr;
+  float* d_bricks = nullptr;
+  uint64_t accounted = 0;          // what the field has added to its map's device_bytes
   std::mutex mtx;
   hipStream_t stream = nullptr;
   DevBuf<float> d_q_points, d_q_out;
@@ -642,6 +651,11 @@ RMCL_INTERNAL rmclhip_status pf_field_enqueue(rmclhip_pf* f, const rmclhip_trans
                                               const rmclhip_transform* Tsb);
 // capi_field.cpp: the kernels' view of a field
 RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd);
+// capi_field.cpp: the geometry of a field over a box (banded: the logical lattice of a banded field, not capped by max_nodes)
+RMCL_INTERNAL rmclhip_status field_layout(const std::string& who, const float* bmin, const float* bmax, const rmclhip_field_params* params,
+                                          rmclhip_field_info* out, bool banded);
+// capi_band_field.cpp: RMCLHIP_ERR_INVALID if `field` is banded and max_dist exceeds its band (null or dense: RMCLHIP_OK)
+RMCL_INTERNAL rmclhip_status field_band_check(const std::string& who, const rmclhip_field* field, float max_dist);
 // capi_refine.cpp: the refinement in two halves, so that the sharded filter has every device's launch in flight before it waits for any.
 // refine_check refuses what the header lists (params null: the defaults are written to *out); refine_enqueue uploads the beams and
 // launches on `stream`; refine_finish waits for the stream and ADDS this call's counts to *stats (nullable)

@@ -727,6 +727,27 @@ rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip
   return RMCLHIP_OK;
 }
 
+// the same with a banded field on every replica (capi_band_field.cpp)
+rmclhip_status rmclhip_pf_sharded_set_field_banded(rmclhip_pf_sharded* h, const rmclhip_band_field_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_field_banded");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_field_banded: null");
+  if (params) {   // refuse before any replica is touched
+    rmclhip_field_info logical;
+    rmclhip_band_field_info info;
+    for (PfRank& R : h->ranks)
+      if (rmclhip_status st = rmclhip_band_field_layout_host(R.map->info.bbox_min, R.map->info.bbox_max, params, &logical, &info)) return st;
+  }
+  for (PfRank& R : h->ranks) {
+    rmclhip_field* fd = nullptr;
+    if (params)
+      if (rmclhip_status st = rmclhip_field_create_banded(R.ctx, R.map, params, &fd)) return st;
+    const rmclhip_status st = rmclhip_pf_set_field(R.pf, fd);
+    rmclhip_field_destroy(fd);
+    if (st) return st;
+  }
+  return RMCLHIP_OK;
+}
+
 // every replica refines its own block on its own field (capi_refine.cpp); no collective, attributes and weights are not touched
 rmclhip_status rmclhip_pf_sharded_refine(rmclhip_pf_sharded* h, const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
                                          const rmclhip_refine_params* params, rmclhip_refine_stats* stats_out) {
@@ -737,6 +758,8 @@ rmclhip_status rmclhip_pf_sharded_refine(rmclhip_pf_sharded* h, const rmclhip_ra
     if (!R.pf->field) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_refine: no distance field is set (rmclhip_pf_sharded_set_field)");
   rmclhip_refine_params p;
   if (rmclhip_status st = refine_check("pf_sharded_refine", h, h->n_total, beams, n_beams, Tsb, params, &p)) return st;
+  for (PfRank& R : h->ranks)
+    if (rmclhip_status st = field_band_check("pf_sharded_refine", R.pf->field, p.max_dist)) return st;
   if (h->n_total == 0) return RMCLHIP_OK;
   for (PfRank& R : h->ranks) {   // every rank's launch is in flight before the host waits for any
     if (R.hi == R.lo) continue;

@@ -93,6 +93,7 @@ rmclhip_status rmclhip_field_refine(rmclhip_field* field, rmclhip_transform* pos
   if (!field) return fail(RMCLHIP_ERR_INVALID, "field_refine: null");
   rmclhip_refine_params p;
   if (rmclhip_status st = refine_check("field_refine", poses_dev, n_particles, beams, n_beams, Tsb, params, &p)) return st;
+  if (rmclhip_status st = field_band_check("field_refine", field, p.max_dist)) return st;
   if (n_particles == 0u) return RMCLHIP_OK;
   HIPCHK(hipSetDevice(field->ctx->device));
   std::lock_guard<std::mutex> lock(field->mtx);
@@ -110,6 +111,7 @@ rmclhip_status rmclhip_pf_refine(rmclhip_pf* f, rmclhip_transform* poses_dev, ui
   if (!f->field) return fail(RMCLHIP_ERR_INVALID, "pf_refine: no distance field is set (rmclhip_pf_set_field)");
   rmclhip_refine_params p;
   if (rmclhip_status st = refine_check("pf_refine", poses_dev, n_particles, beams, n_beams, Tsb, params, &p)) return st;
+  if (rmclhip_status st = field_band_check("pf_refine", f->field, p.max_dist)) return st;
   if (n_particles == 0u) return RMCLHIP_OK;
   HIPCHK(hipSetDevice(f->ctx->device));
   if (rmclhip_status st = refine_enqueue(f->field, f->stream, f->refine, poses_dev, n_particles, beams, n_beams, Tsb, p, results_dev, stats_out != nullptr))

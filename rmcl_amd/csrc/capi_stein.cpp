@@ -52,6 +52,7 @@ rmclhip_status rmclhip_pf_stein_step(rmclhip_pf* f, rmclhip_transform* poses_dev
   // the parameters refine has too, then this call's own, then (n > 0) the buffers and the beams
   if (rmclhip_status st = refine_check("pf_stein_step", nullptr, 0u, nullptr, 0u, nullptr, &as_refine, &rp)) return st;
   if (rmclhip_status st = stein_check(p, n)) return st;
+  if (rmclhip_status st = field_band_check("pf_stein_step", f->field, p.max_dist)) return st;
   if (rmclhip_status st = refine_check("pf_stein_step", poses_dev, n, beams, n_beams, Tsb, &as_refine, &rp)) return st;
   if (n == 0u) return RMCLHIP_OK;
   if (stats_out) stats_out->n_particles = n;

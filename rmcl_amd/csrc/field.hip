@@ -8,6 +8,9 @@
 //                     the tree query replaced by the lookup -- same Tsm, same end point, same evaluation, same in-order merge.  No
 //                     traversal, no stack: LDS holds the workgroup's Tsm and its beam evaluations only.
 //
+// k_field_query and k_pf_update_field are instantiated on the layout: <false> reads the dense lattice, <true> a banded field's table,
+// bricks and coarse lattice (field_lookup.hip.h, field_corners_banded; the build is band_field.hip).
+//
 // The lookup (field_lookup.hip.h, shared with refine.hip) is eight dependent gathers and seven lerps in a stated float order.  Rays are
 // dealt beam-minor: the lanes of a wave hold consecutive beams of one particle, Tsm is a wave-uniform LDS read, and the end points of
 // neighbouring beams fall into neighbouring cells.
@@ -47,13 +50,15 @@ __global__ void __launch_bounds__(256) k_field_build(const FieldBuildParams p) {
   if (p.dist_out != nullptr) p.dist_out[id] = found ? sqrtf(nh.d2) : __uint_as_float(0x7FC00000u);
 }
 
+template <bool kBanded>
 __global__ void __launch_bounds__(256) k_field_query(const FieldView fv, const float* __restrict__ points, size_t n, float* __restrict__ out) {
   const size_t id = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
   if (id >= n) return;
   const float* pp = points + 3u * id;
-  out[id] = field_lookup(fv, mk3(pp[0], pp[1], pp[2]));
+  out[id] = field_lookup<kBanded>(fv, mk3(pp[0], pp[1], pp[2]));
 }
 
+template <bool kBanded>
 __global__ void __launch_bounds__(256) k_pf_update_field(const PfFieldParams p) {
   // LDS: [ Tsm (PB xforms) | evals (PB * n_beams floats) ]
   extern __shared__ uint32_t lds_dyn[];
@@ -77,7 +82,7 @@ __global__ void __launch_bounds__(256) k_pf_update_field(const PfFieldParams p) 
     const f3 dir = qrot(Tsm.R, mk3(bm[3], bm[4], bm[5]));
     const f3 org = xapply(Tsm, mk3(bm[0], bm[1], bm[2]));
     const f3 mean = add3(org, scale3(dir, bm[6]));
-    const float error = field_lookup(p.fv, mean);
+    const float error = field_lookup<kBanded>(p.fv, mean);
     if (p.errors) p.errors[static_cast<size_t>(p0 + pi) * p.n_beams + b] = error;
     const float arg = -(error * error) / sq / 2;
     s_eval[r] = static_cast<float>(exp(static_cast<double>(arg)) / sqrt(static_cast<double>(2 * sq) * 3.14159265358979323846));
@@ -112,7 +117,9 @@ hipError_t launch_field_query(const FieldView& fv, const float* points, size_t n
   if (n == 0u) return hipSuccess;
   const size_t blocks = (n + 255u) / 256u;
   if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_field_query, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, fv, points, n, out);
+  // lat == nullptr: a banded field (band_field.hip)
+  if (fv.lat != nullptr) hipLaunchKernelGGL(k_field_query<false>, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, fv, points, n, out);
+  else hipLaunchKernelGGL(k_field_query<true>, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, fv, points, n, out);
   return hipGetLastError();
 }
 
@@ -120,7 +127,8 @@ hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s) {
   const uint32_t nblocks = (p.n_particles + p.particles_per_block - 1u) / p.particles_per_block;
   const size_t lds = sizeof(xform) * p.particles_per_block + sizeof(float) * static_cast<size_t>(p.particles_per_block) * p.n_beams;
   if (lds > 65536u) return hipErrorInvalidValue;   // the caller deals at most 8192 beams to a workgroup
-  hipLaunchKernelGGL(k_pf_update_field, dim3(nblocks), dim3(256), lds, s, p);
+  if (p.fv.lat != nullptr) hipLaunchKernelGGL(k_pf_update_field<false>, dim3(nblocks), dim3(256), lds, s, p);
+  else hipLaunchKernelGGL(k_pf_update_field<true>, dim3(nblocks), dim3(256), lds, s, p);
   return hipGetLastError();
 }
 

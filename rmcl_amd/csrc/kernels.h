@@ -491,11 +491,20 @@ constexpr uint32_t kPoseInfoRow = 32u;
 hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s);
 
 // field.hip: the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
+// A banded field (include/rmclhip.h, BANDED DISTANCE FIELD; band_field.hip) has lat == nullptr and the three arrays below: table,
+// nb[0] * nb[1] * nb[2] words (the stored index of a brick or kBandFar), x fastest; coarse, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)
+// floats, x fastest; bricks, kBandBrickNodes floats per stored brick, x fastest inside a brick.
+constexpr uint32_t kBandFar = 0xFFFFFFFFu;
+constexpr uint32_t kBandBrickNodes = 729u;     // 9 * 9 * 9: the 8 cells of a brick per axis and their shared faces
 struct FieldView {
   const float* lat;
   uint32_t n[3];
   float origin[3];
   float cell, inv_cell;
+  const uint32_t* table;
+  const float* coarse;
+  const float* bricks;
+  uint32_t nb[3];
 };
 // one level of the coarse-to-fine build: the nodes (ci * stride, cj * stride, ck * stride), ci < cn[0] ..., of `fv`'s lattice.
 // seed_rec (nullable): the records the previous level left, pn[0] * pn[1] * pn[2] of them at stride pstride -- a node starts from the
@@ -530,6 +539,42 @@ struct PfFieldParams {
   uint32_t particles_per_block;
 };
 hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s);
+
+// band_field.hip: the build of a banded field, in the order the caller runs it.  v: the logical geometry with nb set (its pointers are
+// not read).  All index arithmetic is size_t.
+//   launch_band_nodes     one lane per node of a level: logical node min(c_k * stride, n_k - 1), c_k < cn[k]; seeded (seed_rec nullable)
+//                         from the previous level's node min((i_k + pstride / 2) / pstride, pn[k] - 1); rec_out and dist_out nullable
+//   launch_band_classify  one lane per brick: flags[b] = 1 if the minimum of its eight coarse corners is <= reach or one is NaN, else 0
+//   launch_band_table     incl: the inclusive prefix sums of flags (launch_scan_counts).  table[b] = incl[b] - 1 of a stored brick,
+//                         kBandFar of any other; stored[incl[b] - 1] = b
+//   launch_band_fill      one workgroup per stored brick: its 729 node values, every query seeded from the record of the nearest
+//                         coarse corner; NaN beyond n_k - 1
+struct BandNodesParams {
+  const uint32_t* nodes;
+  const uint32_t* tris;
+  uint32_t n_tris;
+  FieldView fv;
+  uint32_t stride, cn[3];
+  const uint32_t* seed_rec;
+  uint32_t pstride, pn[3];
+  uint32_t* rec_out;
+  float* dist_out;
+};
+hipError_t launch_band_nodes(const BandNodesParams& p, hipStream_t s);
+hipError_t launch_band_classify(const FieldView& v, const float* coarse, float reach, uint32_t* flags, hipStream_t s);
+hipError_t launch_band_table(const FieldView& v, const uint32_t* flags, const unsigned long long* incl, uint32_t* table, uint32_t* stored,
+                             hipStream_t s);
+struct BandFillParams {
+  const uint32_t* nodes;
+  const uint32_t* tris;
+  uint32_t n_tris;
+  FieldView fv;
+  const uint32_t* stored;        // n_stored brick numbers
+  uint32_t n_stored;
+  const uint32_t* coarse_rec;    // the records of the coarse lattice's queries
+  float* bricks;
+};
+hipError_t launch_band_fill(const BandFillParams& p, hipStream_t s);
 
 // refine.hip: the damped Gauss-Newton refinement of every particle on the field (include/rmclhip.h, REFINE ON THE FIELD), all
 // iterations in one launch.  poses are rewritten in place for particles that accepted a step; rows (nullable): n_particles

@@ -17,6 +17,7 @@
 namespace rmclhip {
 namespace {
 
+template <bool kBanded>
 __global__ void __launch_bounds__(256) k_field_refine(const RefineKernelParams p) {
   // the current pose's A (21) and b (6) of each of the four waves, parked here while a candidate is evaluated: they are needed again
   // only if the candidate is turned down.  One wave writes and reads its own row; LDS operations of one wave complete in order.
@@ -45,7 +46,7 @@ __global__ void __launch_bounds__(256) k_field_refine(const RefineKernelParams p
     bool accept = false;
     if (evaluate) {
       RefineSums S;
-      refine_pass(p, cand, lane, S);
+      refine_pass<kBanded>(p, cand, lane, S);
       accept = (it == 0u) || (S.C < C);
       if (accept) {
         cur = cand;
@@ -93,7 +94,8 @@ hipError_t launch_field_refine(const RefineKernelParams& p, hipStream_t s) {
   if (p.n_particles == 0u) return hipSuccess;
   if (p.n_beams == 0u || p.n_beams > kRefineMaxBeams || p.iterations > kRefineMaxIterations) return hipErrorInvalidValue;
   const uint32_t nblocks = (p.n_particles + 3u) / 4u;
-  hipLaunchKernelGGL(k_field_refine, dim3(nblocks), dim3(256), 0, s, p);
+  if (p.fv.lat != nullptr) hipLaunchKernelGGL(k_field_refine<false>, dim3(nblocks), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(k_field_refine<true>, dim3(nblocks), dim3(256), 0, s, p);   // a banded field (band_field.hip)
   return hipGetLastError();
 }
 

@@ -23,6 +23,8 @@ __device__ __forceinline__ double refine_wave_sum(double x) {
   return x;
 }
 
+// kBanded: the field's layout (field_lookup.hip.h); a beam whose cell a banded field answers from its coarse lattice is not valid
+template <bool kBanded>
 __device__ __forceinline__ void refine_pass(const RefineKernelParams& p, const xform& pose, uint32_t lane, RefineSums& S) {
   const xform Tsm = xmul(pose, p.Tsb);
   S.C = 0.0;
@@ -46,7 +48,7 @@ __device__ __forceinline__ void refine_pass(const RefineKernelParams& p, const x
       valid = !field_locate(p.fv, pk, i, f, o);
       if (valid) {
         float v[2][2][2];
-        field_corners(p.fv, i, v);
+        const bool fine = field_cell<kBanded>(p.fv, i, f, v);
         d = field_blend(v, f);
         g[0] = field_lerp(field_lerp(v[0][0][1] - v[0][0][0], v[0][1][1] - v[0][1][0], f[1]),
                           field_lerp(v[1][0][1] - v[1][0][0], v[1][1][1] - v[1][1][0], f[1]), f[2]) * p.fv.inv_cell;
@@ -54,7 +56,7 @@ __device__ __forceinline__ void refine_pass(const RefineKernelParams& p, const x
                           field_lerp(v[1][1][0] - v[1][0][0], v[1][1][1] - v[1][0][1], f[0]), f[2]) * p.fv.inv_cell;
         g[2] = field_lerp(field_lerp(v[1][0][0] - v[0][0][0], v[1][0][1] - v[0][0][1], f[0]),
                           field_lerp(v[1][1][0] - v[0][1][0], v[1][1][1] - v[0][1][1], f[0]), f[1]) * p.fv.inv_cell;
-        valid = (fabsf(d) <= 3.402823466e38f) && field_point_finite(g);
+        valid = fine && (fabsf(d) <= 3.402823466e38f) && field_point_finite(g);
       }
     }
     const bool used = valid && (d < p.max_dist);

@@ -75,6 +75,7 @@ __device__ __forceinline__ uint32_t stein_add_per_word(uint32_t* __restrict__ wo
 // ---------------------------------------------------------------------------------------------
 // 1. the drive
 // ---------------------------------------------------------------------------------------------
+template <bool kBanded>
 __global__ void __launch_bounds__(256) k_stein_drive(const SteinKernelParams p) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t pi = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -82,7 +83,7 @@ __global__ void __launch_bounds__(256) k_stein_drive(const SteinKernelParams p) 
   const xform pose = p.r.poses[pi];
   const bool finite = surface_pose_finite(pose);
   RefineSums S;
-  refine_pass(p.r, pose, lane, S);
+  refine_pass<kBanded>(p.r, pose, lane, S);
   double delta[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool ok = false;
   if (finite && S.n_used != 0u)   // wave-uniform
@@ -317,7 +318,8 @@ hipError_t launch_stein_iteration(const SteinKernelParams& p, hipStream_t s, hip
   hipError_t e = hipMemsetAsync(p.counters, 0, kSteinCounters * sizeof(uint32_t), s);
   if (e == hipSuccess && events) e = hipEventRecord(events[0], s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_stein_drive, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);
+  if (p.r.fv.lat != nullptr) hipLaunchKernelGGL(k_stein_drive<false>, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(k_stein_drive<true>, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);   // a banded field (band_field.hip)
   if (events) e = hipEventRecord(events[1], s);
   if (e == hipSuccess) e = hipMemsetAsync(p.table, 0xFF, p.table_words * sizeof(unsigned long long), s);
   if (e == hipSuccess) e = hipMemsetAsync(p.count, 0, p.table_words * sizeof(uint32_t), s);

@@ -30,6 +30,25 @@ def field_layout(bbox_min, bbox_max, cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX
     return info.as_dict()
 
 
+def band_field_params(cell=0.0, margin=0.0, band=0.5, max_nodes=DEFAULT_MAX_NODES):
+    """rmclhip_band_field_params: max_nodes counts the stored nodes (729 per stored brick, plus the coarse lattice)"""
+    p = _capi.BandFieldParams()
+    _capi.lib().rmclhip_band_field_params_default(C.byref(p))
+    p.cell, p.margin, p.band, p.max_nodes = float(cell), float(margin), float(band), int(max_nodes)
+    return p
+
+
+def band_field_layout(bbox_min, bbox_max, cell=0.0, margin=0.0, band=0.5, max_nodes=DEFAULT_MAX_NODES):
+    """rmclhip_band_field_layout_host (no device needed): (the logical lattice as FieldInfo.as_dict(), the bricks as
+    BandFieldInfo.as_dict()) of a banded field over this box; n_stored and the bytes depend on the map and are 0"""
+    lo = np.ascontiguousarray(bbox_min, dtype=np.float32).reshape(3)
+    hi = np.ascontiguousarray(bbox_max, dtype=np.float32).reshape(3)
+    logical, info = _capi.FieldInfo(), _capi.BandFieldInfo()
+    p = band_field_params(cell, margin, band, max_nodes)
+    _capi.check(_capi.lib().rmclhip_band_field_layout_host(_ptr(lo), _ptr(hi), C.byref(p), C.byref(logical), C.byref(info)))
+    return logical.as_dict(), info.as_dict()
+
+
 REFINE_RESULT = np.dtype([("cost_before", np.float32), ("cost_after", np.float32), ("n_used", np.uint32), ("accepted", np.uint32)])
 
 
@@ -91,14 +110,48 @@ class DistanceFieldHip:
         p = field_params(cell, margin, max_nodes)
         _capi.check(_capi.lib().rmclhip_field_create(self.ctx.handle, hip_map.handle, C.byref(p), C.byref(self._h)))
 
+    @classmethod
+    def banded(cls, hip_map, cell=0.0, margin=0.0, band=0.5, max_nodes=DEFAULT_MAX_NODES):
+        """rmclhip_field_create_banded: the same logical lattice, fine nodes stored only in the bricks within `band` (plus four cell
+        diagonals) of the surface, the rest answered from a coarse lattice; max_nodes counts the stored nodes.  Query, refine and
+        set_field work as on a dense field (refine / stein_step with max_dist > band are refused); download() is download_banded()."""
+        if hip_map is None:
+            raise RuntimeError("NO MAP")
+        self = cls.__new__(cls)
+        self.map, self.ctx = hip_map, hip_map.ctx
+        self._h = C.c_void_p()
+        p = band_field_params(cell, margin, band, max_nodes)
+        _capi.check(_capi.lib().rmclhip_field_create_banded(self.ctx.handle, hip_map.handle, C.byref(p), C.byref(self._h)))
+        return self
+
     @property
     def handle(self):
         return self._h
 
     def info(self):
+        """the (logical) lattice; bytes is what the field holds on the device"""
         fi = _capi.FieldInfo()
         _capi.check(_capi.lib().rmclhip_field_get_info(self._h, C.byref(fi)))
         return fi.as_dict()
+
+    def band_info(self):
+        """rmclhip_field_get_band_info as a dict; a dense field raises"""
+        bi = _capi.BandFieldInfo()
+        _capi.check(_capi.lib().rmclhip_field_get_band_info(self._h, C.byref(bi)))
+        return bi.as_dict()
+
+    def download_banded(self):
+        """(table uint32 [nb_z, nb_y, nb_x], coarse float32 [nb_z + 1, nb_y + 1, nb_x + 1], bricks float32 [n_stored, 9, 9, 9]) of a
+        banded field, x fastest everywhere"""
+        b = self.band_info()
+        nb = b["nb"]
+        table = np.zeros(b["n_bricks"], dtype=np.uint32)
+        coarse = np.zeros(b["n_coarse"], dtype=np.float32)
+        bricks = np.zeros(max(b["n_stored"], 1) * 729, dtype=np.float32)
+        _capi.check(_capi.lib().rmclhip_field_download_banded(self._h, _ptr(table), table.size, _ptr(coarse), coarse.size, _ptr(bricks),
+                                                              bricks.size))
+        return (table.reshape(nb[2], nb[1], nb[0]), coarse.reshape(nb[2] + 1, nb[1] + 1, nb[0] + 1),
+                bricks[:b["n_stored"] * 729].reshape(b["n_stored"], 9, 9, 9))
 
     def download(self):
         """the node values as a float32 array [n_z, n_y, n_x] (x fastest)"""

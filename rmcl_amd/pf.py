@@ -234,8 +234,8 @@ class PCDSensorUpdaterHip:
         _capi.check(_capi.lib().rmclhip_pf_set_error_output(self._h, _as_ptr(errors_dev)))
 
     def set_field(self, field):
-        """answer correspondence_type 1 from a DistanceFieldHip of this updater's map (rmclhip_pf_set_field); None: off.  The handle
-        keeps the field alive: the field object may be closed afterwards."""
+        """answer correspondence_type 1 from a DistanceFieldHip (dense or DistanceFieldHip.banded) of this updater's map
+        (rmclhip_pf_set_field); None: off.  The handle keeps the field alive: the field object may be closed afterwards."""
         if not self._h:
             self.init()
         _capi.check(_capi.lib().rmclhip_pf_set_field(self._h, None if field is None else field.handle))
@@ -623,6 +623,11 @@ class ShardedParticleFilterHip:
             return
         p = _capi.FieldParams(float(cell), float(margin), int(max_nodes))
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_field(self._h, C.byref(p)))
+
+    def set_field_banded(self, cell=0.0, margin=0.0, band=0.5, max_nodes=1 << 26):
+        """set_field with a banded field on every device (rmclhip_pf_sharded_set_field_banded)"""
+        p = _capi.BandFieldParams(float(cell), float(margin), int(max_nodes), float(band), 0)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_field_banded(self._h, C.byref(p)))
 
     def refine(self, beams, Tsb, params=None, **kwargs):
         """every device refines its own block on its own field (rmclhip_pf_sharded_refine; set_field first), no collective; attributes
