@@ -1,7 +1,7 @@
 // capi_band_field.cpp -- see capi_internal.h
 #include "capi_internal.h"
 
-// ---- the banded distance field (include/rmclhip.h, BANDED DISTANCE FIELD, states the layout; kernels: band_field.hip) ----
+// ---- the banded distance field (include/rmclhip.h, BANDED DISTANCE FIELD, states the layout; kernels: field_build.hip) ----
 void rmclhip_band_field_params_default(rmclhip_band_field_params* out) {
   if (!out) return;
   out->cell = 0.0f;
@@ -58,96 +58,57 @@ RMCL_INTERNAL rmclhip_status field_band_check(const std::string& who, const rmcl
   return RMCLHIP_OK;
 }
 
-namespace {
-// the build's temporaries: freed when the build leaves, however it leaves
-struct BandScratch {
-  uint32_t* rec16 = nullptr;
-  uint32_t* rec8 = nullptr;
-  uint32_t* flags = nullptr;
-  uint32_t* stored = nullptr;
-  unsigned long long* incl = nullptr;
-  unsigned long long* block_tot = nullptr;
-  ~BandScratch() {
-    void* all[6] = {rec16, rec8, flags, stored, incl, block_tot};
-    for (void* q : all)
-      if (q) (void)hipFree(q);
-  }
-};
-template <class T>
-hipError_t band_alloc(T** out, size_t count) { return hipMalloc(reinterpret_cast<void**>(out), std::max<size_t>(count, 1u) * sizeof(T)); }
-}  // namespace
-
 // Coarse first: every 16th logical node per axis, then every 8th (the coarse lattice, each query started from the level before);
 // the bricks are classified and numbered from it, one count is read back, and only then are the fine nodes allocated and filled.
 static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
-  const rmclhip_map* m = fd->map;
+  const std::string who = "field_create_banded";
   rmclhip_band_field_info& bi = fd->band;
-  BandScratch sc;
+  BuildScratch sc;
   hipStream_t s = fd->stream;
-#define BANDCHK(x)                                                                                                            \
-  do {                                                                                                                        \
-    const hipError_t e_ = (x);                                                                                                \
-    if (e_ != hipSuccess) {                                                                                                   \
-      (void)hipGetLastError();                                                                                                \
-      return fail(e_ == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string("field_create_banded: ") + hipGetErrorString(e_)); \
-    }                                                                                                                         \
-  } while (0)
-  BANDCHK(band_alloc(&fd->d_coarse, bi.n_coarse));
-  BANDCHK(band_alloc(&fd->d_table, bi.n_bricks));
-  BANDCHK(band_alloc(&sc.rec8, bi.n_coarse));
-  BANDCHK(band_alloc(&sc.flags, bi.n_bricks));
-  BANDCHK(band_alloc(&sc.stored, bi.n_bricks));
-  BANDCHK(band_alloc(&sc.incl, bi.n_bricks));
-  BANDCHK(band_alloc(&sc.block_tot, (bi.n_bricks + 1023u) / 1024u));
+  uint32_t *rec16 = nullptr, *rec8 = nullptr, *flags = nullptr, *stored = nullptr;
+  unsigned long long *incl = nullptr, *block_tot = nullptr;
+  HIPCHK_AS(who, dev_alloc(&fd->d_coarse, bi.n_coarse));
+  HIPCHK_AS(who, dev_alloc(&fd->d_table, bi.n_bricks));
+  HIPCHK_AS(who, sc.alloc(&rec8, bi.n_coarse));
+  HIPCHK_AS(who, sc.alloc(&flags, bi.n_bricks));
+  HIPCHK_AS(who, sc.alloc(&stored, bi.n_bricks));
+  HIPCHK_AS(who, sc.alloc(&incl, bi.n_bricks));
+  HIPCHK_AS(who, sc.alloc(&block_tot, (bi.n_bricks + 1023u) / 1024u));
 
-  BandNodesParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.nodes = m->d_nodes;
-  p.tris = m->d_tris;
-  p.n_tris = m->info.n_records;
-  p.fv = field_view(fd);
+  FieldBuildParams p = field_build_params(fd);
+  uint32_t cn[3];
   const uint32_t n_max = std::max(fd->info.n[0], std::max(fd->info.n[1], fd->info.n[2]));
   if (n_max > 2u * 16u) {   // (a level of two nodes per axis prunes nothing)
-    p.stride = 16u;
     size_t total = 1;
-    for (int k = 0; k < 3; ++k) { p.cn[k] = (fd->info.n[k] - 1u + 15u) / 16u + 1u; total *= p.cn[k]; }
-    BANDCHK(band_alloc(&sc.rec16, total));
-    p.rec_out = sc.rec16;
-    BANDCHK(launch_band_nodes(p, s));
-    p.seed_rec = sc.rec16;
-    p.pstride = 16u;
-    for (int k = 0; k < 3; ++k) p.pn[k] = p.cn[k];
+    for (int k = 0; k < 3; ++k) { cn[k] = (fd->info.n[k] - 1u + 15u) / 16u + 1u; total *= cn[k]; }
+    HIPCHK_AS(who, sc.alloc(&rec16, total));
+    HIPCHK_AS(who, field_level_step(p, 16u, cn, rec16, nullptr, s));
   }
-  p.stride = 8u;
-  for (int k = 0; k < 3; ++k) p.cn[k] = bi.nb[k] + 1u;
-  p.rec_out = sc.rec8;
-  p.dist_out = fd->d_coarse;
-  BANDCHK(launch_band_nodes(p, s));
-  BANDCHK(launch_band_classify(p.fv, fd->d_coarse, bi.reach, sc.flags, s));
-  BANDCHK(launch_scan_counts(sc.flags, static_cast<uint32_t>(bi.n_bricks), sc.incl, sc.block_tot, s));
-  BANDCHK(launch_band_table(p.fv, sc.flags, sc.incl, fd->d_table, sc.stored, s));
+  for (int k = 0; k < 3; ++k) cn[k] = bi.nb[k] + 1u;
+  HIPCHK_AS(who, field_level_step(p, 8u, cn, rec8, fd->d_coarse, s));
+  HIPCHK_AS(who, launch_band_classify(p.fv, fd->d_coarse, bi.reach, flags, s));
+  HIPCHK_AS(who, launch_scan_counts(flags, static_cast<uint32_t>(bi.n_bricks), incl, block_tot, s));
+  HIPCHK_AS(who, launch_band_table(p.fv, flags, incl, fd->d_table, stored, s));
   unsigned long long n_stored = 0;
-  BANDCHK(hipMemcpyAsync(&n_stored, sc.incl + (bi.n_bricks - 1u), sizeof(n_stored), hipMemcpyDeviceToHost, s));
-  BANDCHK(hipStreamSynchronize(s));
+  HIPCHK_AS(who, upload_on(s, &n_stored, incl + (bi.n_bricks - 1u), sizeof(n_stored), hipMemcpyDeviceToHost));
   bi.n_stored = n_stored;
   if (n_stored > (max_nodes - bi.n_coarse) / kBandBrickNodes)   // 729 n_stored + n_coarse > max_nodes, without the overflow
     return fail(RMCLHIP_ERR_INVALID,
                 "field_create_banded: the stored bricks and the coarse lattice have more than max_nodes nodes (a larger cell, a smaller band or "
                 "margin, or a larger max_nodes)");
-  BANDCHK(band_alloc(&fd->d_bricks, static_cast<size_t>(n_stored) * kBandBrickNodes));
+  HIPCHK_AS(who, dev_alloc(&fd->d_bricks, static_cast<size_t>(n_stored) * kBandBrickNodes));
   BandFillParams f;
   std::memset(&f, 0, sizeof(f));
-  f.nodes = m->d_nodes;
-  f.tris = m->d_tris;
-  f.n_tris = m->info.n_records;
+  f.nodes = p.nodes;
+  f.tris = p.tris;
+  f.n_tris = p.n_tris;
   f.fv = p.fv;
-  f.stored = sc.stored;
+  f.stored = stored;
   f.n_stored = static_cast<uint32_t>(n_stored);
-  f.coarse_rec = sc.rec8;
+  f.coarse_rec = rec8;
   f.bricks = fd->d_bricks;
-  BANDCHK(launch_band_fill(f, s));
-  BANDCHK(hipStreamSynchronize(s));
-#undef BANDCHK
+  HIPCHK_AS(who, launch_band_fill(f, s));
+  HIPCHK_AS(who, hipStreamSynchronize(s));
   bi.bytes = (bi.n_bricks * sizeof(uint32_t) + bi.n_coarse * sizeof(float)) + n_stored * kBandBrickNodes * sizeof(float);
   fd->info.bytes = bi.bytes;
   {
@@ -160,32 +121,17 @@ static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
 
 rmclhip_status rmclhip_field_create_banded(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_band_field_params* params, rmclhip_field** out) {
   ApiGuard guard_("rmclhip_field_create_banded");
-  if (!out) return fail(RMCLHIP_ERR_INVALID, "field_create_banded: out is null");
-  *out = nullptr;
-  if (!ctx || !map) return fail(RMCLHIP_ERR_INVALID, "field_create_banded: NO MAP");
-  if (map->ctx != ctx) return fail(RMCLHIP_ERR_INVALID, "field_create_banded: the map belongs to another context");
+  if (rmclhip_status st = field_create_check("field_create_banded", ctx, map, out)) return st;
   rmclhip_field_info info{};
   rmclhip_band_field_info band{};
   if (rmclhip_status st = band_layout("field_create_banded", map->info.bbox_min, map->info.bbox_max, params, &info, &band)) return st;
-  if (map->info.n_faces == 0u || map->info.n_records == 0u) return fail(RMCLHIP_ERR_INVALID, "field_create_banded: the map has no faces");
   rmclhip_band_field_params p;
   rmclhip_band_field_params_default(&p);
   if (params) p = *params;
-  HIPCHK(hipSetDevice(ctx->device));
-  rmclhip_field* fd = new rmclhip_field();
-  fd->ctx = ctx;
-  ctx_retain(ctx);
-  fd->map = map;
-  rmclhip_map_retain(map);
-  fd->info = info;
+  rmclhip_field* fd = nullptr;
+  if (rmclhip_status st = field_new("field_create_banded", ctx, map, info, &fd)) return st;
   fd->banded = true;
   fd->band = band;
-  const hipError_t e = hipStreamCreateWithFlags(&fd->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    field_release(fd);
-    return fail(RMCLHIP_ERR_HIP, std::string("field_create_banded: ") + hipGetErrorString(e));
-  }
   if (rmclhip_status st = band_build(fd, p.max_nodes)) {
     field_release(fd);   // frees what the build allocated; nothing was added to the map's device_bytes
     return st;

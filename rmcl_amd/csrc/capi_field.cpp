@@ -1,7 +1,7 @@
 // capi_field.cpp -- see capi_internal.h
 #include "capi_internal.h"
 
-// ---- the map's distance field (include/rmclhip.h, DISTANCE FIELD, states the geometry and the lookup; kernels: field.hip) ----
+// ---- the map's distance field (include/rmclhip.h, DISTANCE FIELD, states the geometry and the lookup; kernels: field_build.hip, field.hip) ----
 void rmclhip_field_params_default(rmclhip_field_params* out) {
   if (!out) return;
   out->cell = 0.0f;
@@ -92,52 +92,22 @@ RMCL_INTERNAL void field_release(rmclhip_field* fd) {
   delete fd;
 }
 
-// Coarse to fine, as ensure_near_grid builds the near grid: the nodes far from any surface are the expensive, unbounded queries, and
-// there are 4096 x fewer of them at every 16th node per axis than in the lattice.  Each level leaves the record it found per node;
-// the next starts every query from the record of the previous level's nearest node.
-static rmclhip_status field_build(rmclhip_field* fd) {
-  const rmclhip_map* m = fd->map;
-  FieldBuildParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.nodes = m->d_nodes;
-  p.tris = m->d_tris;
-  p.n_tris = m->info.n_records;
-  p.fv = field_view(fd);
-  const uint32_t n_max = std::max(fd->info.n[0], std::max(fd->info.n[1], fd->info.n[2]));
-  uint32_t* d_prev = nullptr;
-  uint32_t* d_rec = nullptr;
-  hipError_t e = hipSuccess;
-  for (uint32_t stride = 16u; stride >= 1u && e == hipSuccess; stride >>= 2) {
-    if (stride > 1u && n_max <= 2u * stride) continue;   // a level of two nodes per axis prunes nothing
-    p.stride = stride;
-    size_t total = 1;
-    for (int k = 0; k < 3; ++k) { p.cn[k] = (fd->info.n[k] - 1u) / stride + 1u; total *= p.cn[k]; }
-    p.seed_rec = d_prev;
-    d_rec = nullptr;
-    if (stride > 1u) e = hipMalloc(reinterpret_cast<void**>(&d_rec), total * sizeof(uint32_t));
-    p.rec_out = d_rec;
-    p.dist_out = (stride == 1u) ? fd->d_lat : nullptr;
-    if (e == hipSuccess) e = launch_field_build(p, fd->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(fd->stream);
-    if (d_prev) (void)hipFree(d_prev);
-    d_prev = d_rec;
-    p.pstride = stride;
-    for (int k = 0; k < 3; ++k) p.pn[k] = p.cn[k];
-  }
-  if (d_prev) (void)hipFree(d_prev);
-  if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("field_create: ") + hipGetErrorString(e));
+RMCL_INTERNAL rmclhip_status hip_status(const std::string& who, hipError_t e) {
+  if (e == hipSuccess) return RMCLHIP_OK;
+  (void)hipGetLastError();
+  return fail(e == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, who + ": " + hipGetErrorString(e));
+}
+
+RMCL_INTERNAL rmclhip_status field_create_check(const std::string& who, const rmclhip_ctx* ctx, const rmclhip_map* map, rmclhip_field** out) {
+  if (!out) return fail(RMCLHIP_ERR_INVALID, who + ": out is null");
+  *out = nullptr;
+  if (!ctx || !map) return fail(RMCLHIP_ERR_INVALID, who + ": NO MAP");
+  if (map->ctx != ctx) return fail(RMCLHIP_ERR_INVALID, who + ": the map belongs to another context");
   return RMCLHIP_OK;
 }
 
-rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_params* params, rmclhip_field** out) {
-  ApiGuard guard_("rmclhip_field_create");
-  if (!out) return fail(RMCLHIP_ERR_INVALID, "field_create: out is null");
-  *out = nullptr;
-  if (!ctx || !map) return fail(RMCLHIP_ERR_INVALID, "field_create: NO MAP");
-  if (map->ctx != ctx) return fail(RMCLHIP_ERR_INVALID, "field_create: the map belongs to another context");
-  rmclhip_field_info info{};
-  if (rmclhip_status st = field_layout("field_create", map->info.bbox_min, map->info.bbox_max, params, &info, false)) return st;
-  if (map->info.n_faces == 0u || map->info.n_records == 0u) return fail(RMCLHIP_ERR_INVALID, "field_create: the map has no faces");
+RMCL_INTERNAL rmclhip_status field_new(const std::string& who, rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_info& info, rmclhip_field** out) {
+  if (map->info.n_faces == 0u || map->info.n_records == 0u) return fail(RMCLHIP_ERR_INVALID, who + ": the map has no faces");
   HIPCHK(hipSetDevice(ctx->device));
   rmclhip_field* fd = new rmclhip_field();
   fd->ctx = ctx;
@@ -145,24 +115,71 @@ rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rm
   fd->map = map;
   rmclhip_map_retain(map);
   fd->info = info;
-  hipError_t e = hipStreamCreateWithFlags(&fd->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) {
-    e = hipMalloc(reinterpret_cast<void**>(&fd->d_lat), info.bytes);
-    if (e == hipSuccess) {
-      std::lock_guard<std::mutex> lock(map->grid_mtx);
-      map->bytes += info.bytes;
-      fd->accounted = info.bytes;
-    } else {
-      fd->d_lat = nullptr;
-    }
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  if (rmclhip_status st = hip_status(who, hipStreamCreateWithFlags(&fd->stream, hipStreamNonBlocking))) {
     field_release(fd);
-    return fail(e == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP, std::string("field_create: ") + hipGetErrorString(e));
+    return st;
   }
+  *out = fd;
+  return RMCLHIP_OK;
+}
+
+RMCL_INTERNAL FieldBuildParams field_build_params(const rmclhip_field* fd) {
+  FieldBuildParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.nodes = fd->map->d_nodes;
+  p.tris = fd->map->d_tris;
+  p.n_tris = fd->map->info.n_records;
+  p.fv = field_view(fd);
+  return p;
+}
+
+RMCL_INTERNAL hipError_t field_level_step(FieldBuildParams& p, uint32_t stride, const uint32_t* cn, uint32_t* rec_out, float* dist_out, hipStream_t s) {
+  p.stride = stride;
+  for (int k = 0; k < 3; ++k) p.cn[k] = cn[k];
+  p.rec_out = rec_out;
+  p.dist_out = dist_out;
+  const hipError_t e = launch_field_level(p, s);
+  p.seed_rec = rec_out;
+  p.pstride = stride;
+  for (int k = 0; k < 3; ++k) p.pn[k] = cn[k];
+  return e;
+}
+
+// Coarse to fine, as ensure_near_grid builds the near grid: the nodes far from any surface are the expensive, unbounded queries, and
+// there are 4096 x fewer of them at every 16th node per axis than in the lattice.  Each level leaves the record it found per node;
+// the next starts every query from the record of the previous level's nearest node.  The stream orders the levels.
+static rmclhip_status field_build(rmclhip_field* fd) {
+  const std::string who = "field_create";
+  HIPCHK_AS(who, dev_alloc(&fd->d_lat, fd->info.n_nodes));
+  {
+    std::lock_guard<std::mutex> lock(fd->map->grid_mtx);
+    fd->map->bytes += fd->info.bytes;
+    fd->accounted = fd->info.bytes;
+  }
+  FieldBuildParams p = field_build_params(fd);
+  BuildScratch sc;
+  const uint32_t n_max = std::max(fd->info.n[0], std::max(fd->info.n[1], fd->info.n[2]));
+  for (uint32_t stride = 16u; stride >= 1u; stride >>= 2) {
+    if (stride > 1u && n_max <= 2u * stride) continue;   // a level of two nodes per axis prunes nothing
+    uint32_t cn[3];
+    size_t total = 1;
+    for (int k = 0; k < 3; ++k) { cn[k] = (fd->info.n[k] - 1u) / stride + 1u; total *= cn[k]; }
+    uint32_t* d_rec = nullptr;
+    if (stride > 1u) HIPCHK_AS(who, sc.alloc(&d_rec, total));
+    HIPCHK_AS(who, field_level_step(p, stride, cn, d_rec, stride == 1u ? fd->d_lat : nullptr, fd->stream));
+  }
+  return hip_status(who, hipStreamSynchronize(fd->stream));
+}
+
+rmclhip_status rmclhip_field_create(rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_params* params, rmclhip_field** out) {
+  ApiGuard guard_("rmclhip_field_create");
+  if (rmclhip_status st = field_create_check("field_create", ctx, map, out)) return st;
+  rmclhip_field_info info{};
+  if (rmclhip_status st = field_layout("field_create", map->info.bbox_min, map->info.bbox_max, params, &info, false)) return st;
+  rmclhip_field* fd = nullptr;
+  if (rmclhip_status st = field_new("field_create", ctx, map, info, &fd)) return st;
   if (rmclhip_status st = field_build(fd)) {
-    field_release(fd);
+    field_release(fd);   // frees what the build allocated and takes its bytes off the map's device_bytes
     return st;
   }
   *out = fd;

@@ -8,8 +8,8 @@
 //   capi_pc2scan.cpp   PointCloud2 bytes -> range image of a spherical model, as a free function and as an operator's dataset (kernels: pc2scan.hip)
 //   capi_deskew.cpp    PointCloud2 bytes + per-point times + the scan's motion -> OnDn model + dataset of an operator, or a compensated cloud; the host helpers (kernel: deskew.hip)
 //   capi_pf.cpp        particle-filter sensor update, motion update, resamplers
-//   capi_field.cpp     the map's distance field: layout, coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field.hip)
-//   capi_band_field.cpp the banded distance field: layout, the coarse build, classification, the bricks' fill, download (kernels: band_field.hip; the lookups are field.hip's)
+//   capi_field.cpp     the map's distance field: layout, what both layouts' builds and create entry points share, the coarse-to-fine build, download, lookup, and the sensor update of correspondence_type 1 answered from it (kernels: field_build.hip, field.hip)
+//   capi_band_field.cpp the banded distance field: layout, the coarse build, classification, the bricks' fill, download (kernels: field_build.hip; the lookups are field.hip's)
 //   capi_stein.cpp     the Stein variational step of a cloud on a filter handle's field: parameters, scratch, the iterations' launches, counts (kernels: stein.hip)
 //   capi_refine.cpp    the damped Gauss-Newton refinement of particles on a distance field: parameters, launch, counts (kernel: refine.hip)
 //   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
@@ -72,6 +72,14 @@ inline rmclhip_status fail(rmclhip_status st, const std::string& msg) {
       return fail(RMCLHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
   } while (0)
 
+// a HIP call of the entry point `who` (capi_field.cpp): on failure the error is cleared and becomes RMCLHIP_ERR_NOMEM (out of memory)
+// or RMCLHIP_ERR_HIP, with the message "<who>: <HIP's error string>"
+RMCL_INTERNAL rmclhip_status hip_status(const std::string& who, hipError_t e);
+#define HIPCHK_AS(who, expr)                                          \
+  do {                                                                \
+    if (rmclhip_status st_ = hip_status(who, (expr))) return st_;     \
+  } while (0)
+
 inline xform to_x(const rmclhip_transform* T) {
   xform r;
   std::memcpy(&r, T, sizeof(r));
@@ -119,6 +127,30 @@ struct DevBuf {
   }
 };
 
+// count (at least one) elements of device memory; *out is null on failure
+template <typename T>
+hipError_t dev_alloc(T** out, size_t count) {
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(out), std::max<size_t>(count, 1u) * sizeof(T));
+  if (e != hipSuccess) *out = nullptr;
+  return e;
+}
+
+// the temporary device buffers of a field's build: freed when the build leaves, however it leaves
+struct BuildScratch {
+  std::vector<void*> owned;
+  BuildScratch() = default;
+  BuildScratch(const BuildScratch&) = delete;
+  BuildScratch& operator=(const BuildScratch&) = delete;
+  ~BuildScratch() {
+    for (void* q : owned) (void)hipFree(q);
+  }
+  template <typename T>
+  hipError_t alloc(T** out, size_t count) {
+    const hipError_t e = dev_alloc(out, count);
+    if (e == hipSuccess) owned.push_back(*out);
+    return e;
+  }
+};
 
 // Upload on the handle's OWN stream, then wait for it.  A plain hipMemcpy runs on the null stream, which the handles'
 // hipStreamNonBlocking streams do not synchronise with: a copy from pageable memory may return once the data is staged,
@@ -654,6 +686,14 @@ RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd);
 // capi_field.cpp: the geometry of a field over a box (banded: the logical lattice of a banded field, not capped by max_nodes)
 RMCL_INTERNAL rmclhip_status field_layout(const std::string& who, const float* bmin, const float* bmax, const rmclhip_field_params* params,
                                           rmclhip_field_info* out, bool banded);
+// capi_field.cpp: what rmclhip_field_create and rmclhip_field_create_banded share.  field_create_check: the refusals that come before
+// the layout (RMCLHIP_OK leaves *out null); field_new: refuses a map without faces, else a handle with `info` that holds its context,
+// its map and a stream of its own and is given up with field_release; field_build_params: the map and the geometry of a level, nothing
+// else set; field_level_step: launches the level of `stride` and cn[3] nodes on s, then makes it the level the next one is seeded from
+RMCL_INTERNAL rmclhip_status field_create_check(const std::string& who, const rmclhip_ctx* ctx, const rmclhip_map* map, rmclhip_field** out);
+RMCL_INTERNAL rmclhip_status field_new(const std::string& who, rmclhip_ctx* ctx, rmclhip_map* map, const rmclhip_field_info& info, rmclhip_field** out);
+RMCL_INTERNAL FieldBuildParams field_build_params(const rmclhip_field* fd);
+RMCL_INTERNAL hipError_t field_level_step(FieldBuildParams& p, uint32_t stride, const uint32_t* cn, uint32_t* rec_out, float* dist_out, hipStream_t s);
 // capi_band_field.cpp: RMCLHIP_ERR_INVALID if `field` is banded and max_dist exceeds its band (null or dense: RMCLHIP_OK)
 RMCL_INTERNAL rmclhip_status field_band_check(const std::string& who, const rmclhip_field* field, float max_dist);
 // capi_refine.cpp: the refinement in two halves, so that the sharded filter has every device's launch in flight before it waits for any.
@@ -661,6 +701,10 @@ RMCL_INTERNAL rmclhip_status field_band_check(const std::string& who, const rmcl
 // launches on `stream`; refine_finish waits for the stream and ADDS this call's counts to *stats (nullable)
 RMCL_INTERNAL rmclhip_status refine_check(const std::string& who, const void* poses_dev, uint32_t n, const rmclhip_range_measurement* beams, uint32_t n_beams,
                                           const rmclhip_transform* Tsb, const rmclhip_refine_params* params, rmclhip_refine_params* out);
+// refine_kernel_params: what the refine and the Stein kernels read of a field, a cloud, its beams (device records) and the parameters;
+// rows and counters are left null
+RMCL_INTERNAL RefineKernelParams refine_kernel_params(const rmclhip_field* field, rmclhip_transform* poses_dev, uint32_t n, const float* beams_dev,
+                                                      uint32_t n_beams, const rmclhip_transform* Tsb, const rmclhip_refine_params& params);
 RMCL_INTERNAL rmclhip_status refine_enqueue(const rmclhip_field* field, hipStream_t stream, RefineScratch& sc, rmclhip_transform* poses_dev, uint32_t n,
                                             const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
                                             const rmclhip_refine_params& params, rmclhip_refine_result* results_dev, bool want_stats);

@@ -707,19 +707,22 @@ rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* h, const rmclh
 }
 
 // ---- the distance field on the sharded cloud (capi_field.cpp has the single-device entry points) ----
-// every replica builds its own field from its own copy of the map; its filter handle keeps the only reference
-rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip_field_params* params) {
-  ApiGuard guard_("rmclhip_pf_sharded_set_field");
-  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_field: null");
-  if (params) {   // refuse before any replica is touched
+// every replica builds its own field from its own copy of the map; its filter handle keeps the only reference.  dense or banded: the
+// layout's parameters (at most one is given); neither: every replica's field is taken off
+static rmclhip_status sharded_set_field(rmclhip_pf_sharded* h, const rmclhip_field_params* dense, const rmclhip_band_field_params* banded) {
+  for (PfRank& R : h->ranks) {   // refuse before any replica is touched
     rmclhip_field_info info;
-    for (PfRank& R : h->ranks)
-      if (rmclhip_status st = rmclhip_field_layout_host(R.map->info.bbox_min, R.map->info.bbox_max, params, &info)) return st;
+    rmclhip_band_field_info band;
+    const float *lo = R.map->info.bbox_min, *hi = R.map->info.bbox_max;
+    if (rmclhip_status st = banded ? rmclhip_band_field_layout_host(lo, hi, banded, &info, &band)
+                            : dense ? rmclhip_field_layout_host(lo, hi, dense, &info) : RMCLHIP_OK)
+      return st;
   }
   for (PfRank& R : h->ranks) {
     rmclhip_field* fd = nullptr;
-    if (params)
-      if (rmclhip_status st = rmclhip_field_create(R.ctx, R.map, params, &fd)) return st;
+    if (rmclhip_status st = banded ? rmclhip_field_create_banded(R.ctx, R.map, banded, &fd)
+                            : dense ? rmclhip_field_create(R.ctx, R.map, dense, &fd) : RMCLHIP_OK)
+      return st;
     const rmclhip_status st = rmclhip_pf_set_field(R.pf, fd);
     rmclhip_field_destroy(fd);
     if (st) return st;
@@ -727,25 +730,17 @@ rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip
   return RMCLHIP_OK;
 }
 
+rmclhip_status rmclhip_pf_sharded_set_field(rmclhip_pf_sharded* h, const rmclhip_field_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_field");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_field: null");
+  return sharded_set_field(h, params, nullptr);
+}
+
 // the same with a banded field on every replica (capi_band_field.cpp)
 rmclhip_status rmclhip_pf_sharded_set_field_banded(rmclhip_pf_sharded* h, const rmclhip_band_field_params* params) {
   ApiGuard guard_("rmclhip_pf_sharded_set_field_banded");
   if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_field_banded: null");
-  if (params) {   // refuse before any replica is touched
-    rmclhip_field_info logical;
-    rmclhip_band_field_info info;
-    for (PfRank& R : h->ranks)
-      if (rmclhip_status st = rmclhip_band_field_layout_host(R.map->info.bbox_min, R.map->info.bbox_max, params, &logical, &info)) return st;
-  }
-  for (PfRank& R : h->ranks) {
-    rmclhip_field* fd = nullptr;
-    if (params)
-      if (rmclhip_status st = rmclhip_field_create_banded(R.ctx, R.map, params, &fd)) return st;
-    const rmclhip_status st = rmclhip_pf_set_field(R.pf, fd);
-    rmclhip_field_destroy(fd);
-    if (st) return st;
-  }
-  return RMCLHIP_OK;
+  return sharded_set_field(h, nullptr, params);
 }
 
 // every replica refines its own block on its own field (capi_refine.cpp); no collective, attributes and weights are not touched

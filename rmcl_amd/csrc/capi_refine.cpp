@@ -28,6 +28,25 @@ RMCL_INTERNAL rmclhip_status refine_check(const std::string& who, const void* po
   return RMCLHIP_OK;
 }
 
+RMCL_INTERNAL RefineKernelParams refine_kernel_params(const rmclhip_field* field, rmclhip_transform* poses_dev, uint32_t n, const float* beams_dev,
+                                                      uint32_t n_beams, const rmclhip_transform* Tsb, const rmclhip_refine_params& params) {
+  RefineKernelParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.fv = field_view(field);
+  p.poses = reinterpret_cast<xform*>(poses_dev);
+  p.n_particles = n;
+  p.beams = beams_dev;
+  p.n_beams = n_beams;
+  p.Tsb = to_x(Tsb);
+  p.iterations = params.iterations;
+  p.dof_mask = params.dof_mask;
+  p.max_dist = params.max_dist;
+  p.max_step_trans = params.max_step_trans;
+  p.max_step_rot = params.max_step_rot;
+  p.lambda0 = params.lambda0;
+  return p;
+}
+
 RMCL_INTERNAL rmclhip_status refine_enqueue(const rmclhip_field* field, hipStream_t stream, RefineScratch& sc, rmclhip_transform* poses_dev, uint32_t n,
                                             const rmclhip_range_measurement* beams, uint32_t n_beams, const rmclhip_transform* Tsb,
                                             const rmclhip_refine_params& params, rmclhip_refine_result* results_dev, bool want_stats) {
@@ -45,20 +64,7 @@ RMCL_INTERNAL rmclhip_status refine_enqueue(const rmclhip_field* field, hipStrea
   // the beams come from pageable host memory: wait for the copy, the caller may reuse them when this returns
   HIPCHK(upload_on(stream, sc.beams.p, beams, nf * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(hipMemsetAsync(sc.counters.p, 0, 4u * sizeof(uint32_t), stream));
-  RefineKernelParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.fv = field_view(field);
-  p.poses = reinterpret_cast<xform*>(poses_dev);
-  p.n_particles = n;
-  p.beams = sc.beams.p;
-  p.n_beams = n_beams;
-  p.Tsb = to_x(Tsb);
-  p.iterations = params.iterations;
-  p.dof_mask = params.dof_mask;
-  p.max_dist = params.max_dist;
-  p.max_step_trans = params.max_step_trans;
-  p.max_step_rot = params.max_step_rot;
-  p.lambda0 = params.lambda0;
+  RefineKernelParams p = refine_kernel_params(field, poses_dev, n, sc.beams.p, n_beams, Tsb, params);
   p.rows = rows;
   p.counters = sc.counters.p;
   HIPCHK(launch_field_refine(p, stream));

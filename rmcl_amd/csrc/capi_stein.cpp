@@ -80,18 +80,8 @@ rmclhip_status rmclhip_pf_stein_step(rmclhip_pf* f, rmclhip_transform* poses_dev
   HIPCHK(upload_on(f->stream, f->refine.beams.p, beams, nf * sizeof(float), hipMemcpyHostToDevice));
   SteinKernelParams k;
   std::memset(&k, 0, sizeof(k));
-  k.r.fv = field_view(f->field);
-  k.r.poses = reinterpret_cast<xform*>(poses_dev);
-  k.r.n_particles = n;
-  k.r.beams = f->refine.beams.p;
-  k.r.n_beams = n_beams;
-  k.r.Tsb = to_x(Tsb);
-  k.r.iterations = 1u;
-  k.r.dof_mask = p.dof_mask;
-  k.r.max_dist = p.max_dist;
-  k.r.max_step_trans = p.max_step_trans;
-  k.r.max_step_rot = p.max_step_rot;
-  k.r.lambda0 = p.lambda0;
+  k.r = refine_kernel_params(f->field, poses_dev, n, f->refine.beams.p, n_beams, Tsb, rp);
+  k.r.iterations = 1u;   // of the refinement's arithmetic per launch; p.iterations is the loop below
   k.h_trans = p.h_trans;
   k.h_rot = p.h_rot;
   k.repulsion = p.repulsion;

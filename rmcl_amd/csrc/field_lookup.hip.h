@@ -1,6 +1,7 @@
 // field_lookup.hip.h -- the distance field's lookup (include/rmclhip.h, "THE LOOKUP at a point P"), shared by field.hip (the value
 // alone: k_field_query, k_pf_update_field) and refine.hip (the value and its gradient from the same eight corners).  Index, fraction
-// and clamping live here once; every float operation is in the header's order (the library is built without contraction).
+// and clamping live here once; every float operation is in the header's order (the library is built without contraction).  The
+// arrays it reads, of either layout, are built by field_build.hip.
 #pragma once
 #include "pf_common.hip.h"
 

@@ -490,8 +490,8 @@ hipError_t launch_hypotheses(const xform* poses, const void* attrs, uint32_t n, 
 constexpr uint32_t kPoseInfoRow = 32u;
 hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s);
 
-// field.hip: the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
-// A banded field (include/rmclhip.h, BANDED DISTANCE FIELD; band_field.hip) has lat == nullptr and the three arrays below: table,
+// field.hip: reading the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
+// A banded field (include/rmclhip.h, BANDED DISTANCE FIELD) has lat == nullptr and the three arrays below: table,
 // nb[0] * nb[1] * nb[2] words (the stored index of a brick or kBandFar), x fastest; coarse, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)
 // floats, x fastest; bricks, kBandBrickNodes floats per stored brick, x fastest inside a brick.
 constexpr uint32_t kBandFar = 0xFFFFFFFFu;
@@ -506,22 +506,6 @@ struct FieldView {
   const float* bricks;
   uint32_t nb[3];
 };
-// one level of the coarse-to-fine build: the nodes (ci * stride, cj * stride, ck * stride), ci < cn[0] ..., of `fv`'s lattice.
-// seed_rec (nullable): the records the previous level left, pn[0] * pn[1] * pn[2] of them at stride pstride -- a node starts from the
-// record of the previous level's node nearest to it; rec_out (nullable): cn[0] * cn[1] * cn[2] records, x fastest; dist_out
-// (nullable, stride 1 only): the lattice itself
-struct FieldBuildParams {
-  const uint32_t* nodes;
-  const uint32_t* tris;
-  uint32_t n_tris;
-  FieldView fv;
-  uint32_t stride, cn[3];
-  const uint32_t* seed_rec;
-  uint32_t pstride, pn[3];
-  uint32_t* rec_out;
-  float* dist_out;
-};
-hipError_t launch_field_build(const FieldBuildParams& p, hipStream_t s);
 // the lookup alone: n points (xyz, map coordinates) -> n distances
 hipError_t launch_field_query(const FieldView& fv, const float* points, size_t n, float* out, hipStream_t s);
 // the sensor update of correspondence_type 1 answered from the field: k_pf_update<64, 3>'s end points, evaluation and in-order merge
@@ -540,16 +524,13 @@ struct PfFieldParams {
 };
 hipError_t launch_pf_update_field(const PfFieldParams& p, hipStream_t s);
 
-// band_field.hip: the build of a banded field, in the order the caller runs it.  v: the logical geometry with nb set (its pointers are
-// not read).  All index arithmetic is size_t.
-//   launch_band_nodes     one lane per node of a level: logical node min(c_k * stride, n_k - 1), c_k < cn[k]; seeded (seed_rec nullable)
-//                         from the previous level's node min((i_k + pstride / 2) / pstride, pn[k] - 1); rec_out and dist_out nullable
-//   launch_band_classify  one lane per brick: flags[b] = 1 if the minimum of its eight coarse corners is <= reach or one is NaN, else 0
-//   launch_band_table     incl: the inclusive prefix sums of flags (launch_scan_counts).  table[b] = incl[b] - 1 of a stored brick,
-//                         kBandFar of any other; stored[incl[b] - 1] = b
-//   launch_band_fill      one workgroup per stored brick: its 729 node values, every query seeded from the record of the nearest
-//                         coarse corner; NaN beyond n_k - 1
-struct BandNodesParams {
+// field_build.hip: the build of a field.  All index arithmetic is size_t.
+// launch_field_level: one level of a coarse-to-fine build, one lane per node: the logical nodes min(c_k * stride, n_k - 1), c_k < cn[k],
+// of `fv`'s lattice (its pointers are not read).  seed_rec (nullable): the records the previous level left, pn[0] * pn[1] * pn[2] of
+// them at stride pstride -- a node i starts from the record of the previous level's node min((i_k + pstride / 2) / pstride, pn[k] - 1),
+// the one nearest to it; rec_out (nullable): cn[0] * cn[1] * cn[2] records, x fastest; dist_out (nullable): as many distances -- the
+// dense lattice at stride 1, a banded field's coarse lattice at stride 8
+struct FieldBuildParams {
   const uint32_t* nodes;
   const uint32_t* tris;
   uint32_t n_tris;
@@ -560,7 +541,13 @@ struct BandNodesParams {
   uint32_t* rec_out;
   float* dist_out;
 };
-hipError_t launch_band_nodes(const BandNodesParams& p, hipStream_t s);
+hipError_t launch_field_level(const FieldBuildParams& p, hipStream_t s);
+// a banded field's bricks, in the order the caller runs them.  v: the logical geometry with nb set (its pointers are not read).
+//   launch_band_classify  one lane per brick: flags[b] = 1 if the minimum of its eight coarse corners is <= reach or one is NaN, else 0
+//   launch_band_table     incl: the inclusive prefix sums of flags (launch_scan_counts).  table[b] = incl[b] - 1 of a stored brick,
+//                         kBandFar of any other; stored[incl[b] - 1] = b
+//   launch_band_fill      one workgroup per stored brick: its 729 node values, every query seeded from the record of the nearest
+//                         coarse corner; NaN beyond n_k - 1
 hipError_t launch_band_classify(const FieldView& v, const float* coarse, float reach, uint32_t* flags, hipStream_t s);
 hipError_t launch_band_table(const FieldView& v, const uint32_t* flags, const unsigned long long* incl, uint32_t* table, uint32_t* stored,
                              hipStream_t s);

@@ -95,7 +95,7 @@ hipError_t launch_field_refine(const RefineKernelParams& p, hipStream_t s) {
   if (p.n_beams == 0u || p.n_beams > kRefineMaxBeams || p.iterations > kRefineMaxIterations) return hipErrorInvalidValue;
   const uint32_t nblocks = (p.n_particles + 3u) / 4u;
   if (p.fv.lat != nullptr) hipLaunchKernelGGL(k_field_refine<false>, dim3(nblocks), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_field_refine<true>, dim3(nblocks), dim3(256), 0, s, p);   // a banded field (band_field.hip)
+  else hipLaunchKernelGGL(k_field_refine<true>, dim3(nblocks), dim3(256), 0, s, p);   // a banded field
   return hipGetLastError();
 }
 

@@ -319,7 +319,7 @@ hipError_t launch_stein_iteration(const SteinKernelParams& p, hipStream_t s, hip
   if (e == hipSuccess && events) e = hipEventRecord(events[0], s);
   if (e != hipSuccess) return e;
   if (p.r.fv.lat != nullptr) hipLaunchKernelGGL(k_stein_drive<false>, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(k_stein_drive<true>, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);   // a banded field (band_field.hip)
+  else hipLaunchKernelGGL(k_stein_drive<true>, dim3(blocks_of(n, 4u)), dim3(256), 0, s, p);   // a banded field
   if (events) e = hipEventRecord(events[1], s);
   if (e == hipSuccess) e = hipMemsetAsync(p.table, 0xFF, p.table_words * sizeof(unsigned long long), s);
   if (e == hipSuccess) e = hipMemsetAsync(p.count, 0, p.table_words * sizeof(uint32_t), s);

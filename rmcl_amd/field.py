@@ -103,26 +103,23 @@ class DistanceFieldHip:
     """rmclhip_field: built once from a HipMap, immutable.  An updater it is set on keeps it alive past close()."""
 
     def __init__(self, hip_map, cell=0.0, margin=0.0, max_nodes=DEFAULT_MAX_NODES):
-        if hip_map is None:
-            raise RuntimeError("NO MAP")
-        self.map, self.ctx = hip_map, hip_map.ctx
-        self._h = C.c_void_p()
-        p = field_params(cell, margin, max_nodes)
-        _capi.check(_capi.lib().rmclhip_field_create(self.ctx.handle, hip_map.handle, C.byref(p), C.byref(self._h)))
+        self._create(hip_map, _capi.lib().rmclhip_field_create, field_params(cell, margin, max_nodes))
 
     @classmethod
     def banded(cls, hip_map, cell=0.0, margin=0.0, band=0.5, max_nodes=DEFAULT_MAX_NODES):
         """rmclhip_field_create_banded: the same logical lattice, fine nodes stored only in the bricks within `band` (plus four cell
         diagonals) of the surface, the rest answered from a coarse lattice; max_nodes counts the stored nodes.  Query, refine and
         set_field work as on a dense field (refine / stein_step with max_dist > band are refused); download() is download_banded()."""
+        self = cls.__new__(cls)
+        self._create(hip_map, _capi.lib().rmclhip_field_create_banded, band_field_params(cell, margin, band, max_nodes))
+        return self
+
+    def _create(self, hip_map, create, params):
         if hip_map is None:
             raise RuntimeError("NO MAP")
-        self = cls.__new__(cls)
         self.map, self.ctx = hip_map, hip_map.ctx
         self._h = C.c_void_p()
-        p = band_field_params(cell, margin, band, max_nodes)
-        _capi.check(_capi.lib().rmclhip_field_create_banded(self.ctx.handle, hip_map.handle, C.byref(p), C.byref(self._h)))
-        return self
+        _capi.check(create(self.ctx.handle, hip_map.handle, C.byref(params), C.byref(self._h)))
 
     @property
     def handle(self):

@@ -3,7 +3,8 @@ deterministically from fixed seeds -- and proved non-vacuous without a device by
 
 Maps come from cpc_cases.build_map; the cells are explicit, so every lattice stays below 25 000 nodes and the brute-force oracle over it
 takes seconds.  TABLE holds what include/rmclhip.h (DISTANCE FIELD) and capi_field.cpp's level schedule make of each map: the node
-counts per axis and the number of levels of the coarse-to-fine build.  "floor" is not in the table: its lattice (cell 0.5, margin 1.0,
+counts per axis and the number of levels of the dense field's coarse-to-fine build (k_field_level, which builds the banded field's
+coarse lattice on the same maps too: band_layout).  "floor" is not in the table: its lattice (cell 0.5, margin 1.0,
 so that it has volume) serves the rank-three refinement alone.
 
 NaN.  The header says "NaN", never which one: an invalid operation makes 0xFFC00000 on x86 and 0x7FC00000 on the device, and a NaN
@@ -15,6 +16,7 @@ import math
 
 import numpy as np
 
+import band_field_ref as bfr
 import cpc_cases as cc
 import field_ref as fr
 import refine_ref as rr
@@ -70,6 +72,19 @@ def layout(name):
     cell, margin = cell_margin(name)
     vv = np.asarray(v, F).reshape(-1, 3)
     return fr.layout(vv.min(0), vv.max(0), cell=cell, margin=margin)
+
+
+# ---- the banded field on the same maps --------------------------------------------------------------------------------------------------
+BAND_N_MAX_OVER_32 = ("fan20k", "cadmix20k", "chain200")     # the banded build runs its stride-16 level, with a clamped last node
+
+
+def band_layout(name):
+    """(logical, bricks) of band_field_ref.layout for the map's cell and margin at band = half a cell: every brick of every map is
+    then within reach of the surface (tests/test_field_cases_cpu.py)"""
+    v, _ = build_map(name)
+    cell, margin = cell_margin(name)
+    vv = np.asarray(v, F).reshape(-1, 3)
+    return bfr.layout(vv.min(0), vv.max(0), cell=cell, margin=margin, band=0.5 * cell)
 
 
 # ---- the level schedule of field_build (capi_field.cpp) ------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import time
 import numpy as np
 import pytest
 
+import band_field_ref as bfr
 import cpc_cases as cc
 import field_cases as fc
 import field_ref as fr
@@ -83,6 +84,26 @@ def test_chain2000_has_nan_nodes_and_finite_ones(orc):
     for name in fc.MAPS:
         if name != "chain2000":
             assert not np.isnan(fc.oracle_lattice(orc, name)[1]).any(), name
+
+
+@pytest.mark.parametrize("name", fc.MAPS)
+def test_banded_cut_of_the_oracle_lattice(orc, name):
+    """what tests/test_gpu_field_hard.py's banded test takes for granted, on the oracle's lattice: at band = half a cell every brick
+    is stored (so that test says nothing about FAR bricks), every lattice is ragged (NaN padding in the last bricks), three maps run
+    the banded build's stride-16 level, and chain2000's bricks hold NaN nodes"""
+    info, lat, _ = fc.oracle_lattice(orc, name)
+    logical, bricks = fc.band_layout(name)
+    assert fr.same_layout(dict(info, bytes=0), logical)
+    cut = bfr.build(logical, bricks, lat)
+    n_nan = int(np.isnan(lat).sum())
+    print("[field-hard] %-9s banded at half a cell: %d of %d bricks stored, %d NaN nodes, n_max %d" % (
+        name, cut["n_stored"], bricks["n_bricks"], n_nan, max(logical["n"])))
+    assert cut["n_stored"] == bricks["n_bricks"] >= 1 and not (cut["table"] == bfr.FAR).any()
+    assert bfr.is_ragged(logical) and np.isnan(cut["bricks"]).any()
+    assert (max(logical["n"]) > 32) == (name in fc.BAND_N_MAX_OVER_32)
+    assert (n_nan > 0) == (name == "chain2000")
+    if name == "chain2000":
+        assert np.isnan(cut["coarse"]).any() and np.isfinite(cut["coarse"]).any()
 
 
 @pytest.mark.parametrize("name", [m for m in fc.MAPS if m in cc.WELL_SCALED + cc.ONE_SIDED])

@@ -1,4 +1,4 @@
-"""The banded distance field on the device (include/rmclhip.h, BANDED DISTANCE FIELD; k_band_nodes, k_band_classify, k_band_table,
+"""The banded distance field on the device (include/rmclhip.h, BANDED DISTANCE FIELD; k_field_level, k_band_classify, k_band_table,
 k_band_fill and the banded instantiations of k_field_query, k_pf_update_field, k_field_refine and k_stein_drive) on the smallest maps
 that have FAR, STORED and ragged bricks (tests/band_field_ref.py, CASES; tests/test_band_field_cpu.py proves them non-vacuous).
 

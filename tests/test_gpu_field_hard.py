@@ -1,4 +1,4 @@
-"""The distance field's build, lookup, sensor update and refinement (k_field_build, k_field_query, k_pf_update_field, k_field_refine)
+"""The distance field's build, lookup, sensor update and refinement (k_field_level, k_field_query, k_pf_update_field, k_field_refine)
 on deep, sliver, degenerate, duplicated, tiny, far-away and overflowing maps -- the inputs of tests/field_cases.py, which
 tests/test_field_cases_cpu.py proves non-vacuous without a device.
 
@@ -7,7 +7,8 @@ oracle at every node with the comparison of tests/test_gpu_cpc_hard.py (1e-5 rel
 float64 within cpc_cases.f64_bound, two-sided on the well-scaled maps and from below on slivers and the CAD mix), and the layout.  The
 lookup, the update's errors and attributes and the refinement's poses, rows and counts against their numpy restatements
 (tests/field_ref.py, tests/refine_ref.py) fed with the device's own lattice: the same NaN pattern and the same bytes everywhere else
-(field_cases.same_bits says why a NaN's payload is not compared).
+(field_cases.same_bits says why a NaN's payload is not compared).  The banded build (k_field_level at strides 16 and 8, k_band_fill)
+on every one of these maps against the restatement's cut of the device's own dense lattice (tests/band_field_ref.py).
 
 The last test prints the module's wall time and one line per map (recorded in profiles/field_hard_cases.txt)."""
 import time
@@ -15,6 +16,7 @@ import time
 import numpy as np
 import pytest
 
+import band_field_ref as bfr
 import cpc_cases as cc
 import field_cases as fc
 import field_ref as fr
@@ -293,6 +295,31 @@ def test_sharded_field_update_and_refine_equal_the_unsharded_calls(ra, orc, ctx,
     assert all(st[k] == single_st[k] for k in ("n_particles", "n_moved", "n_no_beams", "n_not_finite"))
     assert abs(st["cost_after_sum"] - single_st["cost_after_sum"]) <= 1e-12 * single_st["cost_after_sum"]     # rank sums added in rank order
     spf.close()
+
+
+# ---- 6. the banded build on the same maps -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", fc.MAPS)
+def test_banded_build_is_the_cut_of_the_dense_lattice(ra, world, name):
+    """both layouts' node values come from one kernel and one query: at band = half a cell every brick is stored
+    (tests/test_field_cases_cpu.py), so every node of the dense lattice is held a second time, by k_band_fill or the coarse level"""
+    w = world(name)
+    cell, margin = fc.cell_margin(name)
+    bf = ra.DistanceFieldHip.banded(w.hm, cell=cell, margin=margin, band=0.5 * cell)
+    info, band = bf.info(), bf.band_info()
+    table, coarse, bricks = bf.download_banded()
+    bf.close()
+    assert fr.same_layout(dict(w.info, bytes=info["bytes"]), info), (w.info, info)
+    logical, ref_b = fc.band_layout(name)
+    ref = bfr.build(logical, ref_b, w.lat)
+    print("[field-hard] %-9s banded: %d of %d bricks stored, %d bytes, %d NaN nodes in the bricks" % (
+        name, band["n_stored"], band["n_bricks"], band["bytes"], np.isnan(bricks).sum()))
+    assert bfr.same_layout((dict(logical, bytes=ref["bytes"]), dict(ref_b, n_stored=ref["n_stored"], bytes=ref["bytes"])), (info, band)), (info, band)
+    assert band["n_stored"] == ref["n_stored"] == band["n_bricks"] and band["bytes"] == info["bytes"] == ref["bytes"]
+    assert np.array_equal(table, ref["table"])
+    for key, got in (("coarse", coarse), ("bricks", bricks)):
+        assert got.shape == ref[key].shape, key
+        msg = fc.same_bits(got, ref[key])
+        assert msg is None, "%s %s: %s" % (name, key, msg)
 
 
 def test_zz_wall_time_of_this_module():
