@@ -2,7 +2,9 @@
 the header's precision and order, vectorised over particles and pairs (element-wise numpy arithmetic rounds every operation to the
 array's type, which is the header's "unfused").  The pass, the solve, the limit and the candidate are refine_ref's; the random word is
 the resamplers' stream (adaptive_ref).  step(..., brute=True) sums over ALL pairs instead of the adjacent bins: with max_per_bin >= n
-the two are the same bytes, which is the proof in numbers that the cell list covers the kernel's support.  Not a test module.
+the two are the same bytes, which is the proof in numbers that the cell list covers the kernel's support.  The table of occupied bins
+(mix64, bin_key, table_words, table_slots) is restated too: where a cloud's bins land decides which words and scan blocks a case
+reaches (tests/stein_cases.py).  Not a test module.
 """
 import numpy as np
 
@@ -104,6 +106,65 @@ def cell_list(t, finite, p, it):
     return b, count, listed, listed_b, n_bins, n_thinned
 
 
+# ---- the table of occupied bins (kld_bins.hip.h, k_stein_insert): where bins land -------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def mix64(x):
+    """splitmix64's finaliser on a Python int, as kld_bins.hip.h's mix64"""
+    x &= _M64
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def table_words(n):
+    """kld_table_words: the power of two >= max(64, 2 n)"""
+    words = 64
+    while words < 2 * n:
+        words <<= 1
+    return words
+
+
+def bin_key(b):
+    """the 42-bit key of a bin index (bx, by, bz) as bins() gives it (0 on a locked axis): index + 8192 in 14 bits each, x | y << 14 |
+    z << 28, so a locked axis holds 8192"""
+    bx, by, bz = (int(v) + 8192 for v in b)
+    assert 0 <= bx <= 16383 and 0 <= by <= 16383 and 0 <= bz <= 16383
+    return bx | (by << 14) | (bz << 28)
+
+
+def table_slots(keys, words):
+    """linear probing from mix64(key) & (words - 1) over `words` words, the distinct keys inserted in the order given:
+    (occupied slots (a set), {key: home slot}, {key: the slot it is stored at in THIS order}).  The occupied set -- and the sum of the
+    displacements -- is the same for every insertion order; which key sits where inside a run is the order's (on the device: the
+    atomics')."""
+    assert words >= 64 and words & (words - 1) == 0
+    stored, home, used = {}, {}, {}
+    for key in keys:
+        key = int(key)
+        if key in stored:
+            continue
+        assert len(stored) < words
+        home[key] = sl = mix64(key) & (words - 1)
+        while sl in used:
+            sl = (sl + 1) & (words - 1)
+        used[sl] = key
+        stored[key] = sl
+    return set(used), home, stored
+
+
+def table_of(poses, p):
+    """table_slots of a cloud's finite-pose particles in index order, in the table of len(poses) particles: (words, occupied, home,
+    stored)"""
+    R, t = rr.pose_arrays(poses)
+    finite = np.isfinite(R).all(axis=1) & np.isfinite(t).all(axis=1)
+    words = table_words(len(R))
+    return (words,) + table_slots([bin_key(b) for b in bins(t[finite], p)], words)
+
+
 # ---- the sums and the move ---------------------------------------------------------------------------------------------------------------
 def quantise(x, counts):
     """Q(x) = int64(rint(double(x) * 2^32)) where `counts`, 0 elsewhere"""
@@ -134,14 +195,14 @@ def drives(info, lattice, R, t, finite, Tsb, beams, p):
     return drive, C, n_used
 
 
-def iteration(info, lattice, R, t, Tsb, beams, p, it, brute=False):
-    """one iteration at the poses (R, t): (R', t', rows, counts dict)"""
+def pair_terms(R, t, finite, p, it, brute=False):
+    """every pair (i, j) at the poses (R, t): (e [n, n, 6], counts [n, n] bool, a [n, n], wu [n, n], the cell list's tuple); row i is
+    particle i, column j its candidate neighbour"""
     n = len(R)
     mask = p["dof_mask"] & 0x3F
     free = [k for k in range(6) if (mask >> k) & 1]
-    finite = np.isfinite(R).all(axis=1) & np.isfinite(t).all(axis=1)
-    drive, C, n_used = drives(info, lattice, R, t, finite, Tsb, beams, p)
-    b, count, listed, listed_b, n_bins, n_thinned = cell_list(t, finite, p, it)
+    cl = cell_list(t, finite, p, it)
+    b, count, listed, listed_b = cl[:4]
     with np.errstate(all="ignore"):
         w_bin = (count.astype(F) / np.where(listed_b > 0, listed_b, 1).astype(F)).astype(F)       # of particle j's bin
         cand = finite[:, None] & listed[None, :] & ~np.eye(n, dtype=bool)
@@ -167,6 +228,18 @@ def iteration(info, lattice, R, t, Tsb, beams, p, it, brute=False):
         kk = u * u
         a = w_bin[None, :] * kk
         wu = w_bin[None, :] * u
+    return e, counts, a, wu, cl
+
+
+def iteration(info, lattice, R, t, Tsb, beams, p, it, brute=False):
+    """one iteration at the poses (R, t): (R', t', rows, counts dict)"""
+    n = len(R)
+    mask = p["dof_mask"] & 0x3F
+    free = [k for k in range(6) if (mask >> k) & 1]
+    finite = np.isfinite(R).all(axis=1) & np.isfinite(t).all(axis=1)
+    drive, C, n_used = drives(info, lattice, R, t, finite, Tsb, beams, p)
+    e, counts, a, wu, (b, count, listed, listed_b, n_bins, n_thinned) = pair_terms(R, t, finite, p, it, brute)
+    with np.errstate(all="ignore"):
         W = quantise(a, counts).sum(axis=1) + (finite.astype(I64) << 32)
         Dk, Rk = np.zeros((n, 6), I64), np.zeros((n, 6), I64)
         for k in free:
@@ -216,6 +289,13 @@ def listed_of(poses, p, it=0):
     R, t = rr.pose_arrays(poses)
     finite = np.isfinite(R).all(axis=1) & np.isfinite(t).all(axis=1)
     return cell_list(t, finite, p, it)[2]
+
+
+def pairs_of(poses, p, it=0, brute=False):
+    """pair_terms of the iteration `it` at these poses"""
+    R, t = rr.pose_arrays(poses)
+    finite = np.isfinite(R).all(axis=1) & np.isfinite(t).all(axis=1)
+    return pair_terms(R, t, finite, p, it, brute)
 
 
 # ---- the clouds the CPU and the GPU tests share -----------------------------------------------------------------------------------------
