@@ -1480,6 +1480,72 @@ inline SurfaceStats constrainToSurface(const HipMapPtr& map, ParticleCloud<VRAM_
   return constrainToSurface(map, cloud.posesView(), cloud.attrsView(), params, max_n_meas);
 }
 
+// The surface sampler (rmclhip.h, SURFACE SAMPLER): poses drawn uniformly by area on the drivable faces of the map -- the global
+// initialisation of a ground robot and the fresh draws of the recovery injection.  SurfaceSampleParams{} holds the library's defaults:
+// min_up_cos 0.7, height 0, align 0, region unbounded, yaw in [-pi, pi].
+struct SurfaceSampleParams : rmclhip_surface_sample_params {
+  SurfaceSampleParams() { rmclhip_surface_sample_params_default(this); }
+};
+using SurfaceSampleInfo = rmclhip_surface_sample_info;
+class SurfaceSamplerHip {
+ public:
+  explicit SurfaceSamplerHip(const HipMapPtr& map, const SurfaceSampleParams& params = SurfaceSampleParams()) : map_(map) {
+    if (!map) throw std::runtime_error("NO MAP");
+    check(rmclhip_surface_sampler_create(map->handle(), &params, &h_));
+  }
+  ~SurfaceSamplerHip() { rmclhip_surface_sampler_destroy(h_); }
+  SurfaceSamplerHip(const SurfaceSamplerHip&) = delete;
+  SurfaceSamplerHip& operator=(const SurfaceSamplerHip&) = delete;
+  rmclhip_surface_sampler* handle() const { return h_; }
+  SurfaceSampleInfo info() const {
+    SurfaceSampleInfo out{};
+    check(rmclhip_surface_sampler_get_info(h_, &out));
+    return out;
+  }
+
+ private:
+  HipMapPtr map_;
+  rmclhip_surface_sampler* h_ = nullptr;
+};
+// the third initialisation: the views receive GLOBAL particles first .. first + poses.size() - 1 of the cloud (seed, epoch) selects
+inline void initSamplesSurface(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs, const SurfaceSamplerHip& sampler, uint64_t seed,
+                               uint32_t epoch = 0, uint32_t first = 0) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("initSamplesSurface: poses.size() != attrs.size()");
+  check(rmclhip_particles_init_surface(sampler.handle(), poses.raw(), attrs.raw(), first, static_cast<uint32_t>(poses.size()), seed, epoch));
+}
+inline void initSamplesSurface(ParticleCloud<VRAM_HIP>& cloud, const SurfaceSamplerHip& sampler, uint64_t seed, uint32_t epoch = 0) {
+  initSamplesSurface(cloud.posesView(), cloud.attrsView(), sampler, seed, epoch);
+}
+// the recovery injection, in place behind a resampler (same seed and step): every slot is replaced with probability p_inject by a fresh
+// draw; returns how many were
+inline uint32_t injectSurface(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs, const SurfaceSamplerHip& sampler, double p_inject,
+                              uint64_t seed, uint32_t step, uint32_t first = 0) {
+  if (poses.size() != attrs.size()) throw std::runtime_error("injectSurface: poses.size() != attrs.size()");
+  uint32_t n = 0;
+  check(rmclhip_particles_inject_surface(sampler.handle(), poses.raw(), attrs.raw(), first, static_cast<uint32_t>(poses.size()), p_inject, seed, step,
+                                         &n));
+  return n;
+}
+inline uint32_t injectSurface(ParticleCloud<VRAM_HIP>& cloud, const SurfaceSamplerHip& sampler, double p_inject, uint64_t seed, uint32_t step) {
+  return injectSurface(cloud.posesView(), cloud.attrsView(), sampler, p_inject, seed, step);
+}
+// The augmented-MCL recovery rule as AMCL runs it (rmclhip_recovery_update_host, a host function): update() takes the cloud's
+// likelihood sum (Resampler statistics) and returns the fraction to replace; reset() follows an injection.  The defaults are AMCL's
+// recovery_alpha_slow 0.001 / recovery_alpha_fast 0.1.
+class Recovery {
+ public:
+  rmclhip_recovery_params params;
+  rmclhip_recovery_state state{0.0, 0.0};
+  Recovery() { rmclhip_recovery_params_default(&params); }
+  Recovery(double alpha_slow, double alpha_fast, double p_max = 1.0) : params{alpha_slow, alpha_fast, p_max} {}
+  double update(double likelihood_sum, uint32_t n) {
+    double p = 0.0;
+    check(rmclhip_recovery_update_host(&state, &params, likelihood_sum, n, &p));
+    return p;
+  }
+  void reset() { check(rmclhip_recovery_reset_host(&state)); }
+};
+
 // The particle filter of ONE process over several devices (rmclhip_comm + rmclhip_pf_sharded: RCCL ncclCommInitAll, weight
 // all-gather, moment all-reduces): sensor update, pose estimate (RmclNode::estimateStats, rmcl_localization.cpp:642-731) and
 // the distributed gladiator tournament for the single-process node (rmcl_localization.cpp:482-552).  The cloud lives in the
@@ -1601,6 +1667,19 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
     SurfaceStats st{};
     check(rmclhip_pf_sharded_get_surface_stats(h_, &st));
     return st;
+  }
+  // one surface sampler per map replica (dropSurfaceSampler takes them off); the cloud (re)created on the surface, every device its own
+  // block; the recovery injection on every device's block, the replaced slots summed
+  void setSurfaceSampler(const SurfaceSampleParams& params) { check(rmclhip_pf_sharded_set_surface_sampler(h_, &params)); }
+  void dropSurfaceSampler() { check(rmclhip_pf_sharded_set_surface_sampler(h_, nullptr)); }
+  void initSamplesSurface(uint32_t n, uint64_t seed, uint32_t epoch = 0) {
+    check(rmclhip_pf_sharded_init_surface(h_, n, seed, epoch));
+    n_ = n;
+  }
+  uint32_t injectSurface(double p_inject, uint64_t seed, uint32_t step) {
+    uint32_t n = 0;
+    check(rmclhip_pf_sharded_inject_surface(h_, p_inject, seed, step, &n));
+    return n;
   }
   void resample(const rmclhip_gladiator_config& cfg, uint64_t seed, uint32_t step) { check(rmclhip_pf_sharded_resample(h_, &cfg, seed, step)); }
   void resampleResidual(const rmclhip_gladiator_config& cfg, uint64_t seed, uint32_t step) { check(rmclhip_pf_sharded_resample_residual(h_, &cfg, seed, step)); }
@@ -1756,6 +1835,28 @@ class AdaptiveResamplerHip : public SensorUpdaterBase {
     check(rmclhip_resampler_adaptive(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), poses_new.raw(), attrs_new.raw(),
                                      static_cast<uint32_t>(poses_new.size()), &kld_, &config_, seed, step_++, &n_new, &last_bins));
     return {n_new};
+  }
+  rmclhip_likelihood_stats computeStats(DeviceView<ParticleAttributes> attrs) {
+    init();
+    rmclhip_likelihood_stats out{0.f, 0.f};
+    check(rmclhip_resampler_compute_stats(h_, attrs.raw(), static_cast<uint32_t>(attrs.size()), &out));
+    return out;
+  }
+  // the same step with recovery: the old cloud's likelihood sum feeds the averages, and behind the resampler the fraction they ask for
+  // is replaced in the new cloud by fresh draws from the sampler (same seed and step); the averages are reset when anything was
+  // injected.  last_p_inject / last_injected: what this call asked for and got.
+  double last_p_inject = 0.0;
+  uint32_t last_injected = 0;
+  ParticleUpdateDynamicResults update(DeviceView<Transform> poses, DeviceView<ParticleAttributes> attrs,
+                                      DeviceView<Transform> poses_new, DeviceView<ParticleAttributes> attrs_new, Recovery& recovery,
+                                      const SurfaceSamplerHip& sampler) {
+    last_p_inject = recovery.update(static_cast<double>(computeStats(attrs).sum), static_cast<uint32_t>(poses.size()));
+    const uint32_t step = step_;
+    const ParticleUpdateDynamicResults res = update(poses, attrs, poses_new, attrs_new);
+    last_injected = injectSurface(DeviceView<Transform>{poses_new.raw(), res.n_particles}, DeviceView<ParticleAttributes>{attrs_new.raw(), res.n_particles},
+                                  sampler, last_p_inject, seed, step);
+    if (last_injected) recovery.reset();
+    return res;
   }
 
  private:

@@ -1009,6 +1009,100 @@ rmclhip_status rmclhip_particles_pack_visualization(rmclhip_ctx* ctx, const rmcl
                                                     const rmclhip_particle_attributes* attrs_dev, uint32_t n, uint32_t max_n_meas,
                                                     float* out, int out_is_device);
 
+/* ---- SURFACE SAMPLER: poses drawn uniformly by area on the drivable faces of the map; recovery injection -------
+ * Global initialisation of a ground robot and the augmented-MCL recovery rule (Thrun, Burgard, Fox: Probabilistic Robotics, table
+ * 8.3; AMCL's recovery_alpha_slow / recovery_alpha_fast) need the same primitive: a pose that stands on a face the robot can stand on,
+ * every square metre of such faces equally likely -- not a 6-D box of air followed by one ray per particle
+ * (rmclhip_particles_init_uniform + rmclhip_pf_constrain_to_surface), whose density follows the projected area, whose floor depends on
+ * a z draw and whose draws outside the building stay where they fell.  (The reference lists neither: docs/RMCL.md.)
+ *
+ * THE SAMPLER, built once per (map, parameters) on the device; the handle retains the map.  Weights live on ORIGINAL FACE IDS
+ * 0 .. n_faces-1 (global face ids of a scene), not on triangle records: a face the builder's spatial splits reference from k leaves
+ * has k identical records and counts once, so the cloud does not depend on the tree.  Per face f, from the record with the LOWEST
+ * index that carries face id f (the records of a face are identical: which one is read does not matter to the bytes):
+ *   1. eligible iff |n.z| >= min_up_cos with n the record's unit normal (a map has no consistent winding: the sign is dropped; a
+ *      NaN normal is not eligible) and region_min[d] <= c_d <= region_max[d] for d = x, y, z with the centroid
+ *      c_d = double(v0_d) + (double(e2_d) - double(e1_d)) / 3.0 of the record's v0, e1 = v0 - v1, e2 = v2 - v0 (bounds converted to double).
+ *   2. a_f = 0.5 * sqrt((double(Ng.x)^2 + double(Ng.y)^2) + double(Ng.z)^2) of the record's float Ng.
+ *   3. a_max = the largest finite a_f > 0 of an eligible face (a maximum: independent of the order).
+ *   4. w_f = uint64(rint(a_f / a_max * 4294967296.0)) for an eligible face with finite a_f > 0, else 0.  (A face more than 2^33 times
+ *      smaller than the largest weighs 0 and is never drawn.)
+ *   5. C[f] = w_0 + ... + w_f in 64 bits (the resamplers' prefix scan), T = C[n_faces - 1]: integers, exact whatever the launch shape.
+ *      (w_f <= 2^32 and a map has fewer than 2^32 faces -- a face id is a 32-bit word -- so T <= (2^32 - 1) * 2^32 < 2^64: no sum wraps.)
+ * No face with a positive weight: RMCLHIP_ERR_INVALID, no handle.  Refused before any launch (RMCLHIP_ERR_INVALID): min_up_cos outside
+ * [0, 1] or NaN; height not finite; region_min[d] > region_max[d] or a NaN bound (infinities are allowed); yaw_min > yaw_max or either
+ * not finite; align not 0 or 1; a map without faces.
+ *
+ * THE DRAW of one pose from two Philox blocks A, B (rmclhip_particles_init_surface and rmclhip_particles_inject_surface name their
+ * counters), one function of (seed, counter) for both callers:
+ *   1. r = A0 * 2^32 + A1; pos = the high 64 bits of the 128-bit product r * T: uniform on [0, T).  The face is the first f with
+ *      C[f] > pos; its record is the one of step "per face" above.
+ *   2. u = (A2 + 0.5) * 2^-32, v = (A3 + 0.5) * 2^-32 in double; u + v > 1.0: u = 1.0 - u, v = 1.0 - v.
+ *      p_d = float((double(v0_d) - u * double(e1_d)) + v * double(e2_d)): the point v0 + u (v1 - v0) + v (v2 - v0).
+ *   3. yaw = float(double(yaw_min) + (double(yaw_max) - double(yaw_min)) * (B0 + 0.5) * 2^-32), the rule of the uniform initialisation;
+ *      R = Quaternion(EulerAngles(0, 0, yaw)) by that initialisation's conversion.
+ *   4. n = the record's unit normal, negated when n.z < 0.  a = (0, 0, 1) (align 0) or n (align 1).
+ *   5. align 1: R = step 5 of the surface constraint above applied to (R, n): the shortest arc that takes the body's z onto n, its
+ *      float arithmetic, its w < 1e-6 half turn about the body's x and its two normalisations.
+ *   6. t_d = p_d + height * a_d in float, the product first.  stamp = 0.
+ * Every operation is IEEE in this order (the library is built without contraction); tests/surface_sample_ref.py restates it. */
+typedef struct {
+  float min_up_cos;                   /* [0.7] */
+  float height;                       /* [0]  the pose stands this far above the face, along a */
+  int align;                          /* [0]  0: roll = pitch = 0; 1: body z on the (flipped) face normal */
+  float region_min[3], region_max[3]; /* [-inf, +inf] */
+  float yaw_min, yaw_max;             /* [-pi_f, pi_f], pi_f = float(pi) */
+} rmclhip_surface_sample_params;
+typedef struct {
+  uint32_t n_faces;        /* of the map */
+  uint32_t n_eligible;     /* faces that pass rule 1 */
+  uint32_t n_weighted;     /* faces with w_f > 0 */
+  uint32_t reserved;
+  double area_eligible;    /* the a_f of the eligible faces with a finite area, added in double in increasing face id (on the host) */
+  uint64_t weight_total;   /* T */
+} rmclhip_surface_sample_info;
+typedef struct rmclhip_surface_sampler rmclhip_surface_sampler;
+void rmclhip_surface_sample_params_default(rmclhip_surface_sample_params* out);
+/* params NULL: the defaults.  Synchronous. */
+rmclhip_status rmclhip_surface_sampler_create(rmclhip_map* map, const rmclhip_surface_sample_params* params, rmclhip_surface_sampler** out);
+void rmclhip_surface_sampler_destroy(rmclhip_surface_sampler* sampler);
+rmclhip_status rmclhip_surface_sampler_get_info(const rmclhip_surface_sampler* sampler, rmclhip_surface_sample_info* out);
+/* Initialisation on the surface.  Global particle i = first + k draws from A = Philox(counter (i, epoch, 2, 1), key = seed),
+ * B = Philox(counter (i, epoch, 3, 1), key) -- stream 1 of the initialisations, behind their draws 0 and 1.  Attributes and contract
+ * are rmclhip_particles_init_uniform's: likelihood {1, 0, 0}, state_sigma 0; element k holds global particle first + k, so slices and
+ * shards equal the whole; count == 0 is RMCLHIP_OK with nothing touched; RMCLHIP_ERR_INVALID for a null sampler, null buffers with
+ * count > 0 or first + count above 2^32 (RMCLHIP_ERR_UNSUPPORTED above 2^32 / 9 particles in one call).  Synchronous on return. */
+rmclhip_status rmclhip_particles_init_surface(rmclhip_surface_sampler* sampler, rmclhip_transform* poses_dev,
+                                              rmclhip_particle_attributes* attrs_dev, uint32_t first, uint32_t count, uint64_t seed,
+                                              uint32_t epoch);
+/* RECOVERY (augmented MCL as AMCL runs it): a slow and a fast running average of the cloud's mean likelihood; when the fast one
+ * drops below the slow one, the fraction p = 1 - w_fast / w_slow of the cloud is replaced by fresh draws from the sampler.
+ * rmclhip_recovery_update_host -- a HOST function, no device needed, in double, in this order:
+ *   avg = likelihood_sum / double(n);
+ *   w_slow == 0: w_slow = avg, else w_slow = w_slow + alpha_slow * (avg - w_slow);  the same for w_fast with alpha_fast;
+ *   p = 0 while !(w_slow > 0), else p = 1.0 - w_fast / w_slow clamped to [0, p_max] (below 0 or NaN: 0).
+ * RMCLHIP_ERR_INVALID, state untouched: null state or params; an alpha outside (0, 1] or NaN; alpha_slow > alpha_fast; p_max outside
+ * [0, 1] or NaN; n == 0; a likelihood_sum that is negative or not finite.  p_inject_out is nullable.
+ * rmclhip_recovery_reset_host zeroes both averages: AMCL does so after it has injected, so one drop does not inject forever.
+ * The defaults {0.001, 0.1, 1.0} are AMCL's recovery_alpha_slow / recovery_alpha_fast; they are not tuned here. */
+typedef struct { double w_slow, w_fast; } rmclhip_recovery_state;                    /* zeros = fresh */
+typedef struct { double alpha_slow, alpha_fast; double p_max; } rmclhip_recovery_params;
+void rmclhip_recovery_params_default(rmclhip_recovery_params* out);
+rmclhip_status rmclhip_recovery_update_host(rmclhip_recovery_state* state, const rmclhip_recovery_params* params, double likelihood_sum,
+                                            uint32_t n, double* p_inject_out);
+rmclhip_status rmclhip_recovery_reset_host(rmclhip_recovery_state* state);
+/* Injection, in place on particles first .. first+count-1 of a cloud any resampler (or a shard of one) produced.  Slot j = first + k
+ * is replaced iff uint64(Philox(counter (j, step, 9, 0), key = seed)[0]) < uint64(floor(p_inject * 4294967296.0)): p_inject 1 replaces
+ * every slot; a threshold of 0 (p_inject below 2^-32) launches nothing and touches nothing.  A replaced slot gets THE DRAW with
+ * A = Philox(counter (j, step, 10, 0), key), B = Philox(counter (j, step, 11, 0), key) -- stream 0 of the resamplers, behind their
+ * draws 0..8, so an injection shares seed and step with the resampler it follows -- and the initialisation's attributes (an unmeasured
+ * particle: its first sensor update replaces its likelihood).  Every other slot keeps its bytes.  n_injected_out (nullable): replaced
+ * slots of this call.  RMCLHIP_ERR_INVALID, nothing touched: p_inject outside [0, 1] or NaN, and rmclhip_particles_init_surface's
+ * refusals.  count == 0: RMCLHIP_OK.  Synchronous on return. */
+rmclhip_status rmclhip_particles_inject_surface(rmclhip_surface_sampler* sampler, rmclhip_transform* poses_dev,
+                                                rmclhip_particle_attributes* attrs_dev, uint32_t first, uint32_t count, double p_inject,
+                                                uint64_t seed, uint32_t step, uint32_t* n_injected_out);
+
 /* ---- multi-GPU: ONE process drives several devices -------------------------------------------------------------
  * (the reference's localisation node is one process: rmcl_localization.cpp:482-552; particle store rmcl_localization.hpp:65-77.
  * The reference has no distributed code -- SURVEY.md 8(e) defines this part.)  Particles are block-partitioned over the
@@ -1061,6 +1155,16 @@ rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* pf, const rmcl
 rmclhip_status rmclhip_pf_sharded_constrain_to_surface(rmclhip_pf_sharded* pf, const rmclhip_surface_params* params,
                                                        rmclhip_surface_stats* stats_out);
 rmclhip_status rmclhip_pf_sharded_get_surface_stats(rmclhip_pf_sharded* pf, rmclhip_surface_stats* out);
+/* the surface sampler on a sharded cloud: one sampler per map replica (params NULL drops them; a refusal leaves the previous ones).
+ * rmclhip_pf_sharded_init_surface (re)creates a cloud of n particles as rmclhip_pf_sharded_init_uniform does, every device filling its
+ * own block with rmclhip_particles_init_surface's values of its global indices; rmclhip_pf_sharded_inject_surface replaces slots of
+ * every device's block in place.  No collective; all devices' launches are enqueued before the host waits for any; the injected counts
+ * are summed on the host (n_injected_out nullable).  Equal, bit for bit, to the single-device calls on the whole cloud.
+ * RMCLHIP_ERR_INVALID without samplers. */
+rmclhip_status rmclhip_pf_sharded_set_surface_sampler(rmclhip_pf_sharded* pf, const rmclhip_surface_sample_params* params);
+rmclhip_status rmclhip_pf_sharded_init_surface(rmclhip_pf_sharded* pf, uint32_t n, uint64_t seed, uint32_t epoch);
+rmclhip_status rmclhip_pf_sharded_inject_surface(rmclhip_pf_sharded* pf, double p_inject, uint64_t seed, uint32_t step,
+                                                 uint32_t* n_injected_out);
 /* One cycle of the filter node on the sharded cloud (rmcl_localization.cpp:84, 432-552): motion update (T_bnew_bold NULL: skipped) ->
  * sensor update -> weight all-gather -> {sum, max} of the gathered weights on every device (stats_out, nullable; no collective) -> resampling (resample: 0 none, 1 gladiator
  * tournament, 2 residual; config / seed / step as rmclhip_pf_sharded_resample).  A device's motion and sensor-update launches share a

@@ -88,6 +88,32 @@ class SurfaceStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class SurfaceSampleParams(C.Structure):
+    """rmclhip_surface_sample_params (the surface sampler)"""
+    _fields_ = [("min_up_cos", C.c_float), ("height", C.c_float), ("align", C.c_int), ("region_min", C.c_float * 3),
+                ("region_max", C.c_float * 3), ("yaw_min", C.c_float), ("yaw_max", C.c_float)]
+
+
+class SurfaceSampleInfo(C.Structure):
+    """rmclhip_surface_sample_info"""
+    _fields_ = [("n_faces", C.c_uint32), ("n_eligible", C.c_uint32), ("n_weighted", C.c_uint32), ("reserved", C.c_uint32),
+                ("area_eligible", C.c_double), ("weight_total", C.c_uint64)]
+
+    def as_dict(self):
+        return {"n_faces": int(self.n_faces), "n_eligible": int(self.n_eligible), "n_weighted": int(self.n_weighted),
+                "area_eligible": float(self.area_eligible), "weight_total": int(self.weight_total)}
+
+
+class RecoveryState(C.Structure):
+    """rmclhip_recovery_state"""
+    _fields_ = [("w_slow", C.c_double), ("w_fast", C.c_double)]
+
+
+class RecoveryParams(C.Structure):
+    """rmclhip_recovery_params"""
+    _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("p_max", C.c_double)]
+
+
 class KldParams(C.Structure):
     """rmclhip_kld_params (occupied bins of pose space + the KLD-sampling bound)"""
     _fields_ = [("bin_xyz", C.c_float * 3), ("bin_rpy", C.c_float * 3), ("min_likelihood_rel", C.c_float), ("epsilon", C.c_double),
@@ -390,6 +416,18 @@ SIGNATURES = {
     "rmclhip_chol6_host": (_i32, [_vp, _vp, C.POINTER(_dbl)]),
     "rmclhip_particles_init_uniform": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32]),
     "rmclhip_particles_init_pose": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, C.c_uint64, _u32, C.POINTER(_dbl)]),
+    "rmclhip_surface_sample_params_default": (None, [C.POINTER(SurfaceSampleParams)]),
+    "rmclhip_surface_sampler_create": (_i32, [_vp, C.POINTER(SurfaceSampleParams), _pp]),
+    "rmclhip_surface_sampler_destroy": (None, [_vp]),
+    "rmclhip_surface_sampler_get_info": (_i32, [_vp, C.POINTER(SurfaceSampleInfo)]),
+    "rmclhip_particles_init_surface": (_i32, [_vp, _vp, _vp, _u32, _u32, C.c_uint64, _u32]),
+    "rmclhip_recovery_params_default": (None, [C.POINTER(RecoveryParams)]),
+    "rmclhip_recovery_update_host": (_i32, [C.POINTER(RecoveryState), C.POINTER(RecoveryParams), _dbl, _u32, C.POINTER(_dbl)]),
+    "rmclhip_recovery_reset_host": (_i32, [C.POINTER(RecoveryState)]),
+    "rmclhip_particles_inject_surface": (_i32, [_vp, _vp, _vp, _u32, _u32, _dbl, C.c_uint64, _u32, C.POINTER(_u32)]),
+    "rmclhip_pf_sharded_set_surface_sampler": (_i32, [_vp, C.POINTER(SurfaceSampleParams)]),
+    "rmclhip_pf_sharded_init_surface": (_i32, [_vp, _u32, C.c_uint64, _u32]),
+    "rmclhip_pf_sharded_inject_surface": (_i32, [_vp, _dbl, C.c_uint64, _u32, C.POINTER(_u32)]),
     "rmclhip_particles_pack_visualization": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _i32]),
     "rmclhip_comm_create": (_i32, [_vp, _u32, _pp]),
     "rmclhip_comm_create_loopback": (_i32, [_vp, _u32, _pp]),

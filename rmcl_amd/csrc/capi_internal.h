@@ -12,7 +12,8 @@
 //   capi_band_field.cpp the banded distance field: layout, the coarse build, classification, the bricks' fill, download (kernels: field_build.hip; the lookups are field.hip's)
 //   capi_stein.cpp     the Stein variational step of a cloud on a filter handle's field: parameters, scratch, the iterations' launches, counts (kernels: stein.hip)
 //   capi_refine.cpp    the damped Gauss-Newton refinement of particles on a distance field: parameters, launch, counts (kernel: refine.hip)
-//   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance) and visualisation channels (kernels: particles.hip)
+//   capi_particles.cpp the particle cloud's initialisations (uniform, pose + covariance, on the surface), the recovery injection and the visualisation channels (kernels: particles.hip)
+//   capi_surface_sample.cpp the surface sampler: parameters, the build of the face weights, info; the recovery averages (host) (kernels: surface_sample.hip, the scan of resample.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
 //   capi_pose_information.cpp the point-to-plane information matrix of a find's correspondences and its host algebra: covariance, degeneracy (kernels: pose_information.hip)
 //   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
@@ -651,6 +652,30 @@ struct ParticlesPoseJob { xform Tlm; float L[36]; double chol_err; };
 RMCL_INTERNAL rmclhip_status particles_uniform_check(const char* who, uint32_t first, uint32_t count, const float* bb_min, const float* bb_max);
 RMCL_INTERNAL rmclhip_status particles_pose_check(const char* who, uint32_t first, uint32_t count, const rmclhip_transform* Tlm, const double* covariance,
                                                   ParticlesPoseJob* job);
+// capi_particles.cpp: the range check of every initialisation, and the context's particle stream (created by the first call; the caller
+// holds ctx->part_mtx)
+RMCL_INTERNAL rmclhip_status particles_range_check(const std::string& who, uint32_t first, uint32_t count);
+RMCL_INTERNAL rmclhip_status particles_stream(rmclhip_ctx* ctx);
+// capi_surface_sample.cpp: the surface sampler.  Immutable once built; its launches run on the context's particle stream (under
+// ctx->part_mtx) or, for a sharded filter's replicas, on the rank's collective stream.  d_count / h_count: the injected slots of the
+// call in flight (device word, pinned host word).
+struct rmclhip_surface_sampler {
+  rmclhip_ctx* ctx = nullptr;
+  rmclhip_map* map = nullptr;
+  rmclhip_surface_sample_params params{};
+  rmclhip_surface_sample_info info{};
+  uint32_t* d_rec = nullptr;
+  unsigned long long* d_incl = nullptr;
+  uint32_t* d_count = nullptr;
+  uint32_t* h_count = nullptr;
+};
+RMCL_INTERNAL rmclhip_status surface_sample_params_check(const std::string& who, const rmclhip_surface_sample_params* p);
+RMCL_INTERNAL SurfaceSampleView surface_sample_view(const rmclhip_surface_sampler* sm);
+// the threshold of an injection (RMCLHIP_ERR_INVALID for p outside [0, 1] or NaN), and its launch on s with the count's clear in front
+// and the count's copy to sm->h_count behind it (no wait; a threshold of 0 enqueues nothing and zeroes *h_count)
+RMCL_INTERNAL rmclhip_status surface_inject_threshold(const std::string& who, double p_inject, unsigned long long* out);
+RMCL_INTERNAL rmclhip_status surface_inject_enqueue(rmclhip_surface_sampler* sm, xform* poses, void* attrs, uint32_t first, uint32_t count,
+                                                    unsigned long long threshold, uint64_t seed, uint32_t step, hipStream_t s);
 extern RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries;   // capi_rcc.cpp: polls that met their sequence number before the checksum matched
 // capi_surface.cpp: the surface constraint's argument check, and the two launches on f->stream with the copy of their class counts to
 // f->h_surf behind them (no wait).  pf_motion_enqueue: the motion update of the handle, constrained when rmclhip_pf_set_surface says so.

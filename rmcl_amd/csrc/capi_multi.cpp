@@ -221,6 +221,7 @@ struct PfRank {
   rmclhip_map* map = nullptr;
   rmclhip_pf* pf = nullptr;
   rmclhip_resampler* rs = nullptr;
+  rmclhip_surface_sampler* sampler = nullptr;   // rmclhip_pf_sharded_set_surface_sampler: this replica's
   uint32_t lo = 0, hi = 0;
   xform* d_poses = nullptr; void* d_attrs = nullptr;          // this rank's shard (cap particles)
   xform* d_poses_new = nullptr; void* d_attrs_new = nullptr;  // tournament output
@@ -441,6 +442,7 @@ void rmclhip_pf_sharded_destroy(rmclhip_pf_sharded* h) {
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (R.h_mom) (void)hipHostFree(R.h_mom);
     if (R.rs) rmclhip_resampler_destroy(R.rs);
+    if (R.sampler) rmclhip_surface_sampler_destroy(R.sampler);
     if (R.pf) rmclhip_pf_destroy(R.pf);
     if (R.map) rmclhip_map_release(R.map);
     if (R.ctx) rmclhip_ctx_destroy(R.ctx);
@@ -547,9 +549,10 @@ rmclhip_status rmclhip_pf_sharded_set_particles(rmclhip_pf_sharded* h, const rmc
 
 // (re)create the cloud in place: every device fills its own block with the values of the GLOBAL particles lo_r .. hi_r - 1 (the random
 // words are a function of the global index: the single-device cloud bit for bit, no collective).  Every rank's launch is enqueued on
-// its collective stream before the host waits for any.  job: the pose form (null: uniform in [bb_min, bb_max]).
+// its collective stream before the host waits for any.  job: the pose form (null: uniform in [bb_min, bb_max]); on_surface: every
+// replica's surface sampler instead of either.
 static rmclhip_status pf_sharded_init_impl(rmclhip_pf_sharded* h, uint32_t n, const float* bb_min, const float* bb_max, const ParticlesPoseJob* job,
-                                           uint64_t seed, uint32_t epoch, const char* who) {
+                                           uint64_t seed, uint32_t epoch, const char* who, bool on_surface = false) {
   h->weights_fresh = false;
   const uint32_t world = static_cast<uint32_t>(h->ranks.size());
   const uint32_t cap = (n + world - 1u) / world;
@@ -562,7 +565,9 @@ static rmclhip_status pf_sharded_init_impl(rmclhip_pf_sharded* h, uint32_t n, co
     if (R.hi == R.lo) continue;
     HIPCHK(hipSetDevice(R.ctx->device));
     HIPCHK(hipDeviceSynchronize());   // the clears above ran on the null stream, which the collective streams do not wait for
-    if (job)
+    if (on_surface)
+      HIPCHK(launch_particles_init_surface(R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, surface_sample_view(R.sampler), seed, epoch, h->comm->streams[r]));
+    else if (job)
       HIPCHK(launch_particles_init_pose(R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, job->Tlm, job->L, seed, epoch, h->comm->streams[r]));
     else
       HIPCHK(launch_particles_init_uniform(R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, bb_min, bb_max, seed, epoch, h->comm->streams[r]));
@@ -703,6 +708,68 @@ rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* h, const rmclh
     if (rmclhip_status st = surface_params_check("pf_sharded_set_surface", params)) return st;
   for (PfRank& R : h->ranks)
     if (rmclhip_status st = rmclhip_pf_set_surface(R.pf, params)) return st;
+  return RMCLHIP_OK;
+}
+
+// ---- the surface sampler on the sharded cloud (capi_surface_sample.cpp / capi_particles.cpp have the single-device entry points) ----
+rmclhip_status rmclhip_pf_sharded_set_surface_sampler(rmclhip_pf_sharded* h, const rmclhip_surface_sample_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_surface_sampler");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_surface_sampler: null");
+  std::vector<rmclhip_surface_sampler*> fresh(h->ranks.size(), nullptr);
+  if (params) {
+    if (rmclhip_status st = surface_sample_params_check("pf_sharded_set_surface_sampler", params)) return st;
+    for (size_t r = 0; r < h->ranks.size(); ++r)
+      if (rmclhip_status st = rmclhip_surface_sampler_create(h->ranks[r].map, params, &fresh[r])) {   // the previous samplers stay
+        const std::string msg = g_err;
+        for (rmclhip_surface_sampler* sm : fresh) rmclhip_surface_sampler_destroy(sm);
+        return fail(st, msg);
+      }
+  }
+  for (size_t r = 0; r < h->ranks.size(); ++r) {
+    rmclhip_surface_sampler_destroy(h->ranks[r].sampler);
+    h->ranks[r].sampler = fresh[r];
+  }
+  return RMCLHIP_OK;
+}
+
+static rmclhip_status pf_sharded_need_samplers(rmclhip_pf_sharded* h, const std::string& who) {
+  for (PfRank& R : h->ranks)
+    if (!R.sampler) return fail(RMCLHIP_ERR_INVALID, who + ": no surface sampler is set (rmclhip_pf_sharded_set_surface_sampler)");
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_pf_sharded_init_surface(rmclhip_pf_sharded* h, uint32_t n, uint64_t seed, uint32_t epoch) {
+  ApiGuard guard_("rmclhip_pf_sharded_init_surface");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_init_surface: null");
+  if (rmclhip_status st = pf_sharded_need_samplers(h, "pf_sharded_init_surface")) return st;
+  if (rmclhip_status st = particles_range_check("pf_sharded_init_surface", 0u, n)) return st;
+  return pf_sharded_init_impl(h, n, nullptr, nullptr, nullptr, seed, epoch, "pf_sharded_init_surface", true);
+}
+
+// every replica replaces slots of its own block in place; the counts land in each sampler's pinned word and are summed here
+rmclhip_status rmclhip_pf_sharded_inject_surface(rmclhip_pf_sharded* h, double p_inject, uint64_t seed, uint32_t step, uint32_t* n_injected_out) {
+  ApiGuard guard_("rmclhip_pf_sharded_inject_surface");
+  if (n_injected_out) *n_injected_out = 0u;
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_inject_surface: null");
+  if (rmclhip_status st = pf_sharded_need_samplers(h, "pf_sharded_inject_surface")) return st;
+  unsigned long long threshold = 0ull;
+  if (rmclhip_status st = surface_inject_threshold("pf_sharded_inject_surface", p_inject, &threshold)) return st;
+  if (h->n_total == 0 || threshold == 0ull) return RMCLHIP_OK;
+  h->weights_fresh = false;
+  trace_mark("inject:");
+  for (uint32_t r = 0; r < h->ranks.size(); ++r) {   // every rank's launch is in flight before the host waits for any
+    PfRank& R = h->ranks[r];
+    *R.sampler->h_count = 0u;
+    if (R.hi == R.lo) continue;
+    HIPCHK(hipSetDevice(R.ctx->device));
+    if (rmclhip_status st = surface_inject_enqueue(R.sampler, R.d_poses, R.d_attrs, R.lo, R.hi - R.lo, threshold, seed, step, h->comm->streams[r]))
+      return st;
+    trace('E', r);
+  }
+  if (rmclhip_status st = comm_wait_all(h->comm)) return st;
+  uint32_t total = 0u;
+  for (PfRank& R : h->ranks) total += *R.sampler->h_count;
+  if (n_injected_out) *n_injected_out = total;
   return RMCLHIP_OK;
 }
 

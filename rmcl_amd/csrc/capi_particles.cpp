@@ -51,7 +51,7 @@ rmclhip_status rmclhip_chol6_host(const double* C, float* L_out, double* err_out
 }
 
 // ---- argument checks shared with the sharded entry points (capi_multi.cpp) -------------------------
-static rmclhip_status particles_range_check(const std::string& who, uint32_t first, uint32_t count) {
+RMCL_INTERNAL rmclhip_status particles_range_check(const std::string& who, uint32_t first, uint32_t count) {
   if (static_cast<uint64_t>(first) + count > (1ull << 32)) return fail(RMCLHIP_ERR_INVALID, who + ": first + count exceeds 2^32 (the particle index is a 32-bit counter word)");
   if (count > kMaxInitCount) return fail(RMCLHIP_ERR_UNSUPPORTED, who + ": more than 2^32 / 9 particles in one call");
   return RMCLHIP_OK;
@@ -80,7 +80,7 @@ RMCL_INTERNAL rmclhip_status particles_pose_check(const char* who_, uint32_t fir
   return RMCLHIP_OK;
 }
 
-static rmclhip_status particles_stream(rmclhip_ctx* ctx) {   // under ctx->part_mtx
+RMCL_INTERNAL rmclhip_status particles_stream(rmclhip_ctx* ctx) {   // under ctx->part_mtx
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->part_stream == nullptr) HIPCHK(hipStreamCreateWithFlags(&ctx->part_stream, hipStreamNonBlocking));
   return RMCLHIP_OK;
@@ -144,6 +144,50 @@ rmclhip_status rmclhip_particles_init_pose(rmclhip_ctx* ctx, rmclhip_transform* 
   HIPCHK(launch_particles_init_pose(reinterpret_cast<xform*>(poses_dev), attrs_dev, first, count, job.Tlm, job.L, seed, epoch, ctx->part_stream));
   HIPCHK(bracket_end_and_wait(ctx));
   if (chol_err_out) *chol_err_out = job.chol_err;
+  return RMCLHIP_OK;
+}
+
+// ---- on the surface: the initialisation and the recovery injection (the sampler: capi_surface_sample.cpp) ----
+static rmclhip_status surface_call_check(const std::string& who, const void* poses_dev, const void* attrs_dev, uint32_t first, uint32_t count) {
+  if (!poses_dev || !attrs_dev) return fail(RMCLHIP_ERR_INVALID, who + ": null particle buffers");
+  return particles_range_check(who, first, count);
+}
+
+rmclhip_status rmclhip_particles_init_surface(rmclhip_surface_sampler* sm, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                              uint32_t first, uint32_t count, uint64_t seed, uint32_t epoch) {
+  ApiGuard guard_("rmclhip_particles_init_surface");
+  if (!sm) return fail(RMCLHIP_ERR_INVALID, "particles_init_surface: null sampler");
+  if (count == 0) return RMCLHIP_OK;
+  if (rmclhip_status st = surface_call_check("particles_init_surface", poses_dev, attrs_dev, first, count)) return st;
+  rmclhip_ctx* ctx = sm->ctx;
+  std::lock_guard<std::mutex> lock(ctx->part_mtx);
+  if (rmclhip_status st = particles_stream(ctx)) return st;
+  HIPCHK(bracket_begin(ctx));
+  HIPCHK(launch_particles_init_surface(reinterpret_cast<xform*>(poses_dev), attrs_dev, first, count, surface_sample_view(sm), seed, epoch,
+                                       ctx->part_stream));
+  HIPCHK(bracket_end_and_wait(ctx));
+  return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_particles_inject_surface(rmclhip_surface_sampler* sm, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                                uint32_t first, uint32_t count, double p_inject, uint64_t seed, uint32_t step,
+                                                uint32_t* n_injected_out) {
+  ApiGuard guard_("rmclhip_particles_inject_surface");
+  if (n_injected_out) *n_injected_out = 0u;
+  if (!sm) return fail(RMCLHIP_ERR_INVALID, "particles_inject_surface: null sampler");
+  unsigned long long threshold = 0ull;
+  if (rmclhip_status st = surface_inject_threshold("particles_inject_surface", p_inject, &threshold)) return st;
+  if (count == 0) return RMCLHIP_OK;
+  if (rmclhip_status st = surface_call_check("particles_inject_surface", poses_dev, attrs_dev, first, count)) return st;
+  if (threshold == 0ull) return RMCLHIP_OK;
+  rmclhip_ctx* ctx = sm->ctx;
+  std::lock_guard<std::mutex> lock(ctx->part_mtx);
+  if (rmclhip_status st = particles_stream(ctx)) return st;
+  HIPCHK(bracket_begin(ctx));
+  if (rmclhip_status st = surface_inject_enqueue(sm, reinterpret_cast<xform*>(poses_dev), attrs_dev, first, count, threshold, seed, step, ctx->part_stream))
+    return st;
+  HIPCHK(bracket_end_and_wait(ctx));
+  if (n_injected_out) *n_injected_out = *sm->h_count;
   return RMCLHIP_OK;
 }
 

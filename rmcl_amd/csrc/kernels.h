@@ -457,6 +457,29 @@ hipError_t launch_particles_init_pose(xform* poses, void* attrs, uint32_t first,
 // out: 7 * n floats on the device: x | y | z | likelihood | likelihood_sigma | likelihood_n_meas | badness
 hipError_t launch_particles_pack_visualization(const xform* poses, const void* attrs, uint32_t n, uint32_t max_n_meas, float* out, hipStream_t s);
 
+// the surface sampler (include/rmclhip.h, SURFACE SAMPLER).  Build (surface_sample.hip, and the scan of resample.hip with a load of
+// its own): rec_of_face[f] = the lowest record index that carries face id f (all-ones on entry: integer atomicMin, independent of the
+// order); area[f] = a_f of an eligible face, -1 of any other; *amax_bits = the bits of the largest finite a_f > 0 (zero on entry:
+// positive doubles order as their bits, integer atomicMax); incl = the inclusive prefix sums of the integer weights.
+struct SurfaceSampleRule { float min_up_cos; float region_min[3], region_max[3]; };
+hipError_t launch_surface_sample_records(const uint32_t* tris, uint32_t n_records, uint32_t n_faces, uint32_t* rec_of_face, hipStream_t s);
+hipError_t launch_surface_sample_areas(const uint32_t* tris, const uint32_t* rec_of_face, uint32_t n_faces, const SurfaceSampleRule& rule,
+                                       double* area, unsigned long long* amax_bits, hipStream_t s);
+hipError_t launch_surface_sample_scan(const double* area, const unsigned long long* amax_bits, uint32_t n_faces, unsigned long long* incl,
+                                      unsigned long long* block_tot, hipStream_t s);
+// what a draw reads (surface_sample.hip.h); T = incl[n_faces - 1] > 0
+struct SurfaceSampleView {
+  const uint32_t* tris; const uint32_t* rec_of_face; const unsigned long long* incl;
+  uint32_t n_faces; unsigned long long T;
+  float height, yaw_min, yaw_max; uint32_t align;
+};
+// particles.hip: the initialisation on the surface (the contract of launch_particles_init_uniform) and the recovery injection in place:
+// slot first + k is replaced iff its 32-bit word < threshold (<= 2^32); *n_injected (device, zeroed by the caller) counts them
+hipError_t launch_particles_init_surface(xform* poses, void* attrs, uint32_t first, uint32_t count, const SurfaceSampleView& sv, uint64_t seed,
+                                         uint32_t epoch, hipStream_t s);
+hipError_t launch_particles_inject_surface(xform* poses, void* attrs, uint32_t first, uint32_t count, const SurfaceSampleView& sv,
+                                           unsigned long long threshold, uint64_t seed, uint32_t step, uint32_t* n_injected, hipStream_t s);
+
 // adaptive.hip: occupied bins of pose space (counts2 = {distinct bins, counted particles}, zeroed by the caller; table: table_words
 // 64-bit words, a power of two >= 2 n, all-ones on entry); resample.hip: systematic resampling -- the integer weights' inclusive
 // prefix sums (incl: n words, block_tot: ceil(n / 1024) words), then the slots [first, first + count) of the new cloud

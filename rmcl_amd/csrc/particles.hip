@@ -3,6 +3,8 @@
 //
 //   k_particles_init_uniform        RmclNode::initSamplesUniform (:277-342): every particle uniform in a 6-D box (x y z roll pitch yaw)
 //   k_particles_init_pose           RmclNode::initSamples (:165-275): x = L z around a pose guess, L L^T = the guess's covariance
+//   k_particles_init_surface        every particle on a drivable face of the map, uniform by area (include/rmclhip.h, SURFACE SAMPLER)
+//   k_particles_inject_surface      the recovery injection: a random fraction of a cloud replaced in place by such draws
 //   k_particles_pack_visualization  RmclNode::visualize (:797-879): x y z, likelihood {mean, sigma, n_meas}, badness as seven dense arrays
 //
 // One lane per particle.  The random words of particle i -- the GLOBAL index, `first` + the element of the buffer the launch was
@@ -17,6 +19,7 @@
 // of a cloud starts at first * 36 B: 4-B aligned only) and the up to three dwords on either side singly.
 #include "kernels.h"
 #include "pf_random.hip.h"
+#include "surface_sample.hip.h"
 
 namespace rmclhip {
 namespace {
@@ -62,11 +65,6 @@ __device__ __forceinline__ void init_words(uint32_t i, uint32_t epoch, uint32_t 
 
 struct UniformBox { float lo[6], hi[6]; };
 
-__device__ __forceinline__ float uniform_in(float lo, float hi, uint32_t w) {
-  const double u = (static_cast<double>(w) + 0.5) * (1.0 / 4294967296.0);
-  return static_cast<float>(static_cast<double>(lo) + (static_cast<double>(hi) - static_cast<double>(lo)) * u);   // lo == hi: lo exactly
-}
-
 __global__ void __launch_bounds__(kPartBlock) k_particles_init_uniform(xform* __restrict__ poses, uint32_t* __restrict__ attrs, uint32_t first,
                                                                        uint32_t count, UniformBox box, uint32_t key0, uint32_t key1,
                                                                        uint32_t epoch, uint32_t attr_lead) {
@@ -108,6 +106,53 @@ __global__ void __launch_bounds__(kPartBlock) k_particles_init_pose(xform* __res
   Pl.t = mk3(x[0], x[1], x[2]);
   Pl.stamp = 0u;
   store_pose(poses, k, xmul(in.Tlm, Pl));   // (stamp: Tlm's, as xmul hands it on)
+}
+
+// the surface sampler's draw (surface_sample.hip.h) of global particle first + k from draws 2 and 3 of the initialisers' stream
+__global__ void __launch_bounds__(kPartBlock) k_particles_init_surface(xform* __restrict__ poses, uint32_t* __restrict__ attrs, uint32_t first,
+                                                                       uint32_t count, SurfaceSampleView sv, uint32_t key0, uint32_t key1,
+                                                                       uint32_t epoch, uint32_t attr_lead) {
+  store_init_attrs(attrs, count, attr_lead);
+  const uint32_t k = blockIdx.x * kPartBlock + threadIdx.x;
+  if (k >= count) return;
+  uint32_t A[4], B[4];
+  philox4x32_10(first + k, epoch, 2u, 1u, key0, key1, A);
+  philox4x32_10(first + k, epoch, 3u, 1u, key0, key1, B);
+  store_pose(poses, k, surface_sample_pose(sv, A, B));
+}
+
+// the recovery injection, in place: slot j = first + k is replaced iff the first word of draw 9 of the resamplers' stream lies below
+// the threshold; its pose is the sampler's draw from draws 10 and 11, its attributes the initialisations'.  A slot that stays is not
+// read and not written.  The replaced records are scattered: a lane stores the nine dwords of its own (4-B aligned) record.
+__global__ void __launch_bounds__(kPartBlock) k_particles_inject_surface(xform* __restrict__ poses, uint32_t* __restrict__ attrs, uint32_t first,
+                                                                         uint32_t count, SurfaceSampleView sv, unsigned long long threshold,
+                                                                         uint32_t key0, uint32_t key1, uint32_t step,
+                                                                         uint32_t* __restrict__ n_injected) {
+  const uint32_t k = blockIdx.x * kPartBlock + threadIdx.x;
+  bool replace = false;
+  if (k < count) {
+    uint32_t r[4];
+    philox4x32_10(first + k, step, 9u, 0u, key0, key1, r);
+    replace = static_cast<unsigned long long>(r[0]) < threshold;
+  }
+  // the count: one atomic per workgroup (one per wave to a single address is what a launch over a million slots then waits for)
+  static_assert(kPartBlock == 256u, "four waves of 64 lanes: the sum below names them");
+  __shared__ uint32_t s_count[4];
+  const uint64_t m = __ballot(replace);
+  if ((threadIdx.x & 63u) == 0u) s_count[threadIdx.x >> 6] = static_cast<uint32_t>(__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    const uint32_t c = (s_count[0] + s_count[1]) + (s_count[2] + s_count[3]);
+    if (c) atomicAdd(n_injected, c);
+  }
+  if (!replace) return;
+  uint32_t A[4], B[4];
+  philox4x32_10(first + k, step, 10u, 0u, key0, key1, A);
+  philox4x32_10(first + k, step, 11u, 0u, key0, key1, B);
+  store_pose(poses, k, surface_sample_pose(sv, A, B));
+  uint32_t* a = attrs + static_cast<size_t>(k) * kAttrDwords;
+#pragma unroll
+  for (uint32_t j = 0; j < kAttrDwords; ++j) a[j] = init_attr_dword(j);
 }
 
 // out: seven arrays of n floats: x | y | z | likelihood | likelihood_sigma | likelihood_n_meas | badness
@@ -158,6 +203,28 @@ hipError_t launch_particles_init_pose(xform* poses, void* attrs, uint32_t first,
   hipLaunchKernelGGL(k_particles_init_pose, dim3((count + kPartBlock - 1u) / kPartBlock), dim3(kPartBlock), 0, s, poses,
                      static_cast<uint32_t*>(attrs), first, count, in, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), epoch,
                      lead_dwords(attrs));
+  return hipGetLastError();
+}
+
+hipError_t launch_particles_init_surface(xform* poses, void* attrs, uint32_t first, uint32_t count, const SurfaceSampleView& sv, uint64_t seed,
+                                         uint32_t epoch, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  if (count > kMaxInitCount || (reinterpret_cast<uintptr_t>(poses) & 15u) || (reinterpret_cast<uintptr_t>(attrs) & 3u) || sv.n_faces == 0 || sv.T == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_particles_init_surface, dim3((count + kPartBlock - 1u) / kPartBlock), dim3(kPartBlock), 0, s, poses,
+                     static_cast<uint32_t*>(attrs), first, count, sv, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), epoch,
+                     lead_dwords(attrs));
+  return hipGetLastError();
+}
+
+hipError_t launch_particles_inject_surface(xform* poses, void* attrs, uint32_t first, uint32_t count, const SurfaceSampleView& sv,
+                                           unsigned long long threshold, uint64_t seed, uint32_t step, uint32_t* n_injected, hipStream_t s) {
+  if (count == 0 || threshold == 0) return hipSuccess;
+  if (count > kMaxInitCount || (reinterpret_cast<uintptr_t>(poses) & 15u) || (reinterpret_cast<uintptr_t>(attrs) & 3u) || sv.n_faces == 0 || sv.T == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_particles_inject_surface, dim3((count + kPartBlock - 1u) / kPartBlock), dim3(kPartBlock), 0, s, poses,
+                     static_cast<uint32_t*>(attrs), first, count, sv, threshold, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
+                     step, n_injected);
   return hipGetLastError();
 }
 

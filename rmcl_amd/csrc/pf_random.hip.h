@@ -4,8 +4,11 @@
 //
 // Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
 //   stream 0: the resamplers   (champion or slot index, step, draw 0..7: gladiator 0 1, residual 2 3 4, systematic 5 6 7;
-//                               particle index, step + iteration, draw 8: the Stein step's thinning of full bins, stein.hip)
-//   stream 1: the initialisers (global particle index, epoch, draw 0..1)
+//                               particle index, step + iteration, draw 8: the Stein step's thinning of full bins, stein.hip;
+//                               slot index, step, draw 9 10 11: the recovery injection -- 9 decides whether the slot is replaced,
+//                               10 and 11 are the surface sampler's two blocks, particles.hip)
+//   stream 1: the initialisers (global particle index, epoch, draw 0..1: uniform and pose + covariance; draw 2 3: the surface
+//                               sampler's two blocks of the initialisation on the surface)
 // reproducible, independent of the launch shape and of how the particle range is sharded across GPUs.  Transcendentals are evaluated in
 // double and rounded to float (see oracle).
 #pragma once
@@ -32,6 +35,12 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   const double r = sqrt(-2.0 * log(u1)), ang = 6.283185307179586476925 * u2;
   z0 = static_cast<float>(r * cos(ang));
   z1 = static_cast<float>(r * sin(ang));
+}
+
+// a uniform draw in [lo, hi] from one word: the initialisations' box (particles.hip) and the surface sampler's yaw (surface_sample.hip.h)
+__device__ __forceinline__ float uniform_in(float lo, float hi, uint32_t w) {
+  const double u = (static_cast<double>(w) + 0.5) * (1.0 / 4294967296.0);
+  return static_cast<float>(static_cast<double>(lo) + (static_cast<double>(hi) - static_cast<double>(lo)) * u);   // lo == hi: lo exactly
 }
 
 // rmagine Quaternion <- EulerAngles (ZYX): cos / sin of the float half angles in double, rounded to float, then float products

@@ -8,8 +8,9 @@
 //                          tests/adaptive_ref.py restates them in numpy): slot j reads position pos_j of [0, T), T = C[n-1]; its source
 //                          is the first i with C[i] > pos_j.  The first slot of a run of equal sources is a copy, every further one is
 //                          perturbed as the gladiator perturbs a winning enemy.
-//   k_scan_*               inclusive 64-bit prefix sums, ONE text for the residual resampler's copy counts and the systematic
-//                          resampler's integer weights w_i = rint(L_i / max * 2^24).  Integers: exact, independent of the launch shape.
+//   k_scan_*               inclusive 64-bit prefix sums, ONE text for the residual resampler's copy counts, the systematic
+//                          resampler's integer weights w_i = rint(L_i / max * 2^24) and the surface sampler's face weights
+//                          w_f = rint(a_f / a_max * 2^32).  Integers: exact, independent of the launch shape.
 //
 // A "perturbed copy" is ONE text too (six_gaussians .. remember_rate_*): the kernels differ in which Philox words feed the Gaussians,
 // where the six noise scales come from and the rule that turns the two distances into a rate.  Random stream = Philox4x32-10 keyed by
@@ -294,6 +295,15 @@ struct ScanWeights {   // ... the systematic resampler's integer weights (sys_we
   double max_l;
   __device__ __forceinline__ unsigned long long operator()(unsigned long long i) const { return sys_weight(attrs[i].mean, max_l); }
 };
+struct ScanFaceAreas {   // ... the surface sampler's integer weights w_f = uint64(rint(a_f / a_max * 2^32)); a_f <= a_max: w_f <= 2^32
+  const double* __restrict__ area;               // a_f of an eligible face, -1 of any other (surface_sample.hip)
+  const unsigned long long* __restrict__ amax_bits;
+  __device__ __forceinline__ unsigned long long operator()(unsigned long long i) const {
+    const double a = area[i], a_max = __longlong_as_double(static_cast<long long>(*amax_bits));
+    if (!(a > 0.0) || !(a <= a_max)) return 0ull;   // not eligible, zero, NaN or +inf (a_max is the largest FINITE area)
+    return static_cast<unsigned long long>(rint(a / a_max * 4294967296.0));
+  }
+};
 
 template <typename Load>
 __global__ void __launch_bounds__(kBlock) k_scan_blocks(Load load, uint32_t n, unsigned long long* __restrict__ incl,
@@ -487,6 +497,14 @@ hipError_t launch_sys_scan(const void* attrs, uint32_t n, double max_l, unsigned
 hipError_t launch_scan_counts(const uint32_t* counts, uint32_t n, unsigned long long* incl, unsigned long long* block_tot, hipStream_t s) {
   if (n == 0) return hipSuccess;
   launch_scan(ScanCounts{counts}, n, incl, block_tot, true, s);
+  return hipGetLastError();
+}
+
+// ... and over the surface sampler's face weights: all three passes whatever n_faces is
+hipError_t launch_surface_sample_scan(const double* area, const unsigned long long* amax_bits, uint32_t n_faces, unsigned long long* incl,
+                                      unsigned long long* block_tot, hipStream_t s) {
+  if (n_faces == 0) return hipSuccess;
+  launch_scan(ScanFaceAreas{area, amax_bits}, n_faces, incl, block_tot, false, s);
   return hipGetLastError();
 }
 

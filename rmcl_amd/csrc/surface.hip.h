@@ -7,6 +7,7 @@
 // the one tests/surface_ref.py performs, in its order (-ffp-contract=off: no contraction).
 #pragma once
 #include "pf_common.hip.h"
+#include "surface_align.hip.h"
 
 namespace rmclhip {
 namespace {
@@ -26,12 +27,6 @@ __device__ __forceinline__ f3 surface_axis(const SurfaceKernelParams& sp, const 
 __device__ __forceinline__ f3 surface_origin(const SurfaceKernelParams& sp, const xform& T, f3 a) {
   const f3 c = mk3(T.t.x - sp.height * a.x, T.t.y - sp.height * a.y, T.t.z - sp.height * a.z);
   return mk3(c.x + sp.probe_up * a.x, c.y + sp.probe_up * a.y, c.z + sp.probe_up * a.z);
-}
-
-__device__ __forceinline__ quat surface_qnormalise(quat q) {
-  const float nrm = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-  quat r; r.x = q.x / nrm; r.y = q.y / nrm; r.z = q.z / nrm; r.w = q.w / nrm;
-  return r;
 }
 
 // The probe of one particle.  `live`: the lane has a particle; every lane of the wave must call (the traversal votes).  pose is
@@ -57,18 +52,7 @@ __device__ __forceinline__ uint32_t surface_constrain_lane(const uint32_t* __res
   if (!(d >= sp.min_up_cos)) return kSurfSteep;
   const f3 p = mk3(O.x + D.x * h.t, O.y + D.y * h.t, O.z + D.z * h.t);
   pose.t = mk3(p.x + sp.height * a.x, p.y + sp.height * a.y, p.z + sp.height * a.z);
-  if (sp.align != 0u) {
-    const f3 zb = qrot(pose.R, mk3(0.0f, 0.0f, 1.0f));
-    quat q;
-    q.w = 1.0f + ((zb.x * n.x + zb.y * n.y) + zb.z * n.z);
-    if (q.w < 1e-6f) {
-      const f3 xb = qrot(pose.R, mk3(1.0f, 0.0f, 0.0f));   // upside down: the half turn about the body's x
-      q.x = xb.x; q.y = xb.y; q.z = xb.z; q.w = 0.0f;
-    } else {
-      q.x = zb.y * n.z - zb.z * n.y; q.y = zb.z * n.x - zb.x * n.z; q.z = zb.x * n.y - zb.y * n.x;
-    }
-    pose.R = surface_qnormalise(qmul(surface_qnormalise(q), pose.R));
-  }
+  if (sp.align != 0u) pose.R = surface_align(pose.R, n);
   return kSurfSnap;
 }
 

@@ -86,6 +86,92 @@ def init_particles_pose(ctx, poses, attrs, pose, covariance, seed, epoch=0, firs
     return err.value
 
 
+def surface_sample_params(**kwargs):
+    """rmclhip_surface_sample_params with the library's defaults (min_up_cos 0.7, height 0, align 0, region unbounded, yaw in
+    [-pi, pi]); keyword arguments replace fields (region_min / region_max: three floats)"""
+    p = _capi.SurfaceSampleParams()
+    _capi.lib().rmclhip_surface_sample_params_default(C.byref(p))
+    for k, v in kwargs.items():
+        if k in ("region_min", "region_max"):
+            setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]))
+        elif k == "align":
+            p.align = int(v)
+        elif hasattr(p, k):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError("surface_sample_params: unknown field %r" % k)
+    return p
+
+
+class SurfaceSamplerHip:
+    """Poses drawn uniformly by area on the drivable faces of a map (rmclhip_surface_sampler): the global initialisation of a ground
+    robot and the fresh draws of the recovery injection.  Built once per (map, parameters); keeps the map alive."""
+
+    def __init__(self, hip_map, params=None, **kwargs):
+        self.map = hip_map
+        self.params = surface_sample_params(**kwargs) if params is None else params
+        self._h = C.c_void_p()
+        _capi.check(_capi.lib().rmclhip_surface_sampler_create(hip_map.handle, C.byref(self.params), C.byref(self._h)))
+
+    def info(self):
+        """{n_faces, n_eligible, n_weighted, area_eligible, weight_total}"""
+        out = _capi.SurfaceSampleInfo()
+        _capi.check(_capi.lib().rmclhip_surface_sampler_get_info(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def init(self, poses, attrs, seed, epoch=0, first=0, count=None):
+        """rmclhip_particles_init_surface: poses / attrs (device views of `count` particles, default all of `poses`) receive the GLOBAL
+        particles first .. first+count-1 of the cloud (seed, epoch) selects, likelihood {1, 0, 0}"""
+        _capi.check(_capi.lib().rmclhip_particles_init_surface(self._h, _as_ptr(poses), _as_ptr(attrs), int(first),
+                                                               _count_of(poses, first, count), int(seed), int(epoch)))
+
+    def inject(self, poses, attrs, p, seed, step, first=0, count=None):
+        """rmclhip_particles_inject_surface: every slot of the cloud is replaced with probability p by a fresh draw, in place;
+        returns how many were"""
+        n = C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_particles_inject_surface(self._h, _as_ptr(poses), _as_ptr(attrs), int(first),
+                                                                 _count_of(poses, first, count), float(p), int(seed), int(step),
+                                                                 C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            _capi.lib().rmclhip_surface_sampler_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def init_particles_surface(sampler, poses, attrs, seed, epoch=0, first=0, count=None):
+    """the third initialisation, beside init_particles_uniform and init_particles_pose: every particle on a drivable face of the map,
+    uniform by area (SurfaceSamplerHip.init)"""
+    sampler.init(poses, attrs, seed, epoch=epoch, first=first, count=count)
+
+
+class RecoveryHip:
+    """The augmented-MCL recovery rule as AMCL runs it (rmclhip_recovery_update_host, a host function): a slow and a fast running
+    average of the cloud's mean likelihood; update() returns the fraction of the cloud to replace by fresh draws, reset() is called
+    after an injection.  The defaults are AMCL's recovery_alpha_slow / recovery_alpha_fast."""
+
+    def __init__(self, alpha_slow=0.001, alpha_fast=0.1, p_max=1.0):
+        self.params = _capi.RecoveryParams(float(alpha_slow), float(alpha_fast), float(p_max))
+        self.state = _capi.RecoveryState(0.0, 0.0)
+
+    def update(self, stats, n):
+        """stats: {"sum": ...} of the cloud's likelihoods (compute_stats), or the sum itself; n: the particles it covers"""
+        total = stats["sum"] if isinstance(stats, dict) else stats
+        p = C.c_double(0.0)
+        _capi.check(_capi.lib().rmclhip_recovery_update_host(C.byref(self.state), C.byref(self.params), float(total), int(n), C.byref(p)))
+        return p.value
+
+    def reset(self):
+        _capi.check(_capi.lib().rmclhip_recovery_reset_host(C.byref(self.state)))
+
+
 VISUALIZATION_CHANNELS = ("x", "y", "z", "likelihood", "likelihood_sigma", "likelihood_n_meas", "badness")
 
 
@@ -464,10 +550,26 @@ class AdaptiveResamplerHip(GladiatorResamplerHip):
         self.step += 1
         return {"n_particles": int(count)}
 
-    def update(self, particle_poses, particle_attrs, particle_poses_new, particle_attrs_new, n_particles, capacity_new=None):
+    def update(self, particle_poses, particle_attrs, particle_poses_new, particle_attrs_new, n_particles, capacity_new=None,
+               recovery=None, sampler=None):
         """Resampler::update with a count of its own: particle_*_new (room for capacity_new particles, default n_particles) receive
-        n_new particles; returns {"n_particles": n_new, "bins": k} (rmclhip_resampler_adaptive)."""
+        n_new particles; returns {"n_particles": n_new, "bins": k} (rmclhip_resampler_adaptive).
+        recovery= (a RecoveryHip) with sampler= (a SurfaceSamplerHip): the likelihood statistics of the old cloud feed the recovery
+        averages, and after the resampler the fraction they ask for is replaced in the new cloud by fresh draws from the sampler
+        (same seed and step); the averages are reset when anything was injected.  The dict then also holds "injected" and
+        "p_inject"."""
+        if (recovery is None) != (sampler is None):
+            raise ValueError("AdaptiveResamplerHip.update: recovery= and sampler= come as a pair")
         self.init()
+        if recovery is not None:
+            p_inject = recovery.update(self.compute_stats(particle_attrs, n_particles), n_particles)
+            step = self.step
+            out = self.update(particle_poses, particle_attrs, particle_poses_new, particle_attrs_new, n_particles, capacity_new)
+            out["injected"] = sampler.inject(particle_poses_new, particle_attrs_new, p_inject, self.seed, step, count=out["n_particles"])
+            out["p_inject"] = p_inject
+            if out["injected"]:
+                recovery.reset()
+            return out
         cap = int(n_particles if capacity_new is None else capacity_new)
         n_new, k = C.c_uint32(0), C.c_uint32(0)
         _capi.check(_capi.lib().rmclhip_resampler_adaptive(
@@ -589,6 +691,27 @@ class ShardedParticleFilterHip:
         _capi.check(_capi.lib().rmclhip_pf_sharded_init_pose(self._h, int(n), _ptr(T), _ptr(cov), int(seed), int(epoch), C.byref(err)))
         self.n_total = int(n)
         return err.value
+
+    def set_surface_sampler(self, params=None, **kwargs):
+        """one surface sampler per map replica (rmclhip_pf_sharded_set_surface_sampler): params (surface_sample_params()), or the
+        library's defaults with the keyword arguments replacing fields"""
+        p = surface_sample_params(**kwargs) if params is None else params
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_surface_sampler(self._h, C.byref(p)))
+
+    def drop_surface_sampler(self):
+        """take the replicas' samplers off (the C ABI's NULL)"""
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_surface_sampler(self._h, None))
+
+    def init_surface(self, n, seed, epoch=0):
+        """(re)create the cloud on the surface: every device fills its own block (rmclhip_pf_sharded_init_surface)"""
+        _capi.check(_capi.lib().rmclhip_pf_sharded_init_surface(self._h, int(n), int(seed), int(epoch)))
+        self.n_total = int(n)
+
+    def inject_surface(self, p, seed, step):
+        """the recovery injection on every device's block; returns the replaced slots (rmclhip_pf_sharded_inject_surface)"""
+        n = C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_pf_sharded_inject_surface(self._h, float(p), int(seed), int(step), C.byref(n)))
+        return int(n.value)
 
     def download(self):
         from .types import PARTICLE_ATTRIBUTES
