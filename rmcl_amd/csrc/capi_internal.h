@@ -16,13 +16,14 @@
 //   capi_surface_sample.cpp the surface sampler: parameters, the build of the face weights, info; the recovery averages (host) (kernels: surface_sample.hip, the scan of resample.hip)
 //   capi_hypotheses.cpp the single-device pose estimate and the pose hypotheses: clusters of the occupied bins (kernels: hypotheses.hip)
 //   capi_pose_information.cpp the point-to-plane information matrix of a find's correspondences and its host algebra: covariance, degeneracy (kernels: pose_information.hip)
-//   capi_multi.cpp     several devices in one process: sharded pose batches, communicators (RCCL / loopback), the sharded filter
+//   several devices in one process (what the three share: multi_internal.h):
+//   capi_comm.cpp      communicators (RCCL resolved with dlopen / the in-process loopback), their two collectives, the debug trace of the sharded entry points
+//   capi_rcc_sharded.cpp pose batches sharded over one operator replica per device (no collective)
+//   capi_pf_sharded.cpp the sharded particle filter: one filter replica per device, every sharded twin of a single-device entry point
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
 // entry point fails with RMCLHIP_ERR_NO_DEVICE.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types only: the library is resolved with dlopen when the first communicator is created
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
@@ -123,6 +124,27 @@ struct DevBuf {
   }
   void release() {
     if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// its pinned host counterpart (hipHostMallocDefault): staging a device copies into and the host reads.  (Hidden members: an out-of-line
+// copy of a header template's member is otherwise an exported weak symbol of the library.)
+template <typename T>
+struct PinnedBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // elements
+  RMCL_INTERNAL hipError_t reserve(size_t n) {
+    if (n <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) cap = n;
+    else p = nullptr;
+    return e;
+  }
+  RMCL_INTERNAL void release() {
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
   }
@@ -676,7 +698,6 @@ RMCL_INTERNAL SurfaceSampleView surface_sample_view(const rmclhip_surface_sample
 RMCL_INTERNAL rmclhip_status surface_inject_threshold(const std::string& who, double p_inject, unsigned long long* out);
 RMCL_INTERNAL rmclhip_status surface_inject_enqueue(rmclhip_surface_sampler* sm, xform* poses, void* attrs, uint32_t first, uint32_t count,
                                                     unsigned long long threshold, uint64_t seed, uint32_t step, hipStream_t s);
-extern RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries;   // capi_rcc.cpp: polls that met their sequence number before the checksum matched
 // capi_surface.cpp: the surface constraint's argument check, and the two launches on f->stream with the copy of their class counts to
 // f->h_surf behind them (no wait).  pf_motion_enqueue: the motion update of the handle, constrained when rmclhip_pf_set_surface says so.
 RMCL_INTERNAL rmclhip_status surface_params_check(const char* who, const rmclhip_surface_params* p);

@@ -50,7 +50,7 @@ rmclhip_status rmclhip_chol6_host(const double* C, float* L_out, double* err_out
   return RMCLHIP_OK;
 }
 
-// ---- argument checks shared with the sharded entry points (capi_multi.cpp) -------------------------
+// ---- argument checks shared with the sharded entry points (capi_pf_sharded.cpp) -------------------------
 RMCL_INTERNAL rmclhip_status particles_range_check(const std::string& who, uint32_t first, uint32_t count) {
   if (static_cast<uint64_t>(first) + count > (1ull << 32)) return fail(RMCLHIP_ERR_INVALID, who + ": first + count exceeds 2^32 (the particle index is a 32-bit counter word)");
   if (count > kMaxInitCount) return fail(RMCLHIP_ERR_UNSUPPORTED, who + ": more than 2^32 / 9 particles in one call");

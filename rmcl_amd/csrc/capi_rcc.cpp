@@ -506,7 +506,13 @@ static inline uint32_t xor_host(const void* p, size_t bytes) {
 }
 // how often a poller saw ITS sequence number in the tag while the result words did not (yet) add up to the tag's sum: the event the
 // checksum exists for (rmclhip_debug_tag_retries; profiles/r05_tag_handoff.txt)
-RMCL_INTERNAL std::atomic<unsigned long long> g_tag_sum_retries{0};
+static std::atomic<unsigned long long> g_tag_sum_retries{0};
+
+rmclhip_status rmclhip_debug_tag_retries(unsigned long long* retries_out) {
+  if (!retries_out) return fail(RMCLHIP_ERR_INVALID, "debug_tag_retries: null");
+  *retries_out = g_tag_sum_retries.load();
+  return RMCLHIP_OK;
+}
 
 RMCL_INTERNAL uint32_t next_seq(rmclhip_rcc* r) {
   if (++r->done_seq == 0u) r->done_seq = 1u;

@@ -1,5 +1,5 @@
 // pose_estimate_host.h -- the host side of RmclNode::estimateStats (rmcl_localization.cpp:642-731), shared by every entry point that
-// fills a rmclhip_pose_estimate: the sharded filter's (capi_multi.cpp), the single-device one and the per-hypothesis one
+// fills a rmclhip_pose_estimate: the sharded filter's (capi_pf_sharded.cpp), the single-device one and the per-hypothesis one
 // (capi_hypotheses.cpp).  The three moment passes (kernels.hip: k_pose_moments) are the caller's: a callable
 //   moments(int pass, double L_sum, const xform& Tbm, double* out32) -> rmclhip_status
 // that leaves the 24 sums + 8 maxima of one pass over ITS particles in out32.  Everything else -- the likelihood statistics, the
