@@ -330,7 +330,8 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2(rmclhip_rcc* rcc, const uint8_t
  *   3. range_est = sqrtf((x*x + y*y) + z*z) of ps; theta_est = (float)atan2((double)y, (double)x);
  *      phi_est = (float)atan2((double)z, (double)range_est)  -- the reference's rule; it is atan(sin(elevation)), see TRUE_ELEVATION
  *   4. id = (int)(((est - min) / inc) + 0.5): the quotient in float, + 0.5 in double, truncated toward zero, compared in double with
- *      [0, size) (NaN rejects).  inc == 0 is accepted for size == 1 only: every point then has id 0 on that axis
+ *      [0, size) (NaN rejects).  inc == 0 is accepted for size == 1 only: every point then has id 0 on that axis.  A negative inc is
+ *      accepted as it is: ids count from min DOWNWARD (phi.min > 0 with phi.inc < 0: row 0 is the top row), nothing is refused
  *   5. a point inside the image with range_est inside [range.min, range.max] is a candidate of cell phi_id * W + theta_id; the
  *      candidate with the LARGEST i wins (the reference's sequential overwrite)
  *   6. ranges[cell] = the winner's range_est, or (float)((double)range.max + 1.0) for a cell nobody hit

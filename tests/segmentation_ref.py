@@ -12,7 +12,8 @@ The rule is the per-scan body of the reference's ScanMapSegmentationEmbreeNode /
     sim only:     outlier_map gets dir * r_sim + orig
     neither:      nothing
 
-Labels: 0 none, 1 inlier, 2 outlier_scan, 3 outlier_map; the clouds are in buffer order.  Also here: the two test scenes of the GPU
+Labels: 0 none, 1 inlier, 2 outlier_scan, 3 outlier_map; the clouds are in buffer order.  segment_f32 is the same rule in the kernels'
+own float32 operations and order, for tests/test_gpu_segmentation_exact.py, which compares bits.  Also here: the two test scenes of the GPU
 tests (meshes, poses, the doctored "real" scans), built from rmcl_amd.synthetic and the oracle alone.
 """
 import numpy as np
@@ -54,6 +55,60 @@ def segment(r_real, r_sim, normals_sim, dirs, origs, range_min, range_max, min_d
     map_pts = np.where(real_ok[:, None], pint_both, pint_o)
     return dict(labels=labels, outlier_scan=preal[labels == OUTLIER_SCAN], outlier_map=map_pts[labels == OUTLIER_MAP],
                 preal=preal, map_points=map_pts)
+
+
+def pinhole_dirs_f32(width, height, fx, fy, cx, cy):
+    """segment.hip seg_pinhole_direction in float32 numpy, buffer order (vid * width + hid)"""
+    f = np.float32
+    vid, hid = np.meshgrid(np.arange(height, dtype=np.float32), np.arange(width, dtype=np.float32), indexing="ij")
+    pX = ((hid - f(cx)) / f(fx)).astype(np.float32)
+    pY = ((vid - f(cy)) / f(fy)).astype(np.float32)
+    d = np.sqrt((pX * pX + pY * pY) + f(1.0) * f(1.0)).astype(np.float32)
+    return np.stack([f(1.0) / d, -(pX / d), -(pY / d)], -1).astype(np.float32).reshape(-1, 3)
+
+
+def segment_f32(r_real, r_sim, normals_sim, dirs, origs, range_min, range_max, min_dist_outlier_scan=0.15, min_dist_outlier_map=0.15,
+                pint_with_origin=False, add_origin=False):
+    """segment.hip's k_segment_classify and the two cloud points of k_segment_scatter in float32, one IEEE operation per step in the
+    kernel's order (devmath.h: scale3 = (a.x * s, a.y * s, a.z * s), add3 / sub3 componentwise, dot_plain = (a.x * b.x + a.y * b.y) +
+    a.z * b.z; the library is built with -ffp-contract=off, float divide and sqrt are correctly rounded).  add_origin: the model is O1Dn
+    or OnDn -- seg_point adds an origin for these two only.  -> dict(labels uint8, outlier_scan, outlier_map (k, 3) float32 in buffer
+    order, plane (n,) float32: plane_distance where both ranges are inside the interval, NaN elsewhere)."""
+    f = np.float32
+    r_real = np.asarray(r_real, f).reshape(-1)
+    r_sim = np.asarray(r_sim, f).reshape(-1)
+    n = len(r_real)
+    d = np.asarray(dirs, f).reshape(n, 3)
+    o = np.broadcast_to(np.asarray(origs, f).reshape(-1, 3), (n, 3))
+    nr = np.asarray(normals_sim, f).reshape(n, 3)
+    lo, hi, thr_scan, thr_map = f(range_min), f(range_max), f(min_dist_outlier_scan), f(min_dist_outlier_map)
+
+    def point(r, with_origin):
+        pt = (d * r[:, None]).astype(f)                                  # scale3(dir, r)
+        return (pt + o).astype(f) if (with_origin and add_origin) else pt
+
+    with np.errstate(all="ignore"):
+        real_ok = (lo <= r_real) & (r_real <= hi)
+        sim_ok = (lo <= r_sim) & (r_sim <= hi)
+        preal = point(r_real, True)
+        pint = point(r_sim, bool(pint_with_origin))
+        nn = ((nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]).astype(f) + nr[:, 2] * nr[:, 2]).astype(f)
+        inv = (f(1.0) / np.sqrt(nn).astype(f)).astype(f)
+        unit = (nr * inv[:, None]).astype(f)
+        df = (preal - pint).astype(f)
+        plane = np.abs(((df[:, 0] * unit[:, 0] + df[:, 1] * unit[:, 1]).astype(f) + df[:, 2] * unit[:, 2]).astype(f))
+        both = real_ok & sim_ok
+        front = r_real < r_sim
+        labels = np.zeros(n, np.uint8)
+        labels[both] = INLIER
+        labels[both & front & (plane > thr_scan)] = OUTLIER_SCAN
+        labels[both & ~front & (plane > thr_map)] = OUTLIER_MAP
+        labels[real_ok & ~sim_ok] = OUTLIER_SCAN
+        labels[~real_ok & sim_ok] = OUTLIER_MAP
+        # k_segment_scatter: preal_s for a scan outlier; for a map outlier dir * r_sim, with the origin if the measured range is invalid
+        map_pts = np.where(real_ok[:, None], pint, point(r_sim, True))
+    return dict(labels=labels, outlier_scan=preal[labels == OUTLIER_SCAN], outlier_map=map_pts[labels == OUTLIER_MAP],
+                plane=np.where(both, plane, f(np.nan)).astype(f))
 
 
 def undecided(r_real, r_sim, normals_sim, dirs, origs, range_min, range_max, **kw):
