@@ -104,6 +104,11 @@ rmclhip_status rmclhip_debug_particles_timing(rmclhip_ctx* ctx, int on, float* l
  * three floats) receives the phases of the last call made while it was on (0 before any).  Off by default.  Works without the
  * experiments library. */
 rmclhip_status rmclhip_debug_stein_timing(rmclhip_pf* pf, int on, float* last_ms3);
+/* TEST aid of the handles' lifecycles (tests/test_gpu_lifecycle.py): the bytes of device memory and of pinned or host-mapped memory the
+ * library's handles hold in this process right now, over every device (memory handed out by rmclhip_malloc is the caller's and is not
+ * counted).  Two relaxed atomic counters kept where the library allocates and frees, which no per-call path does.  Destroying every
+ * handle a piece of code made brings both back to what they were before it.  Exported by librmclhip.so; null: RMCLHIP_ERR_INVALID. */
+rmclhip_status rmclhip_debug_live_bytes(uint64_t* device_bytes, uint64_t* host_bytes);
 
 /* TEST hook of the rotation solve (tests/test_gpu_umeyama.py): out_host[i] = the solve of stats_host[i] by solver 0 = umeyama() on the
  * host (what rmclhip_umeyama_transform calls; ctx may be null), 1 = umeyama() on the device, 2 = umeyama_fast() on the device (the

@@ -437,6 +437,7 @@ SIGNATURES = {
     "rmclhip_debug_trace": (_i32, [_i32, _vp, _sz]),
     "rmclhip_debug_particles_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
     "rmclhip_debug_stein_timing": (_i32, [_vp, _i32, C.POINTER(_f32)]),
+    "rmclhip_debug_live_bytes": (_i32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rmclhip_debug_solve": (_i32, [_vp, _vp, _u32, _i32, _vp]),
     "rmclhip_comm_destroy": (None, [_vp]),
     "rmclhip_comm_size": (_u32, [_vp]),

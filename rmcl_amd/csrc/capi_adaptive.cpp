@@ -47,9 +47,9 @@ rmclhip_status kld_bins_check(const char* who_, const rmclhip_kld_params* p) {
 // {sum, max} of the likelihoods on the resampler's stream, landed on the host
 rmclhip_status resampler_stats(rmclhip_resampler* r, const rmclhip_particle_attributes* attrs_dev, uint32_t n, float* max_out) {
   HIPCHK(launch_likelihood_stats(attrs_dev, n, r->d_psum.p, r->d_pmax.p, r->d_out.p, r->stream));
-  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipMemcpyAsync(r->h_out.p, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
-  *max_out = r->h_out[1];
+  *max_out = r->h_out.p[1];
   return RMCLHIP_OK;
 }
 
@@ -64,7 +64,7 @@ rmclhip_status count_bins_run(rmclhip_resampler* r, const rmclhip_transform* pos
   const float floor_l = p->min_likelihood_rel * max_l;
   HIPCHK(launch_kld_count_bins(reinterpret_cast<const xform*>(poses_dev), attrs_dev, n, p->bin_xyz, p->bin_rpy, floor_l, r->d_kld_table.p, words,
                                r->d_kld_cnt.p, r->stream));
-  uint32_t* h_cnt = reinterpret_cast<uint32_t*>(&r->h_res[5]);
+  uint32_t* h_cnt = reinterpret_cast<uint32_t*>(&r->h_res.p[5]);
   HIPCHK(hipMemcpyAsync(h_cnt, r->d_kld_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
   *k_out = h_cnt[0];

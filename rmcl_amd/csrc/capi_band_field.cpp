@@ -67,8 +67,8 @@ static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
   hipStream_t s = fd->stream;
   uint32_t *rec16 = nullptr, *rec8 = nullptr, *flags = nullptr, *stored = nullptr;
   unsigned long long *incl = nullptr, *block_tot = nullptr;
-  HIPCHK_AS(who, dev_alloc(&fd->d_coarse, bi.n_coarse));
-  HIPCHK_AS(who, dev_alloc(&fd->d_table, bi.n_bricks));
+  HIPCHK_AS(who, fd->d_coarse.reserve(bi.n_coarse));
+  HIPCHK_AS(who, fd->d_table.reserve(bi.n_bricks));
   HIPCHK_AS(who, sc.alloc(&rec8, bi.n_coarse));
   HIPCHK_AS(who, sc.alloc(&flags, bi.n_bricks));
   HIPCHK_AS(who, sc.alloc(&stored, bi.n_bricks));
@@ -85,10 +85,10 @@ static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
     HIPCHK_AS(who, field_level_step(p, 16u, cn, rec16, nullptr, s));
   }
   for (int k = 0; k < 3; ++k) cn[k] = bi.nb[k] + 1u;
-  HIPCHK_AS(who, field_level_step(p, 8u, cn, rec8, fd->d_coarse, s));
-  HIPCHK_AS(who, launch_band_classify(p.fv, fd->d_coarse, bi.reach, flags, s));
+  HIPCHK_AS(who, field_level_step(p, 8u, cn, rec8, fd->d_coarse.p, s));
+  HIPCHK_AS(who, launch_band_classify(p.fv, fd->d_coarse.p, bi.reach, flags, s));
   HIPCHK_AS(who, launch_scan_counts(flags, static_cast<uint32_t>(bi.n_bricks), incl, block_tot, s));
-  HIPCHK_AS(who, launch_band_table(p.fv, flags, incl, fd->d_table, stored, s));
+  HIPCHK_AS(who, launch_band_table(p.fv, flags, incl, fd->d_table.p, stored, s));
   unsigned long long n_stored = 0;
   HIPCHK_AS(who, upload_on(s, &n_stored, incl + (bi.n_bricks - 1u), sizeof(n_stored), hipMemcpyDeviceToHost));
   bi.n_stored = n_stored;
@@ -96,7 +96,7 @@ static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
     return fail(RMCLHIP_ERR_INVALID,
                 "field_create_banded: the stored bricks and the coarse lattice have more than max_nodes nodes (a larger cell, a smaller band or "
                 "margin, or a larger max_nodes)");
-  HIPCHK_AS(who, dev_alloc(&fd->d_bricks, static_cast<size_t>(n_stored) * kBandBrickNodes));
+  HIPCHK_AS(who, fd->d_bricks.reserve(std::max<size_t>(static_cast<size_t>(n_stored) * kBandBrickNodes, 1u)));
   BandFillParams f;
   std::memset(&f, 0, sizeof(f));
   f.nodes = p.nodes;
@@ -106,7 +106,7 @@ static rmclhip_status band_build(rmclhip_field* fd, uint64_t max_nodes) {
   f.stored = stored;
   f.n_stored = static_cast<uint32_t>(n_stored);
   f.coarse_rec = rec8;
-  f.bricks = fd->d_bricks;
+  f.bricks = fd->d_bricks.p;
   HIPCHK_AS(who, launch_band_fill(f, s));
   HIPCHK_AS(who, hipStreamSynchronize(s));
   bi.bytes = (bi.n_bricks * sizeof(uint32_t) + bi.n_coarse * sizeof(float)) + n_stored * kBandBrickNodes * sizeof(float);
@@ -159,8 +159,8 @@ rmclhip_status rmclhip_field_download_banded(rmclhip_field* field, uint32_t* tab
     return fail(RMCLHIP_ERR_INVALID, "field_download_banded: a capacity is smaller than n_bricks, n_coarse or 729 * n_stored");
   HIPCHK(hipSetDevice(field->ctx->device));
   std::lock_guard<std::mutex> lock(field->mtx);
-  if (table) HIPCHK(upload_on(field->stream, table, field->d_table, bi.n_bricks * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (coarse) HIPCHK(upload_on(field->stream, coarse, field->d_coarse, bi.n_coarse * sizeof(float), hipMemcpyDeviceToHost));
-  if (bricks && n_fine != 0u) HIPCHK(upload_on(field->stream, bricks, field->d_bricks, n_fine * sizeof(float), hipMemcpyDeviceToHost));
+  if (table) HIPCHK(upload_on(field->stream, table, field->d_table.p, bi.n_bricks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (coarse) HIPCHK(upload_on(field->stream, coarse, field->d_coarse.p, bi.n_coarse * sizeof(float), hipMemcpyDeviceToHost));
+  if (bricks && n_fine != 0u) HIPCHK(upload_on(field->stream, bricks, field->d_bricks.p, n_fine * sizeof(float), hipMemcpyDeviceToHost));
   return RMCLHIP_OK;
 }

@@ -61,14 +61,14 @@ rmclhip_status rmclhip_field_layout_host(const float* bbox_min, const float* bbo
 
 RMCL_INTERNAL FieldView field_view(const rmclhip_field* fd) {
   FieldView v;
-  v.lat = fd->d_lat;
+  v.lat = fd->d_lat.p;
   for (int k = 0; k < 3; ++k) { v.n[k] = fd->info.n[k]; v.origin[k] = fd->info.origin[k]; }
   v.cell = fd->info.cell;
   v.inv_cell = fd->info.inv_cell;
   // a banded field (capi_band_field.cpp): lat is null
-  v.table = fd->d_table;
-  v.coarse = fd->d_coarse;
-  v.bricks = fd->d_bricks;
+  v.table = fd->d_table.p;
+  v.coarse = fd->d_coarse.p;
+  v.bricks = fd->d_bricks.p;
   for (int k = 0; k < 3; ++k) v.nb[k] = fd->band.nb[k];
   return v;
 }
@@ -77,11 +77,6 @@ RMCL_INTERNAL void field_release(rmclhip_field* fd) {
   if (!fd || fd->refs.fetch_sub(1) != 1) return;
   (void)hipSetDevice(fd->ctx->device);
   if (fd->stream) (void)hipStreamSynchronize(fd->stream);
-  fd->d_q_points.release(); fd->d_q_out.release(); fd->refine.release();
-  if (fd->d_lat) (void)hipFree(fd->d_lat);
-  if (fd->d_table) (void)hipFree(fd->d_table);
-  if (fd->d_coarse) (void)hipFree(fd->d_coarse);
-  if (fd->d_bricks) (void)hipFree(fd->d_bricks);
   if (fd->accounted) {
     std::lock_guard<std::mutex> lock(fd->map->grid_mtx);
     fd->map->bytes -= fd->accounted;
@@ -126,8 +121,8 @@ RMCL_INTERNAL rmclhip_status field_new(const std::string& who, rmclhip_ctx* ctx,
 RMCL_INTERNAL FieldBuildParams field_build_params(const rmclhip_field* fd) {
   FieldBuildParams p;
   std::memset(&p, 0, sizeof(p));
-  p.nodes = fd->map->d_nodes;
-  p.tris = fd->map->d_tris;
+  p.nodes = fd->map->d_nodes.p;
+  p.tris = fd->map->d_tris.p;
   p.n_tris = fd->map->info.n_records;
   p.fv = field_view(fd);
   return p;
@@ -150,7 +145,7 @@ RMCL_INTERNAL hipError_t field_level_step(FieldBuildParams& p, uint32_t stride, 
 // the next starts every query from the record of the previous level's nearest node.  The stream orders the levels.
 static rmclhip_status field_build(rmclhip_field* fd) {
   const std::string who = "field_create";
-  HIPCHK_AS(who, dev_alloc(&fd->d_lat, fd->info.n_nodes));
+  HIPCHK_AS(who, fd->d_lat.reserve(fd->info.n_nodes));
   {
     std::lock_guard<std::mutex> lock(fd->map->grid_mtx);
     fd->map->bytes += fd->info.bytes;
@@ -166,7 +161,7 @@ static rmclhip_status field_build(rmclhip_field* fd) {
     for (int k = 0; k < 3; ++k) { cn[k] = (fd->info.n[k] - 1u) / stride + 1u; total *= cn[k]; }
     uint32_t* d_rec = nullptr;
     if (stride > 1u) HIPCHK_AS(who, sc.alloc(&d_rec, total));
-    HIPCHK_AS(who, field_level_step(p, stride, cn, d_rec, stride == 1u ? fd->d_lat : nullptr, fd->stream));
+    HIPCHK_AS(who, field_level_step(p, stride, cn, d_rec, stride == 1u ? fd->d_lat.p : nullptr, fd->stream));
   }
   return hip_status(who, hipStreamSynchronize(fd->stream));
 }
@@ -205,7 +200,7 @@ rmclhip_status rmclhip_field_download(rmclhip_field* field, float* out, size_t c
   if (capacity < field->info.n_nodes) return fail(RMCLHIP_ERR_INVALID, "field_download: capacity is smaller than n_nodes");
   HIPCHK(hipSetDevice(field->ctx->device));
   std::lock_guard<std::mutex> lock(field->mtx);
-  HIPCHK(upload_on(field->stream, out, field->d_lat, field->info.bytes, hipMemcpyDeviceToHost));
+  HIPCHK(upload_on(field->stream, out, field->d_lat.p, field->info.bytes, hipMemcpyDeviceToHost));
   return RMCLHIP_OK;
 }
 
@@ -214,7 +209,7 @@ rmclhip_status rmclhip_field_device_view(const rmclhip_field* field, const float
   if (!field || !lattice_dev) return fail(RMCLHIP_ERR_INVALID, "field_device_view: null");
   *lattice_dev = nullptr;
   if (field->banded) return fail(RMCLHIP_ERR_INVALID, "field_device_view: the field is banded, it has no dense lattice");
-  *lattice_dev = field->d_lat;
+  *lattice_dev = field->d_lat.p;
   return RMCLHIP_OK;
 }
 

@@ -22,6 +22,9 @@
 //   capi_pf_sharded.cpp the sharded particle filter: one filter replica per device, every sharded twin of a single-device entry point
 // Host-side orchestration only: device memory, streams, launches.  There is no CPU compute path: without a HIP device every compute
 // entry point fails with RMCLHIP_ERR_NO_DEVICE.
+// Ownership: every allocation is a member (or a local) of type DevBuf, PinnedBuf or MappedBuf below and goes with its owner; a
+// plain pointer in a handle is borrowed or points into one of them, and says so.  A destroy function sets the handle's device, waits
+// for its stream, destroys what has an order (graph, events, stream), drops the references it holds and deletes the handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -108,69 +111,107 @@ struct ApiGuard {
   }
 };
 
-template <typename T>
-struct DevBuf {
+// ---- owned memory ----------------------------------------------------------------------------------
+// Every byte of device, pinned and host-mapped memory the library holds belongs to one of three move-only owners, which free it in
+// their destructors: a handle's destroy function names no buffer.  These two functions are the only callers of HIP's allocation and
+// free functions in this directory (tests/test_abi.py; rmclhip_malloc / rmclhip_free, which hand memory to the caller, excepted).  They
+// keep the two process-wide counts rmclhip_debug_live_bytes reads -- allocation is never on a per-call path, every buffer is grow-only --
+// and report a failed free under RMCLHIP_DEBUG.
+enum MemKind { kMemDevice = 0, kMemPinned = 1, kMemMapped = 2 };
+extern RMCL_INTERNAL std::atomic<uint64_t> g_live_bytes[2];   // [0] device, [1] pinned + host-mapped (capi_map.cpp)
+
+// *p: the allocation (null on failure); *d (kMemMapped only): its device alias
+RMCL_INTERNAL inline hipError_t mem_alloc(MemKind kind, size_t bytes, void** p, void** d = nullptr) {
+  hipError_t e = kind == kMemDevice   ? hipMalloc(p, bytes)
+                 : kind == kMemPinned ? hipHostMalloc(p, bytes, hipHostMallocDefault)
+                                      : hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) { *p = nullptr; return e; }
+  if (kind == kMemMapped && (e = hipHostGetDevicePointer(d, *p, 0)) != hipSuccess) {
+    (void)hipHostFree(*p);
+    *p = *d = nullptr;
+    return e;
+  }
+  g_live_bytes[kind != kMemDevice].fetch_add(bytes, std::memory_order_relaxed);
+  return hipSuccess;
+}
+RMCL_INTERNAL inline void mem_free(MemKind kind, void* p, size_t bytes) {
+  if (!p) return;
+  const hipError_t e = kind == kMemDevice ? hipFree(p) : hipHostFree(p);
+  g_live_bytes[kind != kMemDevice].fetch_sub(bytes, std::memory_order_relaxed);
+  if (e != hipSuccess && std::getenv("RMCLHIP_DEBUG"))
+    std::fprintf(stderr, "[rmclhip debug] %s(%p) -> %s\n", kind == kMemDevice ? "hipFree" : "hipHostFree", p, hipGetErrorString(e));
+}
+
+// device (DevBuf) or pinned host memory (PinnedBuf: hipHostMallocDefault, staging a device copies into and the host reads), grow-only
+// (RCCEmbree.cpp:28-33): reserve keeps what is large enough and otherwise replaces it, contents lost.  (Hidden: an out-of-line copy
+// of a header template's member is otherwise an exported weak symbol of the library.)
+template <typename T, MemKind K>
+struct RMCL_INTERNAL OwnedBuf {
   T* p = nullptr;
   size_t cap = 0;  // elements
-  // grow-only (RCCEmbree.cpp:28-33)
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf&) = delete;
+  OwnedBuf& operator=(const OwnedBuf&) = delete;
+  OwnedBuf(OwnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  OwnedBuf& operator=(OwnedBuf&& o) noexcept {
+    if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
+  ~OwnedBuf() { release(); }
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
+    release();
+    const hipError_t e = mem_alloc(K, n * sizeof(T), reinterpret_cast<void**>(&p));
     if (e == hipSuccess) cap = n;
     return e;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    mem_free(K, p, cap * sizeof(T));
     p = nullptr;
     cap = 0;
   }
 };
+template <typename T> using DevBuf = OwnedBuf<T, kMemDevice>;
+template <typename T> using PinnedBuf = OwnedBuf<T, kMemPinned>;
 
-// its pinned host counterpart (hipHostMallocDefault): staging a device copies into and the host reads.  (Hidden members: an out-of-line
-// copy of a header template's member is otherwise an exported weak symbol of the library.)
+// host-mapped coherent memory, which a kernel writes through d and the host reads through h: results, status blocks, completion tags.
+// Grow-only as above; both pointers are null after a failed reserve.
 template <typename T>
-struct PinnedBuf {
-  T* p = nullptr;
+struct RMCL_INTERNAL MappedBuf {
+  T* h = nullptr;
+  T* d = nullptr;  // device alias of h
   size_t cap = 0;  // elements
-  RMCL_INTERNAL hipError_t reserve(size_t n) {
+  MappedBuf() = default;
+  MappedBuf(const MappedBuf&) = delete;
+  MappedBuf& operator=(const MappedBuf&) = delete;
+  MappedBuf(MappedBuf&& o) noexcept : h(o.h), d(o.d), cap(o.cap) { o.h = o.d = nullptr; o.cap = 0; }
+  MappedBuf& operator=(MappedBuf&& o) noexcept {
+    if (this != &o) { release(); h = o.h; d = o.d; cap = o.cap; o.h = o.d = nullptr; o.cap = 0; }
+    return *this;
+  }
+  ~MappedBuf() { release(); }
+  hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
     release();
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), hipHostMallocDefault);
+    const hipError_t e = mem_alloc(kMemMapped, n * sizeof(T), reinterpret_cast<void**>(&h), reinterpret_cast<void**>(&d));
     if (e == hipSuccess) cap = n;
-    else p = nullptr;
     return e;
   }
-  RMCL_INTERNAL void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
+  void release() {
+    mem_free(kMemMapped, h, cap * sizeof(T));
+    h = d = nullptr;
     cap = 0;
   }
 };
 
-// count (at least one) elements of device memory; *out is null on failure
-template <typename T>
-hipError_t dev_alloc(T** out, size_t count) {
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(out), std::max<size_t>(count, 1u) * sizeof(T));
-  if (e != hipSuccess) *out = nullptr;
-  return e;
-}
-
-// the temporary device buffers of a field's build: freed when the build leaves, however it leaves
+// the temporary device buffers of a build: count (at least one) elements each, freed when the build leaves, however it leaves
 struct BuildScratch {
-  std::vector<void*> owned;
-  BuildScratch() = default;
-  BuildScratch(const BuildScratch&) = delete;
-  BuildScratch& operator=(const BuildScratch&) = delete;
-  ~BuildScratch() {
-    for (void* q : owned) (void)hipFree(q);
-  }
+  std::vector<DevBuf<uint8_t>> owned;
   template <typename T>
   hipError_t alloc(T** out, size_t count) {
-    const hipError_t e = dev_alloc(out, count);
-    if (e == hipSuccess) owned.push_back(*out);
+    owned.emplace_back();
+    const hipError_t e = owned.back().reserve(std::max<size_t>(count, 1u) * sizeof(T));
+    *out = reinterpret_cast<T*>(owned.back().p);
     return e;
   }
 };
@@ -192,13 +233,7 @@ struct Pc2ScanScratch {
   DevBuf<unsigned long long> keys;
   DevBuf<float> ranges;
   DevBuf<uint32_t> block_counts;        // 3 per workgroup of points, then 1 per workgroup of cells
-  uint32_t* h_counters = nullptr;       // pinned, host-mapped: {finite, in image, in range, cells filled}
-  uint32_t* h_counters_dev = nullptr;
-  void release() {
-    keys.release(); ranges.release(); block_counts.release();
-    if (h_counters) (void)hipHostFree(h_counters);
-    h_counters = nullptr; h_counters_dev = nullptr;
-  }
+  MappedBuf<uint32_t> h_counters;       // {finite, in image, in range, cells filled}
 };
 
 struct rmclhip_ctx {
@@ -212,12 +247,9 @@ struct rmclhip_ctx {
   // first call under the mutex, which also serialises the calls of one context
   std::mutex p2l_mtx;
   hipStream_t p2l_stream = nullptr;
-  double* p2l_partials = nullptr;
-  size_t p2l_partials_cap = 0;          // doubles
-  cstats* p2l_h_stats = nullptr;        // pinned, host-mapped: [0] the result
-  cstats* p2l_h_stats_dev = nullptr;
-  unsigned long long* p2l_h_done = nullptr;
-  unsigned long long* p2l_h_done_dev = nullptr;
+  DevBuf<double> p2l_partials;
+  MappedBuf<cstats> p2l_h_stats;        // [0] the result
+  MappedBuf<unsigned long long> p2l_h_done;
   uint32_t p2l_seq = 0;
   DevBuf<double> pinfo_partials, pinfo_rows;   // rmclhip_pose_information_p2l: its rows per workgroup and its result row, same stream and mutex
   // rmclhip_pointcloud2_to_scan (the free function): its own stream and scratch, created by the first call under its mutex
@@ -234,7 +266,7 @@ struct rmclhip_ctx {
   bool part_timing = false;              // rmclhip_debug_particles_timing (include/rmclhip_lab.h): bracket those calls with the two events
   hipEvent_t part_ev0 = nullptr, part_ev1 = nullptr;
   float part_last_ms = 0.f;
-  ~rmclhip_ctx();                       // capi_map.cpp
+  ~rmclhip_ctx();                       // capi_map.cpp: the streams and events; the buffers free themselves after it
 };
 
 inline void ctx_retain(rmclhip_ctx* c) { c->refs.fetch_add(1); }
@@ -246,26 +278,26 @@ struct rmclhip_map {
   rmclhip_ctx* ctx = nullptr;
   std::atomic<int> refs{1};
   BvhInfo info;
-  uint32_t* d_nodes = nullptr;
-  uint32_t* d_qnodes = nullptr;  // Node4Q twins
-  uint32_t* d_frontier = nullptr;   // frontier table (layout.h kFrontierDepth): n_frontier x 8 dwords {lo.xyz hi.x | hi.yz ref pad}
+  DevBuf<uint32_t> d_nodes;
+  DevBuf<uint32_t> d_qnodes;  // Node4Q twins
+  DevBuf<uint32_t> d_frontier;   // frontier table (layout.h kFrontierDepth): n_frontier x 8 dwords {lo.xyz hi.x | hi.yz ref pad}
   uint32_t n_frontier = 0;
-  uint32_t* d_frontier_pf = nullptr;   // ... of the filter's tree (find kind 24 walks d_qnodes_pf)
+  DevBuf<uint32_t> d_frontier_pf;   // ... of the filter's tree (find kind 24 walks d_qnodes_pf)
   uint32_t n_frontier_pf = 0;
   // group boxes of the two tables (bvh_build.h frontier_groups_of): 16 x 8 dwords behind each table in ITS allocation, null for a table of <= 64 entries
-  const uint32_t* d_frontier_groups = nullptr;
-  const uint32_t* d_frontier_groups_pf = nullptr;
-  uint32_t* d_qnodes_pf = nullptr;  // Node4Q array of the particle filter's own tree (leaves <= kPfLeafTris, same records)
-  uint32_t* d_cnodes = nullptr;  // Node4C twins
-  uint32_t* d_cnodes16 = nullptr;  // Node16C twins (maps of up to kMaxNodes16 nodes; find kind 32 descends two levels per pass on them), else null
-  uint32_t* d_tris = nullptr;
+  const uint32_t* d_frontier_groups = nullptr;   // inside d_frontier
+  const uint32_t* d_frontier_groups_pf = nullptr;   // inside d_frontier_pf
+  DevBuf<uint32_t> d_qnodes_pf;  // Node4Q array of the particle filter's own tree (leaves <= kPfLeafTris, same records)
+  DevBuf<uint32_t> d_cnodes;  // Node4C twins
+  DevBuf<uint32_t> d_cnodes16;  // Node16C twins (maps of up to kMaxNodes16 nodes; find kind 32 descends two levels per pass on them), else null
+  DevBuf<uint32_t> d_tris;
   uint64_t bytes = 0;
   // near grid of the closest-point queries (kernels.h NearGrid): built on the first rmclhip_rcc_find_cpc of any operator of this map
   // near grids (ensure_near_grid): slot 0 = cells near the surface only (scan points), slot 1 = every cell (the filter's beam ends).
   // A slot is built once under the mutex and never changes or moves afterwards -- other operators' launches may be reading it --
   // and both live until the map is released.
   std::mutex grid_mtx;
-  struct GridSlot { bool ready = false, failed = false; NearGrid g = {}; };
+  struct GridSlot { bool ready = false, failed = false; NearGrid g = {}; DevBuf<uint32_t> cells; };   // g.cells is cells.p
   GridSlot grid_slot[2];
   std::vector<uint32_t> scene_first_face;  // map_create_scene: first global face id of every instance, + the total (else empty)
 };
@@ -275,8 +307,7 @@ struct rmclhip_map {
 struct RefineScratch {
   DevBuf<float> beams;
   DevBuf<uint32_t> rows, counters;
-  const uint32_t* rows_src = nullptr;   // where the rows of the call in flight land (device memory); null: none were asked for
-  void release() { beams.release(); rows.release(); counters.release(); }
+  const uint32_t* rows_src = nullptr;   // where the rows of the call in flight land (the caller's device memory or `rows`); null: none were asked for
 };
 
 // rmclhip_pf_stein_step (capi_stein.cpp): grow-only scratch of a filter handle, freed with it -- the cell list (table, counts, prefix
@@ -289,10 +320,8 @@ struct SteinScratch {
   bool timing = false;
   hipEvent_t events[kSteinEvents] = {nullptr, nullptr, nullptr, nullptr};
   float last_ms[kSteinEvents - 1u] = {0.f, 0.f, 0.f};
-  void release() {
-    table.release(); incl.release(); block_tot.release(); words3.release(); slot_of.release(); records.release(); counters.release();
-    rows.release(); drive.release();
-    for (hipEvent_t& e : events) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  ~SteinScratch() {
+    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -303,14 +332,13 @@ struct rmclhip_field {
   rmclhip_map* map = nullptr;
   std::atomic<int> refs{1};
   rmclhip_field_info info{};
-  float* d_lat = nullptr;
+  DevBuf<float> d_lat;
   // a banded field (capi_band_field.cpp): d_lat is null, the three arrays of BANDED DISTANCE FIELD instead; info is the logical
   // geometry with the actual bytes
   bool banded = false;
   rmclhip_band_field_info band{};
-  uint32_t* d_table = nullptr;
-  float* d_coarse = nullptr;
-  float* d_bricks = nullptr;
+  DevBuf<uint32_t> d_table;
+  DevBuf<float> d_coarse, d_bricks;
   uint64_t accounted = 0;          // what the field has added to its map's device_bytes
   std::mutex mtx;
   hipStream_t stream = nullptr;
@@ -338,8 +366,8 @@ struct rmclhip_rcc {
   DevBuf<uint8_t> d_ds_mask;
   // what the kernels read: the handle's own copies above, or device memory borrowed from the caller
   // (rmclhip_rcc_set_dataset_view: Correspondences_::dataset lives in the caller's rm::Memory<.., VRAM_HIP>)
-  const float* ds_pts = nullptr;
-  const uint8_t* ds_msk = nullptr;
+  const float* ds_pts = nullptr;     // d_ds_points or the caller's view
+  const uint8_t* ds_msk = nullptr;   // d_ds_mask or the caller's view
   uint32_t n_dataset = 0;
   bool ds_has_mask = false;
   // model buffers
@@ -362,15 +390,13 @@ struct rmclhip_rcc {
   // reduction
   DevBuf<double> d_partials;
   DevBuf<double> d_pinfo_partials, d_pinfo_rows;   // rmclhip_rcc_pose_information[_batch] (capi_pose_information.cpp): rows per workgroup, result rows per pose
-  cstats* h_stats = nullptr;       // pinned, host-mapped
-  cstats* h_stats_dev = nullptr;   // device alias of h_stats
-  MicpState* d_state = nullptr;
-  MicpState* h_state = nullptr;    // pinned, host-mapped
-  MicpState* h_state_dev = nullptr;  // device alias of h_state
-  uint32_t* d_counter = nullptr;
+  MappedBuf<cstats> h_stats;
+  DevBuf<MicpState> d_state;
+  MappedBuf<MicpState> h_state;
+  DevBuf<uint32_t> d_counter;
   // device-resident MICP loop as a static hipGraph: per-call inputs travel in one 256-B H2D copy
-  MicpCall* h_call = nullptr;      // pinned
-  MicpCall* d_call = nullptr;
+  PinnedBuf<MicpCall> h_call;
+  DevBuf<MicpCall> d_call;
   hipGraphExec_t micp_exec = nullptr;
   hipGraph_t micp_graph = nullptr;
   struct MicpKey {
@@ -386,19 +412,17 @@ struct rmclhip_rcc {
   int fast_mode = 1;               // rmclhip_rcc_set_micp_fast: 0 off, 1 automatic with the iterations on the host (default), 3 / 4 device loops (A/B)
   DevBuf<double> d_fast_partials;
   DevBuf<unsigned long long> d_fast_mask;
-  double* d_fold_rows = nullptr;      // hand-over area of the loop launch's folding workgroups (kernels.h: kMicpFoldBlocks)
-  uint32_t* d_join_flags = nullptr;   // (first sensor of rmclhip_micp_correct_once) the other sensors' "my rows are complete" words
+  DevBuf<double> d_fold_rows;         // hand-over area of the loop launch's folding workgroups (kernels.h: kMicpFoldBlocks)
+  DevBuf<uint32_t> d_join_flags;      // (first sensor of rmclhip_micp_correct_once) the other sensors' "my rows are complete" words
   hipEvent_t ev_join = nullptr;       // rmclhip_micp_correct_once: this sensor's find (+ moment pass) ran on its own stream; the loop's stream waits for it
-  uint32_t* d_fold_flags = nullptr;
+  uint32_t* d_fold_flags = nullptr;   // inside d_fold_rows, behind the rows
   uint32_t last_fast_rows = 0, last_fast_words = 0;   // partial rows / mask words of the last moment-form attempt (diagnostics)
-  MicpFastStatus* h_fast_status = nullptr;      // pinned, host-mapped
-  MicpFastStatus* h_fast_status_dev = nullptr;
-  unsigned long long* h_done = nullptr;         // pinned, host-mapped completion tags: [0] this handle's chains, [1] the N-sensor loop
-  unsigned long long* h_done_dev = nullptr;
+  MappedBuf<MicpFastStatus> h_fast_status;
+  MappedBuf<unsigned long long> h_done;         // completion tags: [0] this handle's chains, [1] the N-sensor loop
   uint32_t done_seq = 0;                        // sequence number of the last polled call (never 0 in a tag)
   // closest-point correspondences, tracking: record index per dataset point of the previous find_cpc (see rmclhip_rcc_find_cpc)
   DevBuf<uint32_t> d_cpc_rec;
-  const uint32_t* cpc_rec_ptr = nullptr;
+  const uint32_t* cpc_rec_ptr = nullptr;        // d_cpc_rec.p when the records were written (never dereferenced)
   const float* cpc_rec_pts = nullptr;           // the dataset the records were computed for
   uint32_t cpc_rec_n = 0;
   bool cpc_tracking = true;
@@ -409,8 +433,7 @@ struct rmclhip_rcc {
   uint32_t fast_overflows = 0;     // consecutive
   rmclhip_micp_fast_info fast_info = {};
   // Round 4 -- iterations on the host (micp_host.h): what k_micp_publish hands over, and the host's verified copy of it
-  MicpHostBlock* h_mom = nullptr;      // pinned, host-mapped
-  MicpHostBlock* h_mom_dev = nullptr;
+  MappedBuf<MicpHostBlock> h_mom;
   MicpMomentSet mset;                  // valid for the model buffers + dataset it was formed from; dropped by whatever changes either
   bool mset_pending = false;           // a publish is in flight on the stream (speculating find): its tag carries mset_seq
   uint32_t mset_seq = 0;
@@ -425,25 +448,23 @@ struct rmclhip_rcc {
   rmclhip_ccs_info ccs_info = {};
   // N-sensor loop (rmclhip_micp_correct_once): call block + state of the first sensor, kept between calls
   DevBuf<uint8_t> d_multi_blob;
-  MicpMultiState* h_multi_state = nullptr;          // pinned, host-mapped
-  MicpMultiState* h_multi_state_dev = nullptr;
-  MicpMultiFastStatus* h_multi_status = nullptr;    // pinned, host-mapped
-  MicpMultiFastStatus* h_multi_status_dev = nullptr;
+  MappedBuf<MicpMultiState> h_multi_state;
+  MappedBuf<MicpMultiFastStatus> h_multi_status;
   uint32_t multi_holdoff = 0, multi_overflows = 0;
   // batch
   DevBuf<uint8_t> d_raw;           // staged PointCloud2 bytes (set_input_pointcloud2)
   DevBuf<xform> d_Tbm, d_Tsm, d_Tms, d_Tdelta;
   DevBuf<cstats> d_bstats;
-  // correct_batch's results leave through pinned, host-mapped staging (grow-only): the solve launch writes them there, the call
-  // returns on its completion tag and copies them out -- no device-to-host copy launches, no stream synchronisation
-  xform* h_bT = nullptr; xform* h_bT_dev = nullptr; cstats* h_bS = nullptr; cstats* h_bS_dev = nullptr; uint32_t h_batch_cap = 0;
+  // correct_batch's results leave through host-mapped staging: the solve launch writes them there, the call returns on its completion
+  // tag and copies them out -- no device-to-host copy launches, no stream synchronisation
+  MappedBuf<xform> h_bT;
+  MappedBuf<cstats> h_bS;
   // map segmentation (capi_segment.cpp): grow-only scratch of its trace {ranges, normals}, the staged measured ranges, labels when the
-  // caller wants none, the per-workgroup counts; the totals arrive in pinned, host-mapped memory (created by the first call)
+  // caller wants none, the per-workgroup counts; the totals arrive in host-mapped memory (created by the first call)
   DevBuf<float> d_seg_ranges, d_seg_normals, d_seg_real;
   DevBuf<uint8_t> d_seg_labels;
   DevBuf<uint32_t> d_seg_block_counts;
-  uint32_t* h_seg_counts = nullptr;
-  uint32_t* h_seg_counts_dev = nullptr;
+  MappedBuf<uint32_t> h_seg_counts;
   // rmclhip_rcc_set_input_pointcloud2_scan (capi_pc2scan.cpp): the model as set_model_spherical received it (the trig tables alone do
   // not give the bins back), the range image the dataset was made of and the keys, grow-only; host bytes are staged in d_raw
   rmclhip_spherical_model sph_model{{0.f, 0.f, 0u}, {0.f, 0.f, 0u}, {0.f, 0.f}};
@@ -475,23 +496,20 @@ struct rmclhip_rcc {
 // filter's update / motion update, the tournament): a one-thread launch behind the chain stores {seq, 0}, the host polls it -- ~7 us
 // sooner than the stream's own completion signal reaches hipStreamSynchronize (measured on the synchronous find, round 4).
 struct ChainTag {
-  unsigned long long* h = nullptr;
-  unsigned long long* d = nullptr;
+  MappedBuf<unsigned long long> word;
   uint32_t seq = 0;
   hipError_t create() {
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0);
-    if (e == hipSuccess) *h = 0ull;
+    const hipError_t e = word.reserve(1);
+    if (e == hipSuccess) *word.h = 0ull;
     return e;
   }
-  void destroy() { if (h) (void)hipHostFree(h); h = nullptr; d = nullptr; }
   // wait for the end of what `stream` holds (BLOCK wait mode, or no tag: hipStreamSynchronize)
   hipError_t wait_chain_end(const rmclhip_ctx* ctx, hipStream_t stream) {
-    if (h == nullptr || ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(stream);
+    if (word.h == nullptr || ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(stream);
     seq = (seq == 0xFFFFFFFFu) ? 1u : seq + 1u;
-    if (const hipError_t e = launch_host_tag(d, seq, stream)) return e;
+    if (const hipError_t e = launch_host_tag(word.d, seq, stream)) return e;
     const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-    volatile const unsigned long long* tag = h;
+    volatile const unsigned long long* tag = word.h;
     for (uint32_t spins = 0;; ++spins) {
       if (*tag == static_cast<unsigned long long>(seq)) { std::atomic_thread_fence(std::memory_order_acquire); return hipSuccess; }
 #if defined(__x86_64__) || defined(__i386__)
@@ -537,11 +555,10 @@ struct rmclhip_pf {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   rmclhip_pf_params params{2.0f, 100.0f, 100.0f, 0.0f, {0.05f, 80.0f}, 10000u, 0u};
   DevBuf<float> d_beams;
-  float* h_beams = nullptr;  // pinned staging
+  PinnedBuf<float> h_beams;  // staging
   hipEvent_t ev_beams = nullptr;      // behind the last copy out of h_beams
   bool beams_copy_pending = false;
-  size_t h_beams_cap = 0;
-  float* errors_dev = nullptr;
+  float* errors_dev = nullptr;   // rmclhip_pf_set_error_output: the caller's device memory
   int variant = 0;
   uint32_t refill_thr = 0, tail_lanes = 8;  // schedule knobs of the round-3 kernel (0: from `refill`); rmclhip_pf_set_schedule
   // rmclhip_pf_set_mapping: 0 beam-minor blocks of ~2048 rays (default), 1 particle-minor blocks (measured neutral, kept for A/B); nothing else is accepted
@@ -570,9 +587,9 @@ struct rmclhip_pf {
   // h_surf (pinned, 4 words) behind that launch on `stream`
   bool surface_on = false;
   rmclhip_surface_params surface{};
-  uint32_t* d_surf = nullptr;
-  uint32_t* h_surf = nullptr;
-  uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: borrowed device memory, one word per particle of the next constrained launches
+  DevBuf<uint32_t> d_surf;
+  PinnedBuf<uint32_t> h_surf;
+  uint32_t* surf_faces = nullptr;  // rmclhip_debug_surface_faces: the caller's device memory, one word per particle of the next constrained launches
   RefineScratch refine;            // rmclhip_pf_refine (capi_refine.cpp)
   SteinScratch stein;              // rmclhip_pf_stein_step (capi_stein.cpp)
   rmclhip_field* field = nullptr;  // rmclhip_pf_set_field (capi_field.cpp): correspondence_type 1 is answered from this lattice; the handle holds a reference
@@ -584,9 +601,9 @@ struct rmclhip_resampler {
   hipStream_t stream = nullptr;
   DevBuf<double> d_psum;
   DevBuf<float> d_pmax, d_out;
-  float* h_out = nullptr;  // pinned {sum, max}
+  PinnedBuf<float> h_out;  // {sum, max}
   ChainTag tag;            // completion tag of the tournament (a kernel-only synchronous call)
-  unsigned long long* h_res = nullptr;   // pinned: residual resampling's {sum, max, expect, n_draws} + the draws' total (5 words)
+  PinnedBuf<unsigned long long> h_res;   // residual resampling's {sum, max, expect, n_draws} + the draws' total (5 words)
   // residual resampling: {double sum, double max, u64 expect, u64 n_draws} on the device, the draws' particle / count / prefix sums
   DevBuf<unsigned long long> d_res_stats, d_res_incl, d_res_btot;
   DevBuf<uint32_t> d_res_idx, d_res_cnt;
@@ -686,10 +703,10 @@ struct rmclhip_surface_sampler {
   rmclhip_map* map = nullptr;
   rmclhip_surface_sample_params params{};
   rmclhip_surface_sample_info info{};
-  uint32_t* d_rec = nullptr;
-  unsigned long long* d_incl = nullptr;
-  uint32_t* d_count = nullptr;
-  uint32_t* h_count = nullptr;
+  DevBuf<uint32_t> d_rec;
+  DevBuf<unsigned long long> d_incl;
+  DevBuf<uint32_t> d_count;
+  PinnedBuf<uint32_t> h_count;
 };
 RMCL_INTERNAL rmclhip_status surface_sample_params_check(const std::string& who, const rmclhip_surface_sample_params* p);
 RMCL_INTERNAL SurfaceSampleView surface_sample_view(const rmclhip_surface_sampler* sm);
@@ -704,7 +721,6 @@ RMCL_INTERNAL rmclhip_status surface_params_check(const char* who, const rmclhip
 RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const xform& T_bnew_bold, double forget_rate,
                                                uint32_t max_n_meas, bool collision);
 RMCL_INTERNAL rmclhip_status pf_surface_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const rmclhip_surface_params& sp, uint32_t max_n_meas);
-RMCL_INTERNAL void pf_surface_release(rmclhip_pf* f);
 // capi_adaptive.cpp: the checks and launches the pose hypotheses share with the adaptive count.  kld_table_words: the size of the bin
 // table count_bins_run fills for n particles; resampler_stats: the likelihoods' maximum, landed on the host
 inline uint64_t kld_table_words(uint32_t n) { uint64_t words = 64; while (words < 2ull * n) words <<= 1; return words; }

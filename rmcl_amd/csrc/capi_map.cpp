@@ -6,6 +6,14 @@
 
 
 RMCL_INTERNAL thread_local std::string g_err;
+RMCL_INTERNAL std::atomic<uint64_t> g_live_bytes[2];
+
+rmclhip_status rmclhip_debug_live_bytes(uint64_t* device_bytes, uint64_t* host_bytes) {
+  if (!device_bytes || !host_bytes) return fail(RMCLHIP_ERR_INVALID, "debug_live_bytes: null");
+  *device_bytes = g_live_bytes[0].load(std::memory_order_relaxed);
+  *host_bytes = g_live_bytes[1].load(std::memory_order_relaxed);
+  return RMCLHIP_OK;
+}
 
 const char* rmclhip_last_error(void) { return g_err.c_str(); }
 const char* rmclhip_version(void) { return "rmclhip 0.1 (gfx950)"; }
@@ -42,30 +50,17 @@ rmclhip_status rmclhip_ctx_create(int device, rmclhip_ctx** out) {
 
 void rmclhip_ctx_destroy(rmclhip_ctx* ctx) { ctx_release(ctx); }
 
-// the scratch of rmclhip_statistics_p2l (capi_rcc.cpp) belongs to the context and goes with its last holder
+// the streams of the free functions belong to the context and go with its last holder; their scratch frees itself after this body,
+// which is why the device is set whether or not a stream exists
 rmclhip_ctx::~rmclhip_ctx() {
-  if (part_stream != nullptr) {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(part_stream);
-    part_viz.release();
-    if (part_ev0) (void)hipEventDestroy(part_ev0);
-    if (part_ev1) (void)hipEventDestroy(part_ev1);
-    (void)hipStreamDestroy(part_stream);
-  }
-  if (pc2_stream != nullptr) {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(pc2_stream);
-    pc2.release(); pc2_raw.release(); deskew_aux.release();
-    (void)hipStreamDestroy(pc2_stream);
-  }
-  if (p2l_stream == nullptr) return;
   (void)hipSetDevice(device);
-  (void)hipStreamSynchronize(p2l_stream);
-  if (p2l_partials) (void)hipFree(p2l_partials);
-  pinfo_partials.release(); pinfo_rows.release();
-  if (p2l_h_stats) (void)hipHostFree(p2l_h_stats);
-  if (p2l_h_done) (void)hipHostFree(p2l_h_done);
-  (void)hipStreamDestroy(p2l_stream);
+  for (hipStream_t s : {part_stream, pc2_stream, p2l_stream}) {
+    if (s == nullptr) continue;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+  if (part_ev0) (void)hipEventDestroy(part_ev0);
+  if (part_ev1) (void)hipEventDestroy(part_ev1);
 }
 
 rmclhip_status rmclhip_ctx_set_wait_mode(rmclhip_ctx* ctx, int mode) {
@@ -206,59 +201,51 @@ RMCL_INTERNAL rmclhip_status map_upload(rmclhip_ctx* ctx, const BvhHost& bvh, rm
   m->ctx = ctx;
   m->info = bvh.info;
   const size_t nb = bvh.nodes.size() * sizeof(Node4), tb = bvh.tris.size() * sizeof(TriRec);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_nodes), nb);
+  hipError_t e = m->d_nodes.reserve(nb / 4);
   // + 3 zeroed records: the packet kernel always requests a full 4-record leaf
   const size_t tb_pad = (kMaxLeafTris - 1) * sizeof(TriRec);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_tris), tb + tb_pad);
-  if (e == hipSuccess) e = hipMemset(reinterpret_cast<char*>(m->d_tris) + tb, 0, tb_pad);
-  if (e == hipSuccess) e = hipMemcpy(m->d_nodes, bvh.nodes.data(), nb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = m->d_tris.reserve((tb + tb_pad) / 4);
+  if (e == hipSuccess) e = hipMemset(reinterpret_cast<char*>(m->d_tris.p) + tb, 0, tb_pad);
+  if (e == hipSuccess) e = hipMemcpy(m->d_nodes.p, bvh.nodes.data(), nb, hipMemcpyHostToDevice);
   const size_t qb = bvh.qnodes.size() * sizeof(Node4Q);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_qnodes), qb);
-  if (e == hipSuccess) e = hipMemcpy(m->d_qnodes, bvh.qnodes.data(), qb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = m->d_qnodes.reserve(qb / 4);
+  if (e == hipSuccess) e = hipMemcpy(m->d_qnodes.p, bvh.qnodes.data(), qb, hipMemcpyHostToDevice);
   const size_t qpb = bvh.qnodes_pf.size() * sizeof(Node4Q);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_qnodes_pf), qpb);
-  if (e == hipSuccess) e = hipMemcpy(m->d_qnodes_pf, bvh.qnodes_pf.data(), qpb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = m->d_qnodes_pf.reserve(qpb / 4);
+  if (e == hipSuccess) e = hipMemcpy(m->d_qnodes_pf.p, bvh.qnodes_pf.data(), qpb, hipMemcpyHostToDevice);
   // the two frontier tables, each with its group boxes (bvh_build.h frontier_groups_of) behind it in the same allocation; a table of
   // <= 64 entries is one block of the cull: nothing to skip, the kernels get no group pointer
-  auto upload_frontier = [&](const std::vector<Node4C::Child>& table, const std::vector<Node4C::Child>& groups, uint32_t** d_table,
+  auto upload_frontier = [&](const std::vector<Node4C::Child>& table, const std::vector<Node4C::Child>& groups, DevBuf<uint32_t>& d_table,
                              const uint32_t** d_groups, size_t* bytes) {
     const size_t fb = table.size() * sizeof(Node4C::Child), gb = groups.size() * sizeof(Node4C::Child);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(d_table), std::max<size_t>(fb + gb, 32));
-    if (e == hipSuccess && fb) e = hipMemcpy(*d_table, table.data(), fb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && gb) e = hipMemcpy(reinterpret_cast<char*>(*d_table) + fb, groups.data(), gb, hipMemcpyHostToDevice);
-    *d_groups = (table.size() > 64 && groups.size() == kFrontierGroups) ? *d_table + fb / 4 : nullptr;
+    if (e == hipSuccess) e = d_table.reserve(std::max<size_t>(fb + gb, 32) / 4);
+    if (e == hipSuccess && fb) e = hipMemcpy(d_table.p, table.data(), fb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && gb) e = hipMemcpy(reinterpret_cast<char*>(d_table.p) + fb, groups.data(), gb, hipMemcpyHostToDevice);
+    *d_groups = (table.size() > 64 && groups.size() == kFrontierGroups) ? d_table.p + fb / 4 : nullptr;
     *bytes = fb + gb;
   };
   size_t fb = 0, fpb = 0;
-  upload_frontier(bvh.frontier, bvh.frontier_groups, &m->d_frontier, &m->d_frontier_groups, &fb);
+  upload_frontier(bvh.frontier, bvh.frontier_groups, m->d_frontier, &m->d_frontier_groups, &fb);
   m->n_frontier = static_cast<uint32_t>(bvh.frontier.size());
-  upload_frontier(bvh.frontier_pf, bvh.frontier_groups_pf, &m->d_frontier_pf, &m->d_frontier_groups_pf, &fpb);
+  upload_frontier(bvh.frontier_pf, bvh.frontier_groups_pf, m->d_frontier_pf, &m->d_frontier_groups_pf, &fpb);
   m->n_frontier_pf = static_cast<uint32_t>(bvh.frontier_pf.size());
   const size_t cb = bvh.cnodes.size() * sizeof(Node4C);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_cnodes), cb);
-  if (e == hipSuccess) e = hipMemcpy(m->d_cnodes, bvh.cnodes.data(), cb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_tris, bvh.tris.data(), tb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = m->d_cnodes.reserve(cb / 4);
+  if (e == hipSuccess) e = hipMemcpy(m->d_cnodes.p, bvh.cnodes.data(), cb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->d_tris.p, bvh.tris.data(), tb, hipMemcpyHostToDevice);
   // the 16-wide twins for the cooperative descent of find kind 32 (512 B per node: 8 MB for a 100 k-triangle map), derived on the device;
   // maps beyond kMaxNodes16 nodes (~18 M triangles) go without -- the descent then walks the four-wide nodes
   constexpr size_t kMaxNodes16 = 6000000;   // (3 GB of twins for the largest: a 10 M-triangle map carries 1.7 GB, of 288)
   size_t c16b = 0;
   if (e == hipSuccess && bvh.cnodes.size() <= kMaxNodes16) {
     c16b = bvh.cnodes.size() * sizeof(Node16C);
-    e = hipMalloc(reinterpret_cast<void**>(&m->d_cnodes16), c16b);
-    if (e == hipSuccess) e = launch_build_cnodes16(m->d_cnodes, static_cast<uint32_t>(bvh.cnodes.size()), m->d_cnodes16, nullptr);
+    e = m->d_cnodes16.reserve(c16b / 4);
+    if (e == hipSuccess) e = launch_build_cnodes16(m->d_cnodes.p, static_cast<uint32_t>(bvh.cnodes.size()), m->d_cnodes16.p, nullptr);
   }
   // the map is read by kernels on the handles' non-blocking streams, which do not synchronise with the null stream these
   // copies ran on: make sure every byte has landed before the handle is handed out
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    if (m->d_nodes) (void)hipFree(m->d_nodes);
-    if (m->d_qnodes) (void)hipFree(m->d_qnodes);
-    if (m->d_qnodes_pf) (void)hipFree(m->d_qnodes_pf);
-    if (m->d_frontier) (void)hipFree(m->d_frontier);
-    if (m->d_frontier_pf) (void)hipFree(m->d_frontier_pf);
-    if (m->d_cnodes) (void)hipFree(m->d_cnodes);
-    if (m->d_cnodes16) (void)hipFree(m->d_cnodes16);
-    if (m->d_tris) (void)hipFree(m->d_tris);
     delete m;
     return fail(e == hipErrorOutOfMemory ? RMCLHIP_ERR_NOMEM : RMCLHIP_ERR_HIP,
                 std::string("map_create upload: ") + hipGetErrorString(e));
@@ -281,16 +268,6 @@ void rmclhip_map_release(rmclhip_map* map) {
   if (!map) return;
   if (map->refs.fetch_sub(1) == 1) {
     (void)hipSetDevice(map->ctx->device);
-    if (map->d_nodes) (void)hipFree(map->d_nodes);
-    if (map->d_qnodes) (void)hipFree(map->d_qnodes);
-    if (map->d_qnodes_pf) (void)hipFree(map->d_qnodes_pf);
-    if (map->d_frontier) (void)hipFree(map->d_frontier);
-    if (map->d_frontier_pf) (void)hipFree(map->d_frontier_pf);
-    if (map->d_cnodes) (void)hipFree(map->d_cnodes);
-    if (map->d_cnodes16) (void)hipFree(map->d_cnodes16);
-    if (map->d_tris) (void)hipFree(map->d_tris);
-    for (auto& gs : map->grid_slot)
-      if (gs.g.cells) (void)hipFree(const_cast<uint32_t*>(gs.g.cells));
     ctx_release(map->ctx);
     delete map;
   }
@@ -459,8 +436,6 @@ rmclhip_status rmclhip_debug_solve(rmclhip_ctx* ctx, const rmclhip_cross_statist
   if (e == hipSuccess) e = hipMemcpy(d_in.p, stats_host, static_cast<size_t>(n) * sizeof(cstats), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = launch_debug_solve(d_in.p, n, solver == 2, d_out.p, nullptr);
   if (e == hipSuccess) e = hipMemcpy(out_host, d_out.p, static_cast<size_t>(n) * sizeof(xform), hipMemcpyDeviceToHost);
-  d_in.release();
-  d_out.release();
   HIPCHK(e);
   return RMCLHIP_OK;
 }

@@ -72,32 +72,32 @@ static hipError_t launch_moment_loop(rmclhip_rcc* r, bool tiled, const FindParam
   const uint8_t* dmask = r->ds_has_mask ? r->ds_msk : nullptr;
   if (tiled)
     return launch_micp_fast_loop_tiled(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_fast_partials.p,
-                                       r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter, r->h_state_dev,
-                                       r->h_fast_status_dev, r->h_done_dev, r->stream, cl, r->d_fold_rows, r->d_fold_flags);
+                                       r->d_fast_mask.p, r->W, fp.tiles_x, fp.tile_w_log2, wpb, n_iter, r->h_state.d,
+                                       r->h_fast_status.d, r->h_done.d, r->stream, cl, r->d_fold_rows.p, r->d_fold_flags);
   return launch_micp_fast(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nullptr, r->d_fast_partials.p,
-                          r->d_fast_mask.p, n_iter, r->h_state_dev, r->h_fast_status_dev, r->h_done_dev, r->stream, &cl);
+                          r->d_fast_mask.p, n_iter, r->h_state.d, r->h_fast_status.d, r->h_done.d, r->stream, &cl);
 }
 
 // Moment form (micp.hip "gate-stable moment form"), fast modes 1, 3 and 4, launched directly with the per-call data BY VALUE -- no
 // H2D copy node, no graph launch (a graph replay costs the host 10-16 us whatever it holds).  *out: code 0 = served, the correction
-// is in r->h_state; 1 / 2 = the caller runs the per-iteration form, which recomputes the correction from scratch.
+// is in r->h_state.h; 1 / 2 = the caller runs the per-iteration form, which recomputes the correction from scratch.
 static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uint32_t n_iter, float maxd, uint32_t nred,
                                            MicpFastStatus* out) {
   HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
   HIPCHK(r->d_fast_mask.reserve((static_cast<size_t>(nred) + 63u) / 64u));
   MicpFastStatus fs{};
-  bool fs_ready = false;     // the host ran the iterations: `fs` (and r->h_state) are final, nothing to wait for
+  bool fs_ready = false;     // the host ran the iterations: `fs` (and r->h_state.h) are final, nothing to wait for
   FindParams fp;
   fill_find_params(r, fp, 1);
-  fp.Tsm = r->h_call->Tsm;
-  fp.Tms = r->h_call->Tms;
-  MicpCallLite cl = micp_call_lite(r, Tbo, maxd, r->h_call->seq);
+  fp.Tsm = r->h_call.p->Tsm;
+  fp.Tms = r->h_call.p->Tms;
+  MicpCallLite cl = micp_call_lite(r, Tbo, maxd, r->h_call.p->seq);
   const int fv = find_variant(r, 1);
   const bool tiled = r->fast_mode != 3 && (fv == 23 || fv == 32 || fv == 2);   // the find forms the moments in its epilogue
   if (r->fast_mode == 1) {
     // ---- round 4 default: TWO launches (find with the moment epilogue; fold + publish), the iterations on the HOST from the 82
     // moments + the undecided correspondences (micp_host.h): ~0.5 us per iteration instead of ~2.7 us of one lane's f64 chain
-    if (rmclhip_status st = enqueue_find_with_moments(r, r->h_call->Tsm, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, cl.seq, true)) return st;
+    if (rmclhip_status st = enqueue_find_with_moments(r, r->h_call.p->Tsm, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap, cl.seq, true)) return st;
     HIPCHK(wait_moments(r, cl.seq, maxd, maxd, r->fast_rho_cap, r->fast_tau_cap));
     if (r->mset.valid) {
       xform T_s = xidentity();
@@ -115,15 +115,15 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
         // micp.hip micp_close_sensor
         fs.iter = n_iter;
         const xform Tso = xmul(Tbo, r->Tsb);
-        r->h_state->T_snew_sold = T_s;
-        r->h_state->T_onew_oold = xmul(xmul(Tso, T_s), xinv(Tso));
-        r->h_state->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(r->Tsb, last)));
+        r->h_state.h->T_snew_sold = T_s;
+        r->h_state.h->T_onew_oold = xmul(xmul(Tso, T_s), xinv(Tso));
+        r->h_state.h->stats_o = cs_merge(cs_identity(), cs_transform(Tbo, cs_transform(r->Tsb, last)));
       }
       fs_ready = true;
     } else {
       // more undecided correspondences than the host takes: the device loop on the rows the find left (a sequence number of its own:
       // the publish launch used this one for its hand-over flags and its tag)
-      cl.seq = r->h_call->seq = next_seq(r);
+      cl.seq = r->h_call.p->seq = next_seq(r);
       // kind and row layout are the ones enqueue_find_with_moments actually ran (it replaces kind 24 by 23 to get the epilogue):
       // the loop folds THOSE rows instead of paying a moment pass of its own
       const int ufv = r->last_moment_find_kind;
@@ -147,10 +147,10 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
   }
   if (!fs_ready) {
     // sum of the tag: the status block, plus the state block when the loop ran to its end (code 0)
-    DoneCheck chk; chk.base = r->h_fast_status; chk.base_bytes = sizeof(MicpFastStatus); chk.code = &r->h_fast_status->code;
-    chk.extra[0] = r->h_state; chk.extra_bytes[0] = sizeof(MicpState);
-    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
-    fs = *r->h_fast_status;
+    DoneCheck chk; chk.base = r->h_fast_status.h; chk.base_bytes = sizeof(MicpFastStatus); chk.code = &r->h_fast_status.h->code;
+    chk.extra[0] = r->h_state.h; chk.extra_bytes[0] = sizeof(MicpState);
+    HIPCHK(wait_done(r->ctx, r->h_done.h, r->h_call.p->seq, chk, r->stream));
+    fs = *r->h_fast_status.h;
   } else {
     ++r->fast_info.host_loops;
   }
@@ -168,26 +168,26 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
 // the previous iteration in its prologue) + one closing solve -- n_iter + 1 launches instead of 2 * n_iter.  k_micp_close writes the
 // result straight into host-mapped memory (no copy node).  Without iterations: k_micp_init + a copy of that state.
 static rmclhip_status enqueue_micp_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
-  HIPCHK(hipMemcpyAsync(r->d_call, r->h_call, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream));
+  HIPCHK(hipMemcpyAsync(r->d_call.p, r->h_call.p, sizeof(MicpCall), hipMemcpyHostToDevice, r->stream));
   FindParams p;
   fill_find_params(r, p, 1);
-  p.Tsm_arr = &r->d_call->Tsm;
-  p.Tms_arr = &r->d_call->Tms;
+  p.Tsm_arr = &r->d_call.p->Tsm;
+  p.Tms_arr = &r->d_call.p->Tms;
   HIPCHK(launch_find(p, r->kind, find_variant(r, p.nposes), r->stream));
   if (n_iter == 0) {
-    HIPCHK(launch_micp_init(r->d_state, r->stream));
-    HIPCHK(hipMemcpyAsync(r->h_state, r->d_state, sizeof(MicpState), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(launch_micp_init(r->d_state.p, r->stream));
+    HIPCHK(hipMemcpyAsync(r->h_state.h, r->d_state.p, sizeof(MicpState), hipMemcpyDeviceToHost, r->stream));
     return RMCLHIP_OK;
   }
   const uint8_t* dmask = r->ds_has_mask ? r->ds_msk : nullptr;
   const uint32_t nb = reduce_num_blocks(nred, 1);
   double* part[2] = {r->d_partials.p, r->d_partials.p + static_cast<size_t>(nb) * 16};
   for (uint32_t i = 0; i < n_iter; ++i)
-    HIPCHK(launch_micp_iter(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_call,
-                            part[(i + 1u) & 1u], part[i & 1u], r->d_state + (i & 1u), r->d_state + ((i + 1u) & 1u),
+    HIPCHK(launch_micp_iter(r->ds_pts, dmask, r->d_points.p, r->d_normals.p, r->d_hits.p, nred, nb, r->d_call.p,
+                            part[(i + 1u) & 1u], part[i & 1u], r->d_state.p + (i & 1u), r->d_state.p + ((i + 1u) & 1u),
                             i == 0, r->stream));
-  HIPCHK(launch_micp_close(part[(n_iter - 1u) & 1u], nb, r->d_call, r->d_state + (n_iter & 1u), r->h_state_dev,
-                           r->h_done_dev, r->stream));
+  HIPCHK(launch_micp_close(part[(n_iter - 1u) & 1u], nb, r->d_call.p, r->d_state.p + (n_iter & 1u), r->h_state.d,
+                           r->h_done.d, r->stream));
   return RMCLHIP_OK;
 }
 
@@ -197,7 +197,7 @@ static rmclhip_status enqueue_micp_chain(rmclhip_rcc* r, uint32_t n_iter, uint32
 static rmclhip_status micp_per_iteration_chain(rmclhip_rcc* r, uint32_t n_iter, uint32_t nred) {
   // k_micp_close publishes a completion tag the host polls (a fresh sequence number: a moment-form attempt may have published one
   // for this call already)
-  r->h_call->seq = next_seq(r);
+  r->h_call.p->seq = next_seq(r);
   if (r->use_graph) {
     rmclhip_rcc::MicpKey key;
     std::memset(&key, 0, sizeof(key));
@@ -232,8 +232,8 @@ static rmclhip_status micp_per_iteration_chain(rmclhip_rcc* r, uint32_t n_iter, 
   if (n_iter == 0) {
     HIPCHK(hipStreamSynchronize(r->stream));
   } else {
-    DoneCheck chk; chk.base = r->h_state; chk.base_bytes = sizeof(MicpState);
-    HIPCHK(wait_done(r->ctx, r->h_done, r->h_call->seq, chk, r->stream));
+    DoneCheck chk; chk.base = r->h_state.h; chk.base_bytes = sizeof(MicpState);
+    HIPCHK(wait_done(r->ctx, r->h_done.h, r->h_call.p->seq, chk, r->stream));
   }
   return RMCLHIP_OK;
 }
@@ -253,15 +253,15 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
     // (or, in the moment form of mode 1, on the host from the moments the find published)
     uint32_t nred = 0;
     if (rmclhip_status st = micp_prepare_operator(r, &nred)) return st;
-    r->h_call->Tsm = xmul(xmul(Tom, Tbo), r->Tsb);
-    r->h_call->Tms = xinv(r->h_call->Tsm);
-    r->h_call->Tsb = r->Tsb;
-    r->h_call->Tbo = Tbo;
-    r->h_call->max_dist = maxd;
-    r->h_call->gate_lo = maxd; r->h_call->gate_hi = maxd;
-    r->h_call->rho_cap = r->fast_rho_cap;
-    r->h_call->tau_cap = r->fast_tau_cap;
-    r->h_call->seq = next_seq(r);
+    r->h_call.p->Tsm = xmul(xmul(Tom, Tbo), r->Tsb);
+    r->h_call.p->Tms = xinv(r->h_call.p->Tsm);
+    r->h_call.p->Tsb = r->Tsb;
+    r->h_call.p->Tbo = Tbo;
+    r->h_call.p->max_dist = maxd;
+    r->h_call.p->gate_lo = maxd; r->h_call.p->gate_hi = maxd;
+    r->h_call.p->rho_cap = r->fast_rho_cap;
+    r->h_call.p->tau_cap = r->fast_tau_cap;
+    r->h_call.p->seq = next_seq(r);
     // moment form first; any outcome other than "done" falls through to the per-iteration form (the device loops need >= 2
     // iterations to pay for their moment pass; the host form -- two launches, no reduction launch at all -- serves 1 as well)
     const bool fast_eligible = r->fast_mode != 0 && n_iter >= ((r->fast_mode == 1) ? 1u : 2u);
@@ -272,21 +272,21 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
       MicpFastStatus fs;
       if (rmclhip_status st = micp_try_moment_form(r, Tbo, n_iter, maxd, nred, &fs)) return st;
       if (fs.code == 0u) {
-        from_x(r->h_state->T_onew_oold, T_out);
-        if (stats_out) from_cs(r->h_state->stats_o, stats_out);
+        from_x(r->h_state.h->T_onew_oold, T_out);
+        if (stats_out) from_cs(r->h_state.h->stats_o, stats_out);
         return RMCLHIP_OK;
       }
     }
     if (rmclhip_status st = micp_per_iteration_chain(r, n_iter, nred)) return st;
     if (fast_tried) {
-      const xform Tb = xmul(xmul(xinv(Tbo), r->h_state->T_onew_oold), Tbo);
+      const xform Tb = xmul(xmul(xinv(Tbo), r->h_state.h->T_onew_oold), Tbo);
       const bool overflow = r->last_fast.code == 2u;
       micp_caps_after_fallback(r, xmul(xmul(xinv(r->Tsb), Tb), r->Tsb), overflow, r->last_fast.max_rho, r->last_fast.max_tau);
       // too many uncertain correspondences twice in a row: stop trying for a while
       if (overflow && ++r->fast_overflows >= 2u) { r->fast_holdoff = 32u; r->fast_overflows = 0; }
     }
-    from_x(r->h_state->T_onew_oold, T_out);
-    if (stats_out) from_cs(r->h_state->stats_o, stats_out);
+    from_x(r->h_state.h->T_onew_oold, T_out);
+    if (stats_out) from_cs(r->h_state.h->stats_o, stats_out);
     return RMCLHIP_OK;
   }
   // schedule (B), lidar_corrector_embree_benchmark.cpp:127-135: re-raycast from the corrected pose every iteration
@@ -297,13 +297,13 @@ rmclhip_status rmclhip_rcc_correct_once(rmclhip_rcc* r, const rmclhip_transform*
     if (rmclhip_status st = find_enqueue(r, xmul(Tom_cur, Tbo))) return st;
     ReduceTail tail;
     tail.mode = kTailStats;
-    tail.stats_out = r->h_stats_dev;
-    tail.done = r->h_done_dev;
+    tail.stats_out = r->h_stats.d;
+    tail.done = r->h_done.d;
     tail.seq = next_seq(r);
     if (rmclhip_status st = reduce_enqueue(r, xidentity(), nullptr, maxd, 1, tail)) return st;
-    DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
-    HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
-    const cstats Cs_o = cs_transform(Tbo, cs_transform(r->Tsb, r->h_stats[0]));
+    DoneCheck chk; chk.base = &r->h_stats.h[0]; chk.base_bytes = sizeof(cstats);
+    HIPCHK(wait_done(r->ctx, r->h_done.h, tail.seq, chk, r->stream));
+    const cstats Cs_o = cs_transform(Tbo, cs_transform(r->Tsb, r->h_stats.h[0]));
     last = cs_merge(cs_identity(), Cs_o);
     T_onew_oold = xmul(T_onew_oold, umeyama(last));
   }
@@ -377,12 +377,8 @@ static rmclhip_status micp_multi_prepare(MicpMultiJob& j, const rmclhip_transfor
   c.seq = next_seq(r0);
   // call + state live with the first sensor and persist between calls (an allocation per call cost more than the loop)
   HIPCHK(r0->d_multi_blob.reserve(sizeof(MicpMultiCall) + sizeof(MicpMultiState)));
-  if (!r0->h_multi_state) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r0->h_multi_state), sizeof(MicpMultiState), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r0->h_multi_state_dev), r0->h_multi_state, 0));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r0->h_multi_status), sizeof(MicpMultiFastStatus), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r0->h_multi_status_dev), r0->h_multi_status, 0));
-  }
+  HIPCHK(r0->h_multi_state.reserve(1));
+  HIPCHK(r0->h_multi_status.reserve(1));
   return RMCLHIP_OK;
 }
 
@@ -462,7 +458,7 @@ static rmclhip_status micp_multi_host_form(MicpMultiJob& j, uint32_t* code, Micp
   // leave them in the device's moment loop as well: the caller goes straight to the per-iteration form, whose end learns the caps from
   // this status.  Too many undecided correspondences for the host (> kMicpHostMaxUnc = 1024 in a sensor): the device's moment loop
   // takes up to 4096.  Either way a fresh sequence number: the publish launches used the first
-  if (hs.code == 1u) *j.sensors[0]->h_multi_status = hs;
+  if (hs.code == 1u) *j.sensors[0]->h_multi_status.h = hs;
   for (uint32_t s = 0; s < j.n_sensors; ++s) drop_moment_set(j.sensors[s]);
   c.seq = next_seq(j.sensors[0]);
   return RMCLHIP_OK;
@@ -478,9 +474,9 @@ static rmclhip_status micp_multi_enqueue_finds(const MicpMultiJob& j) {
   // moment form the join is a flag: a one-lane kernel behind the sensor's moment pass stores the call's sequence number, the loop
   // kernel -- launched without waiting -- polls it before it touches that sensor's rows.  The per-iteration form (fallback) records
   // an event on every other sensor's stream and waits for it.
-  if (j.n_sensors > 1u && !r0->d_join_flags) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r0->d_join_flags), kMaxMicpSensors * sizeof(uint32_t)));
-    HIPCHK(hipMemset(r0->d_join_flags, 0, kMaxMicpSensors * sizeof(uint32_t)));
+  if (j.n_sensors > 1u && !r0->d_join_flags.p) {
+    HIPCHK(r0->d_join_flags.reserve(kMaxMicpSensors));
+    HIPCHK(hipMemset(r0->d_join_flags.p, 0, kMaxMicpSensors * sizeof(uint32_t)));
     HIPCHK(hipDeviceSynchronize());
   }
   for (uint32_t s = 0; s < j.n_sensors; ++s) {
@@ -515,31 +511,31 @@ static rmclhip_status micp_multi_device_loop(const MicpMultiJob& j, uint32_t* co
     fp.Tsb[s] = cl.Tsb; fp.Tbo[s] = cl.Tbo; fp.weight[s] = c.weight[s];
     fp.max_dist[s] = cl.max_dist; fp.rho_cap[s] = cl.rho_cap; fp.tau_cap[s] = cl.tau_cap;
     if (s != 0u) {
-      HIPCHK(launch_signal_flag(r0->d_join_flags + s, c.seq, r->stream));
+      HIPCHK(launch_signal_flag(r0->d_join_flags.p + s, c.seq, r->stream));
       fp.join_mask |= 1u << s;
     }
   }
-  fp.join_flags = r0->d_join_flags;
+  fp.join_flags = r0->d_join_flags.p;
   fp.n_sensors = j.n_sensors;
   fp.seq = c.seq;
   fp.n_iter = j.n_iter;
-  fp.state_out = r0->h_multi_state_dev;
-  fp.status = r0->h_multi_status_dev;
-  fp.done = r0->h_done_dev + 1;
+  fp.state_out = r0->h_multi_state.d;
+  fp.status = r0->h_multi_status.d;
+  fp.done = r0->h_done.d + 1;
   HIPCHK(launch_micp_multi_fast_loop(fp, r0->stream));
-  DoneCheck chk; chk.base = r0->h_multi_status; chk.base_bytes = sizeof(MicpMultiFastStatus); chk.code = &r0->h_multi_status->code;
-  chk.extra[0] = &r0->h_multi_state->T_onew_oold; chk.extra_bytes[0] = sizeof(xform);
-  chk.extra[1] = &r0->h_multi_state->merged_o; chk.extra_bytes[1] = sizeof(cstats);
-  chk.extra[2] = &r0->h_multi_state->merged_weighted_o; chk.extra_bytes[2] = sizeof(cstats);
-  HIPCHK(wait_done(r0->ctx, r0->h_done + 1, c.seq, chk, r0->stream));
-  const MicpMultiFastStatus fs = *r0->h_multi_status;
+  DoneCheck chk; chk.base = r0->h_multi_status.h; chk.base_bytes = sizeof(MicpMultiFastStatus); chk.code = &r0->h_multi_status.h->code;
+  chk.extra[0] = &r0->h_multi_state.h->T_onew_oold; chk.extra_bytes[0] = sizeof(xform);
+  chk.extra[1] = &r0->h_multi_state.h->merged_o; chk.extra_bytes[1] = sizeof(cstats);
+  chk.extra[2] = &r0->h_multi_state.h->merged_weighted_o; chk.extra_bytes[2] = sizeof(cstats);
+  HIPCHK(wait_done(r0->ctx, r0->h_done.h + 1, c.seq, chk, r0->stream));
+  const MicpMultiFastStatus fs = *r0->h_multi_status.h;
   for (uint32_t s = 0; s < j.n_sensors; ++s) micp_record_attempt(j.sensors[s], fs.code, fs.n_uncertain, fs.max_rho[s], fs.max_tau[s]);
   *code = fs.code;
   if (fs.code > 2u) return fail(RMCLHIP_ERR_HIP, "micp_correct_once: the moment-form loop did not report a status");
   if (fs.code == 0u) {
     r0->multi_overflows = 0;
-    res->T_onew_oold = r0->h_multi_state->T_onew_oold;
-    res->merged_o = r0->h_multi_state->merged_o;
+    res->T_onew_oold = r0->h_multi_state.h->T_onew_oold;
+    res->merged_o = r0->h_multi_state.h->merged_o;
   }
   return RMCLHIP_OK;
 }
@@ -601,7 +597,7 @@ rmclhip_status rmclhip_micp_correct_once(rmclhip_rcc* const* sensors, uint32_t n
     if (route.moment) {
       // caps for the next attempt from the pre-transforms this correction ended with (see rmclhip_rcc_correct_once); too many
       // undecided correspondences twice in a row: stop trying for a while
-      const MicpMultiFastStatus& ms = *r0->h_multi_status;
+      const MicpMultiFastStatus& ms = *r0->h_multi_status.h;
       for (uint32_t s = 0; s < n_sensors; ++s)
         micp_caps_after_fallback(sensors[s], res.T_snew_sold[s], code == 2u, ms.max_rho[s], ms.max_tau[s]);
       if (code == 2u && ++r0->multi_overflows >= 2u) { r0->multi_holdoff = 32u; r0->multi_overflows = 0; }

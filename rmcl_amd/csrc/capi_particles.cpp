@@ -187,7 +187,7 @@ rmclhip_status rmclhip_particles_inject_surface(rmclhip_surface_sampler* sm, rmc
   if (rmclhip_status st = surface_inject_enqueue(sm, reinterpret_cast<xform*>(poses_dev), attrs_dev, first, count, threshold, seed, step, ctx->part_stream))
     return st;
   HIPCHK(bracket_end_and_wait(ctx));
-  if (n_injected_out) *n_injected_out = *sm->h_count;
+  if (n_injected_out) *n_injected_out = *sm->h_count.p;
   return RMCLHIP_OK;
 }
 

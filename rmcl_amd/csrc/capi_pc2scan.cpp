@@ -59,11 +59,7 @@ static rmclhip_status pc2scan_check(const char* who, const uint8_t* data, size_t
 // grow-only scratch of one owner for this launch; points the launch parameters at it
 static hipError_t pc2scan_scratch(Pc2ScanScratch& sc, Pc2ScanParams& p) {
   const size_t n_cells = static_cast<size_t>(p.W) * p.H;
-  if (!sc.h_counters) {
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&sc.h_counters), 4 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&sc.h_counters_dev), sc.h_counters, 0);
-    if (e != hipSuccess) { sc.release(); return e; }
-  }
+  if (const hipError_t e = sc.h_counters.reserve(4)) return e;
   if (const hipError_t e = sc.keys.reserve(n_cells)) return e;
   const size_t n_bin_blocks = pc2scan_blocks(p.n_points);
   if (const hipError_t e = sc.block_counts.reserve(3 * n_bin_blocks + pc2scan_blocks(n_cells))) return e;
@@ -105,11 +101,11 @@ rmclhip_status rmclhip_pointcloud2_to_scan(rmclhip_ctx* ctx, const uint8_t* data
     HIPCHK(ctx->pc2.ranges.reserve(n_cells));
     p.ranges = ctx->pc2.ranges.p;
   }
-  HIPCHK(launch_pc2scan(p, ctx->pc2.h_counters_dev, ctx->pc2_stream));
+  HIPCHK(launch_pc2scan(p, ctx->pc2.h_counters.d, ctx->pc2_stream));
   if (!ranges_is_device && n_cells)
     HIPCHK(hipMemcpyAsync(ranges_out, p.ranges, n_cells * sizeof(float), hipMemcpyDeviceToHost, ctx->pc2_stream));
   HIPCHK(hipStreamSynchronize(ctx->pc2_stream));
-  pc2scan_stats(p, ctx->pc2.h_counters, stats);
+  pc2scan_stats(p, ctx->pc2.h_counters.h, stats);
   return RMCLHIP_OK;
 }
 
@@ -148,9 +144,9 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2_scan(rmclhip_rcc* r, const uint
   p.model_tab = r->d_model_tab.p;
   p.ds_points = n_cells ? r->d_ds_points.p : nullptr;
   p.ds_mask = r->d_ds_mask.p;
-  HIPCHK(launch_pc2scan(p, r->pc2.h_counters_dev, r->stream));
+  HIPCHK(launch_pc2scan(p, r->pc2.h_counters.d, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
-  pc2scan_stats(p, r->pc2.h_counters, stats);
+  pc2scan_stats(p, r->pc2.h_counters.h, stats);
   if (ranges_dev_out) *ranges_dev_out = r->pc2.ranges.p;
   return RMCLHIP_OK;
 }

@@ -31,12 +31,7 @@ void rmclhip_pf_destroy(rmclhip_pf* f) {
   if (!f) return;
   (void)hipSetDevice(f->ctx->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  f->d_beams.release(); f->d_evals.release(); f->d_gpow.release(); f->d_order.release(); f->tag.destroy();
-  pf_surface_release(f);
-  f->refine.release();
-  f->stein.release();
   field_release(f->field);
-  if (f->h_beams) (void)hipHostFree(f->h_beams);
   if (f->ev0) (void)hipEventDestroy(f->ev0);
   if (f->ev1) (void)hipEventDestroy(f->ev1);
   if (f->ev_beams) (void)hipEventDestroy(f->ev_beams);
@@ -78,18 +73,12 @@ static rmclhip_status pf_upload_beams(rmclhip_pf* f, const rmclhip_range_measure
   // the staging buffer may still be the source of the PREVIOUS call's copy: wait for that copy alone (its event), not for whatever else
   // the stream holds -- a motion update enqueued just before this call keeps running (rmclhip_pf_sharded_step)
   if (f->beams_copy_pending) { HIPCHK(hipEventSynchronize(f->ev_beams)); f->beams_copy_pending = false; }
-  if (f->h_beams_cap < nf) {
-    if (f->h_beams) (void)hipHostFree(f->h_beams);
-    f->h_beams = nullptr;
-    f->h_beams_cap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&f->h_beams), nf * sizeof(float), hipHostMallocDefault));
-    f->h_beams_cap = nf;
-  }
-  std::memcpy(f->h_beams, beams, nf * sizeof(float));
+  HIPCHK(f->h_beams.reserve(nf));
+  std::memcpy(f->h_beams.p, beams, nf * sizeof(float));
   f->beams_at_origin = true;
   for (uint32_t b = 0; b < n_beams && f->beams_at_origin; ++b)
     f->beams_at_origin = beams[b].orig.x == 0.0f && beams[b].orig.y == 0.0f && beams[b].orig.z == 0.0f;
-  HIPCHK(hipMemcpyAsync(f->d_beams.p, f->h_beams, nf * sizeof(float), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipMemcpyAsync(f->d_beams.p, f->h_beams.p, nf * sizeof(float), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipEventRecord(f->ev_beams, f->stream));
   f->beams_copy_pending = true;
   return RMCLHIP_OK;
@@ -100,9 +89,9 @@ static rmclhip_status pf_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, 
   if (f->field) return pf_field_enqueue(f, poses, attrs, n, n_beams, Tsb);   // rmclhip_pf_set_field: no tree is touched
   PfParams p;
   std::memset(&p, 0, sizeof(p));
-  p.nodes = f->map->d_nodes;
-  p.qnodes = f->pf_tree ? f->map->d_qnodes_pf : f->map->d_qnodes;
-  p.tris = f->map->d_tris;
+  p.nodes = f->map->d_nodes.p;
+  p.qnodes = f->pf_tree ? f->map->d_qnodes_pf.p : f->map->d_qnodes.p;
+  p.tris = f->map->d_tris.p;
   p.poses = reinterpret_cast<const xform*>(poses);
   p.attrs = attrs;
   p.n_particles = n;
@@ -397,8 +386,8 @@ rmclhip_status rmclhip_resampler_create(rmclhip_ctx* ctx, rmclhip_resampler** ou
   if (e == hipSuccess) e = r->d_psum.reserve(256);
   if (e == hipSuccess) e = r->d_pmax.reserve(256);
   if (e == hipSuccess) e = r->d_out.reserve(2);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_out), 2 * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_res), 8 * sizeof(unsigned long long), hipHostMallocDefault);
+  if (e == hipSuccess) e = r->h_out.reserve(2);
+  if (e == hipSuccess) e = r->h_res.reserve(8);
   if (e == hipSuccess) e = r->tag.create();
   if (e != hipSuccess) {
     rmclhip_resampler_destroy(r);
@@ -413,15 +402,6 @@ void rmclhip_resampler_destroy(rmclhip_resampler* r) {
   if (!r) return;
   (void)hipSetDevice(r->ctx->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);
-  r->d_psum.release();
-  r->d_pmax.release();
-  r->d_out.release();
-  r->d_res_stats.release(); r->d_res_incl.release(); r->d_res_btot.release(); r->d_res_idx.release(); r->d_res_cnt.release();
-  r->d_kld_table.release(); r->d_sys_incl.release(); r->d_sys_btot.release(); r->d_kld_cnt.release();
-  r->d_hyp_u32.release(); r->d_hyp_u64.release(); r->d_hyp_labels.release(); r->d_hyp_rec.release(); r->d_hyp_mom.release();
-  if (r->h_out) (void)hipHostFree(r->h_out);
-  if (r->h_res) (void)hipHostFree(r->h_res);
-  r->tag.destroy();
   if (r->stream) (void)hipStreamDestroy(r->stream);
   ctx_release(r->ctx);
   delete r;
@@ -433,10 +413,10 @@ rmclhip_status rmclhip_resampler_compute_stats(rmclhip_resampler* r, const rmclh
   if (!r || !out || (!attrs_dev && n)) return fail(RMCLHIP_ERR_INVALID, "resampler_compute_stats: null");
   HIPCHK(hipSetDevice(r->ctx->device));
   HIPCHK(launch_likelihood_stats(attrs_dev, n, r->d_psum.p, r->d_pmax.p, r->d_out.p, r->stream));
-  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipMemcpyAsync(r->h_out.p, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
-  out->sum = r->h_out[0];
-  out->max = r->h_out[1];
+  out->sum = r->h_out.p[0];
+  out->max = r->h_out.p[1];
   return RMCLHIP_OK;
 }
 
@@ -445,10 +425,10 @@ rmclhip_status rmclhip_resampler_compute_stats_weights(rmclhip_resampler* r, con
   if (!r || !out || (!weights_dev && n)) return fail(RMCLHIP_ERR_INVALID, "resampler_compute_stats_weights: null");
   HIPCHK(hipSetDevice(r->ctx->device));
   HIPCHK(launch_likelihood_stats_dense(weights_dev, n, r->d_psum.p, r->d_pmax.p, r->d_out.p, r->stream));
-  HIPCHK(hipMemcpyAsync(r->h_out, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipMemcpyAsync(r->h_out.p, r->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
-  out->sum = r->h_out[0];
-  out->max = r->h_out[1];
+  out->sum = r->h_out.p[0];
+  out->max = r->h_out.p[1];
   return RMCLHIP_OK;
 }
 
@@ -532,7 +512,7 @@ RMCL_INTERNAL rmclhip_status residual_prepare_enqueue(ResidualJob& j) {
   HIPCHK(r->d_res_stats.reserve(4));
   // ResidualResamplerCPU.cpp:72-85
   HIPCHK(launch_residual_prepare(j.attrs, j.n_particles, j.n_new, r->d_psum.p, r->d_pmax.p, r->d_res_stats.p, j.st));
-  HIPCHK(hipMemcpyAsync(r->h_res, r->d_res_stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
+  HIPCHK(hipMemcpyAsync(r->h_res.p, r->d_res_stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
   return RMCLHIP_OK;
 }
 RMCL_INTERNAL rmclhip_status residual_draws_enqueue(ResidualJob& j, bool first_try) {
@@ -541,8 +521,8 @@ RMCL_INTERNAL rmclhip_status residual_draws_enqueue(ResidualJob& j, bool first_t
   HIPCHK(hipSetDevice(r->ctx->device));
   if (first_try) {
     double sum; unsigned long long expect;
-    std::memcpy(&sum, &r->h_res[0], sizeof(double));
-    expect = r->h_res[2];
+    std::memcpy(&sum, &r->h_res.p[0], sizeof(double));
+    expect = r->h_res.p[2];
     if (!(sum > 0.0)) return fail(RMCLHIP_ERR_INVALID, "resampler_residual: the likelihoods sum to zero (or NaN): nothing to resample from");
     if (expect == 0ull)
       return fail(RMCLHIP_ERR_INVALID, "resampler_residual: every particle's share L / sum * N_new truncates to 0 -- no draw would ever insert "
@@ -563,11 +543,11 @@ RMCL_INTERNAL rmclhip_status residual_draws_enqueue(ResidualJob& j, bool first_t
   HIPCHK(r->d_res_btot.reserve(nb));
   HIPCHK(launch_residual_draws(j.attrs, j.n_particles, j.n_new, r->d_res_stats.p, j.n_draws, j.seed, j.step, r->d_res_idx.p, r->d_res_cnt.p,
                                r->d_res_incl.p, r->d_res_btot.p, j.st));
-  HIPCHK(hipMemcpyAsync(&r->h_res[4], r->d_res_incl.p + (j.n_draws - 1u), sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
+  HIPCHK(hipMemcpyAsync(&r->h_res.p[4], r->d_res_incl.p + (j.n_draws - 1u), sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
   return RMCLHIP_OK;
 }
 RMCL_INTERNAL void residual_draws_done(ResidualJob& j) {   // after the wait that follows residual_draws_enqueue
-  if (j.active && !j.filled) j.filled = j.r->h_res[4] >= j.n_new;
+  if (j.active && !j.filled) j.filled = j.r->h_res.p[4] >= j.n_new;
 }
 RMCL_INTERNAL rmclhip_status residual_fill_enqueue(ResidualJob& j, bool want_n_draws) {
   if (!j.active) return RMCLHIP_OK;
@@ -579,7 +559,7 @@ RMCL_INTERNAL rmclhip_status residual_fill_enqueue(ResidualJob& j, bool want_n_d
   HIPCHK(launch_residual_fill(reinterpret_cast<const xform*>(j.poses), j.attrs, r->d_res_idx.p, r->d_res_incl.p, j.n_draws,
                               reinterpret_cast<xform*>(j.poses_new), j.attrs_new, j.n_new, j.first, j.count, c8, r->d_res_stats.p, j.seed,
                               j.step, j.st));
-  if (want_n_draws) HIPCHK(hipMemcpyAsync(r->h_res, r->d_res_stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
+  if (want_n_draws) HIPCHK(hipMemcpyAsync(r->h_res.p, r->d_res_stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, j.st));
   return RMCLHIP_OK;
 }
 
@@ -606,7 +586,7 @@ rmclhip_status rmclhip_resampler_residual(rmclhip_resampler* r, const rmclhip_tr
   const bool want = n_draws_out && static_cast<uint64_t>(first) + count == n_new;
   if (rmclhip_status st = residual_fill_enqueue(j, want)) return st;
   HIPCHK(hipStreamSynchronize(j.st));
-  if (want) *n_draws_out = r->h_res[3];
+  if (want) *n_draws_out = r->h_res.p[3];
   return RMCLHIP_OK;
 }
 

@@ -25,11 +25,6 @@ struct PfRank {
   DevBuf<float> d_w_all;                               // cap * world: the dense weights of the n_total <= cap * world particles
   DevBuf<double> d_mom_part, d_mom;                    // 256 * 32; 32 (+ 32 reduced)
   PinnedBuf<double> h_mom;                             // 32 (+ 32)
-  RMCL_INTERNAL void release_buffers() {
-    d_poses.release(); d_poses_new.release(); d_attrs.release(); d_attrs_new.release();
-    d_poses_all.release(); d_poses_pad.release(); d_attrs_all.release(); d_attrs_pad.release();
-    d_w_send.release(); d_w_pad.release(); d_w_all.release(); d_mom_part.release(); d_mom.release(); h_mom.release();
-  }
 };
 
 struct rmclhip_pf_sharded {
@@ -52,12 +47,12 @@ void rmclhip_pf_sharded_destroy(rmclhip_pf_sharded* h) {
   if (!h) return;
   for (PfRank& R : h->ranks) {
     if (R.ctx) (void)hipSetDevice(R.ctx->device);
-    R.release_buffers();
     if (R.rs) rmclhip_resampler_destroy(R.rs);
     if (R.sampler) rmclhip_surface_sampler_destroy(R.sampler);
     if (R.pf) rmclhip_pf_destroy(R.pf);
     if (R.map) rmclhip_map_release(R.map);
     if (R.ctx) rmclhip_ctx_destroy(R.ctx);
+    R = PfRank();   // the rank's buffers go while its device is current
   }
   delete h;
 }
@@ -313,8 +308,8 @@ rmclhip_status rmclhip_pf_sharded_set_surface(rmclhip_pf_sharded* h, const rmclh
 static void pf_sharded_sum_surface_stats(rmclhip_pf_sharded* h, rmclhip_surface_stats* out) {
   std::memset(out, 0, sizeof(*out));
   for (PfRank& R : h->ranks) {
-    if (R.hi == R.lo || !R.pf->h_surf) continue;
-    out->n_particles += R.pf->h_surf[0]; out->n_snapped += R.pf->h_surf[1]; out->n_missed += R.pf->h_surf[2]; out->n_steep += R.pf->h_surf[3];
+    if (R.hi == R.lo || !R.pf->h_surf.p) continue;
+    out->n_particles += R.pf->h_surf.p[0]; out->n_snapped += R.pf->h_surf.p[1]; out->n_missed += R.pf->h_surf.p[2]; out->n_steep += R.pf->h_surf.p[3];
   }
 }
 
@@ -322,7 +317,7 @@ rmclhip_status rmclhip_pf_sharded_get_surface_stats(rmclhip_pf_sharded* h, rmclh
   ApiGuard guard_("rmclhip_pf_sharded_get_surface_stats");
   if (!h || !out) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_get_surface_stats: null");
   for (PfRank& R : h->ranks) {   // (a step leaves the counts' copy behind the motion launch on the rank's stream)
-    if (R.hi == R.lo || !R.pf->h_surf) continue;
+    if (R.hi == R.lo || !R.pf->h_surf.p) continue;
     HIPCHK(hipSetDevice(R.ctx->device));
     HIPCHK(hipStreamSynchronize(R.pf->stream));
   }
@@ -395,7 +390,7 @@ rmclhip_status rmclhip_pf_sharded_inject_surface(rmclhip_pf_sharded* h, double p
   trace_mark("inject:");
   for (uint32_t r = 0; r < h->ranks.size(); ++r) {   // every rank's launch is in flight before the host waits for any
     PfRank& R = h->ranks[r];
-    *R.sampler->h_count = 0u;   // (of a rank without particles too: the sum below reads every rank's)
+    *R.sampler->h_count.p = 0u;   // (of a rank without particles too: the sum below reads every rank's)
     if (R.hi == R.lo) continue;
     HIPCHK(hipSetDevice(R.ctx->device));
     if (rmclhip_status st = surface_inject_enqueue(R.sampler, R.d_poses.p, R.d_attrs.p, R.lo, R.hi - R.lo, threshold, seed, step, h->comm->streams[r]))
@@ -404,7 +399,7 @@ rmclhip_status rmclhip_pf_sharded_inject_surface(rmclhip_pf_sharded* h, double p
   }
   if (rmclhip_status st = comm_wait_all(h->comm)) return st;
   uint32_t total = 0u;
-  for (PfRank& R : h->ranks) total += *R.sampler->h_count;
+  for (PfRank& R : h->ranks) total += *R.sampler->h_count.p;
   if (n_injected_out) *n_injected_out = total;
   return RMCLHIP_OK;
 }
@@ -530,11 +525,11 @@ rmclhip_status rmclhip_pf_allreduce_stats(rmclhip_pf_sharded* h, rmclhip_likelih
   // the host needs ONE copy: rank 0's (the other ranks keep theirs on the device, ordered on their streams)
   PfRank& R0 = h->ranks[0];
   HIPCHK(hipSetDevice(R0.ctx->device));
-  HIPCHK(hipMemcpyAsync(R0.rs->h_out, R0.rs->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, h->comm->streams[0]));
+  HIPCHK(hipMemcpyAsync(R0.rs->h_out.p, R0.rs->d_out.p, 2 * sizeof(float), hipMemcpyDeviceToHost, h->comm->streams[0]));
   HIPCHK(hipStreamSynchronize(h->comm->streams[0]));
   trace('W', 0u);
-  out->sum = R0.rs->h_out[0];
-  out->max = R0.rs->h_out[1];
+  out->sum = R0.rs->h_out.p[0];
+  out->max = R0.rs->h_out.p[1];
   return RMCLHIP_OK;
 }
 

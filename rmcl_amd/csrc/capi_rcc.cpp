@@ -16,22 +16,17 @@ rmclhip_status rmclhip_rcc_create(rmclhip_ctx* ctx, rmclhip_map* map, rmclhip_rc
   hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreate(&r->ev0);
   if (e == hipSuccess) e = hipEventCreate(&r->ev1);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_stats), sizeof(cstats) * 2, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_stats_dev), r->h_stats, 0);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_state), sizeof(MicpState), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_state_dev), r->h_state, 0);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_state), 2 * sizeof(MicpState));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_fast_status), sizeof(MicpFastStatus), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_fast_status_dev), r->h_fast_status, 0);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_done), 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_done_dev), r->h_done, 0);
-  if (e == hipSuccess) r->h_done[0] = r->h_done[1] = 0ull;
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_mom), sizeof(MicpHostBlock), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_mom_dev), r->h_mom, 0);
-  if (e == hipSuccess) std::memset(r->h_mom, 0, sizeof(MicpHostBlock));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_counter), sizeof(uint32_t));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&r->h_call), sizeof(MicpCall), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&r->d_call), sizeof(MicpCall));
+  if (e == hipSuccess) e = r->h_stats.reserve(2);
+  if (e == hipSuccess) e = r->h_state.reserve(1);
+  if (e == hipSuccess) e = r->d_state.reserve(2);
+  if (e == hipSuccess) e = r->h_fast_status.reserve(1);
+  if (e == hipSuccess) e = r->h_done.reserve(2);
+  if (e == hipSuccess) r->h_done.h[0] = r->h_done.h[1] = 0ull;
+  if (e == hipSuccess) e = r->h_mom.reserve(1);
+  if (e == hipSuccess) std::memset(r->h_mom.h, 0, sizeof(MicpHostBlock));
+  if (e == hipSuccess) e = r->d_counter.reserve(1);
+  if (e == hipSuccess) e = r->h_call.reserve(1);
+  if (e == hipSuccess) e = r->d_call.reserve(1);
   if (e != hipSuccess) {
     rmclhip_rcc_destroy(r);
     return fail(RMCLHIP_ERR_HIP, std::string("rcc_create: ") + hipGetErrorString(e));
@@ -50,39 +45,14 @@ void rmclhip_rcc_destroy(rmclhip_rcc* r) {
     if (e_ != hipSuccess && std::getenv("RMCLHIP_DEBUG")) std::fprintf(stderr, "[rmclhip debug] %s -> %s\n", #x, hipGetErrorString(e_)); \
   } while (0)
   if (r->stream) DBG_STEP(hipStreamSynchronize(r->stream));
-  r->d_model_tab.release(); r->d_ds_points.release(); r->d_ds_mask.release();
-  r->d_hits.release(); r->d_ranges.release(); r->d_points.release(); r->d_normals.release(); r->d_face_ids.release();
-  r->d_partials.release(); r->d_pinfo_partials.release(); r->d_pinfo_rows.release(); r->d_Tbm.release(); r->d_Tsm.release(); r->d_Tms.release(); r->d_Tdelta.release();
-  r->d_bstats.release();
-  if (r->h_bT) DBG_STEP(hipHostFree(r->h_bT));
-  if (r->h_bS) DBG_STEP(hipHostFree(r->h_bS));
-  r->d_raw.release();
   DBG_STEP(hipPeekAtLastError());
-  if (r->h_stats) DBG_STEP(hipHostFree(r->h_stats));
-  if (r->h_state) DBG_STEP(hipHostFree(r->h_state));
-  if (r->d_state) DBG_STEP(hipFree(r->d_state));
-  if (r->d_counter) DBG_STEP(hipFree(r->d_counter));
   if (r->micp_exec) DBG_STEP(hipGraphExecDestroy(r->micp_exec));
   if (r->micp_graph) DBG_STEP(hipGraphDestroy(r->micp_graph));
-  if (r->h_fast_status) DBG_STEP(hipHostFree(r->h_fast_status));
-  if (r->h_done) DBG_STEP(hipHostFree(r->h_done));
-  if (r->h_mom) DBG_STEP(hipHostFree(r->h_mom));
-  r->d_cpc_rec.release();
-  r->d_fast_partials.release(); r->d_fast_mask.release(); r->d_tile_planes.release();
-  if (r->d_fold_rows) DBG_STEP(hipFree(r->d_fold_rows));
   if (r->ev_join) DBG_STEP(hipEventDestroy(r->ev_join));
-  if (r->d_join_flags) DBG_STEP(hipFree(r->d_join_flags));
-  r->d_multi_blob.release();
-  r->d_seg_ranges.release(); r->d_seg_normals.release(); r->d_seg_real.release(); r->d_seg_labels.release(); r->d_seg_block_counts.release();
-  if (r->h_seg_counts) DBG_STEP(hipHostFree(r->h_seg_counts));
-  r->pc2.release(); r->d_deskew_aux.release();
-  if (r->h_multi_state) DBG_STEP(hipHostFree(r->h_multi_state));
-  if (r->h_multi_status) DBG_STEP(hipHostFree(r->h_multi_status));
-  if (r->h_call) DBG_STEP(hipHostFree(r->h_call));
-  if (r->d_call) DBG_STEP(hipFree(r->d_call));
   if (r->ev0) DBG_STEP(hipEventDestroy(r->ev0));
   if (r->ev1) DBG_STEP(hipEventDestroy(r->ev1));
   if (r->stream) DBG_STEP(hipStreamDestroy(r->stream));
+#undef DBG_STEP
   rmclhip_map_release(r->map);
   ctx_release(r->ctx);
   delete r;
@@ -255,14 +225,13 @@ rmclhip_status rmclhip_rcc_set_dataset_from_ranges(rmclhip_rcc* r, const float* 
   DevBuf<float> d_r;
   HIPCHK(d_r.reserve(n));
   hipError_t e = upload_on(r->stream, d_r.p, ranges, n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemsetAsync(r->d_counter, 0, sizeof(uint32_t), r->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(r->d_counter.p, 0, sizeof(uint32_t), r->stream);
   if (e == hipSuccess)
     e = launch_dataset_from_ranges(d_r.p, r->d_model_tab.p, r->kind, r->W, r->H, r->orig, r->pin_fc, r->range.min, r->range.max,
-                                   r->d_ds_points.p, r->d_ds_mask.p, r->d_counter, r->stream);
+                                   r->d_ds_points.p, r->d_ds_mask.p, r->d_counter.p, r->stream);
   uint32_t nv = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&nv, r->d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&nv, r->d_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-  d_r.release();
   r->ds_pts = r->d_ds_points.p;
   r->ds_msk = r->d_ds_mask.p;
   if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("dataset_from_ranges: ") + hipGetErrorString(e));
@@ -322,13 +291,13 @@ rmclhip_status rmclhip_rcc_set_input_pointcloud2(rmclhip_rcc* r, const uint8_t* 
     HIPCHK(hipMemcpyAsync(r->d_raw.p, data, nbytes, hipMemcpyHostToDevice, r->stream));
     d_data = r->d_raw.p;
   }
-  HIPCHK(hipMemsetAsync(r->d_counter, 0, sizeof(uint32_t), r->stream));
+  HIPCHK(hipMemsetAsync(r->d_counter.p, 0, sizeof(uint32_t), r->stream));
   HIPCHK(launch_pointcloud2_unpack(d_data, L->point_step, L->row_step, L->offset_x, L->offset_y, L->offset_z, L->datatype == 8u,
                                    h.skip_begin, h.increment, w.skip_begin, w.increment, ow, oh, range.min, range.max,
-                                   r->d_model_tab.p, r->d_ds_points.p, r->d_ds_mask.p, r->d_counter, r->stream));
+                                   r->d_model_tab.p, r->d_ds_points.p, r->d_ds_mask.p, r->d_counter.p, r->stream));
   if (rmclhip_status st = rebuild_tile_planes(r)) return st;   // the directions just written are the O1Dn model
   uint32_t nv = 0;
-  HIPCHK(hipMemcpyAsync(&nv, r->d_counter, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipMemcpyAsync(&nv, r->d_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
   if (n_valid_out) *n_valid_out = nv;
   return RMCLHIP_OK;
@@ -412,13 +381,13 @@ RMCL_INTERNAL int find_variant(const rmclhip_rcc* r, uint32_t nposes) {
 RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t nposes, int kind) {
   const int v = kind >= 0 ? kind : find_variant(r, nposes);
   std::memset(&p, 0, sizeof(p));
-  p.nodes = r->map->d_nodes;
-  p.qnodes = r->map->d_qnodes;
-  p.cnodes = r->map->d_cnodes;
-  p.cnodes16 = r->descent_wide ? r->map->d_cnodes16 : nullptr;
-  p.tris = r->map->d_tris;
+  p.nodes = r->map->d_nodes.p;
+  p.qnodes = r->map->d_qnodes.p;
+  p.cnodes = r->map->d_cnodes.p;
+  p.cnodes16 = r->descent_wide ? r->map->d_cnodes16.p : nullptr;
+  p.tris = r->map->d_tris.p;
   p.n_nodes = r->map->info.n_nodes;
-  p.frontier = r->map->d_frontier;
+  p.frontier = r->map->d_frontier.p;
   p.n_frontier = r->map->n_frontier;
   p.frontier_groups = r->map->d_frontier_groups;
   {
@@ -450,9 +419,9 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
     // the same BVH2 cut at leaves of <= 2 instead of <= 4 triangles, the same record array (layout.h): pose batches 6-10 % faster
     // (profiles/r03_find_variants_ab.txt).  That tree has its own node numbering, hence its own frontier table.
     uint32_t need = r->map->info.stack_need;
-    if ((v == 24 || v == 22) && r->map->d_qnodes_pf != nullptr) {
-      p.qnodes = r->map->d_qnodes_pf;
-      p.frontier = r->map->d_frontier_pf;
+    if ((v == 24 || v == 22) && r->map->d_qnodes_pf.p != nullptr) {
+      p.qnodes = r->map->d_qnodes_pf.p;
+      p.frontier = r->map->d_frontier_pf.p;
       p.n_frontier = r->map->n_frontier_pf;
       p.frontier_groups = r->map->d_frontier_groups_pf;
       need = r->map->info.stack_need_pf;
@@ -548,9 +517,9 @@ RMCL_INTERNAL hipError_t wait_done(const rmclhip_ctx* ctx, volatile const unsign
 RMCL_INTERNAL hipError_t wait_chain_end(rmclhip_rcc* r) {
   if (r->ctx->wait_block.load(std::memory_order_relaxed)) return hipStreamSynchronize(r->stream);
   const uint32_t seq = next_seq(r);
-  if (const hipError_t e = launch_host_tag(r->h_done_dev, seq, r->stream)) return e;
+  if (const hipError_t e = launch_host_tag(r->h_done.d, seq, r->stream)) return e;
   DoneCheck none;
-  return wait_done(r->ctx, r->h_done, seq, none, r->stream);
+  return wait_done(r->ctx, r->h_done.h, seq, none, r->stream);
 }
 
 RMCL_INTERNAL float adaptive_max_dist(const rmclhip_rcc* r, double p) {
@@ -574,7 +543,7 @@ RMCL_INTERNAL void gate_band(const rmclhip_rcc* r, float centre, float* lo, floa
 
 // wait for the tag of a publish launch and take a verified copy of the block (see wait_done for why the sum is checked)
 RMCL_INTERNAL hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, float hi, float rho_cap, float tau_cap) {
-  const MicpHostBlock* hb = r->h_mom;
+  const MicpHostBlock* hb = r->h_mom.h;
   auto block_sum = [hb]() -> uint32_t {
     uint32_t x = xor_host(hb->mom, sizeof(hb->mom));
     const uint32_t code = *reinterpret_cast<const volatile uint32_t*>(&hb->code);
@@ -588,7 +557,7 @@ RMCL_INTERNAL hipError_t wait_moments(rmclhip_rcc* r, uint32_t seq, float lo, fl
   if (r->ctx->wait_block.load(std::memory_order_relaxed)) e = hipStreamSynchronize(r->stream);
   else {
     const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-    volatile const unsigned long long* tag = r->h_done;
+    volatile const unsigned long long* tag = r->h_done.h;
     for (uint32_t spins = 0;; ++spins) {
       const unsigned long long t = *tag;
       if (static_cast<uint32_t>(t) == seq) {
@@ -644,12 +613,12 @@ RMCL_INTERNAL rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp,
   fp.mom_gate_lo = lo; fp.mom_gate_hi = hi; fp.mom_rho_cap = rho_cap; fp.mom_tau_cap = tau_cap;
   fp.mom_partials = r->d_fast_partials.p;
   fp.mom_unc_mask = r->d_fast_mask.p;
-  if (!r->d_fold_rows) {
+  if (!r->d_fold_rows.p) {
     const size_t bytes = kMicpFoldBlocks * kMicpFastMoments * sizeof(double) + kMicpFoldBlocks * sizeof(uint32_t);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&r->d_fold_rows), bytes));
-    HIPCHK(hipMemset(r->d_fold_rows, 0, bytes));
+    HIPCHK(r->d_fold_rows.reserve((bytes + sizeof(double) - 1u) / sizeof(double)));
+    HIPCHK(hipMemset(r->d_fold_rows.p, 0, bytes));
     HIPCHK(hipDeviceSynchronize());
-    r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows + kMicpFoldBlocks * kMicpFastMoments);
+    r->d_fold_flags = reinterpret_cast<uint32_t*>(r->d_fold_rows.p + kMicpFoldBlocks * kMicpFastMoments);
   }
   r->last_fast_rows = nb; r->last_fast_words = wpb * nb;
   *nb_out = nb; *wpb_out = wpb;
@@ -676,7 +645,7 @@ RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xfo
     if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, lo, hi, rho_cap, tau_cap, &nb, &wpb)) return st;
     HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
     HIPCHK(launch_micp_publish_tiled(r->ds_pts, r->d_points.p, r->d_normals.p, nred, nb, r->d_fast_partials.p, r->d_fast_mask.p, r->W,
-                                     fp.tiles_x, fp.tile_w_log2, wpb, r->h_mom_dev, r->h_done_dev, seq, r->d_fold_rows, r->d_fold_flags,
+                                     fp.tiles_x, fp.tile_w_log2, wpb, r->h_mom.d, r->h_done.d, seq, r->d_fold_rows.p, r->d_fold_flags,
                                      r->stream));
   } else {
     HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(micp_fast_blocks(nred)) * kMicpFastMoments));
@@ -686,7 +655,7 @@ RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xfo
     cl.gate_lo = lo; cl.gate_hi = hi; cl.max_dist = hi; cl.rho_cap = rho_cap; cl.tau_cap = tau_cap; cl.seq = seq;
     HIPCHK(launch_find(fp, r->kind, fv, r->stream));
     HIPCHK(launch_micp_moments_publish(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                       r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom_dev, r->h_done_dev, r->stream));
+                                       r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom.d, r->h_done.d, r->stream));
   }
   return RMCLHIP_OK;
 }
@@ -827,8 +796,8 @@ RMCL_INTERNAL rmclhip_status ensure_near_grid(rmclhip_map* m, hipStream_t stream
     g.inv[k] = static_cast<float>(g.n[k]) / ext[k];
     total *= g.n[k];
   }
-  uint32_t* d_cells = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_cells), total * sizeof(uint32_t));
+  DevBuf<uint32_t> cells, coarse;
+  hipError_t e = cells.reserve(total);
   if (e != hipSuccess) { slot.failed = true; (void)hipGetLastError(); return RMCLHIP_OK; }   // (a map too large for the table simply runs without it)
   // coarse to fine: a grid of a quarter of the resolution first (its cells far from any surface are the expensive, unbounded queries:
   // 64 x fewer of them), then the full grid with every cell seeded from its coarse parent
@@ -838,23 +807,21 @@ RMCL_INTERNAL rmclhip_status ensure_near_grid(rmclhip_map* m, hipStream_t stream
   NearGrid c = g;
   size_t ctotal = 1;
   for (int k = 0; k < 3; ++k) { c.n[k] = (g.n[k] + 3u) / 4u; c.inv[k] = g.inv[k] * static_cast<float>(c.n[k]) / static_cast<float>(g.n[k]); ctotal *= c.n[k]; }
-  uint32_t* d_coarse = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&d_coarse), ctotal * sizeof(uint32_t));
+  e = coarse.reserve(ctotal);
   if (e == hipSuccess)
-    e = launch_cpc_find(m->d_nodes, m->d_tris, nullptr, static_cast<uint32_t>(ctotal), 0.f, xidentity(), xidentity(), nullptr, nullptr, nullptr, nullptr,
-                        nullptr, false, stream, nullptr, d_coarse, m->info.n_records, 3.0e38f, nullptr, &c);
-  c.cells = d_coarse;
+    e = launch_cpc_find(m->d_nodes.p, m->d_tris.p, nullptr, static_cast<uint32_t>(ctotal), 0.f, xidentity(), xidentity(), nullptr, nullptr, nullptr, nullptr,
+                        nullptr, false, stream, nullptr, coarse.p, m->info.n_records, 3.0e38f, nullptr, &c);
+  c.cells = coarse.p;
   if (e == hipSuccess)
-    e = launch_cpc_find(m->d_nodes, m->d_tris, nullptr, static_cast<uint32_t>(total), 0.f, xidentity(), xidentity(), nullptr, nullptr, nullptr, nullptr,
-                        nullptr, false, stream, nullptr, d_cells, m->info.n_records, 3.0e38f, &c, &g, skip_d2);
+    e = launch_cpc_find(m->d_nodes.p, m->d_tris.p, nullptr, static_cast<uint32_t>(total), 0.f, xidentity(), xidentity(), nullptr, nullptr, nullptr, nullptr,
+                        nullptr, false, stream, nullptr, cells.p, m->info.n_records, 3.0e38f, &c, &g, skip_d2);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (d_coarse) (void)hipFree(d_coarse);
   if (e != hipSuccess) {
-    (void)hipFree(d_cells);
     slot.failed = true;
     return fail(RMCLHIP_ERR_HIP, std::string("near grid: ") + hipGetErrorString(e));
   }
-  g.cells = d_cells;
+  slot.cells = std::move(cells);
+  g.cells = slot.cells.p;
   slot.g = g;
   slot.ready = true;
   m->bytes += total * sizeof(uint32_t);
@@ -884,7 +851,7 @@ rmclhip_status rmclhip_rcc_find_cpc(rmclhip_rcc* r, const rmclhip_transform* Tbm
   }
   const NearGrid* grid = nullptr;
   if (r->cpc_grid) { if (rmclhip_status gst = ensure_near_grid(r->map, r->stream, false, &grid)) return gst; }
-  HIPCHK(launch_cpc_find(quad ? r->map->d_cnodes : r->map->d_nodes, r->map->d_tris, r->ds_pts, r->n_dataset,
+  HIPCHK(launch_cpc_find(quad ? r->map->d_cnodes.p : r->map->d_nodes.p, r->map->d_tris.p, r->ds_pts, r->n_dataset,
                          r->max_dist, Tsm, xinv(Tsm), (r->out_mask & RMCLHIP_OUT_HITS) ? r->d_hits.p : nullptr,
                          (r->out_mask & RMCLHIP_OUT_RANGES) ? r->d_ranges.p : nullptr, (r->out_mask & RMCLHIP_OUT_POINTS) ? r->d_points.p : nullptr,
                          (r->out_mask & RMCLHIP_OUT_NORMALS) ? r->d_normals.p : nullptr,
@@ -982,7 +949,7 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
         MicpCallLite cl{};
         cl.gate_lo = lo; cl.gate_hi = hi; cl.max_dist = maxd; cl.rho_cap = rho_cap; cl.tau_cap = tau_cap; cl.seq = next_seq(r);
         HIPCHK(launch_micp_moments_publish(r->ds_pts, r->ds_has_mask ? r->ds_msk : nullptr, r->d_points.p, r->d_normals.p, r->d_hits.p, nred,
-                                           r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom_dev, r->h_done_dev, r->stream));
+                                           r->d_fast_partials.p, r->d_fast_mask.p, cl, r->h_mom.d, r->h_done.d, r->stream));
         HIPCHK(wait_moments(r, cl.seq, lo, hi, rho_cap, tau_cap));
         if (!r->mset.valid) r->mset_passes = 2u;   // too many undecided correspondences: a second pass would find as many
       }
@@ -995,8 +962,8 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
   }
   ReduceTail tail;
   tail.mode = kTailStats;
-  tail.stats_out = r->h_stats_dev;  // host-mapped: the finalize launch writes the 64-B result straight to the host
-  tail.done = r->h_done_dev;
+  tail.stats_out = r->h_stats.d;  // host-mapped: the finalize launch writes the 64-B result straight to the host
+  tail.done = r->h_done.d;
   tail.seq = next_seq(r);
   const bool timed = r->kernel_timing;
   r->find_timing_pending = false;   // the events are reused
@@ -1005,10 +972,10 @@ rmclhip_status rmclhip_rcc_compute_cross_statistics(rmclhip_rcc* r, const rmclhi
   if (rmclhip_status st = reduce_enqueue(r, to_x(T_snew_sold), nullptr, adaptive_max_dist(r, convergence_progress), 1, tail))
     return st;
   if (timed) HIPCHK(hipEventRecord(r->ev1, r->stream));
-  DoneCheck chk; chk.base = &r->h_stats[0]; chk.base_bytes = sizeof(cstats);
-  HIPCHK(wait_done(r->ctx, r->h_done, tail.seq, chk, r->stream));
+  DoneCheck chk; chk.base = &r->h_stats.h[0]; chk.base_bytes = sizeof(cstats);
+  HIPCHK(wait_done(r->ctx, r->h_done.h, tail.seq, chk, r->stream));
   r->reduce_timing_pending = timed;   // the events are read when rmclhip_rcc_last_kernel_ms asks for them
-  from_cs(r->h_stats[0], out);
+  from_cs(r->h_stats.h[0], out);
   return RMCLHIP_OK;
 }
 
@@ -1133,20 +1100,16 @@ RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx) {
   if (ctx->p2l_stream != nullptr) return RMCLHIP_OK;
   hipStream_t s = nullptr;
   HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_stats), sizeof(cstats), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_stats_dev), ctx->p2l_h_stats, 0);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->p2l_h_done), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->p2l_h_done_dev), ctx->p2l_h_done, 0);
+  hipError_t e = ctx->p2l_h_stats.reserve(1);
+  if (e == hipSuccess) e = ctx->p2l_h_done.reserve(1);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    if (ctx->p2l_h_stats) (void)hipHostFree(ctx->p2l_h_stats);
-    if (ctx->p2l_h_done) (void)hipHostFree(ctx->p2l_h_done);
-    ctx->p2l_h_stats = nullptr; ctx->p2l_h_done = nullptr;
+    ctx->p2l_h_stats.release(); ctx->p2l_h_done.release();
     (void)hipStreamDestroy(s);
     return fail(RMCLHIP_ERR_HIP, std::string("statistics_p2l: ") + hipGetErrorString(e));
   }
-  *ctx->p2l_h_done = 0ull;
-  ctx->p2l_stream = s;   // last: the destructor frees the scratch iff the stream exists
+  *ctx->p2l_h_done.h = 0ull;
+  ctx->p2l_stream = s;
   return RMCLHIP_OK;
 }
 
@@ -1162,25 +1125,20 @@ rmclhip_status rmclhip_statistics_p2l(rmclhip_ctx* ctx, const rmclhip_transform*
   HIPCHK(hipSetDevice(ctx->device));
   if (rmclhip_status st = ctx_p2l_ensure(ctx)) return st;
   const uint32_t nb = reduce_num_blocks(n, 1);
-  if (ctx->p2l_partials_cap < static_cast<size_t>(nb) * 16u) {
-    if (ctx->p2l_partials) (void)hipFree(ctx->p2l_partials);
-    ctx->p2l_partials = nullptr; ctx->p2l_partials_cap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&ctx->p2l_partials), static_cast<size_t>(nb) * 16u * sizeof(double)));
-    ctx->p2l_partials_cap = static_cast<size_t>(nb) * 16u;
-  }
+  HIPCHK(ctx->p2l_partials.reserve(static_cast<size_t>(nb) * 16u));
   ReduceParams p;
   std::memset(&p, 0, sizeof(p));
   p.dataset_points = dataset_points; p.dataset_mask = dataset_mask;
   p.model_points = model_points; p.model_normals = model_normals; p.model_mask = model_mask;
   p.n = n; p.nposes = 1; p.max_dist = max_dist;
   p.Tpre = to_x(Tpre);
-  p.partials = ctx->p2l_partials; p.nblocks = nb;
+  p.partials = ctx->p2l_partials.p; p.nblocks = nb;
   if (++ctx->p2l_seq == 0u) ctx->p2l_seq = 1u;
   HIPCHK(launch_reduce_partials(p, ctx->p2l_stream));
-  HIPCHK(launch_reduce_finalize(ctx->p2l_partials, nb, 1, ctx->p2l_h_stats_dev, ctx->p2l_h_done_dev, ctx->p2l_seq, ctx->p2l_stream));
-  DoneCheck chk; chk.base = ctx->p2l_h_stats; chk.base_bytes = sizeof(cstats);
-  HIPCHK(wait_done(ctx, ctx->p2l_h_done, ctx->p2l_seq, chk, ctx->p2l_stream));
-  from_cs(*ctx->p2l_h_stats, out);
+  HIPCHK(launch_reduce_finalize(ctx->p2l_partials.p, nb, 1, ctx->p2l_h_stats.d, ctx->p2l_h_done.d, ctx->p2l_seq, ctx->p2l_stream));
+  DoneCheck chk; chk.base = ctx->p2l_h_stats.h; chk.base_bytes = sizeof(cstats);
+  HIPCHK(wait_done(ctx, ctx->p2l_h_done.h, ctx->p2l_seq, chk, ctx->p2l_stream));
+  from_cs(*ctx->p2l_h_stats.h, out);
   return RMCLHIP_OK;
 }
 
@@ -1195,27 +1153,21 @@ rmclhip_status rmclhip_rcc_correct_batch(rmclhip_rcc* r, const rmclhip_transform
   HIPCHK(hipSetDevice(r->ctx->device));
   const size_t n = static_cast<size_t>(r->W) * r->H;
   if (r->n_dataset != n) return fail(RMCLHIP_ERR_INVALID, "correct_batch: dataset size != model size");
-  if (nposes > r->h_batch_cap) {
+  if (nposes > r->h_bT.cap || nposes > r->h_bS.cap) {
     HIPCHK(hipStreamSynchronize(r->stream));
-    if (r->h_bT) (void)hipHostFree(r->h_bT);
-    if (r->h_bS) (void)hipHostFree(r->h_bS);
-    r->h_bT = nullptr; r->h_bS = nullptr; r->h_batch_cap = 0;
     const uint32_t cap = std::max(nposes, 64u);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_bT), sizeof(xform) * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_bT_dev), r->h_bT, 0));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_bS), sizeof(cstats) * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_bS_dev), r->h_bS, 0));
-    r->h_batch_cap = cap;
+    HIPCHK(r->h_bT.reserve(cap));
+    HIPCHK(r->h_bS.reserve(cap));
   }
   if (rmclhip_status st = find_batch_enqueue(r, Tbm, nposes)) return st;
   ReduceTail tail;
   tail.mode = kTailBatchSolve;
-  tail.Tdelta_out = r->h_bT_dev;
-  tail.stats_out = r->h_bS_dev;
+  tail.Tdelta_out = r->h_bT.d;
+  tail.stats_out = r->h_bS.d;
   if (rmclhip_status st = reduce_enqueue(r, xidentity(), nullptr, r->max_dist, nposes, tail)) return st;
   HIPCHK(wait_chain_end(r));
-  std::memcpy(Tdelta_out, r->h_bT, sizeof(xform) * nposes);
-  if (stats_out) std::memcpy(stats_out, r->h_bS, sizeof(cstats) * nposes);
+  std::memcpy(Tdelta_out, r->h_bT.h, sizeof(xform) * nposes);
+  if (stats_out) std::memcpy(stats_out, r->h_bS.h, sizeof(cstats) * nposes);
   return RMCLHIP_OK;
 }
 

@@ -22,11 +22,10 @@ void rmclhip_rcc_sharded_destroy(rmclhip_rcc_sharded* h) {
   if (!h) return;
   for (RccRank& R : h->ranks) {
     if (R.ctx) (void)hipSetDevice(R.ctx->device);
-    R.h_Tdelta.release();
-    R.h_stats.release();
     if (R.rcc) rmclhip_rcc_destroy(R.rcc);
     if (R.map) rmclhip_map_release(R.map);
     if (R.ctx) rmclhip_ctx_destroy(R.ctx);
+    R = RccRank();   // the rank's staging goes while its device is current
   }
   delete h;
 }

@@ -84,7 +84,7 @@ rmclhip_status rmclhip_rcc_autotune(rmclhip_rcc* r, const rmclhip_transform* Tbm
   const TuneCand* best = nullptr;
   float best_ms = 0.f;
   for (const TuneCand& c : kTuneSingle) {
-    if (c.kind == 32 && (r->kind == kModelOnDn || r->map->d_cnodes == nullptr)) continue;   // (no common pyramid / no child-major nodes: kind 23)
+    if (c.kind == 32 && (r->kind == kModelOnDn || r->map->d_cnodes.p == nullptr)) continue;   // (no common pyramid / no child-major nodes: kind 23)
     r->tuned_kind = c.kind; r->tuned_frontier = c.frontier;
     if (c.descent_cap != 0u) r->descent_final_cap = c.descent_cap;
     float t[5];
@@ -185,7 +185,7 @@ rmclhip_status rmclhip_rcc_time_reduce(rmclhip_rcc* r, const rmclhip_transform* 
   const xform T = to_x(Tpre);
   ReduceTail tail;
   tail.mode = kTailStats;
-  tail.stats_out = r->h_stats_dev + 1;
+  tail.stats_out = r->h_stats.d + 1;
   if (rmclhip_status st = reduce_enqueue(r, T, nullptr, r->max_dist, 1, tail)) return st;
   HIPCHK(hipStreamSynchronize(r->stream));
   r->reduce_timing_pending = false;
@@ -375,14 +375,14 @@ rmclhip_status rmclhip_debug_probe_find(rmclhip_rcc* r, const rmclhip_transform*
   const size_t ntiles = static_cast<size_t>(p.tiles_x) * p.tiles_y, dwords = ntiles * 512u;
   if (n_tiles_out) *n_tiles_out = static_cast<uint32_t>(ntiles);
   if (log_cap_dwords < dwords) return fail(RMCLHIP_ERR_INVALID, "debug_probe_find: log buffer too small");
-  uint32_t* d_log = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_log), dwords * sizeof(uint32_t)));
+  DevBuf<uint32_t> log;
+  HIPCHK(log.reserve(dwords));
+  uint32_t* const d_log = log.p;
   hipError_t e = hipMemsetAsync(d_log, 0, dwords * sizeof(uint32_t), r->stream);
   // a few launches first: the timeline of a warm launch (map in L2) is the one of interest
   for (int i = 0; i < 3 && e == hipSuccess; ++i) e = launch_find_probe(p, mode, d_log, r->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(log_out, d_log, dwords * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-  (void)hipFree(d_log);
   if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("debug_probe_find: ") + hipGetErrorString(e));
   return RMCLHIP_OK;
 }
@@ -431,8 +431,9 @@ rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* r, const rmclhip_transform*
   const size_t dwords = static_cast<size_t>(nblocks) * 4u * ((variant == 31 || variant == 32) ? 24u : 8u);
   if (n_waves_out) *n_waves_out = nblocks * 4u;
   if (cap_dwords < dwords) return fail(RMCLHIP_ERR_INVALID, "debug_wave_clock: buffer too small");
-  uint32_t* d = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&d), dwords * sizeof(uint32_t)));
+  DevBuf<uint32_t> d_clock;
+  HIPCHK(d_clock.reserve(dwords));
+  uint32_t* const d = d_clock.p;
   hipError_t e = hipSuccess;
   FindParams warm = p;
   for (int i = 0; i < 5 && e == hipSuccess; ++i) e = launch_find(warm, r->kind, variant, r->stream);   // warm, un-instrumented
@@ -441,7 +442,6 @@ rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* r, const rmclhip_transform*
   if (e == hipSuccess) e = launch_find(p, r->kind, variant, r->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d, dwords * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(RMCLHIP_ERR_HIP, std::string("debug_wave_clock: ") + hipGetErrorString(e));
   return RMCLHIP_OK;
 }

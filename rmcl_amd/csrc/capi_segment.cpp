@@ -18,10 +18,7 @@ static rmclhip_status segment_check(const char* who, const rmclhip_rcc* r, const
 static rmclhip_status segment_enqueue(rmclhip_rcc* r, const rmclhip_transform* Tbm, const float* ranges_real, int ranges_is_device,
                                       const rmclhip_segmentation_params* sp, const rmclhip_segmentation_views* out) {
   const size_t n = static_cast<size_t>(r->W) * r->H;
-  if (!r->h_seg_counts) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_seg_counts), 2 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->h_seg_counts_dev), r->h_seg_counts, 0));
-  }
+  HIPCHK(r->h_seg_counts.reserve(2));
   HIPCHK(r->d_seg_ranges.reserve(n));
   HIPCHK(r->d_seg_normals.reserve(3 * n));
   HIPCHK(r->d_seg_block_counts.reserve(2 * ((n + kSegBlock - 1u) / kSegBlock)));
@@ -61,7 +58,7 @@ static rmclhip_status segment_enqueue(rmclhip_rcc* r, const rmclhip_transform* T
   p.outlier_scan_xyz = v.outlier_scan_xyz_dev;
   p.outlier_map_xyz = v.outlier_map_xyz_dev;
   p.counts_dev = v.counts_dev;
-  p.counts_host = r->h_seg_counts_dev;
+  p.counts_host = r->h_seg_counts.d;
   HIPCHK(launch_segment(p, r->stream));
   return RMCLHIP_OK;
 }
@@ -87,6 +84,6 @@ rmclhip_status rmclhip_rcc_segment(rmclhip_rcc* r, const rmclhip_transform* Tbm,
   if (rmclhip_status st = segment_enqueue(r, Tbm, ranges_real, ranges_is_device, sp, out)) return st;
   // the scatter launch has stored the totals in host-mapped memory when the stream is idle
   HIPCHK(hipStreamSynchronize(r->stream));
-  if (counts_out) { counts_out[0] = r->h_seg_counts[0]; counts_out[1] = r->h_seg_counts[1]; }
+  if (counts_out) { counts_out[0] = r->h_seg_counts.h[0]; counts_out[1] = r->h_seg_counts.h[1]; }
   return RMCLHIP_OK;
 }

@@ -35,39 +35,33 @@ static SurfaceKernelParams surface_kernel_params(const rmclhip_surface_params& p
 
 // the 4-word count block on the device and its pinned landing place (once per handle)
 static rmclhip_status pf_surface_buffers(rmclhip_pf* f) {
-  if (!f->d_surf) HIPCHK(hipMalloc(reinterpret_cast<void**>(&f->d_surf), 4 * sizeof(uint32_t)));
-  if (!f->h_surf) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&f->h_surf), 4 * sizeof(uint32_t), hipHostMallocDefault));
-    std::memset(f->h_surf, 0, 4 * sizeof(uint32_t));
+  HIPCHK(f->d_surf.reserve(4));
+  if (!f->h_surf.p) {
+    HIPCHK(f->h_surf.reserve(4));
+    std::memset(f->h_surf.p, 0, 4 * sizeof(uint32_t));
   }
   return RMCLHIP_OK;
-}
-
-RMCL_INTERNAL void pf_surface_release(rmclhip_pf* f) {
-  if (f->d_surf) (void)hipFree(f->d_surf);
-  if (f->h_surf) (void)hipHostFree(f->h_surf);
-  f->d_surf = nullptr; f->h_surf = nullptr;
 }
 
 RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const xform& T_bnew_bold, double forget_rate,
                                                uint32_t max_n_meas, bool collision) {
   if (!f->surface_on) {
-    HIPCHK(launch_pf_motion(f->map->d_qnodes, f->map->d_tris, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream));
+    HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream));
     return RMCLHIP_OK;
   }
   if (rmclhip_status st = pf_surface_buffers(f)) return st;
   const SurfaceKernelParams k = surface_kernel_params(f->surface);
-  HIPCHK(hipMemsetAsync(f->d_surf, 0, 4 * sizeof(uint32_t), f->stream));
-  HIPCHK(launch_pf_motion(f->map->d_qnodes, f->map->d_tris, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream, &k, f->d_surf, f->surf_faces));
-  HIPCHK(hipMemcpyAsync(f->h_surf, f->d_surf, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipMemsetAsync(f->d_surf.p, 0, 4 * sizeof(uint32_t), f->stream));
+  HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream, &k, f->d_surf.p, f->surf_faces));
+  HIPCHK(hipMemcpyAsync(f->h_surf.p, f->d_surf.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
   return RMCLHIP_OK;
 }
 
 RMCL_INTERNAL rmclhip_status pf_surface_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const rmclhip_surface_params& sp, uint32_t max_n_meas) {
   if (rmclhip_status st = pf_surface_buffers(f)) return st;
-  HIPCHK(hipMemsetAsync(f->d_surf, 0, 4 * sizeof(uint32_t), f->stream));
-  HIPCHK(launch_surface_constrain(f->map->d_qnodes, f->map->d_tris, poses, attrs, n, surface_kernel_params(sp), max_n_meas, f->d_surf, f->surf_faces, f->stream));
-  HIPCHK(hipMemcpyAsync(f->h_surf, f->d_surf, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipMemsetAsync(f->d_surf.p, 0, 4 * sizeof(uint32_t), f->stream));
+  HIPCHK(launch_surface_constrain(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, surface_kernel_params(sp), max_n_meas, f->d_surf.p, f->surf_faces, f->stream));
+  HIPCHK(hipMemcpyAsync(f->h_surf.p, f->d_surf.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
   return RMCLHIP_OK;
 }
 
@@ -85,8 +79,8 @@ rmclhip_status rmclhip_pf_get_surface_stats(rmclhip_pf* f, rmclhip_surface_stats
   ApiGuard guard_("rmclhip_pf_get_surface_stats");
   if (!f || !out) return fail(RMCLHIP_ERR_INVALID, "pf_get_surface_stats: null");
   std::memset(out, 0, sizeof(*out));
-  if (!f->h_surf) return RMCLHIP_OK;
-  out->n_particles = f->h_surf[0]; out->n_snapped = f->h_surf[1]; out->n_missed = f->h_surf[2]; out->n_steep = f->h_surf[3];
+  if (!f->h_surf.p) return RMCLHIP_OK;
+  out->n_particles = f->h_surf.p[0]; out->n_snapped = f->h_surf.p[1]; out->n_missed = f->h_surf.p[2]; out->n_steep = f->h_surf.p[3];
   return RMCLHIP_OK;
 }
 

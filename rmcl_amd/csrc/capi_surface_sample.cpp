@@ -21,7 +21,7 @@ RMCL_INTERNAL rmclhip_status surface_sample_params_check(const std::string& who,
 
 RMCL_INTERNAL SurfaceSampleView surface_sample_view(const rmclhip_surface_sampler* sm) {
   SurfaceSampleView v;
-  v.tris = sm->map->d_tris; v.rec_of_face = sm->d_rec; v.incl = sm->d_incl;
+  v.tris = sm->map->d_tris.p; v.rec_of_face = sm->d_rec.p; v.incl = sm->d_incl.p;
   v.n_faces = sm->info.n_faces; v.T = sm->info.weight_total;
   v.height = sm->params.height; v.yaw_min = sm->params.yaw_min; v.yaw_max = sm->params.yaw_max;
   v.align = static_cast<uint32_t>(sm->params.align);
@@ -32,10 +32,6 @@ RMCL_INTERNAL SurfaceSampleView surface_sample_view(const rmclhip_surface_sample
 void rmclhip_surface_sampler_destroy(rmclhip_surface_sampler* sm) {
   if (!sm) return;
   if (sm->ctx) (void)hipSetDevice(sm->ctx->device);
-  if (sm->d_rec) (void)hipFree(sm->d_rec);
-  if (sm->d_incl) (void)hipFree(sm->d_incl);
-  if (sm->d_count) (void)hipFree(sm->d_count);
-  if (sm->h_count) (void)hipHostFree(sm->h_count);
   if (sm->map) rmclhip_map_release(sm->map);
   ctx_release(sm->ctx);
   delete sm;
@@ -50,29 +46,29 @@ static rmclhip_status surface_sampler_build(rmclhip_surface_sampler* sm) {
   std::lock_guard<std::mutex> lock(ctx->part_mtx);
   if (rmclhip_status st = particles_stream(ctx)) return st;
   hipStream_t s = ctx->part_stream;
-  HIPCHK_AS(who, dev_alloc(&sm->d_rec, nf));
-  HIPCHK_AS(who, dev_alloc(&sm->d_incl, nf));
-  HIPCHK_AS(who, dev_alloc(&sm->d_count, 1));
-  HIPCHK_AS(who, hipHostMalloc(reinterpret_cast<void**>(&sm->h_count), sizeof(uint32_t), hipHostMallocDefault));
-  *sm->h_count = 0u;
+  HIPCHK_AS(who, sm->d_rec.reserve(std::max(nf, 1u)));
+  HIPCHK_AS(who, sm->d_incl.reserve(std::max(nf, 1u)));
+  HIPCHK_AS(who, sm->d_count.reserve(1));
+  HIPCHK_AS(who, sm->h_count.reserve(1));
+  *sm->h_count.p = 0u;
   BuildScratch tmp;
   double* d_area = nullptr;
   unsigned long long *d_amax = nullptr, *d_btot = nullptr;
   HIPCHK_AS(who, tmp.alloc(&d_area, nf));
   HIPCHK_AS(who, tmp.alloc(&d_amax, 1));
   HIPCHK_AS(who, tmp.alloc(&d_btot, (static_cast<size_t>(nf) + 1023u) / 1024u));
-  HIPCHK_AS(who, hipMemsetAsync(sm->d_rec, 0xFF, static_cast<size_t>(nf) * sizeof(uint32_t), s));
+  HIPCHK_AS(who, hipMemsetAsync(sm->d_rec.p, 0xFF, static_cast<size_t>(nf) * sizeof(uint32_t), s));
   HIPCHK_AS(who, hipMemsetAsync(d_amax, 0, sizeof(unsigned long long), s));
   SurfaceSampleRule rule;
   rule.min_up_cos = sm->params.min_up_cos;
   for (int d = 0; d < 3; ++d) { rule.region_min[d] = sm->params.region_min[d]; rule.region_max[d] = sm->params.region_max[d]; }
-  HIPCHK_AS(who, launch_surface_sample_records(sm->map->d_tris, nrec, nf, sm->d_rec, s));
-  HIPCHK_AS(who, launch_surface_sample_areas(sm->map->d_tris, sm->d_rec, nf, rule, d_area, d_amax, s));
-  HIPCHK_AS(who, launch_surface_sample_scan(d_area, d_amax, nf, sm->d_incl, d_btot, s));
+  HIPCHK_AS(who, launch_surface_sample_records(sm->map->d_tris.p, nrec, nf, sm->d_rec.p, s));
+  HIPCHK_AS(who, launch_surface_sample_areas(sm->map->d_tris.p, sm->d_rec.p, nf, rule, d_area, d_amax, s));
+  HIPCHK_AS(who, launch_surface_sample_scan(d_area, d_amax, nf, sm->d_incl.p, d_btot, s));
   std::vector<double> area(nf);
   std::vector<unsigned long long> incl(nf);
   HIPCHK_AS(who, hipMemcpyAsync(area.data(), d_area, static_cast<size_t>(nf) * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK_AS(who, hipMemcpyAsync(incl.data(), sm->d_incl, static_cast<size_t>(nf) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCHK_AS(who, hipMemcpyAsync(incl.data(), sm->d_incl.p, static_cast<size_t>(nf) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIPCHK_AS(who, hipStreamSynchronize(s));
   double sum = 0.0;
   uint32_t n_eligible = 0, n_weighted = 0;
@@ -99,7 +95,7 @@ rmclhip_status rmclhip_surface_sampler_create(rmclhip_map* map, const rmclhip_su
   rmclhip_surface_sample_params_default(&p);
   if (params) p = *params;
   if (rmclhip_status st = surface_sample_params_check("surface_sampler_create", &p)) return st;
-  if (map->info.n_faces == 0 || map->info.n_records == 0 || !map->d_tris) return fail(RMCLHIP_ERR_INVALID, "surface_sampler_create: the map has no faces");
+  if (map->info.n_faces == 0 || map->info.n_records == 0 || !map->d_tris.p) return fail(RMCLHIP_ERR_INVALID, "surface_sampler_create: the map has no faces");
   HIPCHK(hipSetDevice(map->ctx->device));
   rmclhip_surface_sampler* sm = new rmclhip_surface_sampler();
   sm->ctx = map->ctx;
@@ -135,11 +131,11 @@ RMCL_INTERNAL rmclhip_status surface_inject_threshold(const std::string& who, do
 
 RMCL_INTERNAL rmclhip_status surface_inject_enqueue(rmclhip_surface_sampler* sm, xform* poses, void* attrs, uint32_t first, uint32_t count,
                                                     unsigned long long threshold, uint64_t seed, uint32_t step, hipStream_t s) {
-  *sm->h_count = 0u;
+  *sm->h_count.p = 0u;
   if (count == 0 || threshold == 0ull) return RMCLHIP_OK;
-  HIPCHK(hipMemsetAsync(sm->d_count, 0, sizeof(uint32_t), s));
-  HIPCHK(launch_particles_inject_surface(poses, attrs, first, count, surface_sample_view(sm), threshold, seed, step, sm->d_count, s));
-  HIPCHK(hipMemcpyAsync(sm->h_count, sm->d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemsetAsync(sm->d_count.p, 0, sizeof(uint32_t), s));
+  HIPCHK(launch_particles_inject_surface(poses, attrs, first, count, surface_sample_view(sm), threshold, seed, step, sm->d_count.p, s));
+  HIPCHK(hipMemcpyAsync(sm->h_count.p, sm->d_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   return RMCLHIP_OK;
 }
 

@@ -42,6 +42,33 @@ def test_library_exports_every_declared_symbol(ra):
     assert sorted(ra._capi.SIGNATURES) == sorted(set(names) | set(bench_names) | (set(lab_names) - {"rmclhip_lab_version"}))
 
 
+def test_only_the_owners_allocate():
+    """Device, pinned and host-mapped memory of the library is allocated and freed in ONE place, the owning buffer types of
+    capi_internal.h (DevBuf, PinnedBuf, MappedBuf): no other source names HIP's allocation and free functions.  The exception is
+    the pair of public functions of capi_map.cpp that hand memory to the caller, rmclhip_malloc and rmclhip_free."""
+    import glob
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipHostGetDevicePointer)\b")
+    csrc = os.path.join(ROOT, "rmcl_amd", "csrc")
+    files = sorted(p for ext in ("*.cpp", "*.hip", "*.h") for p in glob.glob(os.path.join(csrc, ext)))
+    assert len(files) > 60
+    found = {}
+    for path in files:
+        with open(path) as fh:
+            src = fh.read()
+        name = os.path.basename(path)
+        if name == "capi_map.cpp":
+            # cut the bodies of the two exempt functions out: each runs from its signature to the closing brace in column 0
+            for fn, call in (("rmclhip_malloc", "hipMalloc"), ("rmclhip_free", "hipFree")):
+                m = re.search(r"^rmclhip_status %s\(.*?^}\n" % fn, src, flags=re.S | re.M)
+                assert m and call in m.group(0), fn
+                src = src[:m.start()] + src[m.end():]
+        hits = sorted(set(calls.findall(src)))
+        if hits:
+            found[name] = hits
+    assert sorted(found) == ["capi_internal.h"], found
+    assert found["capi_internal.h"] == ["hipFree", "hipHostFree", "hipHostGetDevicePointer", "hipHostMalloc", "hipMalloc"]
+
+
 def test_pod_layouts(ra):
     T = ra.types
     assert T.TRANSFORM.itemsize == 32 and T.TRANSFORM.fields["t"][1] == 16 and T.TRANSFORM.fields["stamp"][1] == 28
