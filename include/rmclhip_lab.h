@@ -44,6 +44,21 @@ rmclhip_status rmclhip_debug_surface_faces(rmclhip_pf* pf, uint32_t* faces_dev);
  * s_memtime before the traversal, after it, stores issued, 0} (all zero = wave had no tile) */
 rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* rcc, const rmclhip_transform* Tbm_est, uint32_t* out, size_t cap_dwords,
                                         uint32_t* n_waves_out);
+/* TEST read-out of the one table of find traversal kinds and of the launch shape every launcher derives from it
+ * (tests/test_find_kinds_cpu.py): what a find of `kind` over tiles_x x tiles_y tiles and nposes poses would be launched with -- with the
+ * MICP moment epilogue when `moments` != 0 and the kind has one, over a world order of n_tile_order entries (0: pose-major) dealt
+ * `granule` workgroups per XCD turn.  Pure arithmetic: touches no device and no handle; works without the experiments library.  A
+ * number that is no kind: exists = 0 and every other field 0. */
+typedef struct rmclhip_find_launch_shape {
+  uint32_t exists, in_product;   /* a kind at all; built into librmclhip.so */
+  uint32_t tiles_per_block;      /* 64-ray tiles per workgroup = mask words per workgroup of the epilogue = group of the world order */
+  uint32_t grid_x, grid_y;       /* blocks of 256 threads */
+  uint32_t lds_bytes;            /* dynamic LDS per workgroup */
+  uint32_t clock_dwords;         /* what a clocked launch (rmclhip_debug_wave_clock) writes */
+  uint32_t has_moments;          /* the kind has the moment epilogue */
+} rmclhip_find_launch_shape;
+rmclhip_status rmclhip_debug_find_launch_shape(int kind, int moments, uint32_t tiles_x, uint32_t tiles_y, uint32_t nposes,
+                                               uint32_t n_tile_order, uint32_t granule, rmclhip_find_launch_shape* out);
 /* the moments the LAST moment-form attempt of rmclhip_rcc_correct_once worked from (rmclhip.h: rmclhip_rcc_set_micp_fast): the 96 sums
  * of its partial rows (82 used; layout in reduce_common.hip.h) and the number of correspondences it left undecided.  Works without the
  * experiments library. */

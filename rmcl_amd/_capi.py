@@ -58,6 +58,11 @@ class CcsInfo(C.Structure):
     _fields_ = [("calls", C.c_uint32), ("from_moments", C.c_uint32), ("passes", C.c_uint32), ("speculative_finds", C.c_uint32)]
 
 
+class FindLaunchShape(C.Structure):
+    _fields_ = [("exists", C.c_uint32), ("in_product", C.c_uint32), ("tiles_per_block", C.c_uint32), ("grid_x", C.c_uint32),
+                ("grid_y", C.c_uint32), ("lds_bytes", C.c_uint32), ("clock_dwords", C.c_uint32), ("has_moments", C.c_uint32)]
+
+
 class PointCloud2Layout(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
                 ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("offset_z", C.c_uint32), ("datatype", C.c_uint32)]
@@ -367,6 +372,7 @@ SIGNATURES = {
     "rmclhip_host_moment_statistics": (_i32, [_vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32, _f32, _vp, _f32, _vp, C.POINTER(_u32),
                                                C.POINTER(_i32)]),
     "rmclhip_debug_wave_clock": (_i32, [_vp, _vp, _vp, _sz, C.POINTER(_u32)]),
+    "rmclhip_debug_find_launch_shape": (_i32, [_i32, _i32, _u32, _u32, _u32, _u32, _u32, C.POINTER(FindLaunchShape)]),
     "rmclhip_debug_micp_moments": (_i32, [_vp, _vp, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
     "rmclhip_debug_probe_find": (_i32, [_vp, _vp, _i32, _vp, _sz, C.POINTER(_u32)]),
     "rmclhip_rcc_find_batch": (_i32, [_vp, _vp, _u32]),

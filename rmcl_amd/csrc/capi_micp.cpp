@@ -93,7 +93,7 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
   fp.Tms = r->h_call.p->Tms;
   MicpCallLite cl = micp_call_lite(r, Tbo, maxd, r->h_call.p->seq);
   const int fv = find_variant(r, 1);
-  const bool tiled = r->fast_mode != 3 && (fv == 23 || fv == 32 || fv == 2);   // the find forms the moments in its epilogue
+  const bool tiled = r->fast_mode != 3 && find_kind(fv).moments;   // the find forms the moments in its epilogue
   if (r->fast_mode == 1) {
     // ---- round 4 default: TWO launches (find with the moment epilogue; fold + publish), the iterations on the HOST from the 82
     // moments + the undecided correspondences (micp_host.h): ~0.5 us per iteration instead of ~2.7 us of one lane's f64 chain
@@ -129,7 +129,7 @@ static rmclhip_status micp_try_moment_form(rmclhip_rcc* r, const xform& Tbo, uin
       const int ufv = r->last_moment_find_kind;
       FindParams ufp;
       fill_find_params(r, ufp, 1, ufv);
-      HIPCHK(launch_moment_loop(r, r->last_moment_find_tiled, ufp, find_moments_blocks(ufp, ufv), (ufv == 2) ? 1u : 4u, nred, n_iter, cl));
+      HIPCHK(launch_moment_loop(r, r->last_moment_find_tiled, ufp, find_launch_shape(ufp, ufv, true).grid_x, find_kind(ufv).tiles_per_block(), nred, n_iter, cl));
     }
   } else {
     // (fast_mode 4, round 3's default) TWO kernels: the find forms the moments in its epilogue (find_kernel.hip.h: the 10 x 10 factor

@@ -399,7 +399,7 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
   p.model_tab = r->d_model_tab.p;
   p.W = r->W; p.H = r->H;
   p.tile_w_log2 = (r->tile_override > 0) ? static_cast<uint32_t>(r->tile_override - 1)
-                  : ((r->tuned_tile > 0 && v != 0) ? static_cast<uint32_t>(r->tuned_tile - 1) : pick_tile_w_log2(r->H, v == 0, r->ang_aspect));
+                  : ((r->tuned_tile > 0 && !find_kind(v).packet()) ? static_cast<uint32_t>(r->tuned_tile - 1) : pick_tile_w_log2(r->H, find_kind(v).packet(), r->ang_aspect));
   const uint32_t tw = 1u << p.tile_w_log2, th = 64u >> p.tile_w_log2;
   p.tiles_x = (r->W + tw - 1) / tw;
   p.tiles_y = (r->H + th - 1) / th;
@@ -419,7 +419,7 @@ RMCL_INTERNAL void fill_find_params(rmclhip_rcc* r, FindParams& p, uint32_t npos
     // the same BVH2 cut at leaves of <= 2 instead of <= 4 triangles, the same record array (layout.h): pose batches 6-10 % faster
     // (profiles/r03_find_variants_ab.txt).  That tree has its own node numbering, hence its own frontier table.
     uint32_t need = r->map->info.stack_need;
-    if ((v == 24 || v == 22) && r->map->d_qnodes_pf.p != nullptr) {
+    if (find_kind(v).filter_tree && r->map->d_qnodes_pf.p != nullptr) {
       p.qnodes = r->map->d_qnodes_pf.p;
       p.frontier = r->map->d_frontier_pf.p;
       p.n_frontier = r->map->n_frontier_pf;
@@ -599,12 +599,12 @@ RMCL_INTERNAL void learn_caps(rmclhip_rcc* r, float max_rho, float max_tau) {
   r->fast_info.tau_cap = r->fast_tau_cap;
 }
 
-// Arms the moment epilogue of the find `fp` of kind `fv` (23, 32 or 2): one partial row per workgroup (*nb of them) and *wpb mask words
+// Arms the moment epilogue of the find `fp` of kind `fv` (one that has it): one partial row per workgroup (*nb of them) and *wpb mask words
 // per workgroup, the gate band and the caps the rows are good for, and -- allocated and zeroed once per handle -- the area through
 // which the workgroups of the fold hand their sums over (micp.hip fold_hand_over_row)
 RMCL_INTERNAL rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp, int fv, uint32_t nred, float lo, float hi, float rho_cap,
                                                  float tau_cap, uint32_t* nb_out, uint32_t* wpb_out) {
-  const uint32_t nb = find_moments_blocks(fp, fv), wpb = (fv == 2) ? 1u : 4u;
+  const uint32_t nb = find_launch_shape(fp, fv, true).grid_x, wpb = find_kind(fv).tiles_per_block();
   HIPCHK(r->d_fast_partials.reserve(static_cast<size_t>(nb) * kMicpFastMoments));
   HIPCHK(r->d_fast_mask.reserve(static_cast<size_t>(nb) * wpb));
   fp.mom_dataset_points = r->ds_pts;
@@ -625,7 +625,7 @@ RMCL_INTERNAL rmclhip_status arm_moment_epilogue(rmclhip_rcc* r, FindParams& fp,
   return RMCLHIP_OK;
 }
 
-// find + moment epilogue + publish on the handle's stream (kinds 23 / 2), or find + moment pass + publish (any other kind);
+// find + moment epilogue + publish on the handle's stream (the kinds that have it), or find + moment pass + publish (any other kind);
 // the caller waits with wait_moments(seq, ...)
 RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xform& Tsm, float lo, float hi, float rho_cap, float tau_cap,
                                                        uint32_t seq, bool epilogue_allowed) {
@@ -639,8 +639,8 @@ RMCL_INTERNAL rmclhip_status enqueue_find_with_moments(rmclhip_rcc* r, const xfo
   fp.Tsm = Tsm;
   fp.Tms = xinv(Tsm);
   r->last_moment_find_kind = fv;
-  r->last_moment_find_tiled = epilogue_allowed && (fv == 23 || fv == 32 || fv == 2);
-  if (epilogue_allowed && (fv == 23 || fv == 32 || fv == 2)) {
+  r->last_moment_find_tiled = epilogue_allowed && find_kind(fv).moments;
+  if (r->last_moment_find_tiled) {
     uint32_t nb, wpb;
     if (rmclhip_status st = arm_moment_epilogue(r, fp, fv, nred, lo, hi, rho_cap, tau_cap, &nb, &wpb)) return st;
     HIPCHK(launch_find_moments(fp, r->kind, fv, r->stream));
@@ -675,7 +675,7 @@ RMCL_INTERNAL rmclhip_status find_enqueue(rmclhip_rcc* r, const xform& Tbm, bool
     r->ccs_loop = r->ccs_since_find != 0u;
     r->ccs_since_find = 0u; r->ccs_max_rho = 0.f; r->ccs_max_tau = 0.f;
     const int fv = find_variant(r, 1);
-    if (r->ccs_loop && r->fast_mode == 1 && r->n_dataset != 0u && (fv == 23 || fv == 32 || fv == 2) && r->ccs_last_maxd == r->ccs_last_maxd &&
+    if (r->ccs_loop && r->fast_mode == 1 && r->n_dataset != 0u && find_kind(fv).moments && r->ccs_last_maxd == r->ccs_last_maxd &&
         micp_outputs_selected(r)) {
       gate_band(r, r->ccs_last_maxd, &r->pend_lo, &r->pend_hi);
       r->pend_rho = r->fast_rho_cap; r->pend_tau = r->fast_tau_cap;

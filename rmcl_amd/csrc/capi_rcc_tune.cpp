@@ -269,13 +269,13 @@ rmclhip_status rmclhip_rcc_set_variant(rmclhip_rcc* r, int variant) {
   if (!r || variant < 0) return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: bad arguments");
   // bit 13 adds 16 to the traversal kind (kinds 16..31), bit 14 adds 32
   const int kind = (variant & 0xF) | (((variant >> 13) & 1) << 4) | (((variant >> 14) & 1) << 5), tile = (variant >> 4) & 0xF;
-  if (kind == 3 || kind == 18 || kind > 32 || tile > 7 || (variant >> 15) != 0) return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: unknown variant");
+  if ((kind != 15 && !find_kind(kind).exists) || tile > 7 || (variant >> 15) != 0) return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: unknown variant");
   // bit 8 (reduction tail fused into the last block) and bits 10..12 (reduce + solve launches, persistent grid-barrier loop): loop
   // forms measured slower than the default and removed (profiles/r03_micp_loop_forms.txt)
   if ((variant & ((1 << 8) | (7 << 10))) != 0)
     return fail(RMCLHIP_ERR_INVALID, "rcc_set_variant: bits 8 and 10..12 (MICP loop forms) are retired");
   // (kind 1 also selects the one-lane-per-point form of the closest-point query, which the product owns)
-  if (kind != 15 && kind != 1 && !find_kind_in_product(kind) && lab_hooks() == nullptr)
+  if (kind != 15 && kind != 1 && !find_kind(kind).in_product && lab_hooks() == nullptr)
     return fail(RMCLHIP_ERR_UNSUPPORTED, "rcc_set_variant: this traversal kind is an experiment -- it lives in librmclhip_lab.so, "
                                          "which is not loaded (the product builds kinds 0, 2, 23, 24, 32 and the automatic rule 15)");
   r->variant = kind;
@@ -424,12 +424,10 @@ rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* r, const rmclhip_transform*
   p.Tsm = xmul(to_x(Tbm_est), r->Tsb);
   p.Tms = xinv(p.Tsm);
   const int variant = find_variant(r, 1);
-  const uint32_t ntiles = p.tiles_x * p.tiles_y;
-  uint32_t nblocks = (variant == 2) ? ntiles : (ntiles + 3u) / 4u;
-  nblocks = (nblocks + 7u) & ~7u;
-  // kind 31: 16 more words per wave (the descent's phase stamps) behind the [n_waves][8] table
-  const size_t dwords = static_cast<size_t>(nblocks) * 4u * ((variant == 31 || variant == 32) ? 24u : 8u);
-  if (n_waves_out) *n_waves_out = nblocks * 4u;
+  // the descent kinds: 16 more words per wave (the descent's phase stamps) behind the [n_waves][8] table
+  const FindLaunchShape shape = find_launch_shape(p, variant, false);
+  const size_t dwords = shape.clock_dwords;
+  if (n_waves_out) *n_waves_out = shape.grid_x * shape.grid_y * 4u;
   if (cap_dwords < dwords) return fail(RMCLHIP_ERR_INVALID, "debug_wave_clock: buffer too small");
   DevBuf<uint32_t> d_clock;
   HIPCHK(d_clock.reserve(dwords));
@@ -446,12 +444,25 @@ rmclhip_status rmclhip_debug_wave_clock(rmclhip_rcc* r, const rmclhip_transform*
   return RMCLHIP_OK;
 }
 
+rmclhip_status rmclhip_debug_find_launch_shape(int kind, int moments, uint32_t tiles_x, uint32_t tiles_y, uint32_t nposes,
+                                               uint32_t n_tile_order, uint32_t granule, rmclhip_find_launch_shape* out) {
+  if (!out) return fail(RMCLHIP_ERR_INVALID, "debug_find_launch_shape: null");
+  const FindKind K = find_kind(kind);
+  const FindLaunchShape sh = find_launch_shape(kind, moments != 0, tiles_x * tiles_y, nposes, n_tile_order, granule);
+  *out = rmclhip_find_launch_shape{};
+  if (!K.exists) return RMCLHIP_OK;
+  out->exists = 1u; out->in_product = K.in_product ? 1u : 0u; out->tiles_per_block = K.tiles_per_block();
+  out->grid_x = sh.grid_x; out->grid_y = sh.grid_y; out->lds_bytes = sh.lds_bytes; out->clock_dwords = sh.clock_dwords;
+  out->has_moments = K.moments ? 1u : 0u;
+  return RMCLHIP_OK;
+}
+
 // A pose batch in world order (VERDICT r5 #7b): one key per wave-tile of the launch (where its central ray leaves the map's bounding
 // box), a counting sort, and k_find walks the sorted list -- consecutive blocks, hence one XCD's L2, then see one region of the map.
 // Three small launches per batch (~15 us); the v1 batch of the reference's benchmark gains 1 % (100 k faces) / 8 % (1 M) / 15 % (10 M) / 6 % (room),
 // all included (profiles/r06_batch_order_ab.txt).  On by default; rmclhip_rcc_set_batch_order(rcc, 0) restores the pose-major launch (A/B).
 RMCL_INTERNAL rmclhip_status batch_order_enqueue(rmclhip_rcc* r, FindParams& p, int variant) {
-  const uint32_t ntiles = p.tiles_x * p.tiles_y, group = (variant == 2) ? 1u : 4u, ngroups = (ntiles + group - 1u) / group;
+  const uint32_t ntiles = p.tiles_x * p.tiles_y, group = find_kind(variant).tiles_per_block(), ngroups = (ntiles + group - 1u) / group;
   r->last_order_n = 0; r->last_order_ngroups = 0;   // (what rmclhip_debug_batch_order reports of a pose-major launch)
   if (r->batch_order == 0u || p.nposes < 2u || ngroups > 65535u || p.nposes > 32768u || p.Tsm_arr == nullptr) return RMCLHIP_OK;
   const uint32_t n = ngroups * p.nposes;

@@ -1,8 +1,9 @@
 // find_kernel.hip.h -- k_find<model, traversal kind, clocks>: ray-casting correspondences, rm::*Simulator*::simulate as called by
 // RCC*::find (rmcl/src/rmcl/registration/RCCEmbree.cpp:26-36,89-99).  One template, two homes: kernels.hip instantiates the kinds
-// the product can select (0 packet, 2 quad, 23 / 24 one lane per ray with the frontier start) WITHOUT clocks; kernels_lab.hip instantiates
-// the measured-and-rejected kinds and the clocked variants for tools/wave_timeline.py.
+// the product can select WITHOUT clocks; kernels_lab.hip instantiates the measured-and-rejected kinds and the clocked variants for
+// tools/wave_timeline.py.  What a kind IS: find_kinds.h.
 #pragma once
+#include "find_kinds.h"
 #include "traverse.hip.h"
 
 namespace rmclhip {
@@ -11,30 +12,32 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // find
 // ---------------------------------------------------------------------------------------------
-// kTrav: 0 = wave packet, 1 = one lane per ray (while-while), 4 = the same on the quantised 64-B nodes, 5 = one lane
-// per ray with the tail of every wave handed to quads,
-// 2 = four lanes per ray (quad-cooperative; the block
-// of 256 threads then covers ONE 64-ray tile instead of four)
-// kTrav 5..10 share the tail traversal: 6 / 7 add the LDS-resident top of the tree (85 / 341 nodes = levels 0-3 / 0-4 of a
-// full BVH4), 8 adds the one-round-trip leaf, 9 / 10 both
-constexpr int find_top_nodes(int trav) { return (trav == 6 || trav == 9) ? 85 : ((trav == 7 || trav == 10) ? 341 : 0); }
-constexpr bool find_leaf_batch(int trav) { return trav >= 8 && trav <= 10; }
 constexpr int kFindBfRows = 24;  // LDS stack rows per lane (sentinel included) of the branch-free lane traversal in k_find
-constexpr uint32_t kFindTailLdsDwords = 16u * 256u + kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords;
 
-// kinds 19..22: kind 17 + leaving the node phase when 32 / 24 / 16 / 8 lanes hold a leaf
-constexpr int find_leaf_trigger(int trav) { return (trav == 19 || trav == 20 || trav == 23 || (trav >= 26 && trav <= 32)) ? 10 : 0; }   // leave at <= 4/10 of the round's rays
-// kinds 23 / 24: kinds 19 / 22 whose rays start at the map's frontier (traverse.hip.h frontier_start) instead of the root
-// kinds 31 / 32 (round 6): the wave keeps descending cooperatively below the frontier (traverse.hip.h frontier_descent_start); 32 = the product's form (one bit per final leaf and ray), 31 = the first form (sorted hand-over), kept in the lab for A/B
-constexpr bool find_frontier(int trav) { return trav == 23 || trav == 24 || (trav >= 25 && trav <= 32); }
-// LDS of the one-lane-per-ray kinds with quad-finished tails (23, 31, ...), in dwords; kinds 31 and 32 append their waves' descent lists
-constexpr uint32_t kFindBfTailLdsDwords = static_cast<uint32_t>(kFindBfRows) * 256u + kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords;
-// kinds 31 and 32 have no quad tail: its LDS is the lane stacks, then the four waves' descent lists
-constexpr uint32_t kFind31ListsAt = static_cast<uint32_t>(kFindBfRows) * 256u;
-constexpr uint32_t kFind31LdsDwords = kFind31ListsAt + 4u * kDescentWaveDwords;
-static_assert(kFind31ListsAt % 4u == 0u, "the descent lists are read and written 16 B at a time");   // 26: 23 on the quantised nodes; 27: 23 + record prefetch; 28: 23 with the pipelined node step; 29 / 30: 23 with four / three of the five ordering steps
-// kind 25: kind 2 (four lanes per ray) with the frontier start
-constexpr bool find_quad(int trav) { return trav == 2 || trav == 25; }
+constexpr bool find_step_bf(FindStep s) { return s == FindStep::kBf || s == FindStep::kBfTail; }
+// the lane stacks: trace_lane_ww keeps 16 rows from row 0 at a stride of blockDim.x, the branch-free forms kFindBfRows from row 1
+// (row 0: the sentinel) at kBfStride; the quad form kQuadStackEntries per ray, 64 rays
+constexpr uint32_t find_stack_dwords(const FindKind& k) {
+  return k.packet() ? 0u : k.quad() ? kQuadStackEntries * 64u : (find_step_bf(k.step) ? static_cast<uint32_t>(kFindBfRows) : 16u) * 256u;
+}
+// dynamic LDS of a workgroup, in dwords: the stacks | the quad tail's stacks and hand-over rows | the LDS top of the tree, or the
+// four waves' descent lists.  The moment epilogue stages in the lane stacks (24 rows needed: the branch-free kinds have them);
+// behind the quad kind's ray stacks it appends 21 rows of its own (find_moments_wave)
+constexpr uint32_t find_lds_dwords(int kind, bool moments) {
+  const FindKind k = find_kind(kind);
+  return find_stack_dwords(k) + (k.tail ? kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords : 0u) +
+         static_cast<uint32_t>(k.top) * kNodeDwords + (k.descent() ? 4u * kDescentWaveDwords : 0u) +
+         ((moments && k.quad()) ? 21u * 256u : 0u);
+}
+constexpr uint32_t kFindTailLdsDwords = find_lds_dwords(5, false);   // where the LDS top of the tree begins
+constexpr uint32_t kFind31ListsAt = static_cast<uint32_t>(kFindBfRows) * 256u;   // where the descent lists begin
+static_assert(kFind31ListsAt % 4u == 0u, "the descent lists are read and written 16 B at a time");
+// the product's five kinds, pinned: LDS dwords (with the moment epilogue where it has one) and tiles per workgroup
+static_assert(find_lds_dwords(0, false) == 0u && find_kind(0).tiles_per_block() == 4u, "kind 0");
+static_assert(find_lds_dwords(2, false) == 4416u && find_lds_dwords(2, true) == 9792u && find_kind(2).tiles_per_block() == 1u, "kind 2");
+static_assert(find_lds_dwords(23, false) == 11328u && find_lds_dwords(23, true) == 11328u && find_kind(23).tiles_per_block() == 4u, "kind 23");
+static_assert(find_lds_dwords(24, false) == 4096u && find_kind(24).tiles_per_block() == 4u, "kind 24");
+static_assert(find_lds_dwords(32, false) == 10240u && find_lds_dwords(32, true) == 10240u && find_kind(32).tiles_per_block() == 4u, "kind 32");
 
 // the ray of image position (cv, ch) in the SENSOR frame (loc = cv * W + ch)
 template <uint32_t kModel>
@@ -240,14 +243,20 @@ __device__ __forceinline__ void find_moments_wave(const FindParams& p, uint32_t*
 // instantiation by bit 16 of p.descent_levels
 template <uint32_t kModel, int kTrav, bool kClock = false, bool kMoments = false, bool kCarry = false>
 __global__ void __launch_bounds__(256) k_find(const FindParams p) {
-  static_assert(!kCarry || kTrav == 32, "pending candidates belong to kind 32's cooperative leaf loop");
+  // the kind's table row.  `static`: a plain constexpr struct is materialised on the kernel's stack before it is folded away, and
+  // what is computed from the row outside a template argument or `if constexpr` is named as a constexpr scalar below for the same
+  // reason -- either changes the order of the generated code (profiles/find_kind_table.txt)
+  static constexpr FindKind K = find_kind(kTrav);
+  static_assert(K.exists, "not a traversal kind (find_kinds.h)");
+  static_assert(!kCarry || K.coop, "pending candidates belong to kind 32's cooperative leaf loop");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
-  static_assert(!kMoments || ((kTrav == 23 || kTrav == 31 || kTrav == 32 || kTrav == 2) && !kClock), "the moment epilogue is built for kinds 23, 31, 32 and 2");
+  static_assert(!kMoments || ((K.moments || K.lab_moments) && !kClock), "the moment epilogue is not built for this kind (find_kinds.h)");
   __shared__ double s_mom_red[kMoments ? 4 : 1][kMoments ? kMomTile : 1];
   __shared__ uint32_t s_mom_piece[4];
-  constexpr bool kPacket = (kTrav == 0);
-  constexpr bool kQuad = find_quad(kTrav);
-  constexpr int kTop = find_top_nodes(kTrav);
+  constexpr bool kQuad = K.quad();
+  constexpr int kTop = K.top;
+  constexpr bool kBfStack = find_step_bf(K.step);            // trace_lane_ww: first stack row 0; the branch-free forms: row 1
+  constexpr uint32_t kStackDwords = find_stack_dwords(K);   // what lies behind: the quad tail's ray stacks, a hand-over row per wave, the top of the tree
   const uint32_t lane = kQuad ? (threadIdx.x >> 2) : (threadIdx.x & 63u), wave = threadIdx.x >> 6;
   const uint32_t sub = threadIdx.x & 3u;  // quad mode: child slot / triangle slot / output role of this lane
   uint32_t clk_begin = 0, clk_real = 0;
@@ -340,20 +349,20 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
   const float ray_tfar = (valid && finite) ? p.tfar : -1.0f;
 
   uint32_t clk_trace0 = 0, clk_trace1 = 0, clk_visits = 0, clk_dbg[4] = {0u, 0u, 0u, 0u}, clk_descent = 0, clk_start = 0;
-  uint32_t clk_stamps[16] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // kinds 31 and 32, clocked: frontier_descent_start's phase boundaries
+  uint32_t clk_stamps[16] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // the descent kinds, clocked: frontier_descent_start's phase boundaries
   if (kClock && p.wave_clock != nullptr) {
     uint64_t t;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
     clk_trace0 = static_cast<uint32_t>(t);
   }
   RayHit h;
-  uint4 pre_nrec = uint4{0u, 0u, 0u, 0u};   // kind 27: the best record's last 16 B, requested during the traversal
+  uint4 pre_nrec = uint4{0u, 0u, 0u, 0u};   // K.pre: the best record's last 16 B, requested during the traversal
   uint32_t pre_rec = kNone;
-  if (kPacket) {
+  if constexpr (K.step == FindStep::kPacket) {
     trace_packet((cu32p)(p.nodes), (cu32p)(p.tris), org_m, dir_m, ray_tfar, lane, h);
-  } else if (kQuad) {
+  } else if constexpr (K.step == FindStep::kQuad) {
     bool started = false;
-    if constexpr (kTrav == 25 && kModel != kModelOnDn) {
+    if constexpr (K.start == FindStart::kFrontierQuad && kModel != kModelOnDn) {
       if (p.tile_planes != nullptr) {
         // the block's 64-ray tile has ONE pyramid; each wave (16 rays x 4 lanes) culls the frontier against it with its 64 lanes
         // and every lane filters the survivors with its ray (the four lanes of a ray agree and store the same rows)
@@ -374,24 +383,23 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     // where the ray starts: the root -- or, for the frontier kinds, what frontier_start returns.  ALWAYS a struct passed by
     // address, never "null or &start": a pointer chosen at run time forces the struct through scratch memory (8 B per ray
     // written and read back on the critical path of every wave; seen as 1 MiB of extra HBM writes per C2 launch)
-    constexpr bool kWwStack = (kTrav == 4 || kTrav == 22 || kTrav == 24);   // trace_lane_ww: first stack row 0; branch-free forms: row 1
     TraceStart start;
     RayHit coop_seed = {ray_tfar, kNone};   // kind 32: the closest hit among the leaves the wave tested together (frontier_descent_start)
     start.cur = (ray_tfar >= 0.0f) ? 0u : 0x7FFFFFFFu;
-    start.sp = kWwStack ? 0u : 1u;
+    start.sp = kBfStack ? 1u : 0u;
     const TraceStart* sp0 = &start;
     // the ray's slab constants (three IEEE divisions): ONCE per ray, by reference to the frontier start and to the traversal behind it
     // -- each used to build its own, and the first sat under the branches below where the compiler could not merge the two
     const RaySlab rs = make_ray_slab(org_m, dir_m);
-    if constexpr (find_frontier(kTrav) && kModel != kModelOnDn) {   // (OnDn: one origin per ray, no common pyramid)
+    if constexpr (K.frontier() && kModel != kModelOnDn) {   // (OnDn: one origin per ray, no common pyramid)
       if (p.tile_planes != nullptr) {     // (no table: the rays start at the root)
         const float* planes = p.tile_planes + static_cast<size_t>(__builtin_amdgcn_readfirstlane(tile)) * 16u;
-        if (kTrav == 31 || kTrav == 32)
-          start = frontier_descent_start<kFindBfRows, 1, kTrav == 32, kCarry>(p.frontier, p.n_frontier, p.frontier_groups, p.cnodes, p.cnodes16, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar,
+        if constexpr (K.start == FindStart::kDescent)
+          start = frontier_descent_start<kFindBfRows, 1, K.coop, kCarry>(p.frontier, p.n_frontier, p.frontier_groups, p.cnodes, p.cnodes16, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar,
                                                          org_m, dir_m, rs, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload,
                                                          lds_dyn + kFind31ListsAt + wave * kDescentWaveDwords, min(p.descent_final_cap, kDescentCap), p.descent_levels, kClock ? &clk_descent : nullptr,
                                                          kClock ? clk_stamps : nullptr, p.tris, &coop_seed);
-        else if (kTrav == 23 || (kTrav >= 26 && kTrav <= 30))
+        else if constexpr (K.start == FindStart::kFrontierBf)
           start = frontier_start<kFindBfRows, 1>(p.frontier, p.n_frontier, p.scene_center, p.scene_half_diag, planes, Tsm.R, p.tfar, org_m,
                                                  dir_m, rs, ray_tfar, lane, lds_dyn + threadIdx.x, kBfStride, p.frontier_max_preload);
         else
@@ -404,29 +412,22 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
       clk_start = static_cast<uint32_t>(t);
     }
-    if (kTrav == 4) trace_lane_ww<16, true>(p.qnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h);
-    else if (kTrav == 22 || kTrav == 24)
-      trace_lane_ww<16, true, false, true>(p.qnodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h, sp0);
-    else if (kTrav == 21)
-      trace_lane_ww_tail<16, 0, false, true>(
-          p.nodes, p.cnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, lds_dyn + 16u * 256u,
-          lds_dyn + 16u * 256u + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
+    if constexpr (K.step == FindStep::kWw && K.by_start)
+      trace_lane_ww<16, K.quant, K.leaf_batch, K.vote>(K.quant ? p.qnodes : p.nodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h, sp0);
+    else if constexpr (K.step == FindStep::kWw)
+      trace_lane_ww<16, K.quant, K.leaf_batch, K.vote>(K.quant ? p.qnodes : p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h);
+    else if constexpr (K.step == FindStep::kWwTail)
+      trace_lane_ww_tail<16, K.top, K.leaf_batch, K.vote>(
+          p.nodes, p.cnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, lds_dyn + kStackDwords,
+          lds_dyn + kStackDwords + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
           lds_dyn + kFindTailLdsDwords);
-    else if (kTrav == 1) trace_lane_bf<kFindBfRows>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
-    else if (kTrav == 12) trace_lane_bf<kFindBfRows, false, true>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
-    else if (kTrav == 16 || kTrav == 17 || kTrav == 19 || kTrav == 20 || kTrav == 23 || (kTrav >= 26 && kTrav <= 32))
-      trace_lane_bf_tail<kFindBfRows, kTrav != 16 && kTrav != 20, find_leaf_trigger(kTrav), kTrav == 26, kTrav == 27, kTrav == 28, (kTrav == 29 ? 4 : (kTrav == 30 ? 3 : 5)), kTrav < 31>(kTrav == 26 ? p.qnodes : p.nodes, p.cnodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x,
-                                                   lds_dyn + kFindBfRows * 256u,
-                                                   lds_dyn + kFindBfRows * 256u + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
-                                                   kClock ? &clk_visits : nullptr, sp0, kClock ? clk_dbg : nullptr, &pre_nrec, &pre_rec, (kTrav == 32) ? &coop_seed : nullptr);
-    else if (kTrav == 13) trace_lane_bf<kFindBfRows, false, false, true>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
-    else if (kTrav == 14) trace_lane_bf<kFindBfRows, false, true, true>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
-    else if (kTrav >= 5 && kTrav <= 10)
-      trace_lane_ww_tail<16, kTop, find_leaf_batch(kTrav)>(
-          p.nodes, p.cnodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, lds_dyn + 16u * 256u,
-          lds_dyn + 16u * 256u + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
-          lds_dyn + kFindTailLdsDwords);
-    else trace_lane_ww<16>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, blockDim.x, h);
+    else if constexpr (K.step == FindStep::kBf)
+      trace_lane_bf<kFindBfRows, K.quant, K.leaf_batch, K.uniform>(p.nodes, p.tris, org_m, dir_m, ray_tfar, lds_dyn + threadIdx.x, h);
+    else
+      trace_lane_bf_tail<kFindBfRows, K.leaf_batch, K.leaf_trigger, K.quant, K.pre, K.pipe, K.sort_steps, K.tail>(
+          K.quant ? p.qnodes : p.nodes, p.cnodes, p.tris, org_m, dir_m, rs, ray_tfar, lds_dyn + threadIdx.x, lds_dyn + kStackDwords,
+          lds_dyn + kStackDwords + kQuadStackEntries * 64u + (threadIdx.x >> 6) * (kTailRays * kTailXferDwords), h,
+          kClock ? &clk_visits : nullptr, sp0, kClock ? clk_dbg : nullptr, &pre_nrec, &pre_rec, K.coop ? &coop_seed : nullptr);
   }
 
   if (kClock && p.wave_clock != nullptr) {
@@ -453,7 +454,7 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
     // the record's last 16 B: unit normal + the ORIGINAL face id
     if ((p.normals && w2) || (p.face_ids && w0) || kMoments) {
       uint4 nrec;
-      if (kTrav == 27 && pre_rec == h.rec) nrec = pre_nrec;   // (rays finished by the quad tail fetch it here)
+      if (K.pre && pre_rec == h.rec) nrec = pre_nrec;   // (rays finished by the quad tail fetch it here)
       else nrec = reinterpret_cast<const uint4*>(p.tris)[static_cast<size_t>(h.rec) * 4u + 3u];
       if ((p.normals && w2) || kMoments) {
         f3 n = qrot(Tms.R, mk3(asf(nrec.x), asf(nrec.y), asf(nrec.z)));
@@ -489,12 +490,12 @@ __global__ void __launch_bounds__(256) k_find(const FindParams p) {
                             (wmax(min(clk_dbg[2] >> 6, 4095u), 12) << 20);
     if ((threadIdx.x & 63u) == 0u) {
       uint32_t* w = p.wave_clock + 8u * ((blockIdx.y * gridDim.x + blockIdx.x) * 4u + wave);
-      // kinds 23 / 31: w[2] = cycles of the start (>> 4, 16 bits) | the wave's most leaf visits of a lane << 16 | most node visits << 24 instead of the realtime clock
-      const uint32_t w2 = (kTrav == 23 || kTrav == 31 || kTrav == 32) ? (min((clk_start - clk_trace0) >> 4, 0xFFFFu) | (wmax(min(clk_dbg[3], 255u), 8) << 16) | (wmax(min(clk_visits, 255u), 8) << 24)) : clk_real;
+      // K.clock_start: w[2] = cycles of the start (>> 4, 16 bits) | the wave's most leaf visits of a lane << 16 | most node visits << 24 instead of the realtime clock
+      const uint32_t w2 = K.clock_start ? (min((clk_start - clk_trace0) >> 4, 0xFFFFu) | (wmax(min(clk_dbg[3], 255u), 8) << 16) | (wmax(min(clk_visits, 255u), 8) << 24)) : clk_real;
       w[0] = clk_begin; w[1] = static_cast<uint32_t>(t); w[2] = w2; w[3] = (tile & 0xFFFFFFu) | (xcc << 24);
       w[4] = clk_trace0; w[5] = clk_trace1; w[6] = static_cast<uint32_t>(t2);
-      w[7] = (kTrav == 31 || kTrav == 32) ? clk_descent : clk_w7;   // kinds 31 and 32: what its cooperative descent did (traverse.hip.h frontier_descent_start)
-      if (kTrav == 31 || kTrav == 32) {   // ... and when: 16 more words per wave behind the table of all waves
+      w[7] = K.descent() ? clk_descent : clk_w7;   // the descent kinds: what the cooperative descent did (traverse.hip.h frontier_descent_start)
+      if (K.descent()) {   // ... and when: 16 more words per wave behind the table of all waves
         uint32_t* ws = p.wave_clock + 8u * (gridDim.y * gridDim.x * 4u) + 16u * ((blockIdx.y * gridDim.x + blockIdx.x) * 4u + wave);
 #pragma unroll
         for (uint32_t i = 0; i < 16u; ++i) ws[i] = clk_stamps[i];

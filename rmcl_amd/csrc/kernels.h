@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "devmath.h"
+#include "find_kinds.h"
 #include "layout.h"
 #include "micp_host.h"
 
@@ -47,7 +48,7 @@ struct FindParams {
   float* points;
   float* normals;
   uint32_t* face_ids;
-  // frontier start (kinds 23 / 24): the map's frontier table and what bounds a hit's distance from any origin
+  // frontier start (find_kinds.h FindKind::frontier()): the map's frontier table and what bounds a hit's distance from any origin
   const uint32_t* frontier;      // n_frontier x 8 dwords {lo.xyz hi.x | hi.yz ref pad} (layout.h kFrontierDepth)
   uint32_t n_frontier;
   f3 scene_center;
@@ -266,10 +267,17 @@ uint32_t batch_order_scratch_dwords(uint32_t n);
 hipError_t launch_batch_tile_order(const FindParams& p, ModelKind kind, uint32_t group, f3 bb_min, f3 bb_max, uint32_t* scratch, uint32_t* order,
                                    hipStream_t s);
 hipError_t launch_find(const FindParams& p, ModelKind kind, int variant, hipStream_t s);
-// kinds 23 / 2 with the MICP moment epilogue: grid of find_moments_blocks(p, kind) workgroups, one partial row per workgroup, one mask
-// word per wave (23) or per workgroup (2: a tile is a workgroup) (p.mom_* set by the caller); followed by launch_micp_fast_loop_tiled
-uint32_t find_moments_blocks(const FindParams& p, int variant);
-hipError_t launch_find_moments(const FindParams& p, ModelKind kind, int variant, hipStream_t s);   // variant 23 (a mask word per wave) or 2 (per workgroup)
+// the kinds with the MICP moment epilogue (find_kinds.h FindKind::moments): find_launch_shape(p, variant, true).grid_x workgroups, one
+// partial row per workgroup and one mask word per tile, that is find_kind(variant).tiles_per_block words per workgroup (p.mom_* set by
+// the caller); followed by launch_micp_fast_loop_tiled
+hipError_t launch_find_moments(const FindParams& p, ModelKind kind, int variant, hipStream_t s);
+// THE launch shape of k_find, for every kind and every caller: the grid (gridDim.x % 8 == 0; the one-row grid of the world order when
+// the launch has a tile order), the dynamic LDS and the size of a clocked launch's p.wave_clock.  All zero: no such kind.
+struct FindLaunchShape {
+  uint32_t grid_x, grid_y, lds_bytes, clock_dwords;
+};
+FindLaunchShape find_launch_shape(int kind, bool moments, uint32_t ntiles, uint32_t nposes, uint32_t n_tile_order, uint32_t granule);   // n_tile_order 0: pose-major
+FindLaunchShape find_launch_shape(const FindParams& p, int kind, bool moments);
 // the plane table of the frontier start (kinds 23 / 24): tiles_x * tiles_y * 16 floats for p's model and tiling
 hipError_t launch_tile_planes(const FindParams& p, ModelKind kind, float* planes, hipStream_t s);
 // diagnostics (tools/probe_find.py): per-wave step timeline of one spherical scan; probe_log: tiles x 512 dwords

@@ -1,6 +1,6 @@
 // kernels.hip -- PRODUCTION kernels of librmclhip.so (gfx950, MI355X, CDNA4) for the RMCL / MICP-L hot path.
 //
-//  k_find            (find_kernel.hip.h) ray-casting correspondences, the kinds the product can select (0, 2, 23, 24)
+//  k_find            (find_kernel.hip.h) ray-casting correspondences, the kinds the product can select (find_kinds.h)
 //  k_cpc_find        (traverse.hip.h) closest-point correspondences, CPCEmbree::find
 //  k_reduce_partials rm::statistics_p2l (CorrespondencesCPU.cpp:26-30; gate MICPSensorCPU.cpp:70-84); its 16 sums, the wave that
 //                    finishes them and the completion tag are in reduce_common.hip.h, shared with the MICP iterations
@@ -12,6 +12,8 @@
 // Experiments (rejected traversal kinds, probes, the round-2 particle-filter kernels) live in kernels_lab.hip and ship in
 // librmclhip_lab.so; launch_find / launch_pf_update hand kinds they do not own to that library when it is loaded
 // (lab_hooks.h), and report kLabMissing (kernels.h) otherwise.
+#include <type_traits>
+
 #include "find_kernel.hip.h"
 #include "lab_hooks.h"
 #include "pc2_load.hip.h"
@@ -785,6 +787,18 @@ __global__ void k_compact_records(const uint32_t* __restrict__ padded, uint32_t*
 // ---------------------------------------------------------------------------------------------
 namespace {
 const LabHooks* g_lab = nullptr;
+
+// the run-time sensor model as a compile-time constant: f(std::integral_constant<uint32_t, kModel...>); false = no such model
+template <class F>
+bool with_model(ModelKind kind, F&& f) {
+  switch (kind) {
+    case kModelSpherical: f(std::integral_constant<uint32_t, kModelSpherical>{}); return true;
+    case kModelO1Dn: f(std::integral_constant<uint32_t, kModelO1Dn>{}); return true;
+    case kModelPinhole: f(std::integral_constant<uint32_t, kModelPinhole>{}); return true;
+    case kModelOnDn: f(std::integral_constant<uint32_t, kModelOnDn>{}); return true;
+    default: return false;
+  }
+}
 }
 const LabHooks* lab_hooks() { return g_lab; }
 
@@ -872,134 +886,90 @@ hipError_t launch_batch_tile_order(const FindParams& p, ModelKind kind, uint32_t
   hipError_t e = hipMemsetAsync(cells, 0, kOrderCells * sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   const dim3 grid((n + 255u) / 256u), block(256);
-  switch (kind) {
-    case kModelSpherical: hipLaunchKernelGGL((k_batch_tile_keys<kModelSpherical>), grid, block, 0, s, p, group, ngroups, bb_min, bb_max, keys, cells); break;
-    case kModelO1Dn: hipLaunchKernelGGL((k_batch_tile_keys<kModelO1Dn>), grid, block, 0, s, p, group, ngroups, bb_min, bb_max, keys, cells); break;
-    case kModelPinhole: hipLaunchKernelGGL((k_batch_tile_keys<kModelPinhole>), grid, block, 0, s, p, group, ngroups, bb_min, bb_max, keys, cells); break;
-    case kModelOnDn: hipLaunchKernelGGL((k_batch_tile_keys<kModelOnDn>), grid, block, 0, s, p, group, ngroups, bb_min, bb_max, keys, cells); break;
-    default: return hipErrorInvalidValue;
-  }
+  const bool known = with_model(kind, [&](auto m) {
+    hipLaunchKernelGGL((k_batch_tile_keys<decltype(m)::value>), grid, block, 0, s, p, group, ngroups, bb_min, bb_max, keys, cells);
+  });
+  if (!known) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_batch_cell_scan, dim3(1), block, 0, s, cells);
   hipLaunchKernelGGL(k_batch_tile_scatter, grid, block, 0, s, keys, cells, ngroups, n, order);
   return hipGetLastError();
 }
 
+FindLaunchShape find_launch_shape(int kind, bool moments, uint32_t ntiles, uint32_t nposes, uint32_t n_tile_order, uint32_t granule) {
+  const FindKind K = find_kind(kind);
+  FindLaunchShape sh = {0u, 0u, 0u, 0u};
+  if (!K.exists) return sh;
+  moments = moments && K.moments;
+  sh.grid_x = ((ntiles + K.tiles_per_block() - 1u) / K.tiles_per_block() + 7u) & ~7u;  // the XCD remap in k_find needs gridDim.x % 8 == 0
+  sh.grid_y = moments ? 1u : nposes;   // (the moment epilogue: one scan, and k_find ignores the world order under it)
+  if (n_tile_order != 0u && !moments) {   // world order: one row of blocks over the sorted (pose, tile) list, one entry per workgroup
+    const uint32_t turn = 8u * max(granule, 1u);
+    sh.grid_x = (n_tile_order + turn - 1u) / turn * turn;   // whole turns of the eight XCDs (k_find's slot mapping)
+    sh.grid_y = 1u;
+  }
+  sh.lds_bytes = find_lds_dwords(kind, moments) * static_cast<uint32_t>(sizeof(uint32_t));
+  sh.clock_dwords = sh.grid_x * sh.grid_y * 4u * K.clock_words();
+  return sh;
+}
+FindLaunchShape find_launch_shape(const FindParams& p, int kind, bool moments) {
+  return find_launch_shape(kind, moments, p.tiles_x * p.tiles_y, p.nposes, p.tile_order != nullptr ? p.n_tile_order : 0u, p.tile_order_granule);
+}
+
+namespace {
+// the product's k_find<model, kTrav, no clocks, kMoments, kCarry>
+template <int kTrav, bool kMoments, bool kCarry = false>
+hipError_t launch_find_one(const FindParams& p, ModelKind kind, hipStream_t s) {
+  static_assert(find_kind(kTrav).in_product && (!kMoments || find_kind(kTrav).moments), "not a kernel of the product (find_kinds.h)");
+  const FindLaunchShape sh = find_launch_shape(p, kTrav, kMoments);
+  const bool known = with_model(kind, [&](auto m) {
+    hipLaunchKernelGGL((k_find<decltype(m)::value, kTrav, false, kMoments, kCarry>), dim3(sh.grid_x, sh.grid_y, 1), dim3(256, 1, 1), sh.lds_bytes, s, p);
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+// kind 32: bit 16 of descent_levels = pending candidates in the cooperative leaf loop, a kernel of its own
+template <bool kMoments>
+hipError_t launch_find_32(const FindParams& p, ModelKind kind, hipStream_t s) {
+  return ((p.descent_levels >> 16) & 1u) ? launch_find_one<32, kMoments, true>(p, kind, s) : launch_find_one<32, kMoments>(p, kind, s);
+}
+}  // namespace
+
+// the two switches below list the product's 40 k_find kernels (x 4 models each), in the order the object file holds them
 hipError_t launch_find(const FindParams& p, ModelKind kind, int variant, hipStream_t s) {
-  if (!find_kind_in_product(variant) || p.wave_clock != nullptr) {
+  if (!find_kind(variant).in_product || p.wave_clock != nullptr) {
     // an experiment's kind, or a clocked launch of any kind (tools/wave_timeline.py): librmclhip_lab.so
     if (g_lab && g_lab->find) return g_lab->find(p, kind, variant, p.wave_clock != nullptr, s);
     return kLabMissing;
   }
-  const uint32_t ntiles = p.tiles_x * p.tiles_y;
-  uint32_t nblocks = (variant == 2) ? ntiles : (ntiles + 3u) / 4u;
-  nblocks = (nblocks + 7u) & ~7u;  // the XCD remap in k_find needs gridDim.x % 8 == 0
-  dim3 grid(nblocks, p.nposes, 1), block(256, 1, 1);
-  if (p.tile_order != nullptr) {   // world order: one row of blocks over the sorted (pose, tile) list
-    const uint32_t nb = p.n_tile_order, turn = 8u * max(p.tile_order_granule, 1u);   // (one entry per workgroup)
-    grid = dim3((nb + turn - 1u) / turn * turn, 1, 1);   // whole turns of the eight XCDs (k_find's slot mapping)
+  switch (variant) {
+    case 0: return launch_find_one<0, false>(p, kind, s);
+    case 2: return launch_find_one<2, false>(p, kind, s);
+    case 23: return launch_find_one<23, false>(p, kind, s);
+    case 32: return launch_find_32<false>(p, kind, s);
+    case 24: return launch_find_one<24, false>(p, kind, s);
+    default: return hipErrorInvalidValue;
   }
-#define RMCL_LAUNCH_FIND(TRAV, LDS)                                                                                   \
-  switch (kind) {                                                                                                     \
-    case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, TRAV>), grid, block, LDS, s, p); break;         \
-    case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, TRAV>), grid, block, LDS, s, p); break;                   \
-    case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, TRAV>), grid, block, LDS, s, p); break;             \
-    case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, TRAV>), grid, block, LDS, s, p); break;                   \
-    default: return hipErrorInvalidValue;                                                                             \
-  }
-  if (variant == 0) {  // wave-packet traversal (needs map stack_need <= 64, checked at map creation)
-    RMCL_LAUNCH_FIND(0, 0)
-  } else if (variant == 2) {  // quad-cooperative: 64 rays per block, 64 stack entries per ray in LDS
-    const size_t lds = kQuadStackEntries * 64u * sizeof(uint32_t);
-    RMCL_LAUNCH_FIND(2, lds)
-  } else if (variant == 23) {  // one lane per ray: frontier start, branch-free step, one-round-trip leaves, quad-finished tails, leaf trigger
-    const size_t lds = (static_cast<size_t>(kFindBfRows) * 256u + kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords) * sizeof(uint32_t);
-    RMCL_LAUNCH_FIND(23, lds)
-  } else if (variant == 32) {  // the cooperative descent below the frontier, one bit per final leaf and ray: + the four waves' lists
-    const size_t lds = static_cast<size_t>(kFind31LdsDwords) * sizeof(uint32_t);
-    if ((p.descent_levels >> 16) & 1u) {   // pending candidates in the cooperative leaf loop: a kernel of its own
-      switch (kind) {
-        case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, false, true>), grid, block, lds, s, p); break;
-        case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, false, true>), grid, block, lds, s, p); break;
-        case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 32, false, false, true>), grid, block, lds, s, p); break;
-        case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 32, false, false, true>), grid, block, lds, s, p); break;
-        default: return hipErrorInvalidValue;
-      }
-    } else {
-      RMCL_LAUNCH_FIND(32, lds)
-    }
-  } else {                     // 24: one lane per ray on the 64-B quantised nodes: frontier start, leaf trigger, 16 LDS rows
-    const size_t lds4 = 16u * 256u * sizeof(uint32_t);
-    RMCL_LAUNCH_FIND(24, lds4)
-  }
-#undef RMCL_LAUNCH_FIND
-  return hipGetLastError();
-}
-
-uint32_t find_moments_blocks(const FindParams& p, int variant) {
-  const uint32_t ntiles = p.tiles_x * p.tiles_y;
-  return (((variant == 2) ? ntiles : (ntiles + 3u) / 4u) + 7u) & ~7u;
 }
 
 hipError_t launch_find_moments(const FindParams& p, ModelKind kind, int variant, hipStream_t s) {
   static_assert(kMomRow == kMicpFastMoments && kMomRow == static_cast<uint32_t>(kMom), "one partial-row layout");
-  if (p.nposes != 1u || p.wave_clock != nullptr || p.mom_partials == nullptr || p.mom_unc_mask == nullptr || (variant != 23 && variant != 32 && variant != 2))
-    return hipErrorInvalidValue;
-  dim3 grid(find_moments_blocks(p, variant), 1, 1), block(256, 1, 1);
-  if (variant == 2) {
-    // quad kind: the ray stacks, then the four waves' staging rows (21 rows of 256 dwords, find_moments_wave)
-    const size_t lds = (static_cast<size_t>(kQuadStackEntries) * 64u + 21u * 256u) * sizeof(uint32_t);
-    switch (kind) {
-      case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 2, false, true>), grid, block, lds, s, p); break;
-      case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 2, false, true>), grid, block, lds, s, p); break;
-      case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 2, false, true>), grid, block, lds, s, p); break;
-      case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 2, false, true>), grid, block, lds, s, p); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (variant == 32) {   // kind 23's epilogue behind the cooperative descent (+ the four waves' lists)
-    const size_t lds31 = static_cast<size_t>(kFind31LdsDwords) * sizeof(uint32_t);
-    if ((p.descent_levels >> 16) & 1u) {   // pending candidates in the cooperative leaf loop
-      switch (kind) {
-        case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, true, true>), grid, block, lds31, s, p); break;
-        case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, true, true>), grid, block, lds31, s, p); break;
-        case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 32, false, true, true>), grid, block, lds31, s, p); break;
-        case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 32, false, true, true>), grid, block, lds31, s, p); break;
-        default: return hipErrorInvalidValue;
-      }
-      return hipGetLastError();
-    }
-    switch (kind) {
-      case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 32, false, true>), grid, block, lds31, s, p); break;
-      case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 32, false, true>), grid, block, lds31, s, p); break;
-      case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 32, false, true>), grid, block, lds31, s, p); break;
-      case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 32, false, true>), grid, block, lds31, s, p); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  const size_t lds = (static_cast<size_t>(kFindBfRows) * 256u + kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords) * sizeof(uint32_t);
-  switch (kind) {
-    case kModelSpherical: hipLaunchKernelGGL((k_find<kModelSpherical, 23, false, true>), grid, block, lds, s, p); break;
-    case kModelO1Dn: hipLaunchKernelGGL((k_find<kModelO1Dn, 23, false, true>), grid, block, lds, s, p); break;
-    case kModelPinhole: hipLaunchKernelGGL((k_find<kModelPinhole, 23, false, true>), grid, block, lds, s, p); break;
-    case kModelOnDn: hipLaunchKernelGGL((k_find<kModelOnDn, 23, false, true>), grid, block, lds, s, p); break;
+  if (p.nposes != 1u || p.wave_clock != nullptr || p.mom_partials == nullptr || p.mom_unc_mask == nullptr) return hipErrorInvalidValue;
+  switch (variant) {
+    case 2: return launch_find_one<2, true>(p, kind, s);
+    case 32: return launch_find_32<true>(p, kind, s);
+    case 23: return launch_find_one<23, true>(p, kind, s);
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 hipError_t launch_tile_planes(const FindParams& p, ModelKind kind, float* planes, hipStream_t s) {
   const uint32_t ntiles = p.tiles_x * p.tiles_y;
   if (ntiles == 0u) return hipSuccess;
   const dim3 grid((ntiles + 3u) / 4u), block(256);
-  switch (kind) {
-    case kModelSpherical: hipLaunchKernelGGL((k_tile_planes<kModelSpherical>), grid, block, 0, s, p, planes); break;
-    case kModelO1Dn: hipLaunchKernelGGL((k_tile_planes<kModelO1Dn>), grid, block, 0, s, p, planes); break;
-    case kModelPinhole: hipLaunchKernelGGL((k_tile_planes<kModelPinhole>), grid, block, 0, s, p, planes); break;
-    default: return hipErrorInvalidValue;   // OnDn: one origin per ray, no pyramid
-  }
-  return hipGetLastError();
+  if (kind == kModelOnDn) return hipErrorInvalidValue;   // one origin per ray, no pyramid: no k_tile_planes<OnDn> either
+  const bool known = with_model(kind, [&](auto m) {
+    if constexpr (decltype(m)::value != kModelOnDn) hipLaunchKernelGGL((k_tile_planes<decltype(m)::value>), grid, block, 0, s, p, planes);
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_find_probe(const FindParams& p, int mode, uint32_t* probe_log, hipStream_t s) {

@@ -371,58 +371,28 @@ namespace {
 
 // spherical model only: the experiments and the clock timelines are run on the benchmark scans
 template <int kTrav, bool kClock>
-hipError_t lab_find_one(const FindParams& p, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 65536u) {
+hipError_t lab_find_one(const FindParams& p, hipStream_t s) {
+  const FindLaunchShape sh = find_launch_shape(p, kTrav, false);
+  if (sh.lds_bytes > 65536u) {
     // more than 64 KB of dynamic LDS per block must be granted per kernel and per device; rare A/B kinds, so simply repeated
     const hipError_t ge = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_find<kModelSpherical, kTrav, kClock>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sh.lds_bytes));
     if (ge != hipSuccess) return ge;
   }
-  hipLaunchKernelGGL((k_find<kModelSpherical, kTrav, kClock>), grid, dim3(256), lds, s, p);
+  hipLaunchKernelGGL((k_find<kModelSpherical, kTrav, kClock>), dim3(sh.grid_x, sh.grid_y, 1), dim3(256), sh.lds_bytes, s, p);
   return hipGetLastError();
 }
 
+// every kind of find_kinds.h (the product's own: clocked only, see lab_find), in the order the object file holds the kernels
 template <bool kClock>
 hipError_t lab_find_kind(const FindParams& p, int variant, hipStream_t s) {
-  const uint32_t ntiles = p.tiles_x * p.tiles_y;
-  uint32_t nblocks = (variant == 2 || variant == 25) ? ntiles : (ntiles + 3u) / 4u;
-  nblocks = (nblocks + 7u) & ~7u;  // the XCD remap in k_find needs gridDim.x % 8 == 0
-  const dim3 grid(nblocks, p.nposes, 1);
-  const size_t lds_bf = static_cast<size_t>(kFindBfRows) * 256u * sizeof(uint32_t);
-  const size_t lds_bf_tail = (static_cast<size_t>(kFindBfRows) * 256u + kQuadStackEntries * 64u + 4u * kTailRays * kTailXferDwords) * sizeof(uint32_t);
-  const size_t lds_ww = 16u * 256u * sizeof(uint32_t);
-  const size_t lds_ww_tail = (kFindTailLdsDwords + static_cast<uint32_t>(find_top_nodes(variant)) * kNodeDwords) * sizeof(uint32_t);
   switch (variant) {
-    case 0: return lab_find_one<0, kClock>(p, grid, 0, s);                                     // (clocked only: the product owns kind 0)
-    case 1: return lab_find_one<1, kClock>(p, grid, lds_bf, s);                                // branch-free step, no tail
-    case 2: return lab_find_one<2, kClock>(p, grid, kQuadStackEntries * 64u * sizeof(uint32_t), s);
-    case 4: return lab_find_one<4, kClock>(p, grid, lds_ww, s);
-    case 5: return lab_find_one<5, kClock>(p, grid, lds_ww_tail, s);                           // while-while + quad-finished tails
-    case 6: return lab_find_one<6, kClock>(p, grid, lds_ww_tail, s);                           // + 85-node LDS top
-    case 7: return lab_find_one<7, kClock>(p, grid, lds_ww_tail, s);                           // + 341-node LDS top
-    case 8: return lab_find_one<8, kClock>(p, grid, lds_ww_tail, s);                           // + one-round-trip leaves
-    case 9: return lab_find_one<9, kClock>(p, grid, lds_ww_tail, s);
-    case 10: return lab_find_one<10, kClock>(p, grid, lds_ww_tail, s);
-    case 11: return lab_find_one<11, kClock>(p, grid, lds_ww, s);                              // the branchy while-while step
-    case 12: return lab_find_one<12, kClock>(p, grid, lds_bf, s);                              // branch-free + one-round-trip leaves
-    case 13: return lab_find_one<13, kClock>(p, grid, lds_bf, s);                              // wave-uniform nodes through the scalar cache
-    case 14: return lab_find_one<14, kClock>(p, grid, lds_bf, s);
-    case 16: return lab_find_one<16, kClock>(p, grid, lds_bf_tail, s);                         // branch-free + tails
-    case 17: return lab_find_one<17, kClock>(p, grid, lds_bf_tail, s);                         // + one-round-trip leaves (round 2's default before the trigger)
-    case 19: return lab_find_one<19, kClock>(p, grid, lds_bf_tail, s);
-    case 20: return lab_find_one<20, kClock>(p, grid, lds_bf_tail, s);                         // 16 + leaf trigger
-    case 21: return lab_find_one<21, kClock>(p, grid, kFindTailLdsDwords * sizeof(uint32_t), s);
-    case 22: return lab_find_one<22, kClock>(p, grid, lds_ww, s);
-    case 23: return lab_find_one<23, kClock>(p, grid, lds_bf_tail, s);                         // 19 + frontier start
-    case 24: return lab_find_one<24, kClock>(p, grid, lds_ww, s);                              // 22 + frontier start
-    case 30: return lab_find_one<30, kClock>(p, grid, lds_bf_tail, s);                           // 23, only the nearest child found
-    case 29: return lab_find_one<29, kClock>(p, grid, lds_bf_tail, s);                           // 23, the middle two children unordered
-    case 28: return lab_find_one<28, kClock>(p, grid, lds_bf_tail, s);                           // 23 with the software-pipelined node step
-    case 27: return lab_find_one<27, kClock>(p, grid, lds_bf_tail, s);                           // 23 + prefetch of the hit record's normal (experiment iv)
-    case 26: return lab_find_one<26, kClock>(p, grid, lds_bf_tail, s);                           // 23 on the quantised nodes
-    case 25: return lab_find_one<25, kClock>(p, grid, kQuadStackEntries * 64u * sizeof(uint32_t), s);   // 2 + frontier start
-    case 31: return lab_find_one<31, kClock>(p, grid, kFind31LdsDwords * sizeof(uint32_t), s);   // 23 + cooperative descent, sorted hand-over of the final entries (round 6's first form)
-    case 32: return lab_find_one<32, kClock>(p, grid, kFind31LdsDwords * sizeof(uint32_t), s);   // (clocked only) 31 with one bit per final leaf and ray instead of the sorted hand-over
+#define RMCL_LAB_KIND(N) case N: return lab_find_one<N, kClock>(p, s);
+    RMCL_LAB_KIND(0) RMCL_LAB_KIND(1) RMCL_LAB_KIND(2) RMCL_LAB_KIND(4) RMCL_LAB_KIND(5) RMCL_LAB_KIND(6) RMCL_LAB_KIND(7) RMCL_LAB_KIND(8)
+    RMCL_LAB_KIND(9) RMCL_LAB_KIND(10) RMCL_LAB_KIND(11) RMCL_LAB_KIND(12) RMCL_LAB_KIND(13) RMCL_LAB_KIND(14) RMCL_LAB_KIND(16) RMCL_LAB_KIND(17)
+    RMCL_LAB_KIND(19) RMCL_LAB_KIND(20) RMCL_LAB_KIND(21) RMCL_LAB_KIND(22) RMCL_LAB_KIND(23) RMCL_LAB_KIND(24) RMCL_LAB_KIND(30) RMCL_LAB_KIND(29)
+    RMCL_LAB_KIND(28) RMCL_LAB_KIND(27) RMCL_LAB_KIND(26) RMCL_LAB_KIND(25) RMCL_LAB_KIND(31) RMCL_LAB_KIND(32)
+#undef RMCL_LAB_KIND
     default: return kLabMissing;
   }
 }
@@ -430,14 +400,13 @@ hipError_t lab_find_kind(const FindParams& p, int variant, hipStream_t s) {
 hipError_t lab_find(const FindParams& p, ModelKind kind, int variant, bool with_clock, hipStream_t s) {
   if (kind != kModelSpherical) return kLabMissing;
   if (with_clock) return lab_find_kind<true>(p, variant, s);
-  if (find_kind_in_product(variant)) return hipErrorInvalidValue;   // the product launches its own kinds
+  if (find_kind(variant).in_product) return hipErrorInvalidValue;   // the product launches its own kinds
   return lab_find_kind<false>(p, variant, s);
 }
 
 hipError_t lab_find_probe(const FindParams& p, int mode, uint32_t* probe_log, hipStream_t s) {
-  const uint32_t ntiles = p.tiles_x * p.tiles_y;
-  uint32_t nblocks = ((ntiles + 3u) / 4u + 7u) & ~7u;
-  const dim3 grid(nblocks, 1, 1), block(256, 1, 1);
+  // k_find_probe is kind 11's traversal (modes 2, 3: with kind 6's 85-node top) on kind 11's grid
+  const dim3 grid(find_launch_shape(11, false, p.tiles_x * p.tiles_y, 1u, 0u, 0u).grid_x, 1, 1), block(256, 1, 1);
   const size_t lds0 = 16u * 256u * sizeof(uint32_t);
   if (mode == 0) hipLaunchKernelGGL((k_find_probe<false, 0>), grid, block, lds0, s, p, probe_log);
   else if (mode == 1) hipLaunchKernelGGL((k_find_probe<true, 0>), grid, block, lds0, s, p, probe_log);

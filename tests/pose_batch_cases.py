@@ -48,8 +48,9 @@ def variant_word(kind, tile_bits=0):
 
 
 def group_of(kind):
-    """tiles per workgroup of a find of this traversal kind: the quad kind runs one tile per workgroup"""
-    return 1 if kind == 2 else 4
+    """tiles per workgroup of a find of this traversal kind: the quad kinds (2, and 25 = 2 with the frontier start) run one tile per
+    workgroup"""
+    return 1 if kind in (2, 25) else 4
 
 
 def tiling(twl, h=H, w=W):

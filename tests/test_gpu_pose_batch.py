@@ -175,7 +175,7 @@ def test_edge_poses_in_the_operators_own_buffers(ra, orc, ctx, variant, map_name
 
 
 # ---- c. one cell --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("variant", find_kinds(0, 2, 23, 24, 32))
+@pytest.mark.parametrize("variant", find_kinds(0, 2, 23, 24, 32, 17, 25))
 def test_a_batch_whose_entries_share_one_cell(ra, orc, ctx, variant):
     """40 poses with NaN translations: one key, the order still a permutation, every output a miss with the miss values; then
     `spread` on the same operator (its buffers and sort scratch go from the largest cell population to the smallest) equals the
