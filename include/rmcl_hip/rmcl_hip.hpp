@@ -1480,6 +1480,18 @@ inline SurfaceStats constrainToSurface(const HipMapPtr& map, ParticleCloud<VRAM_
   return constrainToSurface(map, cloud.posesView(), cloud.attrsView(), params, max_n_meas);
 }
 
+// The sampled odometry model of the motion update (rmclhip.h, MOTION NOISE): every particle's step is composed with a Gaussian whose
+// standard deviations grow with the length and the angle of the step.  MotionNoiseParams{} holds the library's defaults, AMCL's 0.2
+// throughout; sigma(T) is rmclhip_motion_noise_sigma_host: body x y z in metres, roll pitch yaw in radians, zeros for an identity step.
+struct MotionNoiseParams : rmclhip_motion_noise_params {
+  MotionNoiseParams() { rmclhip_motion_noise_params_default(this); }
+  std::array<float, 6> sigma(const Transform& T_bnew_bold) const {
+    std::array<float, 6> s{};
+    check(rmclhip_motion_noise_sigma_host(this, &T_bnew_bold, s.data()));
+    return s;
+  }
+};
+
 // The surface sampler (rmclhip.h, SURFACE SAMPLER): poses drawn uniformly by area on the drivable faces of the map -- the global
 // initialisation of a ground robot and the fresh draws of the recovery injection.  SurfaceSampleParams{} holds the library's defaults:
 // min_up_cos 0.7, height 0, align 0, region unbounded, yaw in [-pi, pi].
@@ -1632,10 +1644,30 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
   }
   // MotionUpdater<MemT>::update on every device's block, in place (rmcl_localization.cpp:432-480; particle_motion.cu:11-46 + the collision
   // ray of TFMotionUpdaterCPU.cpp:17-50): the odometry lookup and the combined forget rate stay with the caller, as for TFMotionUpdaterHip
+  // setNoise: the sampled odometry model (MotionNoiseParams) -- sigma follows every step, the draws are those of (seed, the updater's own
+  // step count, the particle's global index): the single-device updater's, whatever the number of devices
   void motionUpdate(const Transform& T_bnew_bold, double forget_rate, bool check_collision = true) {
     check(rmclhip_pf_sharded_set_params(h_, &config_));
+    const uint32_t step = motion_step_++;
+    if (noise_) {
+      const std::array<float, 6> sigma = noise_->sigma(T_bnew_bold);
+      check(rmclhip_pf_sharded_motion_update_noisy(h_, &T_bnew_bold, forget_rate, check_collision ? 1 : 0, sigma.data(), noise_seed_, step));
+      return;
+    }
     check(rmclhip_pf_sharded_motion_update(h_, &T_bnew_bold, forget_rate, check_collision ? 1 : 0));
   }
+  // motionUpdate draws with (seed, motionStep()); step() draws with the seed and step_index it is given (rmclhip_pf_sharded_set_motion_noise)
+  void setNoise(const MotionNoiseParams& params, uint64_t seed) {
+    check(rmclhip_pf_sharded_set_motion_noise(h_, &params));
+    noise_ = params;
+    noise_seed_ = seed;
+  }
+  void clearNoise() {
+    check(rmclhip_pf_sharded_set_motion_noise(h_, nullptr));
+    noise_.reset();
+  }
+  uint32_t motionStep() const { return motion_step_; }   // motionUpdate calls since construction or reset()
+  void reset() override { motion_step_ = 0; }
   // one cycle of the node (rmcl_localization.cpp:84, 432-552) in ONE call: motion (T_bnew_bold == nullptr: none) -> sensor update -> weight
   // all-gather -> {sum, max} -> resampling (0 none, 1 gladiator, 2 residual); returns the {sum, max} the resampler normalises with
   rmclhip_likelihood_stats step(const Transform* T_bnew_bold, double forget_rate, bool check_collision, int resample,
@@ -1690,11 +1722,16 @@ class PCDSensorUpdaterHipSharded : public SensorUpdaterBase {
   size_t n_ = 0;
   std::vector<RangeMeasurement> beams_;
   Transform Tsb_ = identity();
+  std::optional<MotionNoiseParams> noise_;
+  uint64_t noise_seed_ = 0;
+  uint32_t motion_step_ = 0;
 };
 
 // rmcl::TFMotionUpdaterGPU (+ the wall-collision test of TFMotionUpdaterCPU) on gfx950: MotionUpdater<MemT>.
 // The odometry lookup (TF) and the forget rate (TFMotionUpdaterCPU.cpp:172-174) stay with the caller.
 // surface: set, the particles are kept on the mesh in the same launch (and the collision segment is lifted by the step height).
+// setNoise(params, seed): the sampled odometry model -- every update composes each particle's step with its own Gaussian draw of
+// (seed, step(), particle index), sigma following the step (MotionNoiseParams); the updater counts its updates, reset() starts over.
 class TFMotionUpdaterHip : public SensorUpdaterBase {
  public:
   bool check_collision = true;
@@ -1713,10 +1750,24 @@ class TFMotionUpdaterHip : public SensorUpdaterBase {
     rmclhip_pf_params pp{2.0f, 100.0f, 100.0f, 0.0f, {0.05f, 80.0f}, max_n_meas, 0u};
     check(rmclhip_pf_set_params(h_, &pp));
     check(rmclhip_pf_set_surface(h_, surface ? &*surface : nullptr));
+    const uint32_t step = step_++;
+    if (noise_) {
+      const std::array<float, 6> sigma = noise_->sigma(T_bnew_bold);
+      check(rmclhip_pf_motion_update_noisy(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &T_bnew_bold, forget_rate,
+                                           check_collision ? 1 : 0, sigma.data(), noise_seed_, step, 0u));
+      return {};
+    }
     check(rmclhip_pf_motion_update(h_, poses.raw(), attrs.raw(), static_cast<uint32_t>(poses.size()), &T_bnew_bold,
                                    forget_rate, check_collision ? 1 : 0));
     return {};
   }
+  void setNoise(const MotionNoiseParams& params, uint64_t seed) {
+    noise_ = params;
+    noise_seed_ = seed;
+  }
+  void clearNoise() { noise_.reset(); }
+  uint32_t step() const { return step_; }   // updates since construction or reset(): the `step` of the next update's draws
+  void reset() override { step_ = 0; }
   // counts of the last constrained update (zeros before the first)
   SurfaceStats surfaceStats() {
     init();
@@ -1728,6 +1779,9 @@ class TFMotionUpdaterHip : public SensorUpdaterBase {
  private:
   HipMapPtr map_;
   rmclhip_pf* h_ = nullptr;
+  std::optional<MotionNoiseParams> noise_;
+  uint64_t noise_seed_ = 0;
+  uint32_t step_ = 0;
 };
 
 // rmcl::GladiatorResamplerGPU on gfx950: Resampler<MemT>::update(poses, attrs, poses_new, attrs_new)

@@ -805,6 +805,50 @@ rmclhip_status rmclhip_pf_get_surface_stats(rmclhip_pf* pf, rmclhip_surface_stat
 rmclhip_status rmclhip_pf_constrain_to_surface(rmclhip_pf* pf, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
                                                uint32_t n_particles, const rmclhip_surface_params* params,
                                                rmclhip_surface_stats* stats_out);
+/* ---- MOTION NOISE: the sampled odometry model, per-particle noise that scales with the step ---------------------------------------
+ * (the reference has none: its resamplers' constant noise stands in for it, ResidualResamplerCPU.cpp:92-94 "a-priori noise. how to
+ * get it here?", and TFMotionUpdater.hpp:50 declares a weight_noise nobody reads.)  This is sample_motion_model_odometry with AMCL's
+ * alpha1..4 spelt out per axis: every particle's step is the odometry's step composed with a Gaussian whose standard deviations grow
+ * with the length and the angle of that step.  A robot that stands does not diffuse: there is deliberately no time term.
+ *
+ * HOST, rmclhip_motion_noise_sigma_host: everything in double from the float fields of T = T_bnew_bold,
+ *   s_t = sqrt((t.x^2 + t.y^2) + t.z^2)                                        metres travelled
+ *   s_r = 2 * atan2(sqrt((R.x^2 + R.y^2) + R.z^2), |R.w|)                      radians turned, in [0, pi]; q and -q give the same
+ *   sigma[k]     = float(sqrt((alpha_trans_trans[k] * s_t)^2 + (alpha_trans_rot[k] * s_r)^2))     k = 0 1 2: body x y z, metres
+ *   sigma[3 + k] = float(sqrt((alpha_rot_trans[k]   * s_t)^2 + (alpha_rot_rot[k]   * s_r)^2))     k = 0 1 2: roll pitch yaw, radians
+ * An identity step gives six zeros.  The defaults are 0.2 throughout (AMCL's alpha1..4).  RMCLHIP_ERR_INVALID: a null argument, a
+ * negative or non-finite alpha, a non-finite component of T's rotation or translation.
+ *
+ * DEVICE, rmclhip_pf_motion_update_noisy: rmclhip_pf_motion_update with, per particle of GLOBAL index g = first_index + i, in float32
+ * unless stated (the library is built without contraction; tests/motion_noise_ref.py restates it in numpy):
+ *   1. moved = pose_old * T_bnew_bold, as in rmclhip_pf_motion_update.
+ *   2. A = Philox4x32-10(counter (g, step, 0, 2), key = seed), B = Philox4x32-10(counter (g, step, 1, 2), key): stream 2, so a resampler
+ *      (stream 0) and an initialiser (stream 1) given the same (seed, step) draw disjoint words.  Box-Muller as in the pose
+ *      initialisation (double, rounded to float): (A0, A1) -> z0, z1; (A2, A3) -> z2, z3; (B0, B1) -> z4, z5.
+ *   3. N.t = (z0 * sigma[0], z1 * sigma[1], z2 * sigma[2]); N.R = EulerAngles(z3 * sigma[3], z4 * sigma[4], z5 * sigma[5]) as the pose
+ *      initialisation builds it.  The noise lives in the body frame of the moved pose: forward and lateral error are different things.
+ *   4. pose_new = moved * N (rmclhip_transform_mult; no normalisation afterwards, as in step 1).
+ *   5. the rest runs on pose_new as rmclhip_pf_motion_update runs it on the moved pose: with check_collision the segment runs from the
+ *      old position to the NOISY new one (a particle the noise pushes through a wall is killed); with the surface constraint set, the
+ *      probe starts from the noisy pose and the lifted collision segment ends at its probe origin.  Forgetting is unchanged.
+ * A result depends on (seed, step, g) and on the particle alone: slices called with their first_index, and any sharding, give the
+ * bytes of one call on the whole cloud.  If all six sigmas are zero (+0 or -0) the call IS rmclhip_pf_motion_update: the same kernel,
+ * the same bytes (a product with an exact identity would still turn a -0.0f component into +0.0f).
+ * RMCLHIP_ERR_INVALID, before anything is launched and with the buffers untouched: a null handle, T_bnew_bold or sigma; a negative or
+ * non-finite sigma; forget_rate outside [0, 1] or NaN; null buffers with n > 0; first_index + n above 2^32.  n == 0: RMCLHIP_OK. */
+typedef struct {
+  float alpha_trans_trans[3]; /* metres of body x, y, z noise per metre travelled */
+  float alpha_trans_rot[3];   /* metres of body x, y, z noise per radian turned */
+  float alpha_rot_trans[3];   /* radians of roll, pitch, yaw noise per metre travelled */
+  float alpha_rot_rot[3];     /* radians of roll, pitch, yaw noise per radian turned */
+} rmclhip_motion_noise_params;
+void rmclhip_motion_noise_params_default(rmclhip_motion_noise_params* out);
+rmclhip_status rmclhip_motion_noise_sigma_host(const rmclhip_motion_noise_params* params, const rmclhip_transform* T_bnew_bold,
+                                               float sigma_out[6]);
+rmclhip_status rmclhip_pf_motion_update_noisy(rmclhip_pf* pf, rmclhip_transform* poses_dev, rmclhip_particle_attributes* attrs_dev,
+                                              uint32_t n_particles, const rmclhip_transform* T_bnew_bold, double forget_rate,
+                                              int check_collision, const float sigma[6], uint64_t seed, uint32_t step,
+                                              uint32_t first_index);
 /* gather likelihood.mean of every particle into a dense float array (the payload of the
  * multi-GPU all-gather) */
 rmclhip_status rmclhip_pf_extract_weights(rmclhip_pf* pf, const rmclhip_particle_attributes* attrs_dev,
@@ -1148,6 +1192,17 @@ rmclhip_status rmclhip_pf_update_sharded(rmclhip_pf_sharded* pf, const rmclhip_r
  * that particle alone). */
 rmclhip_status rmclhip_pf_sharded_motion_update(rmclhip_pf_sharded* pf, const rmclhip_transform* T_bnew_bold, double forget_rate,
                                                 int check_collision);
+/* the motion noise on a sharded cloud (MOTION NOISE above): rmclhip_pf_motion_update_noisy on every device's block, each with the
+ * global index of its first particle as first_index -- the single-device call on the whole cloud, bit for bit, whatever the number of
+ * devices.  The same refusals, before any device is touched. */
+rmclhip_status rmclhip_pf_sharded_motion_update_noisy(rmclhip_pf_sharded* pf, const rmclhip_transform* T_bnew_bold, double forget_rate,
+                                                      int check_collision, const float sigma[6], uint64_t seed, uint32_t step);
+/* later rmclhip_pf_sharded_step calls that are given a T_bnew_bold derive sigma from these parameters and that step
+ * (rmclhip_motion_noise_sigma_host) and draw with their own `seed` and `step` arguments: stream 2, disjoint from the resampler's draws
+ * of the same cycle.  NULL switches it off; a fresh handle has it off and returns the bytes it returned before this interface existed.
+ * RMCLHIP_ERR_INVALID: parameters rmclhip_motion_noise_sigma_host refuses (the previous setting stays); a step then refuses a
+ * T_bnew_bold that function refuses, before anything is launched. */
+rmclhip_status rmclhip_pf_sharded_set_motion_noise(rmclhip_pf_sharded* pf, const rmclhip_motion_noise_params* params);
 /* the surface constraint on a sharded cloud: rmclhip_pf_sharded_motion_update and rmclhip_pf_sharded_step honour the setting (NULL
  * switches it off); the standalone pass runs on every device's own block, no collective; the devices' counts are summed on the host.
  * Equal, bit for bit, to the single-device calls.  rmclhip_pf_sharded_get_surface_stats: the sum over the devices' last constrained

@@ -10,7 +10,7 @@ from . import pf  # noqa: F401
 from .pf import (AdaptiveResamplerHip, GladiatorResamplerHip, PCDSensorUpdaterHip, PoseEstimatorHip, ResidualResamplerHip, ShardedParticleFilterHip,  # noqa: F401
                  TFMotionUpdaterHip, beams_from_points, chol6, combined_forget_rate, constrain_to_surface, init_particles_pose,
                  init_particles_uniform, kld_bound, kld_params, pack_visualization, sample_beams,
-                 RecoveryHip, SurfaceSamplerHip, init_particles_surface, surface_sample_params)
+                 RecoveryHip, SurfaceSamplerHip, init_particles_surface, surface_sample_params, motion_noise_params, motion_noise_sigma)
 from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, HipMap, MapMap, RCCHipO1Dn,  # noqa: F401
                            RCCHipOnDn, RCCHipPinhole, RCCHipSpherical, ShardedCorrectorHip, build_bvh_host, build_bvh_host_frontier, build_bvh_host_pf, build_bvh_host_quantised,
                            flatten_scene_host, import_hip_map, import_hip_scene, pose_information_p2l, statistics_p2l)

@@ -85,6 +85,12 @@ class SurfaceParams(C.Structure):
                 ("min_up_cos", C.c_float), ("align", C.c_uint32), ("on_miss", C.c_uint32)]
 
 
+class MotionNoiseParams(C.Structure):
+    """rmclhip_motion_noise_params (the sampled odometry model of the motion update)"""
+    _fields_ = [("alpha_trans_trans", C.c_float * 3), ("alpha_trans_rot", C.c_float * 3), ("alpha_rot_trans", C.c_float * 3),
+                ("alpha_rot_rot", C.c_float * 3)]
+
+
 class SurfaceStats(C.Structure):
     """rmclhip_surface_stats"""
     _fields_ = [("n_particles", C.c_uint32), ("n_snapped", C.c_uint32), ("n_missed", C.c_uint32), ("n_steep", C.c_uint32)]
@@ -457,6 +463,11 @@ SIGNATURES = {
     "rmclhip_pf_sharded_download": (_i32, [_vp, _vp, _vp]),
     "rmclhip_pf_update_sharded": (_i32, [_vp, _vp, _u32, _vp]),
     "rmclhip_pf_sharded_motion_update": (_i32, [_vp, _vp, _dbl, _i32]),
+    "rmclhip_motion_noise_params_default": (None, [C.POINTER(MotionNoiseParams)]),
+    "rmclhip_motion_noise_sigma_host": (_i32, [C.POINTER(MotionNoiseParams), _vp, _vp]),
+    "rmclhip_pf_motion_update_noisy": (_i32, [_vp, _vp, _vp, _u32, _vp, _dbl, _i32, _vp, C.c_uint64, _u32, _u32]),
+    "rmclhip_pf_sharded_motion_update_noisy": (_i32, [_vp, _vp, _dbl, _i32, _vp, C.c_uint64, _u32]),
+    "rmclhip_pf_sharded_set_motion_noise": (_i32, [_vp, C.POINTER(MotionNoiseParams)]),
     "rmclhip_surface_params_default": (None, [_vp]),
     "rmclhip_pf_set_surface": (_i32, [_vp, _vp]),
     "rmclhip_pf_get_surface_stats": (_i32, [_vp, _vp]),

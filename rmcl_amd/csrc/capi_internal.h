@@ -716,10 +716,17 @@ RMCL_INTERNAL rmclhip_status surface_inject_threshold(const std::string& who, do
 RMCL_INTERNAL rmclhip_status surface_inject_enqueue(rmclhip_surface_sampler* sm, xform* poses, void* attrs, uint32_t first, uint32_t count,
                                                     unsigned long long threshold, uint64_t seed, uint32_t step, hipStream_t s);
 // capi_surface.cpp: the surface constraint's argument check, and the two launches on f->stream with the copy of their class counts to
-// f->h_surf behind them (no wait).  pf_motion_enqueue: the motion update of the handle, constrained when rmclhip_pf_set_surface says so.
+// f->h_surf behind them (no wait).  pf_motion_enqueue: the motion update of the handle, constrained when rmclhip_pf_set_surface says so;
+// noise: null = the deterministic update, else the sampled odometry model's draw per particle (capi_motion_noise.cpp).
 RMCL_INTERNAL rmclhip_status surface_params_check(const char* who, const rmclhip_surface_params* p);
 RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const xform& T_bnew_bold, double forget_rate,
-                                               uint32_t max_n_meas, bool collision);
+                                               uint32_t max_n_meas, bool collision, const MotionNoiseKernelParams* noise = nullptr);
+// capi_motion_noise.cpp: the parameters' check, sigma of a step (rmclhip_motion_noise_sigma_host under the caller's name), and the
+// check of a noisy call's sigma with the kernel's view of it -- *on is false when all six are zero: the deterministic launch
+RMCL_INTERNAL rmclhip_status motion_noise_params_check(const char* who, const rmclhip_motion_noise_params* p);
+RMCL_INTERNAL rmclhip_status motion_noise_sigma(const char* who, const rmclhip_motion_noise_params* p, const rmclhip_transform* T, float* sigma_out);
+RMCL_INTERNAL rmclhip_status motion_noise_kernel_params(const char* who, const float* sigma, uint64_t seed, uint32_t step, uint32_t first,
+                                                        MotionNoiseKernelParams* out, bool* on);
 RMCL_INTERNAL rmclhip_status pf_surface_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const rmclhip_surface_params& sp, uint32_t max_n_meas);
 // capi_adaptive.cpp: the checks and launches the pose hypotheses share with the adaptive count.  kld_table_words: the size of the bin
 // table count_bins_run fills for n particles; resampler_stats: the likelihoods' maximum, landed on the host

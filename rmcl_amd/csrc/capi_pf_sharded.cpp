@@ -33,6 +33,8 @@ struct rmclhip_pf_sharded {
   std::vector<PfRank> ranks;
   rmclhip_pf_params params{2.0f, 100.0f, 100.0f, 0.0f, {0.05f, 80.0f}, 10000u, 0u};
   bool weights_fresh = false;   // every rank's d_w_all holds the likelihoods of the cloud as it is (set by the all-gather, cleared by whatever rewrites attributes)
+  bool noise_on = false;        // rmclhip_pf_sharded_set_motion_noise: a step's motion update draws the sampled odometry model's noise
+  rmclhip_motion_noise_params noise{};
 };
 
 // the C ABI speaks of rmclhip_transform, the kernels of xform: one layout (capi_internal.h)
@@ -275,11 +277,40 @@ rmclhip_status rmclhip_pf_update_sharded(rmclhip_pf_sharded* h, const rmclhip_ra
 // MotionUpdater<MemT>::update on every device's block (particle_motion.cu:11-46 + the collision ray of TFMotionUpdaterCPU.cpp:17-50,
 // 207-221): one k_pf_motion per rank on that rank's update stream.  The launches are left in flight -- the sensor update of the same
 // cycle is enqueued behind them on the same streams (rmclhip_pf_sharded_step).
-static rmclhip_status pf_sharded_motion_enqueue(rmclhip_pf_sharded* h, const rmclhip_transform* T_bnew_bold, double forget_rate, int check_collision) {
+// noise: null = the deterministic update; else every rank draws for the GLOBAL indices of its block (first = R.lo)
+static rmclhip_status pf_sharded_motion_enqueue(rmclhip_pf_sharded* h, const rmclhip_transform* T_bnew_bold, double forget_rate, int check_collision,
+                                                const MotionNoiseKernelParams* noise = nullptr) {
   h->weights_fresh = false;   // (a particle that crosses a wall gets likelihood {0, 0, MAX})
   return pf_sharded_enqueue(h, [&](PfRank& R, uint32_t) {
-    return pf_motion_enqueue(R.pf, R.d_poses.p, R.d_attrs.p, R.hi - R.lo, to_x(T_bnew_bold), forget_rate, h->params.max_n_meas, check_collision != 0);
+    MotionNoiseKernelParams nz{};
+    if (noise) { nz = *noise; nz.first = R.lo; }
+    return pf_motion_enqueue(R.pf, R.d_poses.p, R.d_attrs.p, R.hi - R.lo, to_x(T_bnew_bold), forget_rate, h->params.max_n_meas, check_collision != 0,
+                             noise ? &nz : nullptr);
   });
+}
+
+rmclhip_status rmclhip_pf_sharded_motion_update_noisy(rmclhip_pf_sharded* h, const rmclhip_transform* T_bnew_bold, double forget_rate,
+                                                      int check_collision, const float* sigma, uint64_t seed, uint32_t step) {
+  ApiGuard guard_("rmclhip_pf_sharded_motion_update_noisy");
+  if (!h || !T_bnew_bold) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_motion_update_noisy: null");
+  MotionNoiseKernelParams nz{};
+  bool noisy = false;
+  if (rmclhip_status st = motion_noise_kernel_params("pf_sharded_motion_update_noisy", sigma, seed, step, 0u, &nz, &noisy)) return st;
+  if (!(forget_rate >= 0.0 && forget_rate <= 1.0)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_motion_update_noisy: forget_rate outside [0, 1] (or NaN)");
+  if (h->n_total == 0) return RMCLHIP_OK;
+  trace_mark("motion:");
+  if (rmclhip_status st = pf_sharded_motion_enqueue(h, T_bnew_bold, forget_rate, check_collision, noisy ? &nz : nullptr)) return st;
+  return pf_sharded_wait_updates(h);
+}
+
+rmclhip_status rmclhip_pf_sharded_set_motion_noise(rmclhip_pf_sharded* h, const rmclhip_motion_noise_params* params) {
+  ApiGuard guard_("rmclhip_pf_sharded_set_motion_noise");
+  if (!h) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_set_motion_noise: null");
+  if (!params) { h->noise_on = false; return RMCLHIP_OK; }
+  if (rmclhip_status st = motion_noise_params_check("pf_sharded_set_motion_noise", params)) return st;
+  h->noise = *params;
+  h->noise_on = true;
+  return RMCLHIP_OK;
 }
 
 rmclhip_status rmclhip_pf_sharded_motion_update(rmclhip_pf_sharded* h, const rmclhip_transform* T_bnew_bold, double forget_rate,
@@ -672,6 +703,13 @@ rmclhip_status rmclhip_pf_sharded_step(rmclhip_pf_sharded* h, const rmclhip_tran
   if (resample < 0 || resample > 2 || (resample != 0 && !cfg)) return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: bad resampling arguments");
   if (T_bnew_bold && !(forget_rate >= 0.0 && forget_rate <= 1.0))
     return fail(RMCLHIP_ERR_INVALID, "pf_sharded_step: forget_rate outside [0, 1] (or NaN)");
+  MotionNoiseKernelParams nz{};
+  bool noisy = false;
+  if (T_bnew_bold && h->noise_on) {   // rmclhip_pf_sharded_set_motion_noise: sigma of THIS step, drawn with this cycle's seed and step
+    float sigma[6];
+    if (rmclhip_status ns = motion_noise_sigma("pf_sharded_step", &h->noise, T_bnew_bold, sigma)) return ns;
+    if (rmclhip_status ns = motion_noise_kernel_params("pf_sharded_step", sigma, seed, step, 0u, &nz, &noisy)) return ns;
+  }
   if (resample != 0) {   // the resampler's own rule, before the motion and sensor updates change the cloud
     rmclhip_gladiator_config c = *cfg;
     if (resample == 2) c.trans_dist_metric = 0u;
@@ -680,7 +718,7 @@ rmclhip_status rmclhip_pf_sharded_step(rmclhip_pf_sharded* h, const rmclhip_tran
   if (h->n_total == 0) { if (stats_out) { stats_out->sum = 0.f; stats_out->max = 0.f; } return RMCLHIP_OK; }
   if (T_bnew_bold) {
     trace_mark("motion:");
-    if (rmclhip_status st = pf_sharded_motion_enqueue(h, T_bnew_bold, forget_rate, check_collision)) return st;
+    if (rmclhip_status st = pf_sharded_motion_enqueue(h, T_bnew_bold, forget_rate, check_collision, noisy ? &nz : nullptr)) return st;
   }
   if (rmclhip_status st = rmclhip_pf_update_sharded(h, beams, n_beams, Tsb)) return st;
   rmclhip_likelihood_stats st_local;

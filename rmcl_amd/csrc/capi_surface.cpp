@@ -44,15 +44,17 @@ static rmclhip_status pf_surface_buffers(rmclhip_pf* f) {
 }
 
 RMCL_INTERNAL rmclhip_status pf_motion_enqueue(rmclhip_pf* f, xform* poses, void* attrs, uint32_t n, const xform& T_bnew_bold, double forget_rate,
-                                               uint32_t max_n_meas, bool collision) {
+                                               uint32_t max_n_meas, bool collision, const MotionNoiseKernelParams* noise) {
   if (!f->surface_on) {
-    HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream));
+    HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream, nullptr, nullptr,
+                            nullptr, noise));
     return RMCLHIP_OK;
   }
   if (rmclhip_status st = pf_surface_buffers(f)) return st;
   const SurfaceKernelParams k = surface_kernel_params(f->surface);
   HIPCHK(hipMemsetAsync(f->d_surf.p, 0, 4 * sizeof(uint32_t), f->stream));
-  HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream, &k, f->d_surf.p, f->surf_faces));
+  HIPCHK(launch_pf_motion(f->map->d_qnodes.p, f->map->d_tris.p, poses, attrs, n, T_bnew_bold, forget_rate, max_n_meas, collision, f->stream, &k, f->d_surf.p, f->surf_faces,
+                          noise));
   HIPCHK(hipMemcpyAsync(f->h_surf.p, f->d_surf.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
   return RMCLHIP_OK;
 }

@@ -434,11 +434,19 @@ struct SurfaceKernelParams {
   uint32_t axis, align, on_miss;
   float height, probe_up, probe_down, min_up_cos;
 };
+// the motion noise as the kernel takes it (pf_random.hip.h: motion_noise_compose): the six standard deviations, the Philox key (the
+// seed's low and high word), the step, and the global index of the launch's first particle
+struct MotionNoiseKernelParams {
+  float sigma[6];
+  uint32_t key0, key1, step, first;
+};
+// noise: null = the deterministic update (the launches of before); else every particle's moved pose is composed with its draw first.
 // surface: null = the unconstrained update; else the surface constraint runs in the same launch (move -> forget -> collision ray on the
 // lifted segment -> surface ray) and surface_stats (device, 4 words {particles, snapped, missed, steep}, zeroed by the caller) counts
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
                             xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s,
-                            const SurfaceKernelParams* surface = nullptr, uint32_t* surface_stats = nullptr, uint32_t* surface_faces = nullptr);
+                            const SurfaceKernelParams* surface = nullptr, uint32_t* surface_stats = nullptr, uint32_t* surface_faces = nullptr,
+                            const MotionNoiseKernelParams* noise = nullptr);
 // the standalone pass (surface.hip): qnodes = the map's quantised nodes; stats as above.  faces (both launches; nullable, n words): the
 // face every particle's probe hit, kInvalidFace for none (a test output)
 hipError_t launch_surface_constrain(const uint32_t* qnodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,

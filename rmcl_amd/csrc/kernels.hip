@@ -605,11 +605,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAccum
 // LIFTED by the step height: it runs between the probe origins of the old and of the moved pose, so that what is lower than probe_up is
 // climbed and what is taller is a wall; the probe runs on the moved pose whether or not the particle was killed.  The instantiations
 // without it are the kernel of before (`sx` is not read).
+// kNoise: the sampled odometry model (include/rmclhip.h, MOTION NOISE): the moved pose is composed with this particle's Gaussian draw
+// (pf_random.hip.h: motion_noise_compose) before anything else looks at it, so the collision segment ends at the noisy position and the
+// surface constraint probes the noisy pose.  The instantiations without it do not read `nz`.
 struct SurfaceArgs { SurfaceKernelParams sp; uint32_t* stats; uint32_t* faces; };
-template <bool kCollision, bool kSurface = false>
+template <bool kCollision, bool kSurface = false, bool kNoise = false>
 __global__ void __launch_bounds__(256) k_pf_motion(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ tris,
                                                    xform* __restrict__ poses, pattrs* __restrict__ attrs, uint32_t n,
-                                                   xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, SurfaceArgs sx) {
+                                                   xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, SurfaceArgs sx,
+                                                   MotionNoiseKernelParams nz) {
   extern __shared__ uint32_t lds_dyn[];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < n;
@@ -617,6 +621,7 @@ __global__ void __launch_bounds__(256) k_pf_motion(const uint32_t* __restrict__ 
   const xform pose_old = poses[ii];
   g1d L = attrs[ii].likelihood;
   xform pose_new = xmul(pose_old, T_bnew_bold);
+  if (kNoise) pose_new = motion_noise_compose(pose_new, nz.first + ii, nz.step, nz.key0, nz.key1, nz.sigma);
   // `n_meas -= forget_rate * n_meas` on a uint32: double arithmetic, truncating store
   L.n_meas = static_cast<uint32_t>(static_cast<double>(L.n_meas) - forget_rate * static_cast<double>(L.n_meas));
   f3 a_new = mk3(0.0f, 0.0f, 1.0f), O_new = pose_new.t, seg_from = pose_old.t;
@@ -1115,27 +1120,31 @@ hipError_t launch_pf_update(const PfParams& p, int variant, hipStream_t s) {
 
 hipError_t launch_pf_motion(const uint32_t* nodes, const uint32_t* tris, xform* poses, void* attrs, uint32_t n,
                             xform T_bnew_bold, double forget_rate, uint32_t max_n_meas, bool collision, hipStream_t s,
-                            const SurfaceKernelParams* surface, uint32_t* surface_stats, uint32_t* surface_faces) {
+                            const SurfaceKernelParams* surface, uint32_t* surface_stats, uint32_t* surface_faces,
+                            const MotionNoiseKernelParams* noise) {
   if (n == 0) return hipSuccess;
   const dim3 grid((n + 255u) / 256u), block(256);
   SurfaceArgs sx = {};
+  MotionNoiseKernelParams nz = {};
+  if (noise) nz = *noise;
   if (surface) {
     if (!surface_stats) return hipErrorInvalidValue;
     sx.sp = *surface;
     sx.stats = surface_stats;
     sx.faces = surface_faces;
-    if (collision)
-      hipLaunchKernelGGL((k_pf_motion<true, true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
-                         reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
-    else
-      hipLaunchKernelGGL((k_pf_motion<false, true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
-                         reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
-  } else if (collision)
-    hipLaunchKernelGGL((k_pf_motion<true>), grid, block, 16u * 256u * sizeof(uint32_t), s, nodes, tris, poses,
-                       reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx);
-  else
-    hipLaunchKernelGGL((k_pf_motion<false>), grid, block, 0, s, nodes, tris, poses, reinterpret_cast<pattrs*>(attrs), n,
-                       T_bnew_bold, forget_rate, max_n_meas, sx);
+  }
+  // (the collision ray and the surface ray keep their stacks in LDS: 16 words per lane)
+#define RMCL_PF_MOTION(C, S, N)                                                                                               \
+  hipLaunchKernelGGL((k_pf_motion<C, S, N>), grid, block, ((C) || (S)) ? 16u * 256u * sizeof(uint32_t) : 0u, s, nodes, tris, poses, \
+                     reinterpret_cast<pattrs*>(attrs), n, T_bnew_bold, forget_rate, max_n_meas, sx, nz)
+  if (noise) {
+    if (surface) { if (collision) RMCL_PF_MOTION(true, true, true); else RMCL_PF_MOTION(false, true, true); }
+    else if (collision) RMCL_PF_MOTION(true, false, true);
+    else RMCL_PF_MOTION(false, false, true);
+  } else if (surface) { if (collision) RMCL_PF_MOTION(true, true, false); else RMCL_PF_MOTION(false, true, false); }
+  else if (collision) RMCL_PF_MOTION(true, false, false);
+  else RMCL_PF_MOTION(false, false, false);
+#undef RMCL_PF_MOTION
   return hipGetLastError();
 }
 

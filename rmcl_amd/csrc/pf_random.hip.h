@@ -1,6 +1,6 @@
 // pf_random.hip.h -- the counter-based random stream of the particle filter and the Euler -> quaternion step its draws end in, shared
-// by the resamplers (resample.hip) and the cloud initialisation (particles.hip): ONE text, so that a particle drawn by either is the
-// same function of (seed, counter) down to the bit.  Device code only.
+// by the resamplers (resample.hip), the cloud initialisation (particles.hip) and the motion update's noise (kernels.hip): ONE text, so
+// that a particle drawn by any of them is the same function of (seed, counter) down to the bit.  Device code only.
 //
 // Random stream = Philox4x32-10 keyed by the 64-bit seed with a 128-bit counter (index, step / epoch, draw, stream):
 //   stream 0: the resamplers   (champion or slot index, step, draw 0..7: gladiator 0 1, residual 2 3 4, systematic 5 6 7;
@@ -9,6 +9,8 @@
 //                               10 and 11 are the surface sampler's two blocks, particles.hip)
 //   stream 1: the initialisers (global particle index, epoch, draw 0..1: uniform and pose + covariance; draw 2 3: the surface
 //                               sampler's two blocks of the initialisation on the surface)
+//   stream 2: the motion noise (global particle index, step, draw 0..1: the six Gaussians of the sampled odometry model,
+//                               motion_noise_compose below)
 // reproducible, independent of the launch shape and of how the particle range is sharded across GPUs.  Transcendentals are evaluated in
 // double and rounded to float (see oracle).
 #pragma once
@@ -54,6 +56,26 @@ __device__ __forceinline__ quat euler_to_quat(float roll, float pitch, float yaw
   q.y = cr * sp * cy + sr * cp * sy;
   q.z = cr * cp * sy - sr * sp * cy;
   return q;
+}
+
+// The sampled odometry model's draw (include/rmclhip.h, MOTION NOISE): moved * N, with N a zero-mean Gaussian in the body frame of the
+// moved pose -- N.t = (z0 s0, z1 s1, z2 s2), N.R = EulerAngles(z3 s3, z4 s4, z5 s5) -- and z the three Box-Muller pairs of
+// A = philox((g, step, 0, 2), seed), B = philox((g, step, 1, 2), seed): (A0, A1), (A2, A3), (B0, B1).  g is the GLOBAL particle index.
+// No normalisation afterwards, as in xmul everywhere else; the stamp is `moved`'s.  tests/motion_noise_ref.py restates it.
+__device__ __forceinline__ xform motion_noise_compose(const xform& moved, uint32_t g, uint32_t step, uint32_t key0, uint32_t key1,
+                                                      const float (&sigma)[6]) {
+  uint32_t A[4], B[4];
+  philox4x32_10(g, step, 0u, 2u, key0, key1, A);
+  philox4x32_10(g, step, 1u, 2u, key0, key1, B);
+  float z[6];
+  box_muller(A[0], A[1], z[0], z[1]);
+  box_muller(A[2], A[3], z[2], z[3]);
+  box_muller(B[0], B[1], z[4], z[5]);
+  xform N;
+  N.t = mk3(z[0] * sigma[0], z[1] * sigma[1], z[2] * sigma[2]);
+  N.R = euler_to_quat(z[3] * sigma[3], z[4] * sigma[4], z[5] * sigma[5]);
+  N.stamp = 0u;
+  return xmul(moved, N);
 }
 
 // rmagine EulerAngles <- Quaternion (textbook ZYX extraction): the float products ...

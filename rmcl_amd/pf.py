@@ -222,6 +222,41 @@ def constrain_to_surface(updater_or_map, poses, attrs, n, params):
     return st.as_dict()
 
 
+_NOISE_FIELDS = ("alpha_trans_trans", "alpha_trans_rot", "alpha_rot_trans", "alpha_rot_rot")
+
+
+def motion_noise_params(**kwargs):
+    """rmclhip_motion_noise_params with the library's defaults (0.2 throughout, AMCL's alpha1..4); keyword arguments replace fields:
+    alpha_trans_trans (m per m) and alpha_trans_rot (m per rad) for body x y z, alpha_rot_trans (rad per m) and alpha_rot_rot (rad per
+    rad) for roll pitch yaw -- three floats each, or one float for all three"""
+    p = _capi.MotionNoiseParams()
+    _capi.lib().rmclhip_motion_noise_params_default(C.byref(p))
+    for k, v in kwargs.items():
+        if k not in _NOISE_FIELDS:
+            raise TypeError("motion_noise_params: unknown field %r" % k)
+        v3 = [float(v)] * 3 if np.ndim(v) == 0 else [float(x) for x in v]
+        if len(v3) != 3:
+            raise TypeError("motion_noise_params: %s takes one float or three" % k)
+        setattr(p, k, (C.c_float * 3)(*v3))
+    return p
+
+
+def motion_noise_sigma(params, T_bnew_bold):
+    """rmclhip_motion_noise_sigma_host (no device needed): the six standard deviations (body x y z in metres, roll pitch yaw in radians)
+    of the sampled odometry model for the step T_bnew_bold; an identity step gives zeros"""
+    T = np.ascontiguousarray(T_bnew_bold, dtype=TRANSFORM).reshape(1)
+    out = np.zeros(6, dtype=np.float32)
+    _capi.check(_capi.lib().rmclhip_motion_noise_sigma_host(None if params is None else C.byref(params), _ptr(T), _ptr(out)))
+    return out
+
+
+def _noise_sigma(noise, T_bnew_bold):
+    """noise of an update call -> six float32 sigmas: a MotionNoiseParams (sigma of this step) or six sigmas as they are"""
+    if isinstance(noise, _capi.MotionNoiseParams):
+        return motion_noise_sigma(noise, T_bnew_bold)
+    return np.ascontiguousarray(noise, dtype=np.float32).reshape(6)
+
+
 class TFMotionUpdaterHip:
     """rmcl::TFMotionUpdaterGPU on gfx950 + the wall-collision test of TFMotionUpdaterCPU (MotionUpdater<MemT>).
     surface: None, or types.surface_params(...) -- update() then keeps the particles on the mesh in the same launch."""
@@ -241,11 +276,20 @@ class TFMotionUpdaterHip:
     def reset(self):
         """TFMotionUpdaterCPU::reset forgets the previous odometry pose (host-side state of the caller)."""
 
-    def update(self, particle_poses, particle_attrs, n_particles, T_bnew_bold, forget_rate):
+    def update(self, particle_poses, particle_attrs, n_particles, T_bnew_bold, forget_rate, noise=None, seed=0, step=0, first=0):
+        """noise: None (the deterministic update), motion_noise_params(...) (sigma follows this step) or six sigmas -- every particle's
+        step is then composed with its own Gaussian draw of (seed, step, first + i) (rmclhip_pf_motion_update_noisy)"""
         self.init()
         T = np.ascontiguousarray(T_bnew_bold, dtype=TRANSFORM).reshape(1)
         _capi.check(_capi.lib().rmclhip_pf_set_params(self._h, C.byref(self.config)))
         _capi.check(_capi.lib().rmclhip_pf_set_surface(self._h, None if self.surface is None else C.byref(self.surface)))
+        if noise is not None:
+            sigma = _noise_sigma(noise, T)
+            _capi.check(_capi.lib().rmclhip_pf_motion_update_noisy(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs),
+                                                                   int(n_particles), _ptr(T), float(forget_rate),
+                                                                   int(bool(self.check_collision)), _ptr(sigma), int(seed), int(step),
+                                                                   int(first)))
+            return {}
         _capi.check(_capi.lib().rmclhip_pf_motion_update(self._h, _as_ptr(particle_poses), _as_ptr(particle_attrs),
                                                          int(n_particles), _ptr(T), float(forget_rate),
                                                          int(bool(self.check_collision))))
@@ -727,12 +771,23 @@ class ShardedParticleFilterHip:
         _capi.check(_capi.lib().rmclhip_pf_update_sharded(self._h, _ptr(b), len(b), _ptr(T)))
         return self.weights(0)
 
-    def motion_update(self, T_bnew_bold, forget_rate, check_collision=True):
+    def motion_update(self, T_bnew_bold, forget_rate, check_collision=True, noise=None, seed=0, step=0):
         """TFMotionUpdater*::update on every device's block, in place (rmclhip_pf_sharded_motion_update): pose <- pose * T_bnew_bold,
-        n_meas -= forget_rate * n_meas, and with check_collision the wall-collision ray of the CPU updater"""
+        n_meas -= forget_rate * n_meas, and with check_collision the wall-collision ray of the CPU updater.  noise (None,
+        motion_noise_params(...) or six sigmas), seed, step: as TFMotionUpdaterHip.update (rmclhip_pf_sharded_motion_update_noisy)"""
         T = np.ascontiguousarray(T_bnew_bold, dtype=TRANSFORM).reshape(1)
         _capi.check(_capi.lib().rmclhip_pf_sharded_set_params(self._h, C.byref(self.config_)))   # (max_n_meas of a collided particle)
+        if noise is not None:
+            sigma = _noise_sigma(noise, T)
+            _capi.check(_capi.lib().rmclhip_pf_sharded_motion_update_noisy(self._h, _ptr(T), float(forget_rate), int(bool(check_collision)),
+                                                                           _ptr(sigma), int(seed), int(step)))
+            return
         _capi.check(_capi.lib().rmclhip_pf_sharded_motion_update(self._h, _ptr(T), float(forget_rate), int(bool(check_collision))))
+
+    def set_motion_noise(self, params):
+        """step() with a T_bnew_bold then draws the sampled odometry model's noise with its own seed and step
+        (rmclhip_pf_sharded_set_motion_noise); None: off"""
+        _capi.check(_capi.lib().rmclhip_pf_sharded_set_motion_noise(self._h, None if params is None else C.byref(params)))
 
     def set_surface(self, params):
         """the surface constraint of motion_update and step on every device's block (rmclhip_pf_sharded_set_surface); None: off"""
