@@ -42,6 +42,19 @@ using CrossStatistics = rmclhip_cross_statistics;
 using PoseInformation = rmclhip_pose_information;
 using PoseCovariance = rmclhip_pose_covariance;
 using PoseCovarianceParams = rmclhip_pose_covariance_params;
+// M-estimator weights in the point-to-plane reduction (rmclhip.h, ROBUST MICP)
+using RobustStatistics = rmclhip_robust_statistics;
+struct RobustParams : rmclhip_robust_params {
+  // the library's defaults for a kernel: MAD scale, the kernel's customary tuning, scale_min 1e-3
+  explicit RobustParams(int kernel_ = RMCLHIP_ROBUST_HUBER) { rmclhip_robust_params_default(kernel_, this); }
+  // ... with a fixed scale c
+  static RobustParams fixed(int kernel_, float c) {
+    RobustParams p(kernel_);
+    p.scale_mode = RMCLHIP_ROBUST_SCALE_FIXED;
+    p.scale = c;
+    return p;
+  }
+};
 using ParticleAttributes = rmclhip_particle_attributes;
 using RangeMeasurement = rmclhip_range_measurement;
 
@@ -411,6 +424,24 @@ inline PoseInformation pose_information_p2l(const Transform& Tpre, const PointCl
                                      model.mask.size() ? model.mask.raw() : nullptr, static_cast<uint32_t>(n), params.max_dist, &out));
   return out;
 }
+// statistics_p2l with M-estimator weights on the same views (rmclhip_statistics_p2l_robust).  weights_out (nullable): device memory of
+// min(dataset, model) floats that receives every element's weight, 0 where masked or gated out
+inline RobustStatistics statistics_p2l_robust(const Transform& Tpre, const PointCloudView_<VRAM_HIP>& dataset, const PointCloudView_<VRAM_HIP>& model,
+                                              const UmeyamaReductionConstraints& params, const RobustParams& robust, float* weights_out = nullptr) {
+  rmclhip_ctx* ctx = dataset.ctx ? dataset.ctx : model.ctx;
+  if (!ctx) throw std::runtime_error("statistics_p2l_robust: views without a context (use watch() / modelView())");
+  if (dataset.ctx && model.ctx && dataset.ctx != model.ctx) throw std::runtime_error("statistics_p2l_robust: dataset and model live on different contexts");
+  if (model.normals.size() < model.points.size()) throw std::runtime_error("statistics_p2l_robust: the model view needs normals");
+  if ((dataset.mask.size() && dataset.mask.size() < dataset.points.size()) || (model.mask.size() && model.mask.size() < model.points.size()))
+    throw std::runtime_error("statistics_p2l_robust: mask shorter than its points");
+  const size_t n = dataset.points.size() < model.points.size() ? dataset.points.size() : model.points.size();
+  RobustStatistics out;
+  check(rmclhip_statistics_p2l_robust(ctx, &Tpre, reinterpret_cast<const float*>(dataset.points.raw()), dataset.mask.size() ? dataset.mask.raw() : nullptr,
+                                      reinterpret_cast<const float*>(model.points.raw()), reinterpret_cast<const float*>(model.normals.raw()),
+                                      model.mask.size() ? model.mask.raw() : nullptr, static_cast<uint32_t>(n), params.max_dist, &robust, weights_out,
+                                      &out));
+  return out;
+}
 
 // ---- rmagine::Bundle and its attributes (rmagine/simulation/SimulationResults.hpp as used by Correspondences.hpp:81-85,
 // scan_map_segmentation_embree.cpp:82-85, lidar_corrector_embree_benchmark.cpp:95-100) -------------------------------------------
@@ -503,6 +534,27 @@ class Correspondences_<VRAM_HIP> {
     check(rmclhip_rcc_pose_information(h_, &T_snew_sold, convergence_progress, &out));
     return out;
   }
+  // computeCrossStatistics with M-estimator weights (rmclhip.h, ROBUST MICP): weighted means and covariance, sum w, sum w r^2, sum r^2,
+  // the scale used; sensor frame; reads the buffers of the last find and changes nothing
+  RobustStatistics computeRobustStatistics(const Transform& T_snew_sold, double convergence_progress, const RobustParams& robust) const {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    RobustStatistics out;
+    check(rmclhip_rcc_compute_robust_statistics(h_, &T_snew_sold, convergence_progress, &robust, &out));
+    return out;
+  }
+  // the weight of every correspondence of the last find at T_snew_sold, 0 where masked or gated out: an outlier map
+  std::vector<float> robustWeights(const Transform& T_snew_sold, double convergence_progress, const RobustParams& robust) const {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    uint32_t w = 0, h = 0, nd = 0;
+    check(rmclhip_rcc_input_views(h_, nullptr, &w, &h, nullptr, nullptr, &nd));
+    const size_t nm = static_cast<size_t>(w) * h;
+    std::vector<float> out(nm < nd ? nm : nd);
+    float none = 0.f;
+    check(rmclhip_rcc_robust_weights(h_, &T_snew_sold, convergence_progress, &robust, out.empty() ? &none : out.data(), 0));
+    return out;
+  }
   // one per pose of the last correctBatch (identity pre-transform)
   std::vector<PoseInformation> computePoseInformationBatch(uint32_t nposes, double convergence_progress = 0.0) const {
     bindDataset();
@@ -589,6 +641,16 @@ class Correspondences_<VRAM_HIP> {
     Transform T;
     check(rmclhip_rcc_correct_once(h_, &Tom, &Tbo, iterations, convergence_progress, refind_each_iteration ? 1 : 0, &T,
                                    stats_o));
+    return T;
+  }
+  // ... with M-estimator weights re-evaluated every iteration, the scale selected once after the find (rmclhip_rcc_correct_once_robust);
+  // stats_s: the last iteration's statistics, SENSOR frame
+  Transform correctOnceRobust(const Transform& Tom, const Transform& Tbo, uint32_t iterations, double convergence_progress,
+                              const RobustParams& robust, RobustStatistics* stats_s = nullptr) {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    Transform T;
+    check(rmclhip_rcc_correct_once_robust(h_, &Tom, &Tbo, iterations, convergence_progress, &robust, &T, stats_s));
     return T;
   }
   // v1 SphereCorrector::correct (lidar_corrector_embree_benchmark.cpp:127-135)

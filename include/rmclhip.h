@@ -1376,6 +1376,77 @@ void rmclhip_pose_covariance_params_default(rmclhip_pose_covariance_params* out)
 rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
                                             rmclhip_pose_covariance* out);
 
+/* ---- ROBUST MICP: M-estimator weights in the point-to-plane reduction ----------------------------------------------
+ * rmclhip_statistics_p2l trusts a correspondence fully (|r| < max_dist) or not at all.  Here every gated-in correspondence enters the
+ * 16 sums with a weight w(r) in [0, 1] of its own residual, and a correction iterates reduction and solve with the weights re-evaluated
+ * at every pre-transform (iteratively reweighted least squares).
+ *
+ * RESIDUAL.  r_i = (Ii - Di) . Ni in f32, Di = Tpre * dataset_points[i]: the value rmclhip_statistics_p2l gates on, by the same f32
+ * expressions.  The hard gate |r_i| < max_dist comes first (a NaN r fails it); masked or gated-out elements have weight 0 and touch no sum.
+ * WEIGHTS, all in f32 with IEEE division and no fused operation, u = r / c for a scale c > 0:
+ *   NONE 1 | HUBER |r| <= c ? 1 : c / |r| | CAUCHY 1 / (1 + u u) | TUKEY |r| < c ? (1 - u u)^2 : 0 | GEMAN_MCCLURE 1 / ((1 + u u)(1 + u u))
+ * r = 0 gives 1 for every kernel.  numpy float32 reproduces every weight bit for bit.
+ * SCALE.  FIXED: c = scale.  MAD: c = max((float)(tuning * 1.4826 * (double)median), scale_min), median = the exact lower median of
+ * |r| over the m gated-in correspondences (element (m - 1) / 2 of the sorted values; radix selection on the device, integers only: the
+ * same inputs give the same value whatever the schedule); m == 0: c = scale_min.
+ * SUMS.  The 16 sums of rmclhip_statistics_p2l with every term multiplied by (double)w, same grid, same order of additions: with weight
+ * 1 throughout, `stats` equals rmclhip_statistics_p2l's bytes.  The means and the covariance divide by weight_sum; n_meas is the number
+ * of gated-in correspondences (the covariance is zeroed when that is 1); weight_sum == 0 leaves means and covariance zero. */
+enum {
+  RMCLHIP_ROBUST_NONE = 0, RMCLHIP_ROBUST_HUBER = 1, RMCLHIP_ROBUST_CAUCHY = 2, RMCLHIP_ROBUST_TUKEY = 3, RMCLHIP_ROBUST_GEMAN_MCCLURE = 4
+};
+enum { RMCLHIP_ROBUST_SCALE_FIXED = 0, RMCLHIP_ROBUST_SCALE_MAD = 1 };
+typedef struct rmclhip_robust_params {
+  int32_t kernel;        /* RMCLHIP_ROBUST_* */
+  int32_t scale_mode;    /* RMCLHIP_ROBUST_SCALE_FIXED | RMCLHIP_ROBUST_SCALE_MAD */
+  float scale;           /* FIXED: c itself */
+  float tuning;          /* MAD: c = tuning * 1.4826 * median|r| */
+  float scale_min;       /* MAD: floor of c (a perfect synthetic scan has median 0) */
+  uint32_t reserved;
+} rmclhip_robust_params;
+typedef struct rmclhip_robust_statistics {
+  rmclhip_cross_statistics stats;   /* weighted means and covariance; n_meas = gated-in count */
+  double weight_sum, wrss, rss;     /* sum w, sum w r^2, sum r^2 (r widened to double before squaring) */
+  float scale;                      /* the c that was used */
+  float median_abs_residual;        /* MAD mode, else 0 */
+} rmclhip_robust_statistics;
+/* MAD, the kernel's customary tuning (HUBER 1.345, CAUCHY 2.385, TUKEY 4.685, GEMAN_MCCLURE 1, NONE 1), scale 1, scale_min 1e-3; an
+ * unknown kernel gives NONE's */
+void rmclhip_robust_params_default(int kernel, rmclhip_robust_params* out);
+/* RMCLHIP_ERR_INVALID with a message that names the field: an unknown kernel or scale_mode; a non-finite or non-positive scale (FIXED),
+ * tuning or scale_min (MAD) */
+rmclhip_status rmclhip_robust_params_check(const rmclhip_robust_params* params);
+/* the weight above on the host: the expression the kernels evaluate, compiled with the library's host flags.  c must be > 0 */
+float rmclhip_robust_weight_host(int kernel, float c, float r);
+/* beside rmclhip_statistics_p2l on caller-owned device views (same stream and scratch owner, synchronous).  weights_out_dev (nullable):
+ * n floats, the weight of every element, 0 where masked or gated out.  n == 0: identity statistics, scale = c of an empty set. */
+rmclhip_status rmclhip_statistics_p2l_robust(rmclhip_ctx* ctx, const rmclhip_transform* Tpre, const float* dataset_points_xyz_dev,
+                                             const uint8_t* dataset_mask_dev, const float* model_points_xyz_dev,
+                                             const float* model_normals_xyz_dev, const uint8_t* model_mask_dev, uint32_t n, float max_dist,
+                                             const rmclhip_robust_params* params, float* weights_out_dev,
+                                             rmclhip_robust_statistics* out);
+/* The three operator forms below only READ the last find's correspondences, as rmclhip_rcc_compute_cross_statistics does (max_dist'
+ * from convergence_progress); they refuse what it refuses and leave the published moment set, rmclhip_ccs_info and what
+ * rmclhip_rcc_compute_cross_statistics returns untouched.  Synchronous. */
+rmclhip_status rmclhip_rcc_compute_robust_statistics(rmclhip_rcc* rcc, const rmclhip_transform* T_snew_sold, double convergence_progress,
+                                                     const rmclhip_robust_params* params, rmclhip_robust_statistics* out);
+/* one weight per correspondence (min(dataset, model) floats) into host memory, or device memory with on_device != 0 */
+rmclhip_status rmclhip_rcc_robust_weights(rmclhip_rcc* rcc, const rmclhip_transform* T_snew_sold, double convergence_progress,
+                                          const rmclhip_robust_params* params, float* weights_out, int on_device);
+/* the scale alone: *c_out, the median (0 in FIXED mode) and the gated-in count m; each pointer may be NULL */
+rmclhip_status rmclhip_rcc_residual_scale(rmclhip_rcc* rcc, const rmclhip_transform* T_snew_sold, double convergence_progress,
+                                          const rmclhip_robust_params* params, float* c_out, float* median_out, uint32_t* m_out);
+/* rmclhip_rcc_correct_once (schedule R) with the weights: one find at Tom * Tbo; in MAD mode the scale is selected once, at the
+ * identity pre-transform, and held; then n_iter x { weighted reduction at T_snew_sold, rmclhip_umeyama_transform, T_snew_sold *= U },
+ * one launch per iteration, everything on the operator's stream with one synchronisation at the end.  stats_s_out (nullable): the last
+ * iteration's statistics, SENSOR frame.  n_iter == 0: identity and identity statistics.  An iteration whose weights sum to zero does
+ * not move the pose.  The find rewrites the model buffers and, as every find does, drops the published moment set, which described the
+ * old buffers: the next rmclhip_rcc_compute_cross_statistics pays one moment pass (or streams) and returns what it returns after a
+ * rmclhip_rcc_find at Tom * Tbo.  rmclhip_ccs_info itself is not touched by the call. */
+rmclhip_status rmclhip_rcc_correct_once_robust(rmclhip_rcc* rcc, const rmclhip_transform* Tom, const rmclhip_transform* Tbo, uint32_t n_iter,
+                                               double convergence_progress, const rmclhip_robust_params* params,
+                                               rmclhip_transform* T_onew_oold_out, rmclhip_robust_statistics* stats_s_out);
+
 /* ---- DISTANCE FIELD: the closest-point sensor update by lookup ----------------------------------------------------
  * sensor_update.correspondence_type 1 (evaluate_cpc) scores a beam by the distance of its end point to the surface: the likelihood
  * is smooth in the pose, without the grazing-ray cliffs of ray casting -- what AMCL users know as the likelihood-field model, and the

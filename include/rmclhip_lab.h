@@ -132,6 +132,11 @@ rmclhip_status rmclhip_debug_live_bytes(uint64_t* device_bytes, uint64_t* host_b
 rmclhip_status rmclhip_debug_solve(rmclhip_ctx* ctx, const rmclhip_cross_statistics* stats_host, uint32_t n, int solver,
                                    rmclhip_transform* out_host);
 
+/* A/B of the robust scale selection (tools/robust_micp_time.py; ROBUST MICP of rmclhip.h): on != 0, every histogram pass recomputes
+ * the residual from the correspondences; 0 (default), the first pass writes the keys to scratch and the others read those.  The selected
+ * median is the same either way.  Process-wide.  Works without the experiments library. */
+rmclhip_status rmclhip_debug_robust_select_recompute(int on);
+
 #ifdef __cplusplus
 }
 #endif

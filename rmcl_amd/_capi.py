@@ -154,6 +154,23 @@ class PoseCovarianceParams(C.Structure):
                 ("min_eig_rot", C.c_double)]
 
 
+class RobustParams(C.Structure):
+    """rmclhip_robust_params (include/rmclhip.h, ROBUST MICP)"""
+    _fields_ = [("kernel", C.c_int32), ("scale_mode", C.c_int32), ("scale", C.c_float), ("tuning", C.c_float), ("scale_min", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+class RobustStatistics(C.Structure):
+    """rmclhip_robust_statistics (types.ROBUST_STATISTICS is its numpy twin, which the entry points fill): `stats` holds the 64 bytes
+    of a CROSS_STATISTICS record"""
+    _fields_ = [("stats", C.c_uint8 * 64), ("weight_sum", C.c_double), ("wrss", C.c_double), ("rss", C.c_double), ("scale", C.c_float),
+                ("median_abs_residual", C.c_float)]
+
+
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_GEMAN_MCCLURE = 0, 1, 2, 3, 4
+ROBUST_SCALE_FIXED, ROBUST_SCALE_MAD = 0, 1
+
+
 class MapInfo(C.Structure):
     _fields_ = [("n_faces", C.c_uint32), ("n_vertices", C.c_uint32), ("n_nodes", C.c_uint32),
                 ("n_tri_records", C.c_uint32), ("max_depth", C.c_uint32), ("stack_need", C.c_uint32),
@@ -493,6 +510,15 @@ SIGNATURES = {
     "rmclhip_pose_information_solve_host": (_i32, [_vp, _dbl, _vp]),
     "rmclhip_pose_covariance_params_default": (None, [C.POINTER(PoseCovarianceParams)]),
     "rmclhip_pose_covariance_host": (_i32, [_vp, C.POINTER(PoseCovarianceParams), _vp]),
+    "rmclhip_robust_params_default": (None, [C.c_int, C.POINTER(RobustParams)]),
+    "rmclhip_robust_params_check": (_i32, [C.POINTER(RobustParams)]),
+    "rmclhip_robust_weight_host": (_f32, [C.c_int, _f32, _f32]),
+    "rmclhip_statistics_p2l_robust": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, C.POINTER(RobustParams), _vp, _vp]),
+    "rmclhip_rcc_compute_robust_statistics": (_i32, [_vp, _vp, _dbl, C.POINTER(RobustParams), _vp]),
+    "rmclhip_rcc_robust_weights": (_i32, [_vp, _vp, _dbl, C.POINTER(RobustParams), _vp, C.c_int]),
+    "rmclhip_rcc_residual_scale": (_i32, [_vp, _vp, _dbl, C.POINTER(RobustParams), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_u32)]),
+    "rmclhip_rcc_correct_once_robust": (_i32, [_vp, _vp, _vp, _u32, _dbl, C.POINTER(RobustParams), _vp, _vp]),
+    "rmclhip_debug_robust_select_recompute": (_i32, [C.c_int]),
     "rmclhip_field_params_default": (None, [C.POINTER(FieldParams)]),
     "rmclhip_field_layout_host": (_i32, [_vp, _vp, C.POINTER(FieldParams), C.POINTER(FieldInfo)]),
     "rmclhip_field_create": (_i32, [_vp, _vp, C.POINTER(FieldParams), _pp]),

@@ -236,6 +236,19 @@ struct Pc2ScanScratch {
   MappedBuf<uint32_t> h_counters;       // {finite, in image, in range, cells filled}
 };
 
+// ROBUST MICP (capi_robust.cpp): grow-only scratch of one owner (a context's free function, an operator) -- two sets of partial rows,
+// the scale selection's histograms and keys, the small device block the kernels keep between launches, and the host-mapped block
+// their last launches write the results into (no copy launch: the call waits for the stream and reads them)
+struct RobustDevBlock { RobustScale scale; xform state[2]; };
+struct RobustOutBlock { RobustScale scale; RobustLoopOut loop; RobustStats stats; };
+struct RobustScratch {
+  DevBuf<double> partials;
+  DevBuf<uint32_t> sel, keys;
+  DevBuf<float> weights;
+  DevBuf<RobustDevBlock> dev;
+  MappedBuf<RobustOutBlock> out;
+};
+
 struct rmclhip_ctx {
   int device = 0;
   hipDeviceProp_t props;
@@ -252,6 +265,7 @@ struct rmclhip_ctx {
   MappedBuf<unsigned long long> p2l_h_done;
   uint32_t p2l_seq = 0;
   DevBuf<double> pinfo_partials, pinfo_rows;   // rmclhip_pose_information_p2l: its rows per workgroup and its result row, same stream and mutex
+  RobustScratch robust;                        // rmclhip_statistics_p2l_robust, same stream and mutex
   // rmclhip_pointcloud2_to_scan (the free function): its own stream and scratch, created by the first call under its mutex
   std::mutex pc2_mtx;
   hipStream_t pc2_stream = nullptr;
@@ -390,6 +404,7 @@ struct rmclhip_rcc {
   // reduction
   DevBuf<double> d_partials;
   DevBuf<double> d_pinfo_partials, d_pinfo_rows;   // rmclhip_rcc_pose_information[_batch] (capi_pose_information.cpp): rows per workgroup, result rows per pose
+  RobustScratch robust;            // the robust entry points (capi_robust.cpp)
   MappedBuf<cstats> h_stats;
   DevBuf<MicpState> d_state;
   MappedBuf<MicpState> h_state;

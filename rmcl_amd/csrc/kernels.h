@@ -529,6 +529,41 @@ hipError_t launch_hypotheses(const xform* poses, const void* attrs, uint32_t n, 
 constexpr uint32_t kPoseInfoRow = 32u;
 hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s);
 
+// robust.hip: M-estimator weights in the point-to-plane reduction (include/rmclhip.h, ROBUST MICP).  The views and the
+// grid (reduce_num_blocks(n, 1)) are those of launch_reduce_partials for one pose.
+constexpr uint32_t kRobustRow = 32u;   // a partial row: the 16 weighted sums | gated-in count | sum w r^2 | sum r^2 | 13 x 0
+// scratch of the scale selection, cleared by launch_robust_scale: three histograms (2048 + 2048 + 1024 bins) and the two states between the passes
+constexpr uint32_t kRobustSelWords = 2048u + 2048u + 1024u + 8u;
+struct RobustView {
+  const float* dataset_points;
+  const uint8_t* dataset_mask;   // nullable
+  const float* model_points;
+  const float* model_normals;
+  const uint8_t* model_mask;     // nullable
+  uint32_t n;
+  float max_dist;
+  int32_t kernel;                // RMCLHIP_ROBUST_*
+};
+struct RobustScaleParams { int32_t mode; float scale, tuning, scale_min; };
+struct RobustScale { float c, median; uint32_t m, pad; };
+struct RobustStats { cstats stats; double weight_sum, wrss, rss; float scale, median; };   // rmclhip_robust_statistics
+struct RobustLoopOut { xform T_onew_oold, T_snew_sold; RobustStats stats; };
+// the exact lower median of |r| over the gated-in correspondences at Tpre by three histogram passes (11 + 11 + 10 bits of the f32 pattern),
+// then c by sp (FIXED: sp.scale, the median reported as 0) -> *scale_out with the count m.  keys: n words of scratch the first pass
+// fills and the others read, or nullptr: every pass recomputes r.  scale_copy (nullable, may be host-mapped): a second copy for the host.
+hipError_t launch_robust_scale(const RobustView& v, const xform& Tpre, const RobustScaleParams& sp, uint32_t* sel, uint32_t* keys,
+                               RobustScale* scale_out, RobustScale* scale_copy, hipStream_t s);
+// *scale_out = {c, 0, 0} without a pass over the data (FIXED mode where nobody asks for m)
+hipError_t launch_robust_fixed_scale(float c, RobustScale* scale_out, hipStream_t s);
+// one weighted reduction at Tpre with the scale in *scale_dev: partials[nblocks][kRobustRow], weights_out (nullable, n floats), *out
+// (may be host-mapped, as launch_robust_loop's)
+hipError_t launch_robust_statistics(const RobustView& v, const xform& Tpre, const RobustScale* scale_dev, double* partials, uint32_t nblocks,
+                                    float* weights_out, RobustStats* out, hipStream_t s);
+// n_iter >= 1 iterations { weighted reduction at T_snew_sold, umeyama, T_snew_sold *= U }, one launch each + a closing launch (the form
+// of launch_micp_iter / launch_micp_close): partials[2][nblocks][kRobustRow] and state[2] ping-pong
+hipError_t launch_robust_loop(const RobustView& v, const RobustScale* scale_dev, double* partials, uint32_t nblocks, xform* state,
+                              uint32_t n_iter, const xform& Tsb, const xform& Tbo, RobustLoopOut* out, hipStream_t s);
+
 // field.hip: reading the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
 // A banded field (include/rmclhip.h, BANDED DISTANCE FIELD) has lat == nullptr and the three arrays below: table,
 // nb[0] * nb[1] * nb[2] words (the stored index of a brick or kBandFar), x fastest; coarse, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)

@@ -17,8 +17,11 @@ from . import types as T
 class MICPSensor:
     """MICPSensor_<VRAM_HIP>: one sensor = one correspondence operator + its frames."""
 
-    def __init__(self, name, correspondences, Tsb=None, Tbo=None, merge_weight_multiplier=1.0):
+    def __init__(self, name, correspondences, Tsb=None, Tbo=None, merge_weight_multiplier=1.0, robust=None):
+        """robust: a kernel name ("huber", "cauchy", "tukey", "geman_mcclure") or types.robust_params(...): the sensor's corrections
+        weight every correspondence by its residual (include/rmclhip.h, ROBUST MICP); None: the reference's plain reduction"""
         self.name = name
+        self.robust = robust
         self.correspondences_ = correspondences
         self.Tsb = T.identity() if Tsb is None else Tsb
         self.Tbo = T.identity() if Tbo is None else Tbo
@@ -47,14 +50,19 @@ class MICPSensor:
 class MICPLocalization:
     """The state + correctOnce() of MICPLocalizationNode, minus ROS."""
 
-    def __init__(self, sensors, optimization_iterations=5, adaptive_max_dist=True, disable_correction=False):
+    def __init__(self, sensors, optimization_iterations=5, adaptive_max_dist=True, disable_correction=False, robust=None):
+        """robust: as MICPSensor's, for the localization as a whole (a sensor's own setting is used when this is None).  Honoured for
+        ONE sensor, whose merge_weight_multiplier then plays no part (a lone sensor's weight cancels in the solve); several sensors
+        raise NotImplementedError in correctOnce."""
         self.sensors_vec_ = list(sensors)
+        self.robust = robust
         self.optimization_iterations_ = optimization_iterations  # default 5, micp_localization.cpp:129
         self.adaptive_max_dist_ = adaptive_max_dist              # :139
         self.disable_correction_ = disable_correction
         self.Tom_ = T.identity()
         self.convergence_progress_ = 0.0
         self.correction_stats_latest_ = {}
+        self.robust_statistics_latest_ = None   # ROBUST_STATISTICS of the last robust correction's last iteration, sensor frame
 
     def _device_loop(self, Tom):
         """the inner loop of correctOnce for all sensors resident on the device (rmclhip_micp_correct_once): finds, per-sensor
@@ -85,6 +93,25 @@ class MICPLocalization:
         method, e.g. visualisation hooks of a subclass, do not run) and cannot fill `record`."""
         Tom = self.Tom_
         valid_measurements = sum(s.valid_dataset_measurements for s in self.sensors_vec_)
+        robust = self.robust if self.robust is not None else next((s.robust for s in self.sensors_vec_ if s.robust is not None), None)
+        if robust is not None and not self.disable_correction_ and self.optimization_iterations_ > 0:
+            if len(self.sensors_vec_) != 1:
+                raise NotImplementedError("correctOnce(robust=...): the robust correction runs for one sensor; merging several sensors' "
+                                          "weighted statistics needs real-valued weights where the count-weighted merge of "
+                                          "CrossStatistics has n_meas, which the N-sensor loop does not carry yet")
+            if record is not None:
+                raise ValueError("correctOnce(record=..., robust=...): the robust loop is device-resident and does not return "
+                                 "per-iteration transforms")
+            # (one sensor: its merge_weight_multiplier scales a lone term of the merge and cancels in the solve; it is not read here)
+            s = self.sensors_vec_[0]
+            s.setTom(Tom)
+            s.correspondences_.setTsb(s.Tsb)
+            s.correspondences_.outdated = False
+            T_onew_oold, st = s.correspondences_.correct_once_robust(Tom, s.Tbo, self.optimization_iterations_, self.convergence_progress_,
+                                                                     robust)
+            self.robust_statistics_latest_ = st
+            Cs_o = T.cross_statistics_transform(s.Tbo, T.cross_statistics_transform(s.Tsb, st["stats"]))
+            return self._finish(Tom, T_onew_oold, T.cross_statistics_merge(T.cross_statistics_identity(), Cs_o), valid_measurements)
         if device_loop and not self.disable_correction_ and self.optimization_iterations_ > 0:
             # the device loop returns only the final transform and does not call sensor.findCorrespondences(): per-iteration
             # records and more sensors than the device block holds need the host loop -- say so instead of returning less

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .types import CROSS_STATISTICS, POSE_INFORMATION, TRANSFORM, _ptr
+from .types import CROSS_STATISTICS, POSE_INFORMATION, ROBUST_STATISTICS, TRANSFORM, _ptr, robust_params
 
 
 def _as_ptr(x):
@@ -332,6 +332,20 @@ def pose_information_p2l(ctx, Tpre, dataset_points, dataset_mask, model_points, 
     return out[0].copy()
 
 
+def statistics_p2l_robust(ctx, Tpre, dataset_points, dataset_mask, model_points, model_normals, model_mask, n, max_dist, robust="huber",
+                          weights_out=None):
+    """statistics_p2l with M-estimator weights on the same caller-owned DEVICE views (rmclhip_statistics_p2l_robust).  robust: a kernel
+    name or types.robust_params(...).  weights_out: device memory of n float32 that receives every element's weight (0 where masked or
+    gated out), or None.  Returns a ROBUST_STATISTICS record on the host."""
+    T = np.ascontiguousarray(Tpre, dtype=TRANSFORM).reshape(1)
+    p = robust_params(robust, check=False)
+    out = np.zeros(1, dtype=ROBUST_STATISTICS)
+    _capi.check(_capi.lib().rmclhip_statistics_p2l_robust(ctx.handle, _ptr(T), _as_ptr(dataset_points), _as_ptr(dataset_mask),
+                                                          _as_ptr(model_points), _as_ptr(model_normals), _as_ptr(model_mask), int(n),
+                                                          float(max_dist), C.byref(p), _as_ptr(weights_out), _ptr(out)))
+    return out[0].copy()
+
+
 class UmeyamaReductionConstraints:
     """rmagine::UmeyamaReductionConstraints (only max_dist is used, micp_localization.cpp:525-526)."""
 
@@ -395,6 +409,61 @@ class CorrespondencesHIP:
         out = np.zeros(max(int(nposes), 1), dtype=POSE_INFORMATION)
         _capi.check(_capi.lib().rmclhip_rcc_pose_information_batch(self._h, int(nposes), float(convergence_progress), _ptr(out)))
         return out[:int(nposes)].copy()
+
+    # -- robust MICP (include/rmclhip.h, ROBUST MICP): robust = a kernel name or types.robust_params(...) -----------------------------
+    def compute_robust_statistics(self, T_snew_sold, convergence_progress=0.0, robust="huber"):
+        """computeCrossStatistics with M-estimator weights over the last find's correspondences: a ROBUST_STATISTICS record, sensor
+        frame (rmclhip_rcc_compute_robust_statistics); reads the buffers of the last find, changes nothing"""
+        self._push_params()
+        T = np.ascontiguousarray(T_snew_sold, dtype=TRANSFORM).reshape(1)
+        p = robust_params(robust, check=False)
+        out = np.zeros(1, dtype=ROBUST_STATISTICS)
+        _capi.check(_capi.lib().rmclhip_rcc_compute_robust_statistics(self._h, _ptr(T), float(convergence_progress), C.byref(p), _ptr(out)))
+        return out[0].copy()
+
+    def robust_weights(self, T_snew_sold, convergence_progress=0.0, robust="huber", into=None):
+        """the weight of every correspondence of the last find at T_snew_sold, 0 where masked or gated out: an outlier map
+        (rmclhip_rcc_robust_weights).  into: device memory of min(dataset, model) float32 to fill instead of returning a numpy array"""
+        self._push_params()
+        T = np.ascontiguousarray(T_snew_sold, dtype=TRANSFORM).reshape(1)
+        p = robust_params(robust, check=False)
+        if into is not None:
+            _capi.check(_capi.lib().rmclhip_rcc_robust_weights(self._h, _ptr(T), float(convergence_progress), C.byref(p), _as_ptr(into), 1))
+            return into
+        H, W = self._model_shape
+        w = np.zeros(max(H * W, 1), np.float32)
+        _capi.check(_capi.lib().rmclhip_rcc_robust_weights(self._h, _ptr(T), float(convergence_progress), C.byref(p), _ptr(w), 0))
+        return w[:min(H * W, self._n_dataset_host())]
+
+    def _n_dataset_host(self):
+        n = C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_rcc_input_views(self._h, None, None, None, None, None, C.byref(n)))
+        return n.value
+
+    def residual_scale(self, T_snew_sold, convergence_progress=0.0, robust="huber"):
+        """(c, median |r|, m): the scale the robust reduction would use at T_snew_sold, the exact lower median of |r| over the m
+        gated-in correspondences (0 in the FIXED mode) and m (rmclhip_rcc_residual_scale)"""
+        self._push_params()
+        T = np.ascontiguousarray(T_snew_sold, dtype=TRANSFORM).reshape(1)
+        p = robust_params(robust, check=False)
+        c, med, m = C.c_float(0), C.c_float(0), C.c_uint32(0)
+        _capi.check(_capi.lib().rmclhip_rcc_residual_scale(self._h, _ptr(T), float(convergence_progress), C.byref(p), C.byref(c),
+                                                           C.byref(med), C.byref(m)))
+        return np.float32(c.value), np.float32(med.value), int(m.value)
+
+    def correct_once_robust(self, Tom, Tbo, n_iter, convergence_progress=0.0, robust="huber"):
+        """correct_once (one find, n_iter x reduction + solve) with the weights re-evaluated every iteration, the scale selected once
+        after the find (rmclhip_rcc_correct_once_robust).  Returns (T_onew_oold, ROBUST_STATISTICS of the last iteration, SENSOR frame)."""
+        self._push_params()
+        a = np.ascontiguousarray(Tom, dtype=TRANSFORM).reshape(1)
+        b = np.ascontiguousarray(Tbo, dtype=TRANSFORM).reshape(1)
+        p = robust_params(robust, check=False)
+        T = np.zeros(1, dtype=TRANSFORM)
+        s = np.zeros(1, dtype=ROBUST_STATISTICS)
+        _capi.check(_capi.lib().rmclhip_rcc_correct_once_robust(self._h, _ptr(a), _ptr(b), int(n_iter), float(convergence_progress),
+                                                                C.byref(p), _ptr(T), _ptr(s)))
+        self._last_nposes = 1
+        return T[0].copy(), s[0].copy()
 
     def modelView(self, attributes=None):
         """host copy of {points, mask(hits), normals} (+ ranges, face_ids) of the last find; `attributes`: a subset of the five names

@@ -26,7 +26,12 @@ POSE_INFORMATION = np.dtype([("A", "<f8", (6, 6)), ("g", "<f8", (6,)), ("rss", "
 POSE_COVARIANCE = np.dtype([("covariance", "<f8", (6, 6)), ("eig_trans", "<f8", (3,)), ("eigvec_trans", "<f8", (3, 3)),
                             ("eig_rot", "<f8", (3,)), ("eigvec_rot", "<f8", (3, 3)), ("n_degenerate_trans", "<u4"),
                             ("n_degenerate_rot", "<u4"), ("s2", "<f8")])
-assert TRANSFORM.itemsize == 32 and CROSS_STATISTICS.itemsize == 64
+# rmclhip_robust_statistics (include/rmclhip.h, ROBUST MICP)
+ROBUST_STATISTICS = np.dtype([("stats", CROSS_STATISTICS), ("weight_sum", "<f8"), ("wrss", "<f8"), ("rss", "<f8"), ("scale", "<f4"),
+                              ("median_abs_residual", "<f4")])
+ROBUST_KERNELS = dict(none=_capi.ROBUST_NONE, huber=_capi.ROBUST_HUBER, cauchy=_capi.ROBUST_CAUCHY, tukey=_capi.ROBUST_TUKEY,
+                      geman_mcclure=_capi.ROBUST_GEMAN_MCCLURE)
+assert TRANSFORM.itemsize == 32 and CROSS_STATISTICS.itemsize == 64 and ROBUST_STATISTICS.itemsize == 96
 assert POSE_INFORMATION.itemsize == 352 and POSE_COVARIANCE.itemsize == 496
 assert PARTICLE_ATTRIBUTES.itemsize == 36 and RANGE_MEASUREMENT.itemsize == 64
 
@@ -129,6 +134,34 @@ def pose_information_solve(info, rcond=1e-9):
     info, out = _one(info, POSE_INFORMATION), np.zeros(6, dtype=np.float64)
     _capi.check(_capi.lib().rmclhip_pose_information_solve_host(_ptr(info), float(rcond), _ptr(out)))
     return out
+
+
+def robust_params(kernel="huber", scale=None, tuning=None, scale_min=None, check=True):
+    """rmclhip_robust_params for a kernel given by name (ROBUST_KERNELS) or number: the library's defaults
+    (rmclhip_robust_params_default: MAD scale, the kernel's customary tuning, scale_min 1e-3); scale=c switches to the FIXED mode.  A
+    _capi.RobustParams passes through.  check: refuse invalid parameters here (rmclhip_robust_params_check)."""
+    if isinstance(kernel, _capi.RobustParams):
+        p = kernel
+    else:
+        p = _capi.RobustParams()
+        _capi.lib().rmclhip_robust_params_default(int(ROBUST_KERNELS[kernel] if isinstance(kernel, str) else kernel), C.byref(p))
+        if not isinstance(kernel, str):
+            p.kernel = int(kernel)
+        if scale is not None:
+            p.scale_mode, p.scale = _capi.ROBUST_SCALE_FIXED, float(scale)
+        if tuning is not None:
+            p.tuning = float(tuning)
+        if scale_min is not None:
+            p.scale_min = float(scale_min)
+    if check:
+        _capi.check(_capi.lib().rmclhip_robust_params_check(C.byref(p)))
+    return p
+
+
+def robust_weight(kernel, c, r):
+    """the M-estimator weight w(r) at scale c in float32 on the host (rmclhip_robust_weight_host); kernel by name or number"""
+    k = int(ROBUST_KERNELS[kernel] if isinstance(kernel, str) else kernel)
+    return np.float32(_capi.lib().rmclhip_robust_weight_host(k, float(np.float32(c)), float(np.float32(r))))
 
 
 def pose_covariance_params(sigma=None, rcond=None, degenerate_variance=None, min_eig_trans=None, min_eig_rot=None):
