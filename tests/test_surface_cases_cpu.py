@@ -1,6 +1,8 @@
 """CPU tests of the surface constraint's restatement (tests/surface_ref.py) against answers known in closed form, on hand-built meshes
 of a few triangles; the POD layout of its two structs; the C++ example compiles and prints its usage.  The GPU tests
-(tests/test_gpu_surface.py) hold the kernels to this restatement bit for bit.
+(tests/test_gpu_surface.py) hold the kernels to this restatement bit for bit.  The second half proves that every case of
+tests/surface_cases.py reaches what it was built for -- counts per class, both sides of each threshold, the branch taken and not taken --
+so that tests/test_gpu_surface_edges.py, which runs the same cases on the device, cannot pass vacuously.
 """
 import ctypes as C
 import math
@@ -10,40 +12,11 @@ import time
 import numpy as np
 import pytest
 
+import surface_cases as sc
 import surface_ref as sr
+from surface_cases import join, one, plane_z0, quad
 
 F = np.float32
-
-
-def quad(p00, p10, p11, p01):
-    """two triangles of a quadrilateral, wound p00 -> p10 -> p11 -> p01"""
-    v = np.array([p00, p10, p11, p01], F)
-    return v, np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
-
-
-def join(*parts):
-    vs, fs, base = [], [], 0
-    for v, f in parts:
-        vs.append(v)
-        fs.append(f + np.uint32(base))
-        base += len(v)
-    return np.concatenate(vs).astype(F), np.concatenate(fs).astype(np.uint32)
-
-
-def plane_z0(down=False):
-    """the square [-4, 4]^2 at z = 0 (legs of 8: the geometric normal is (0, 0, +-64), every product with it exact)"""
-    if down:
-        return quad((-4, -4, 0), (-4, 4, 0), (4, 4, 0), (4, -4, 0))
-    return quad((-4, -4, 0), (4, -4, 0), (4, 4, 0), (-4, 4, 0))
-
-
-def one(ra_types, q=(0, 0, 0, 1), t=(0, 0, 0)):
-    poses = np.zeros(1, ra_types.TRANSFORM)
-    sr.set_pose(poses[0], np.array(q, F), np.array(t, F))
-    attrs = np.zeros(1, ra_types.PARTICLE_ATTRIBUTES)
-    attrs["likelihood"]["mean"], attrs["likelihood"]["n_meas"] = 1.0, 7
-    attrs["state_sigma"] = np.arange(6, dtype=F)
-    return poses, attrs
 
 
 @pytest.fixture(scope="module")
@@ -226,6 +199,249 @@ def test_restatement_is_quick_and_its_two_intersectors_agree(orc, T, meshes, nam
     assert dt < 1.0
     assert sa == sb and np.array_equal(ia["face"], ib["face"]) and pa.tobytes() == pb.tobytes()
     assert sa["n_snapped"] >= n // 10 and sa["n_missed"] >= n // 10
+
+
+# ---- the cases of tests/surface_cases.py: each is proved fit for its purpose here, with the restatement alone; the GPU tests
+# (tests/test_gpu_surface_edges.py) rely on these conditions ----------------------------------------------------------------------------
+def run_case(c, bvh=False):
+    mesh, normals = sc.oracle_mesh(c["map"])
+    return sr.constrain(mesh, c["poses"], c["attrs"], c["p"], bvh=bvh, normals=normals)
+
+
+def assert_wanted_classes(c, info):
+    claimed = c["want"] >= 0
+    assert np.array_equal(info["cls"][claimed], c["want"][claimed]), (c["map"], c["note"], info["cls"].tolist(), c["want"].tolist())
+
+
+def class_counts(cls):
+    return tuple(int((cls == k).sum()) for k in (sr.SNAP, sr.MISS, sr.STEEP))
+
+
+@pytest.fixture(scope="module")
+def cube(orc, meshes):
+    m = orc.Mesh(*meshes("cube"))
+    return m, m.face_normals()
+
+
+def test_interval_cloud_sits_on_both_ends_of_the_hit_interval():
+    cases = sc.interval_cloud()
+    mesh, normals = sc.oracle_mesh("plane")
+    n_xy = len(sc.INTERVAL_XY)
+    for c in cases:
+        _, _, st, info = run_case(c)
+        print("interval,", c["note"], st)
+        assert_wanted_classes(c, info)
+        assert np.all(c["want"] >= 0)
+    # the far end: [below, at, above] per (x, y) are snap, snap, miss, and the middle one has t_hit == tfar in float32
+    far = cases[0]
+    assert far["want"].reshape(n_xy, 3).tolist() == [[sr.SNAP, sr.SNAP, sr.MISS]] * n_xy
+    tfar = far["p"]["probe_up"] + far["p"]["probe_down"]
+    for i in range(n_xy):
+        below, at, above = (sr.probe_one(mesh, normals, *sr.pose_Rt(far["poses"][3 * i + j]), far["p"], bvh=False) for j in range(3))
+        assert at[3] == tfar and at[2][2] == tfar and below[3] == np.nextafter(tfar, F(0)) and above[2][2] == np.nextafter(tfar, F(2))
+    # the near end: [well below, below, the three that round onto the plane, above]: only the last one snaps; t_hit == 0 for the three
+    near = cases[1]
+    assert near["want"].reshape(n_xy, 6).tolist() == [[sr.MISS] * 5 + [sr.SNAP]] * n_xy
+    for i in range(n_xy):
+        pr = [sr.probe_one(mesh, normals, *sr.pose_Rt(near["poses"][6 * i + j]), near["p"], bvh=False) for j in range(6)]
+        assert [float(q[2][2]) for q in pr] == [float(F(-0.3) - F(0.25) + F(0.5)), -2.0 ** -24, 0.0, 0.0, 0.0, 2.0 ** -25]
+        for q in pr[2:5]:      # with the near end opened the same ray reports t == 0: it is the strict near side that refuses it
+            assert mesh.intersect(q[2], -q[1], -1.0, float(tfar), bvh=False)[:2] == (True, 0.0)
+        assert float(pr[5][3]) == 2.0 ** -25
+    # zero-length probes and the cases with a zero parameter reach both classes
+    for c in cases[3:]:
+        assert class_counts(run_case(c)[3]["cls"])[0] >= n_xy and class_counts(run_case(c)[3]["cls"])[1] >= n_xy
+
+
+def test_threshold_cloud_is_snap_at_equality_and_steep_one_float_above():
+    cases = sc.threshold_cloud()
+    seen = {sr.SNAP: 0, sr.STEEP: 0}
+    for c in cases:
+        _, _, st, info = run_case(c)
+        assert_wanted_classes(c, info)
+        seen[int(info["cls"][0])] += 1
+    print("threshold cases:", seen)
+    # the trios on the ramp: min_up_cos one float below d, d itself, one float above
+    ramp = [c for c in cases if c["note"].startswith("ramp30 d")]
+    assert len(ramp) == 18
+    for k in range(0, 18, 6):
+        lo, at, hi = (ramp[k + j]["p"]["min_up_cos"] for j in (0, 2, 4))
+        assert np.nextafter(lo, F(2)) == at and np.nextafter(at, F(2)) == hi
+        assert [int(ramp[k + j]["want"][0]) for j in range(6)] == [sr.SNAP] * 4 + [sr.STEEP] * 2
+    assert {float(c["p"]["min_up_cos"]) for c in cases} >= {0.0, 1.0}
+    assert seen[sr.SNAP] >= 10 and seen[sr.STEEP] >= 5
+
+
+def test_upside_down_cloud_takes_the_branch_and_straddles_its_threshold():
+    up, down = sc.upside_down_cloud("plane"), sc.upside_down_cloud("plane_down")
+    assert up["poses"].tobytes() == down["poses"].tobytes()
+    n = len(up["poses"])
+    w = np.array([sc.align_w(sr.pose_Rt(up["poses"][i])[0]) for i in range(n)], F)
+    taken = w < F(1e-6)
+    print("upside down: w =", w.tolist(), "taken", int(taken.sum()), "of", n)
+    assert int(taken.sum()) >= 6 and int((~taken).sum()) >= 4 and int((w == 0).sum()) >= 2
+    # the last two are adjacent float32 rotations, either side of the threshold
+    qa, qb = sr.pose_Rt(up["poses"][n - 2])[0], sr.pose_Rt(up["poses"][n - 1])[0]
+    print("threshold pair: w components", sc.hex32(qa[3]), sc.hex32(qb[3]), "x components", sc.hex32(qa[0]), sc.hex32(qb[0]), "w =", w[n - 2], w[n - 1])
+    assert int(qb[3].view(np.uint32)) - int(qa[3].view(np.uint32)) == 1 and np.array_equal(qa[:3], qb[:3])
+    assert taken[n - 2] and not taken[n - 1]
+    pu, au, su, iu = run_case(up)
+    pd, ad, sd, idn = run_case(down)
+    assert su["n_snapped"] == n and sd["n_snapped"] == n and not iu["flipped"].any() and idn["flipped"].all()
+    assert pu.tobytes() == pd.tobytes() and au.tobytes() == ad.tobytes()
+    # the exact half turns: body z ends on +z and the heading (body x) is kept
+    for k, xb_want, exact in ((0, (1, 0, 0), True), (1, (-1, 0, 0), True), (2, (0, 1, 0), False),
+                              (3, (math.cos(math.radians(37.0)), math.sin(math.radians(37.0)), 0), False)):
+        assert taken[k]
+        R1 = sr.pose_Rt(pu[k])[0]
+        zb, xb = sr.qrot(R1, (0, 0, 1)), sr.qrot(R1, (1, 0, 0))
+        if exact:
+            assert np.array_equal(zb, np.array([0, 0, 1], F)) and np.array_equal(xb, np.array(xb_want, F))
+        else:
+            assert np.allclose(zb, [0, 0, 1], atol=3e-7) and np.allclose(xb, xb_want, atol=3e-7)
+    assert np.array_equal(np.abs(sr.pose_Rt(pu[0])[0]), np.array([0, 0, 0, 1], F))
+    # outside the branch the body z ends on the normal too, as well as float32 allows: q = (zb x n, w) turns by 2 atan(|zb x n| / w) with
+    # |zb x n| = sqrt(2 w) to first order, so an error dw of w turns the result by 2 dw / sqrt(2 w).  w = 1 + zb.z, and zb.z (magnitude
+    # below one) comes out of two quaternion products of seven roundings per component each, from an R that was itself rounded: at most
+    # sixteen roundings of 2^-25, dw <= 2^-21 -- 6.7e-4 rad at the threshold w = 1e-6, less beyond it.  (Seen: 1e-5 to 3e-5.)
+    for k in np.nonzero(~taken)[0]:
+        off = sr.qrot(sr.pose_Rt(pu[k])[0], (0, 0, 1)).astype(np.float64) - np.array([0, 0, 1.0])
+        print("   w = %.4g: body z off the normal by %.3g" % (w[k], np.abs(off).max()))
+        assert np.abs(off).max() <= 2.0 * 2.0 ** -21 / math.sqrt(2.0 * float(w[k]))
+
+
+def test_attitude_cloud_reaches_every_class_on_both_axes(cube):
+    mesh, normals = cube
+    poses, attrs = sc.attitude_cloud(1025)
+    for axis, want_steep in ((0, 0), (1, 50)):
+        _, _, st, info = sr.constrain(mesh, poses, attrs, sr.params(axis=axis, align=1, **sc.PROBE), bvh=False, normals=normals)
+        print("attitudes, seed %d, axis %d:" % (sc.ATTITUDE_SEED, axis), st, "flipped", int(info["flipped"].sum()))
+        assert st["n_snapped"] >= 50 and st["n_missed"] >= 50 and st["n_steep"] >= want_steep and int(info["flipped"].sum()) >= 20
+
+
+def test_nonunit_cloud_changes_the_reach_of_the_body_axis_ray():
+    ns = len(sc.NONUNIT_SCALES)
+    assert sc.NONUNIT_SCALES[:2] == (0.5, 2.0)
+    differ = 0
+    for c in sc.nonunit_cloud():
+        _, _, st, info = run_case(c)
+        cls = info["cls"].reshape(ns, -1)
+        R = np.column_stack([c["poses"]["R"][k] for k in "xyzw"]).astype(np.float64)
+        norms = np.linalg.norm(R, axis=1).reshape(ns, -1)
+        assert np.allclose(norms, np.array(sc.NONUNIT_SCALES)[:, None], rtol=1e-6) and len(set(norms[:, 0].tolist())) == ns
+        print("non-unit,", c["map"], "axis %d align %d:" % (c["p"]["axis"], c["p"]["align"]), [class_counts(r) for r in cls])
+        if c["p"]["axis"] == 0:
+            assert np.all(cls == sr.SNAP)
+        else:
+            differ += int((cls[0] != cls[1]).sum())
+            assert np.all(cls[1] == sr.SNAP)      # norm 2: sixteen times the reach of norm 0.5, and d = 4 cos
+    assert differ >= 1
+
+
+def test_far_cloud_is_the_near_cloud_five_kilometres_out():
+    near, far = sc.far_cloud()
+    assert len(near[0]) == 257 and near[0]["R"].tobytes() == far[0]["R"].tobytes() and near[1].tobytes() == far[1].tobytes()
+    assert np.all(far[0]["t"]["x"] > 4990) and np.all(far[0]["t"]["y"] < -4990) and np.all(far[0]["t"]["z"] > 290)
+    for axis, want_steep in ((0, 0), (1, 5)):
+        p = sr.params(axis=axis, align=1, **sc.PROBE)
+        cls = {}
+        for name, (poses, attrs) in (("ramp30", near), ("ramp30_far", far)):
+            mesh, normals = sc.oracle_mesh(name)
+            _, _, st, info = sr.constrain(mesh, poses, attrs, p, bvh=False, normals=normals)
+            print("far cloud on %s, axis %d:" % (name, axis), st)
+            assert st["n_snapped"] >= 100 and st["n_missed"] >= 30 and st["n_steep"] >= want_steep
+            cls[name] = info["cls"]
+        assert int((cls["ramp30"] != cls["ramp30_far"]).sum()) <= 257 * 2 // 100
+
+
+def test_stack_takes_the_nearer_floor_and_not_the_one_it_starts_on():
+    c = [h for h in sc.hand_clouds() if h["map"] == "stack" and h["p"]["axis"] == 0][0]
+    po, _, st, info = run_case(c)
+    assert info["cls"][:3].tolist() == [sr.SNAP] * 3 and info["flipped"][:3].tolist() == [True, False, False]
+    for i in range(3):
+        assert int(info["face"][i]) in sc.STACK_FACES[i] and float(po["t"]["z"][i]) == sc.STACK_Z[i]
+    # the third probe starts exactly on the upper floor: O.z == 0.75
+    R, t = sr.pose_Rt(c["poses"][2])
+    assert float(sr.origin_of(t, sr.axis_of(R, c["p"]), c["p"])[2]) == 0.75
+
+
+def test_hand_clouds_have_their_closed_form_classes_and_stay_small():
+    seen = set()
+    for c in sc.hand_clouds():
+        assert len(c["poses"]) <= 65
+        _, _, st, info = run_case(c)
+        print("hand map %-10s axis %d:" % (c["map"], c["p"]["axis"]), st, "flipped", int(info["flipped"].sum()))
+        assert_wanted_classes(c, info)
+        seen.add(c["map"])
+    assert seen == set(sc.MAPS)
+    by = {(c["map"], c["p"]["axis"]): run_case(c)[3]["cls"] for c in sc.hand_clouds()}
+    assert by[("hole", 0)][:3].tolist() == [sr.SNAP, sr.MISS, sr.SNAP] and by[("face80", 0)][0] == sr.STEEP
+    assert by[("wall_x1", 0)][0] == sr.MISS and by[("wall_x1", 1)][0] == sr.STEEP
+
+
+def test_kerb_steps_up_down_and_along_the_riser():
+    """up: the existing answers (climbed with probe_up 0.5, killed and without ground with 0.2).  Down: the lifted segment runs above
+    the top the particle leaves, nobody is killed and the probe finds the floor.  Along the riser at x == 1 exactly: the segment lies
+    in the riser's plane (den == 0 is no hit), nobody is killed; the vertical probe runs down the edges the faces share and takes the
+    top from probe_up 0.5 (min t) and the floor from 0.2, where the top is above its origin."""
+    mesh, normals = sc.oracle_mesh("kerb")
+    for c in sc.kerb_steps():
+        po, ao, st, killed = sr.motion_update(mesh, c["poses"], c["attrs"], c["step"], 0.0, True, c["p"], bvh=False, normals=normals)
+        print("kerb,", c["name"], st, "killed", int(killed.sum()))
+        n = len(po)
+        assert np.array_equal(killed, c["want_killed"])
+        assert class_counts(c["want"]) == (st["n_snapped"], st["n_missed"], st["n_steep"])
+        assert np.all(np.abs(po["t"]["z"].astype(np.float64) - c["want_z"]) < 1e-6)
+        assert np.all(ao["likelihood"]["mean"][killed] == 0) and ao[~killed].tobytes() == c["attrs"][~killed].tobytes()
+        if c["name"].startswith("up"):      # the unlifted segment of the unconstrained update crosses the riser in both cases
+            for i in range(n):
+                _, t0 = sr.pose_Rt(c["poses"][i])
+                assert sr.collides(mesh, t0, t0 + np.array([1, 0, 0], F), bvh=False)
+
+
+def test_brute_force_and_bvh_agree_on_every_case(cube):
+    def same(mesh, normals, poses, attrs, p):
+        pa, aa, sa, ia = sr.constrain(mesh, poses, attrs, p, bvh=True, normals=normals)
+        pb, ab, sb, ib = sr.constrain(mesh, poses, attrs, p, bvh=False, normals=normals)
+        assert sa == sb and np.array_equal(ia["cls"], ib["cls"]) and np.array_equal(ia["face"], ib["face"])
+        assert pa.tobytes() == pb.tobytes() and aa.tobytes() == ab.tobytes()
+
+    cases = sc.interval_cloud() + sc.threshold_cloud() + [sc.upside_down_cloud("plane"), sc.upside_down_cloud("plane_down")]
+    cases += sc.nonunit_cloud() + sc.hand_clouds()
+    for c in cases:
+        same(*sc.oracle_mesh(c["map"]), c["poses"], c["attrs"], c["p"])
+    near, far = sc.far_cloud()
+    for axis in (0, 1):
+        p = sr.params(axis=axis, align=1, **sc.PROBE)
+        same(*sc.oracle_mesh("ramp30"), *near, p)
+        same(*sc.oracle_mesh("ramp30_far"), *far, p)
+        same(*cube, *sc.attitude_cloud(1025), p)
+        for poses, attrs, _ in sc.wave_clouds().values():
+            same(*cube, poses, attrs, p)
+    mesh, normals = sc.oracle_mesh("kerb")
+    for c in sc.kerb_steps():
+        a = sr.motion_update(mesh, c["poses"], c["attrs"], c["step"], 0.0, True, c["p"], bvh=True, normals=normals)
+        b = sr.motion_update(mesh, c["poses"], c["attrs"], c["step"], 0.0, True, c["p"], bvh=False, normals=normals)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2] == b[2] and np.array_equal(a[3], b[3])
+
+
+def test_wave_clouds_have_their_dead_lanes_where_they_say(cube):
+    mesh, normals = cube
+    clouds = sc.wave_clouds()
+    assert [len(clouds["n%d" % n][0]) for n in sc.WAVE_COUNTS] == [63, 64, 65, 129]
+    for name, (poses, attrs, dead) in clouds.items():
+        finite = np.ones(len(poses), bool)
+        for grp, keys in (("R", "xyzw"), ("t", "xyz")):
+            for k in keys:
+                finite &= np.isfinite(poses[grp][k])
+        assert np.array_equal(~finite, dead)
+        _, _, st, info = sr.constrain(mesh, poses, attrs, sr.params(axis=1, align=1, **sc.PROBE), bvh=False, normals=normals)
+        print("wave cloud", name, st, "dead", int(dead.sum()))
+        assert np.all(info["cls"][dead] == sr.MISS) and st["n_snapped"] >= int((~dead).sum()) * 6 // 10 and st["n_missed"] > int(dead.sum())
+    assert np.nonzero(clouds["dead_middle"][2])[0].tolist() == list(range(64, 128))
+    assert np.nonzero(~clouds["one_live"][2][:64])[0].tolist() == [37] and not clouds["one_live"][2][64:].any()
+    t = clouds["dead_middle"][0]
+    assert np.isnan(t["t"]["x"]).any() and np.isposinf(t["t"]["y"]).any() and np.isneginf(t["R"]["z"]).any() and np.isnan(t["R"]["w"]).any()
 
 
 def test_pod_sizes_and_defaults(ra):
