@@ -44,6 +44,7 @@ using PoseCovariance = rmclhip_pose_covariance;
 using PoseCovarianceParams = rmclhip_pose_covariance_params;
 // M-estimator weights in the point-to-plane reduction (rmclhip.h, ROBUST MICP)
 using RobustStatistics = rmclhip_robust_statistics;
+using PoseInformationRobust = rmclhip_pose_information_robust;
 struct RobustParams : rmclhip_robust_params {
   // the library's defaults for a kernel: MAD scale, the kernel's customary tuning, scale_min 1e-3
   explicit RobustParams(int kernel_ = RMCLHIP_ROBUST_HUBER) { rmclhip_robust_params_default(kernel_, this); }
@@ -163,6 +164,12 @@ inline PoseCovarianceParams poseCovarianceParams() {
 inline PoseCovariance poseCovariance(const PoseInformation& info, const PoseCovarianceParams& params = poseCovarianceParams()) {
   PoseCovariance c;
   check(rmclhip_pose_covariance_host(&info, &params, &c));
+  return c;
+}
+// ... of a weighted one: the estimated noise divides by weight_sum - 6 (rmclhip_pose_covariance_robust_host)
+inline PoseCovariance poseCovariance(const PoseInformationRobust& info, const PoseCovarianceParams& params = poseCovarianceParams()) {
+  PoseCovariance c;
+  check(rmclhip_pose_covariance_robust_host(&info, &params, &c));
   return c;
 }
 // the Gauss-Newton step xi = A^+ g = (dt, dtheta)
@@ -543,6 +550,15 @@ class Correspondences_<VRAM_HIP> {
     check(rmclhip_rcc_compute_robust_statistics(h_, &T_snew_sold, convergence_progress, &robust, &out));
     return out;
   }
+  // computePoseInformation with the weights (rmclhip_rcc_pose_information_robust): a correspondence the robust loop discounted is
+  // discounted in the information as well; the scale is selected at T_snew_sold; reads the last find's buffers and changes nothing
+  PoseInformationRobust computePoseInformationRobust(const Transform& T_snew_sold, double convergence_progress, const RobustParams& robust) const {
+    bindDataset();
+    check(rmclhip_rcc_set_params(h_, params.max_dist, adaptive_max_dist_min));
+    PoseInformationRobust out;
+    check(rmclhip_rcc_pose_information_robust(h_, &T_snew_sold, convergence_progress, &robust, &out));
+    return out;
+  }
   // the weight of every correspondence of the last find at T_snew_sold, 0 where masked or gated out: an outlier map
   std::vector<float> robustWeights(const Transform& T_snew_sold, double convergence_progress, const RobustParams& robust) const {
     bindDataset();
@@ -721,6 +737,30 @@ inline Transform correctOnce(const std::vector<CorrespondencesHIP*>& sensors, co
   Transform T;
   check(rmclhip_micp_correct_once(h.data(), static_cast<uint32_t>(h.size()), &Tom, Tbo.data(), weights.empty() ? nullptr : weights.data(),
                                   iterations, convergence_progress, &T, merged));
+  return T;
+}
+
+// ... with M-estimator weights (rmclhip_micp_correct_once_robust): robust_params[i] is sensor i's own setting -- sensors differ in
+// noise --, every sensor's scale is selected once behind its find and held, weights[i] multiplies its sum of weights in the solved merge
+// without truncation, an iteration without weight moves nothing.  merged (optional): the unweighted-by-multiplier merge of the last
+// iteration; stats_s (optional): resized to one record per sensor, the last iteration's statistics in each SENSOR's frame.
+inline Transform correctOnceRobust(const std::vector<CorrespondencesHIP*>& sensors, const Transform& Tom, const std::vector<Transform>& Tbo,
+                                   const std::vector<double>& weights, uint32_t iterations, double convergence_progress,
+                                   const std::vector<RobustParams>& robust_params, CrossStatistics* merged = nullptr,
+                                   std::vector<RobustStatistics>* stats_s = nullptr) {
+  if (sensors.empty() || Tbo.size() != sensors.size() || (!weights.empty() && weights.size() != sensors.size()) ||
+      robust_params.size() != sensors.size())
+    throw std::runtime_error("correctOnceRobust: one Tbo, one RobustParams (and weight) per sensor");
+  std::vector<rmclhip_rcc*> h(sensors.size());
+  std::vector<rmclhip_robust_params> p(robust_params.begin(), robust_params.end());
+  for (size_t i = 0; i < sensors.size(); ++i) {
+    sensors[i]->prepareForDeviceLoop();
+    h[i] = sensors[i]->handle();
+  }
+  if (stats_s) stats_s->resize(sensors.size());
+  Transform T;
+  check(rmclhip_micp_correct_once_robust(h.data(), static_cast<uint32_t>(h.size()), &Tom, Tbo.data(), weights.empty() ? nullptr : weights.data(),
+                                         p.data(), iterations, convergence_progress, &T, merged, nullptr, stats_s ? stats_s->data() : nullptr));
   return T;
 }
 

@@ -1447,6 +1447,54 @@ rmclhip_status rmclhip_rcc_correct_once_robust(rmclhip_rcc* rcc, const rmclhip_t
                                                double convergence_progress, const rmclhip_robust_params* params,
                                                rmclhip_transform* T_onew_oold_out, rmclhip_robust_statistics* stats_s_out);
 
+/* ---- ROBUST MICP FOR SENSOR RIGS: weighted merge, the rig loop, weighted pose information ---------------------------
+ * WEIGHTED MERGE.  rmclhip_cross_statistics_merge with real weights where it has the counts: W = wa + wb in double,
+ * w1 = (float)wa / (float)W and w2 = (float)wb / (float)W (float32 divisions), then rmclhip_cross_statistics_merge's expressions,
+ * operation for operation.  out.n_meas = a.n_meas + b.n_meas always; W == 0: zero means and covariance, the counts still add;
+ * *w_out = W (nullable).  wa or wb negative or non-finite: RMCLHIP_ERR_INVALID.  With wa = a.n_meas and wb = b.n_meas the result is
+ * rmclhip_cross_statistics_merge's bytes for every pair of counts whose sum fits 32 bits. */
+rmclhip_status rmclhip_cross_statistics_merge_weighted(const rmclhip_cross_statistics* a, double wa, const rmclhip_cross_statistics* b,
+                                                       double wb, rmclhip_cross_statistics* out, double* w_out);
+/* THE RIG LOOP.  rmclhip_micp_correct_once with the weights, device-resident.  It refuses what rmclhip_micp_correct_once refuses (more
+ * than 8 sensors: RMCLHIP_ERR_UNSUPPORTED; sensors of different contexts, a negative or non-finite multiplier) and what
+ * rmclhip_robust_params_check refuses; every message names the sensor's index, and every refusal of an argument comes before any
+ * launch or change of state (an allocation or HIP error later is returned after every sensor's stream has drained).  params: n_sensors entries, one per sensor -- sensors differ in noise.
+ *   - Every sensor gets one plain find at Tom * Tbo[s] on its own stream (no moment epilogue; the moment set is dropped, as by every find).
+ *   - Every sensor's scale is its own: in MAD mode selected once behind that sensor's find, at the identity pre-transform, under that
+ *     sensor's max_dist' (from convergence_progress), and HELD for all iterations.
+ *   - n_iter times: per sensor the weighted statistics at its T_snew_sold (the reduction of rmclhip_rcc_compute_robust_statistics: same
+ *     rows, same fold); Cs_o = Tbo * (Tsb * stats_s); `merged` folds the Cs_o with weight_sum_s, `merged_w` with
+ *     weight_sum_s * merge_weight_multiplier[s] (NULL: all 1) -- the product is NOT truncated to an integer as the plain loop truncates
+ *     n_meas * multiplier (micp_localization.cpp:934): a weight need not be a count.  T_onew_oold *= umeyama(merged_w) when merged_w's
+ *     weight is above 0; an iteration without weight moves nothing.  The next pre-transforms are formed as in the plain loop.
+ *   - One synchronisation at the end; when the call returns, every sensor's model buffers hold its scan at Tom * Tbo[s].
+ * merged_out: `merged` of the last iteration, *merged_weight_out (nullable) its weight; stats_s_out (nullable): n_sensors records, the
+ * last iteration's statistics in each SENSOR's frame.  n_iter == 0: identity, identity statistics.  ONE sensor with a multiplier above
+ * 0 is rmclhip_rcc_correct_once_robust (the same algebra in the sensor frame, carried to the odometry frame once at the end): its bytes
+ * for T and stats_s_out[0]. */
+rmclhip_status rmclhip_micp_correct_once_robust(rmclhip_rcc* const* sensors, uint32_t n_sensors, const rmclhip_transform* Tom,
+                                                const rmclhip_transform* Tbo, const double* merge_weight_multiplier,
+                                                const rmclhip_robust_params* params, uint32_t n_iter, double convergence_progress,
+                                                rmclhip_transform* T_onew_oold_out, rmclhip_cross_statistics* merged_out,
+                                                double* merged_weight_out, rmclhip_robust_statistics* stats_s_out);
+/* WEIGHTED POSE INFORMATION.  rmclhip_rcc_pose_information with the weights the robust loop ends with: info.A = sum w J^T J,
+ * info.g = sum w J^T r, info.rss = sum w r^2 (every term (double)w * (u[a] * u[b]), the plain call's grid and fold), info.n_meas the
+ * gated-in count; weight_sum = sum w, rss_unweighted = sum r^2.  The scale is selected as rmclhip_rcc_residual_scale selects it at
+ * that pre-transform.  The call only reads the last find's buffers: moment set and rmclhip_ccs_info stay untouched.  With NONE, `info`
+ * is rmclhip_rcc_pose_information's bytes. */
+typedef struct rmclhip_pose_information_robust {
+  rmclhip_pose_information info;
+  double weight_sum, rss_unweighted;
+  float scale, median_abs_residual;
+} rmclhip_pose_information_robust;
+rmclhip_status rmclhip_rcc_pose_information_robust(rmclhip_rcc* rcc, const rmclhip_transform* T_snew_sold, double convergence_progress,
+                                                   const rmclhip_robust_params* params, rmclhip_pose_information_robust* out);
+/* rmclhip_pose_covariance_host's algebra on in->info with s2 = info.rss / (weight_sum - 6) when sigma <= 0: the weights' sum stands
+ * for the count of effective measurements.  That case is refused unless weight_sum > 6.  weight_sum == n_meas gives
+ * rmclhip_pose_covariance_host's bytes. */
+rmclhip_status rmclhip_pose_covariance_robust_host(const rmclhip_pose_information_robust* in, const rmclhip_pose_covariance_params* p,
+                                                   rmclhip_pose_covariance* out);
+
 /* ---- DISTANCE FIELD: the closest-point sensor update by lookup ----------------------------------------------------
  * sensor_update.correspondence_type 1 (evaluate_cpc) scores a beam by the distance of its end point to the surface: the likelihood
  * is smooth in the pose, without the grazing-ray cliffs of ray casting -- what AMCL users know as the likelihood-field model, and the

@@ -13,7 +13,8 @@ from .pf import (AdaptiveResamplerHip, GladiatorResamplerHip, PCDSensorUpdaterHi
                  RecoveryHip, SurfaceSamplerHip, init_particles_surface, surface_sample_params, motion_noise_params, motion_noise_sigma)
 from .registration import (CPCHip, Context, CorrespondencesHIP, DeviceArray, HipMap, MapMap, RCCHipO1Dn,  # noqa: F401
                            RCCHipOnDn, RCCHipPinhole, RCCHipSpherical, ShardedCorrectorHip, build_bvh_host, build_bvh_host_frontier, build_bvh_host_pf, build_bvh_host_quantised,
-                           flatten_scene_host, import_hip_map, import_hip_scene, pose_information_p2l, statistics_p2l, statistics_p2l_robust)
+                           flatten_scene_host, import_hip_map, import_hip_scene, micp_correct_once_robust, pose_information_p2l, statistics_p2l,
+                           statistics_p2l_robust)
 
 from . import field  # noqa: F401
 from .field import DistanceFieldHip, band_field_layout, band_field_params, field_layout, field_params, refine_params, stein_params  # noqa: F401

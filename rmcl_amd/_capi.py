@@ -519,6 +519,10 @@ SIGNATURES = {
     "rmclhip_rcc_residual_scale": (_i32, [_vp, _vp, _dbl, C.POINTER(RobustParams), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_u32)]),
     "rmclhip_rcc_correct_once_robust": (_i32, [_vp, _vp, _vp, _u32, _dbl, C.POINTER(RobustParams), _vp, _vp]),
     "rmclhip_debug_robust_select_recompute": (_i32, [C.c_int]),
+    "rmclhip_cross_statistics_merge_weighted": (_i32, [_vp, _dbl, _vp, _dbl, _vp, C.POINTER(_dbl)]),
+    "rmclhip_micp_correct_once_robust": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _dbl, _vp, _vp, C.POINTER(_dbl), _vp]),
+    "rmclhip_rcc_pose_information_robust": (_i32, [_vp, _vp, _dbl, C.POINTER(RobustParams), _vp]),
+    "rmclhip_pose_covariance_robust_host": (_i32, [_vp, C.POINTER(PoseCovarianceParams), _vp]),
     "rmclhip_field_params_default": (None, [C.POINTER(FieldParams)]),
     "rmclhip_field_layout_host": (_i32, [_vp, _vp, C.POINTER(FieldParams), C.POINTER(FieldInfo)]),
     "rmclhip_field_create": (_i32, [_vp, _vp, C.POINTER(FieldParams), _pp]),

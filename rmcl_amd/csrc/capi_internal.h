@@ -247,6 +247,9 @@ struct RobustScratch {
   DevBuf<float> weights;
   DevBuf<RobustDevBlock> dev;
   MappedBuf<RobustOutBlock> out;
+  // the rig loop (rmclhip_micp_correct_once_robust), on the rig's FIRST sensor: its state between launches and the host-mapped copy
+  DevBuf<RobustRigState> rig;
+  MappedBuf<RobustRigState> rig_out;
 };
 
 struct rmclhip_ctx {
@@ -761,6 +764,8 @@ RMCL_INTERNAL rmclhip_status pose_hypotheses_run(const char* who, rmclhip_resamp
 // capi_rcc.cpp: the stream and host-mapped scratch of the free functions on caller-owned views (rmclhip_statistics_p2l,
 // rmclhip_pose_information_p2l), created by the first call; the caller holds ctx->p2l_mtx
 RMCL_INTERNAL rmclhip_status ctx_p2l_ensure(rmclhip_ctx* ctx);
+// capi_pose_information.cpp: a result row of launch_pose_information[_robust] -> A, g, rss, n_meas
+RMCL_INTERNAL void pose_information_unpack_row(const double* row, rmclhip_pose_information* out);
 // capi_field.cpp: a reference less on a field (the last one frees it; null: nothing), and the sensor update answered from f->field
 RMCL_INTERNAL void field_release(rmclhip_field* fd);
 RMCL_INTERNAL rmclhip_status pf_field_enqueue(rmclhip_pf* f, const rmclhip_transform* poses, rmclhip_particle_attributes* attrs, uint32_t n, uint32_t n_beams,

@@ -448,6 +448,18 @@ rmclhip_status rmclhip_cross_statistics_merge(const rmclhip_cross_statistics* a,
   return RMCLHIP_OK;
 }
 
+rmclhip_status rmclhip_cross_statistics_merge_weighted(const rmclhip_cross_statistics* a, double wa, const rmclhip_cross_statistics* b,
+                                                       double wb, rmclhip_cross_statistics* out, double* w_out) {
+  ApiGuard guard_("rmclhip_cross_statistics_merge_weighted");
+  if (!a || !b || !out) return fail(RMCLHIP_ERR_INVALID, "cross_statistics_merge_weighted: null");
+  if (!(wa >= 0.0) || !std::isfinite(wa) || !(wb >= 0.0) || !std::isfinite(wb))
+    return fail(RMCLHIP_ERR_INVALID, "cross_statistics_merge_weighted: wa and wb must be finite and >= 0");
+  double W = 0.0;
+  from_cs(cs_merge_weighted(to_cs(a), wa, to_cs(b), wb, &W), out);
+  if (w_out) *w_out = W;
+  return RMCLHIP_OK;
+}
+
 rmclhip_status rmclhip_cross_statistics_transform(const rmclhip_transform* T, const rmclhip_cross_statistics* s,
                                                   rmclhip_cross_statistics* out) {
   ApiGuard guard_("rmclhip_cross_statistics_transform");

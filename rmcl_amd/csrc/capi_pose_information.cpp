@@ -5,10 +5,8 @@
 
 static_assert(sizeof(rmclhip_pose_information) == 44 * 8, "PoseInformation layout");
 
-namespace {
-
 // a result row of launch_pose_information (upper triangle of sum u u^T row by row, u = [N ; D x N ; r], then the count)
-void unpack_row(const double* row, rmclhip_pose_information* out) {
+void pose_information_unpack_row(const double* row, rmclhip_pose_information* out) {
   double S[7][7];
   int k = 0;
   for (int a = 0; a < 7; ++a)
@@ -22,6 +20,8 @@ void unpack_row(const double* row, rmclhip_pose_information* out) {
   out->pad = 0;
 }
 
+namespace {
+
 // the launches + the rows' way to the host on `stream`, which the call waits for
 rmclhip_status run(ReduceParams& p, DevBuf<double>& partials, DevBuf<double>& rows, hipStream_t stream,
                    rmclhip_pose_information* out) {
@@ -33,7 +33,7 @@ rmclhip_status run(ReduceParams& p, DevBuf<double>& partials, DevBuf<double>& ro
   std::vector<double> h(static_cast<size_t>(p.nposes) * kPoseInfoRow);
   HIPCHK(hipMemcpyAsync(h.data(), rows.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  for (uint32_t i = 0; i < p.nposes; ++i) unpack_row(h.data() + static_cast<size_t>(i) * kPoseInfoRow, out + i);
+  for (uint32_t i = 0; i < p.nposes; ++i) pose_information_unpack_row(h.data() + static_cast<size_t>(i) * kPoseInfoRow, out + i);
   return RMCLHIP_OK;
 }
 
@@ -274,20 +274,21 @@ void rmclhip_pose_covariance_params_default(rmclhip_pose_covariance_params* out)
   out->min_eig_rot = 1e-3;
 }
 
-rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
-                                            rmclhip_pose_covariance* out) {
-  if (!in || !p || !out) return fail(RMCLHIP_ERR_INVALID, "pose_covariance_host: null");
+// the covariance of both forms: dof = the measurements beyond the six unknowns when the noise is estimated (sigma <= 0) -- n_meas - 6
+// of the plain form, weight_sum - 6 of the robust one; `count` names it in the refusal
+static rmclhip_status pose_covariance(const std::string& who, const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
+                                      double dof, const char* count, rmclhip_pose_covariance* out) {
   if (!(p->rcond >= 0.0) || !std::isfinite(p->rcond) || !(p->degenerate_variance >= 0.0) || !std::isfinite(p->degenerate_variance) ||
       p->sigma != p->sigma || p->min_eig_trans != p->min_eig_trans || p->min_eig_rot != p->min_eig_rot)
-    return fail(RMCLHIP_ERR_INVALID, "pose_covariance_host: rcond and degenerate_variance must be finite and >= 0, no parameter NaN");
-  if (!finite_info(in)) return fail(RMCLHIP_ERR_INVALID, "pose_covariance_host: the information holds non-finite values");
+    return fail(RMCLHIP_ERR_INVALID, who + ": rcond and degenerate_variance must be finite and >= 0, no parameter NaN");
+  if (!finite_info(in)) return fail(RMCLHIP_ERR_INVALID, who + ": the information holds non-finite values");
   double s2;
   if (p->sigma > 0.0) {
     s2 = p->sigma * p->sigma;
   } else {
-    if (in->n_meas <= 6u)
-      return fail(RMCLHIP_ERR_INVALID, "pose_covariance_host: sigma <= 0 estimates the noise from the residuals, which needs n_meas > 6");
-    s2 = in->rss / static_cast<double>(in->n_meas - 6u);
+    if (!(dof > 0.0))
+      return fail(RMCLHIP_ERR_INVALID, who + ": sigma <= 0 estimates the noise from the residuals, which needs " + count + " > 6");
+    s2 = in->rss / dof;
   }
   rmclhip_pose_covariance r;
   std::memset(&r, 0, sizeof(r));
@@ -308,6 +309,21 @@ rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, 
   r.s2 = s2;
   *out = r;
   return RMCLHIP_OK;
+}
+
+rmclhip_status rmclhip_pose_covariance_host(const rmclhip_pose_information* in, const rmclhip_pose_covariance_params* p,
+                                            rmclhip_pose_covariance* out) {
+  if (!in || !p || !out) return fail(RMCLHIP_ERR_INVALID, "pose_covariance_host: null");
+  const double dof = (in->n_meas > 6u) ? static_cast<double>(in->n_meas - 6u) : 0.0;
+  return pose_covariance("pose_covariance_host", in, p, dof, "n_meas", out);
+}
+
+rmclhip_status rmclhip_pose_covariance_robust_host(const rmclhip_pose_information_robust* in, const rmclhip_pose_covariance_params* p,
+                                                   rmclhip_pose_covariance* out) {
+  if (!in || !p || !out) return fail(RMCLHIP_ERR_INVALID, "pose_covariance_robust_host: null");
+  if (!(in->weight_sum >= 0.0) || !std::isfinite(in->weight_sum))
+    return fail(RMCLHIP_ERR_INVALID, "pose_covariance_robust_host: weight_sum must be finite and >= 0");
+  return pose_covariance("pose_covariance_robust_host", &in->info, p, in->weight_sum - 6.0, "weight_sum", out);
 }
 
 }  // extern "C"

@@ -120,6 +120,34 @@ RM_HD cstats cs_merge(const cstats& a, const cstats& b) {
   return r;
 }
 
+// cs_merge with real-valued weights where it has the counts (robust rigs: a sensor's weight is the sum of its M-estimator weights).
+// W = wa + wb in double; the two fractions are f32 divisions of the weights rounded to f32, and the rest is cs_merge's expressions,
+// operation for operation.  With the counts as weights the result is cs_merge's bytes while the counts' sum fits 32 bits: the double
+// sum is exact and rounds to float as the integer sum does.  The counts add whatever the weights are; W == 0 says nothing: zero means
+// and covariance.  The caller guarantees wa, wb >= 0 and finite.
+RM_HD cstats cs_merge_weighted(const cstats& a, double wa, const cstats& b, double wb, double* w_out) {
+  const double W = wa + wb;
+  *w_out = W;
+  cstats r = cs_identity();
+  r.n_meas = a.n_meas + b.n_meas;
+  if (!(W > 0.0)) return r;
+  const float w1 = static_cast<float>(wa) / static_cast<float>(W);
+  const float w2 = static_cast<float>(wb) / static_cast<float>(W);
+  r.dataset_mean = add3(scale3(a.dataset_mean, w1), scale3(b.dataset_mean, w2));
+  r.model_mean = add3(scale3(a.model_mean, w1), scale3(b.model_mean, w2));
+  const f3 m1 = sub3(a.model_mean, r.model_mean), d1 = sub3(a.dataset_mean, r.dataset_mean);
+  const f3 m2 = sub3(b.model_mean, r.model_mean), d2 = sub3(b.dataset_mean, r.dataset_mean);
+  const float mm1[3] = {m1.x, m1.y, m1.z}, dd1[3] = {d1.x, d1.y, d1.z};
+  const float mm2[3] = {m2.x, m2.y, m2.z}, dd2[3] = {d2.x, d2.y, d2.z};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const float P1 = a.covariance[3 * i + j] * w1 + b.covariance[3 * i + j] * w2;
+      const float P2 = (mm1[i] * dd1[j]) * w1 + (mm2[i] * dd2[j]) * w2;
+      r.covariance[3 * i + j] = P1 + P2;
+    }
+  return r;
+}
+
 // Transform * CrossStatistics
 RM_HD cstats cs_transform(const xform& T, const cstats& s) {
   cstats r;

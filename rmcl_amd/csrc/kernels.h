@@ -564,6 +564,34 @@ hipError_t launch_robust_statistics(const RobustView& v, const xform& Tpre, cons
 hipError_t launch_robust_loop(const RobustView& v, const RobustScale* scale_dev, double* partials, uint32_t nblocks, xform* state,
                               uint32_t n_iter, const xform& Tsb, const xform& Tbo, RobustLoopOut* out, hipStream_t s);
 
+// The robust loop of a sensor rig (rmclhip_micp_correct_once_robust).  The call block travels BY VALUE with every launch
+// (no copy node); what the loop keeps between launches is RobustRigState in device memory.  A sensor's rows are the rows it would have
+// alone: block0 is the first workgroup of its share of the ONE streaming launch over all sensors (grid: the sum of the nblocks).
+struct RobustRigSensor {
+  RobustView v;
+  const RobustScale* scale;    // the sensor's own, selected once behind its find and held
+  double* partials;            // [nblocks][kRobustRow]
+  uint32_t nblocks, block0;
+  xform Tsb, Tbo;
+  double weight;               // merge_weight_multiplier: multiplies sum w in the solved merge, never truncated
+};
+struct RobustRigCall { RobustRigSensor s[kMaxMicpSensors]; uint32_t n_sensors, total_blocks; };
+struct RobustRigState {
+  xform T_onew_oold;
+  cstats merged_o, merged_weighted_o;
+  double merged_weight, merged_weighted_weight;   // sum over the sensors of sum w, and of sum w * multiplier
+  xform T_snew_sold[kMaxMicpSensors];
+  RobustStats stats_s[kMaxMicpSensors];           // the last iteration's, sensor frame
+};
+// identity state; then n_iter x {one streaming launch over every sensor at its T_snew_sold, one one-wave step: robust_finalize per sensor,
+// Cs_o = Tbo * (Tsb * stats_s), the two weighted merges, T_onew_oold *= umeyama(merged_weighted_o) if that merge has weight, the next
+// pre-transforms as k_micp_multi_step forms them}; a closing launch copies the state to *out (may be host-mapped).  n_iter >= 1
+hipError_t launch_robust_rig_loop(const RobustRigCall& call, RobustRigState* state, uint32_t n_iter, RobustRigState* out, hipStream_t s);
+
+// pose_information.hip with M-estimator weights: A = sum w u u^T by k_pose_information_partials' grid, mapping and fold, every term
+// (double)w * (u[a] * u[b]); rows_out[kPoseInfoRow] = {the 28 sums | the gated-in count | sum w | sum r^2 | 0}.  *scale_dev: the scale c
+hipError_t launch_pose_information_robust(const ReduceParams& p, int32_t kernel, const RobustScale* scale_dev, double* rows_out, hipStream_t s);
+
 // field.hip: reading the map's distance field (include/rmclhip.h, DISTANCE FIELD).  lat: n[0] * n[1] * n[2] floats, x fastest, then y, then z.
 // A banded field (include/rmclhip.h, BANDED DISTANCE FIELD) has lat == nullptr and the three arrays below: table,
 // nb[0] * nb[1] * nb[2] words (the stored index of a brick or kBandFar), x fastest; coarse, (nb[0] + 1) * (nb[1] + 1) * (nb[2] + 1)

@@ -6,6 +6,7 @@
 //
 // What the sums mean and how the host turns them into a covariance: include/rmclhip.h (POSE COVARIANCE), DESIGN.md 4.12.
 #include "kernels.h"
+#include "robust_host.h"
 #include "wave_sum.hip.h"
 
 namespace rmclhip {
@@ -14,13 +15,15 @@ namespace {
 
 constexpr int kSums = 28;   // upper triangle of the 7 x 7 matrix sum u u^T, row by row
 constexpr int kVals = 32;   // kSums, the count, padding: two groups of 16 for wave_sum16_lds
+constexpr int kWsum = 29, kRssPlain = 30;   // the weighted form alone: sum w, sum r^2 (the plain form leaves them 0)
 static_assert(kVals == static_cast<int>(kPoseInfoRow), "row layout");
 
 // Per-lane f64 accumulators -- the plain form: the 28 products of a correspondence are multiply + add on values its lane already holds
 // (no fused multiply-add: every term is the rounded product, which is what the tests' error bound counts), no MFMA --, summed over the
 // wave through LDS and over the workgroup's four waves in wave order.  Nothing is added across workgroups here: a workgroup's row is a
 // function of its correspondences alone.
-__global__ void __launch_bounds__(256) k_pose_information_partials(const ReduceParams p) {
+template <bool kWeighted>
+__device__ __forceinline__ void pose_information_partials(const ReduceParams& p, int kernel, float c) {
   __shared__ double red[4][kVals];
   __shared__ double s_wsum[4][64 * 17];
   const uint32_t pose = blockIdx.y;
@@ -46,10 +49,21 @@ __global__ void __launch_bounds__(256) k_pose_information_partials(const ReduceP
         const double dx = Di.x, dy = Di.y, dz = Di.z, nx = Ni.x, ny = Ni.y, nz = Ni.z;
         const double u[7] = {nx, ny, nz, dy * nz - dz * ny, dz * nx - dx * nz, dx * ny - dy * nx, static_cast<double>(spd)};
         int k = 0;
+        if constexpr (kWeighted) {
+          // the weight of robust.hip's reduction (robust_host.h) at the same residual: w == 1 adds the very values of the plain form
+          const double wd = static_cast<double>(robust_weight(kernel, c, spd));
 #pragma unroll
-        for (int a = 0; a < 7; ++a)
+          for (int a = 0; a < 7; ++a)
 #pragma unroll
-          for (int b = a; b < 7; ++b) acc[k++] += u[a] * u[b];
+            for (int b = a; b < 7; ++b) acc[k++] += wd * (u[a] * u[b]);
+          acc[kWsum] += wd;
+          acc[kRssPlain] += u[6] * u[6];
+        } else {
+#pragma unroll
+          for (int a = 0; a < 7; ++a)
+#pragma unroll
+            for (int b = a; b < 7; ++b) acc[k++] += u[a] * u[b];
+        }
         acc[kSums] += 1.0;
       }
     }
@@ -71,6 +85,13 @@ __global__ void __launch_bounds__(256) k_pose_information_partials(const ReduceP
     __hip_atomic_store(p.partials + (static_cast<size_t>(pose) * p.nblocks + blockIdx.x) * kVals + threadIdx.x, v, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+__global__ void __launch_bounds__(256) k_pose_information_partials(const ReduceParams p) { pose_information_partials<false>(p, 0, 0.0f); }
+
+// the same pass with M-estimator weights (include/rmclhip.h, ROBUST MICP): same grid, same mapping, same fold
+__global__ void __launch_bounds__(256) k_pose_information_partials_robust(const ReduceParams p, int kernel, const RobustScale* __restrict__ scale) {
+  pose_information_partials<true>(p, kernel, scale->c);
 }
 
 // lane = 32 g + k adds value k of the rows g, g + 2, g + 4, ... in ascending order (eight loads in flight), one xor step joins the
@@ -97,6 +118,13 @@ __global__ void __launch_bounds__(64) k_pose_information_finalize(const double* 
 
 hipError_t launch_pose_information(const ReduceParams& p, double* rows_out, hipStream_t s) {
   hipLaunchKernelGGL(k_pose_information_partials, dim3(p.nblocks, p.nposes), dim3(256), 0, s, p);
+  if (const hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_pose_information_finalize, dim3(p.nposes), dim3(64), 0, s, p.partials, p.nblocks, rows_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pose_information_robust(const ReduceParams& p, int32_t kernel, const RobustScale* scale_dev, double* rows_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_pose_information_partials_robust, dim3(p.nblocks, p.nposes), dim3(256), 0, s, p, kernel, scale_dev);
   if (const hipError_t e = hipGetLastError()) return e;
   hipLaunchKernelGGL(k_pose_information_finalize, dim3(p.nposes), dim3(64), 0, s, p.partials, p.nblocks, rows_out);
   return hipGetLastError();

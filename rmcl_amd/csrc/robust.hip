@@ -9,6 +9,9 @@
 //   k_robust_finalize        one wave folds the rows in finalize_pose's order (reduce_common.hip.h) and divides by sum w
 //   k_robust_iter, _close    the IRLS loop, one launch per iteration: the previous iteration's fold + solve in the prologue of the next
 //                            reduction (the form of k_micp_iter / k_micp_close, micp.hip)
+//   k_robust_rig_partials,   the rig: ONE streaming launch over all sensors -- a workgroup finds its sensor in the call
+//   _step, _init, _close     block and is one of that sensor's own rows --, then one wave finalizes every sensor, merges with real
+//                            weights (cs_merge_weighted, devmath.h), solves and hands out the next pre-transforms (k_micp_multi_step's shape)
 //
 // The weight itself is robust_weight() of robust_host.h, the one definition host and device share: f32, IEEE division, no fused
 // operation (-ffp-contract=off, hipcc's correctly rounded f32 division) -- numpy float32 reproduces every weight bit for bit; keep it so.
@@ -181,16 +184,21 @@ __device__ __forceinline__ float robust_accumulate(const Residual& e, int kernel
   return w;
 }
 
-// the thread's elements in k_reduce_partials' mapping
-__device__ __forceinline__ void robust_stream(const RobustView& v, const xform& Tpre, float c, float* weights_out, double* acc) {
+// the thread's elements in k_reduce_partials' mapping, as workgroup `row` of `nrows` (a launch of its own: blockIdx.x of gridDim.x; a
+// sensor's share of the rig's launch: its row of its nblocks -- the same elements in the same order either way)
+__device__ __forceinline__ void robust_stream_rows(const RobustView& v, const xform& Tpre, float c, float* weights_out, double* acc,
+                                                   uint32_t row, uint32_t nrows) {
 #pragma unroll
   for (int k = 0; k < kRow; ++k) acc[k] = 0.0;
   // (64-bit index: the same elements in the same order as k_reduce_partials' 32-bit one, without its wrap for n within a stride of 2^32)
-  const size_t stride = static_cast<size_t>(gridDim.x) * 256u;
-  for (size_t i = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; i < v.n; i += stride) {
+  const size_t stride = static_cast<size_t>(nrows) * 256u;
+  for (size_t i = static_cast<size_t>(row) * 256u + threadIdx.x; i < v.n; i += stride) {
     const float w = robust_accumulate(robust_residual(v, Tpre, i), v.kernel, c, acc);
     if (weights_out != nullptr) weights_out[i] = w;
   }
+}
+__device__ __forceinline__ void robust_stream(const RobustView& v, const xform& Tpre, float c, float* weights_out, double* acc) {
+  robust_stream_rows(v, Tpre, c, weights_out, acc, blockIdx.x, gridDim.x);
 }
 
 // the wave's sums of the row's two halves (the first half is k_reduce_partials' wave_sum16_lds call); lanes 0..15 hold them afterwards
@@ -342,6 +350,84 @@ __global__ void __launch_bounds__(64) k_robust_close(const double* __restrict__ 
   }
 }
 
+// ---- the rig: N sensors, one streaming launch and one step launch per iteration ----------------------------------------
+// One launch covers every sensor: a workgroup finds its sensor in the call block's table (at most 8 entries, wave-uniform scalar loads from
+// the kernel arguments) and is row blockIdx.x - block0 of that sensor's nblocks -- k_robust_partials' mapping and order of additions, so
+// a sensor's rows are the rows it would have alone.  Pre-transform and scale come from device memory: the step launch before this one
+// (or the init launch) wrote the one, the sensor's own selection behind its find the other.
+__global__ void __launch_bounds__(256) k_robust_rig_partials(const RobustRigCall call, const RobustRigState* __restrict__ st) {
+  __shared__ double red[4][kRow];
+  __shared__ double s_wsum[4][64 * 17];
+  uint32_t s = 0;
+  for (uint32_t k = 1; k < call.n_sensors; ++k)
+    if (blockIdx.x >= call.s[k].block0) s = k;
+  const RobustRigSensor& me = call.s[s];
+  const uint32_t row = blockIdx.x - me.block0;
+  if (row >= me.nblocks) return;   // (never: the grid is the sum of the nblocks)
+  const xform Tpre = st->T_snew_sold[s];
+  double acc[kRow];
+  robust_stream_rows(me.v, Tpre, me.scale->c, nullptr, acc, row, me.nblocks);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  robust_wave_row(acc, &s_wsum[wave][0], lane, &red[wave][0]);
+  __syncthreads();
+  if (threadIdx.x < kRobustRow) {
+    const double t = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    // write-through store, read by the step launch after the kernel boundary (as k_robust_partials)
+    __hip_atomic_store(me.partials + static_cast<size_t>(row) * kRobustRow + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ void __launch_bounds__(64) k_robust_rig_init(RobustRigState* __restrict__ st) {
+  if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+  st->T_onew_oold = xidentity();
+  st->merged_o = cs_identity();
+  st->merged_weighted_o = cs_identity();
+  st->merged_weight = 0.0;
+  st->merged_weighted_weight = 0.0;
+  for (uint32_t s = 0; s < kMaxMicpSensors; ++s) st->T_snew_sold[s] = xidentity();
+}
+
+// One iteration's merge and solve, ONE wave -- k_micp_multi_step (micp.hip) with real weights: per sensor, in order, stats_s <- its rows
+// (robust_finalize); Cs_o = Tbo * (Tsb * stats_s); merged folds the Cs_o with sum w, merged_w with sum w * merge_weight_multiplier.
+// The plain loop truncates n_meas * multiplier to an integer there (micp_localization.cpp:934, a count has to be one); a weight has
+// not: NO truncation here.  T_onew_oold *= umeyama(merged_w) when merged_w has weight, else nothing moves; the next pre-transforms
+// exactly as k_micp_multi_step forms them.
+__global__ void __launch_bounds__(64) k_robust_rig_step(const RobustRigCall call, RobustRigState* __restrict__ st) {
+  cstats merged = cs_identity(), merged_w = cs_identity();
+  double W = 0.0, Ww = 0.0;
+  for (uint32_t s = 0; s < call.n_sensors; ++s) {
+    const RobustRigSensor& me = call.s[s];
+    const RobustStats rs = robust_finalize(me.partials, me.nblocks, *me.scale);   // whole wave
+    if (threadIdx.x == 0u) {
+      st->stats_s[s] = rs;
+      const cstats Cs_o = cs_transform(me.Tbo, cs_transform(me.Tsb, rs.stats));
+      merged = cs_merge_weighted(merged, W, Cs_o, rs.weight_sum, &W);
+      merged_w = cs_merge_weighted(merged_w, Ww, Cs_o, rs.weight_sum * me.weight, &Ww);
+    }
+  }
+  if (threadIdx.x == 0u) {
+    xform T_onew_oold = st->T_onew_oold;
+    if (Ww > 0.0) T_onew_oold = xmul(T_onew_oold, umeyama(merged_w));
+    st->T_onew_oold = T_onew_oold;
+    st->merged_o = merged;
+    st->merged_weighted_o = merged_w;
+    st->merged_weight = W;
+    st->merged_weighted_weight = Ww;
+    for (uint32_t s = 0; s < call.n_sensors; ++s) {
+      const xform T_bnew_bold = xmul(xmul(xinv(call.s[s].Tbo), T_onew_oold), call.s[s].Tbo);
+      st->T_snew_sold[s] = xmul(xmul(xinv(call.s[s].Tsb), T_bnew_bold), call.s[s].Tsb);
+    }
+  }
+}
+
+// closing launch: the state's way to the caller (host-mapped memory: dword stores in address order, consecutive lanes consecutive words)
+__global__ void __launch_bounds__(64) k_robust_rig_close(const RobustRigState* __restrict__ st, RobustRigState* __restrict__ out) {
+  static_assert(sizeof(RobustRigState) % sizeof(uint32_t) == 0, "copied by words");
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(st);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(out);
+  for (uint32_t w = threadIdx.x; w < sizeof(RobustRigState) / sizeof(uint32_t); w += 64u) dst[w] = src[w];
+}
+
 }  // namespace
 
 hipError_t launch_robust_scale(const RobustView& v, const xform& Tpre, const RobustScaleParams& sp, uint32_t* sel, uint32_t* keys,
@@ -384,6 +470,18 @@ hipError_t launch_robust_loop(const RobustView& v, const RobustScale* scale_dev,
     if (const hipError_t e = hipGetLastError()) return e;
   }
   hipLaunchKernelGGL(k_robust_close, dim3(1), dim3(64), 0, s, part[(n_iter - 1u) & 1u], nblocks, scale_dev, state + (n_iter & 1u), Tsb, Tbo, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_robust_rig_loop(const RobustRigCall& call, RobustRigState* state, uint32_t n_iter, RobustRigState* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_robust_rig_init, dim3(1), dim3(64), 0, s, state);
+  if (const hipError_t e = hipGetLastError()) return e;
+  for (uint32_t i = 0; i < n_iter; ++i) {
+    hipLaunchKernelGGL(k_robust_rig_partials, dim3(call.total_blocks), dim3(256), 0, s, call, state);
+    hipLaunchKernelGGL(k_robust_rig_step, dim3(1), dim3(64), 0, s, call, state);
+    if (const hipError_t e = hipGetLastError()) return e;
+  }
+  hipLaunchKernelGGL(k_robust_rig_close, dim3(1), dim3(64), 0, s, state, out);
   return hipGetLastError();
 }
 

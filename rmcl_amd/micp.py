@@ -52,8 +52,9 @@ class MICPLocalization:
 
     def __init__(self, sensors, optimization_iterations=5, adaptive_max_dist=True, disable_correction=False, robust=None):
         """robust: as MICPSensor's, for the localization as a whole (a sensor's own setting is used when this is None).  Honoured for
-        ONE sensor, whose merge_weight_multiplier then plays no part (a lone sensor's weight cancels in the solve); several sensors
-        raise NotImplementedError in correctOnce."""
+        ONE sensor, whose merge_weight_multiplier then plays no part (a lone sensor's weight cancels in the solve), and for 2 to 8
+        sensors in correctOnce(device_loop=True), every sensor under its own setting where it has one; several sensors in the host
+        loop raise NotImplementedError."""
         self.sensors_vec_ = list(sensors)
         self.robust = robust
         self.optimization_iterations_ = optimization_iterations  # default 5, micp_localization.cpp:129
@@ -62,7 +63,8 @@ class MICPLocalization:
         self.Tom_ = T.identity()
         self.convergence_progress_ = 0.0
         self.correction_stats_latest_ = {}
-        self.robust_statistics_latest_ = None   # ROBUST_STATISTICS of the last robust correction's last iteration, sensor frame
+        # ROBUST_STATISTICS of the last robust correction's last iteration, sensor frame (a rig: the list of its sensors' records)
+        self.robust_statistics_latest_ = None
 
     def _device_loop(self, Tom):
         """the inner loop of correctOnce for all sensors resident on the device (rmclhip_micp_correct_once): finds, per-sensor
@@ -86,6 +88,28 @@ class MICPLocalization:
                                                           float(self.convergence_progress_), _ptr(Tout), _ptr(merged)))
         return Tout[0].copy(), merged[0].copy()
 
+    def _sensor_robust(self, s):
+        """a sensor's own robust setting, the localization's where it has none"""
+        return s.robust if s.robust is not None else self.robust
+
+    def _robust_rig_loop(self, Tom):
+        """the robust inner loop for 2..8 sensors resident on the device (rmclhip_micp_correct_once_robust): every sensor's parameters
+        are its own (sensor.robust, else the localization's; a sensor with neither runs the plain weight 1).  Fills
+        robust_statistics_latest_ with the list of per-sensor records, sensor frames."""
+        from .registration import micp_correct_once_robust
+        if len(self.sensors_vec_) > 8:
+            raise ValueError("correctOnce(device_loop=True, robust=...): at most 8 sensors (rmclhip_micp_correct_once_robust)")
+        for s in self.sensors_vec_:
+            s.setTom(Tom)
+            s.correspondences_.setTsb(s.Tsb)
+            s.correspondences_.outdated = False
+        robust = [self._sensor_robust(s) if self._sensor_robust(s) is not None else "none" for s in self.sensors_vec_]
+        T_onew_oold, merged, _, stats = micp_correct_once_robust(
+            [s.correspondences_ for s in self.sensors_vec_], Tom, np.array([s.Tbo for s in self.sensors_vec_], dtype=T.TRANSFORM),
+            [float(s.merge_weight_multiplier) for s in self.sensors_vec_], robust, self.optimization_iterations_, self.convergence_progress_)
+        self.robust_statistics_latest_ = [st.copy() for st in stats]
+        return T_onew_oold, merged, stats
+
     def correctOnce(self, record=None, device_loop=False):
         """micp_localization.cpp:856-1016. `record`, if a list, receives T_onew_oold after each iteration.
         device_loop=True runs the inner loop (finds + iterations) on the device for all sensors at once; it sets every
@@ -95,13 +119,16 @@ class MICPLocalization:
         valid_measurements = sum(s.valid_dataset_measurements for s in self.sensors_vec_)
         robust = self.robust if self.robust is not None else next((s.robust for s in self.sensors_vec_ if s.robust is not None), None)
         if robust is not None and not self.disable_correction_ and self.optimization_iterations_ > 0:
-            if len(self.sensors_vec_) != 1:
-                raise NotImplementedError("correctOnce(robust=...): the robust correction runs for one sensor; merging several sensors' "
-                                          "weighted statistics needs real-valued weights where the count-weighted merge of "
-                                          "CrossStatistics has n_meas, which the N-sensor loop does not carry yet")
+            if len(self.sensors_vec_) != 1 and not device_loop:
+                raise NotImplementedError("correctOnce(robust=...): the host loop runs the robust correction for one sensor; merging "
+                                          "several sensors' weighted statistics needs real-valued weights where the count-weighted merge "
+                                          "of CrossStatistics has n_meas.  The device-resident rig loop carries them: "
+                                          "correctOnce(device_loop=True) takes 2 to 8 sensors")
             if record is not None:
                 raise ValueError("correctOnce(record=..., robust=...): the robust loop is device-resident and does not return "
                                  "per-iteration transforms")
+            if len(self.sensors_vec_) != 1:
+                return self._finish(Tom, *self._robust_rig_loop(Tom)[:2], valid_measurements)
             # (one sensor: its merge_weight_multiplier scales a lone term of the merge and cancels in the solve; it is not read here)
             s = self.sensors_vec_[0]
             s.setTom(Tom)
@@ -147,21 +174,36 @@ class MICPLocalization:
                 record.append(T_onew_oold.copy())
         return self._finish(Tom, T_onew_oold, Cmerged_o, valid_measurements)
 
-    def poseInformation(self, T_onew_oold=None, covariance_params=None):
+    def poseInformation(self, T_onew_oold=None, covariance_params=None, robust=None):
         """What publishPose (micp_localization.cpp:1062-1076) needs instead of its guessed diagonal: the sensors' point-to-plane
         information over the correspondences of their last find, each carried sensor -> base (Tsb) -> odom (Tbo) and merged with the
         sensor's merge_weight_multiplier.  T_onew_oold: the correction the loop ended with (None: identity), the pre-transform of the
         last iteration's statistics.  Returns (POSE_INFORMATION, POSE_COVARIANCE) in the odom frame (the base frame where Tbo is the
-        identity); covariance_params: types.pose_covariance_params(...)."""
+        identity); covariance_params: types.pose_covariance_params(...).
+        robust: the weighted information (rmclhip_rcc_pose_information_robust) per sensor -- a kernel name or types.robust_params(...)
+        for every sensor, or True: every sensor's own setting as correctOnce uses it.  A correspondence the robust loop discounted is
+        discounted here as well; the estimated noise divides by the merged weight_sum - 6 (types.pose_covariance_robust)."""
         T_onew_oold = T.identity() if T_onew_oold is None else T_onew_oold
         merged = T.pose_information_identity()
+        weight_sum = rss_plain = 0.0
         for s in self.sensors_vec_:
             T_bnew_bold = T.mult(T.mult(T.inv(s.Tbo), T_onew_oold), s.Tbo)
             T_snew_sold = T.mult(T.mult(T.inv(s.Tsb), T_bnew_bold), s.Tsb)
-            info_s = s.correspondences_.computePoseInformation(T_snew_sold, self.convergence_progress_)
+            if robust is None:
+                info_s = s.correspondences_.computePoseInformation(T_snew_sold, self.convergence_progress_)
+            else:
+                p = self._sensor_robust(s) if robust is True else robust
+                rec = s.correspondences_.pose_information_robust(T_snew_sold, self.convergence_progress_, "none" if p is None else p)
+                info_s = rec["info"]
+                weight_sum += float(s.merge_weight_multiplier) * float(rec["weight_sum"])
+                rss_plain += float(s.merge_weight_multiplier) * float(rec["rss_unweighted"])
             info_o = T.pose_information_transform(s.Tbo, T.pose_information_transform(s.Tsb, info_s))
             merged = T.pose_information_merge(merged, info_o, s.merge_weight_multiplier)
-        return merged, T.pose_covariance(merged, covariance_params)
+        if robust is None:
+            return merged, T.pose_covariance(merged, covariance_params)
+        rec = np.zeros((), dtype=T.POSE_INFORMATION_ROBUST)
+        rec["info"], rec["weight_sum"], rec["rss_unweighted"] = merged, weight_sum, rss_plain
+        return merged, T.pose_covariance_robust(rec, covariance_params)
 
     def _finish(self, Tom, T_onew_oold, Cmerged_o, valid_measurements):
         T_onew_map = T.mult(Tom, T_onew_oold)                                             # :972

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .types import CROSS_STATISTICS, POSE_INFORMATION, ROBUST_STATISTICS, TRANSFORM, _ptr, robust_params
+from .types import CROSS_STATISTICS, POSE_INFORMATION, POSE_INFORMATION_ROBUST, ROBUST_STATISTICS, TRANSFORM, _ptr, robust_params
 
 
 def _as_ptr(x):
@@ -346,6 +346,41 @@ def statistics_p2l_robust(ctx, Tpre, dataset_points, dataset_mask, model_points,
     return out[0].copy()
 
 
+def micp_correct_once_robust(sensors, Tom, Tbo, merge_weight_multiplier, robust, n_iter, convergence_progress=0.0):
+    """the robust correction of a rig of 1..8 correspondence operators on one device (rmclhip_micp_correct_once_robust): one find per
+    sensor, every sensor's scale selected once behind its find and held, then n_iter x {weighted statistics per sensor, weighted merge,
+    solve}.  Tbo: one transform per sensor; merge_weight_multiplier: one factor per sensor or None (all 1), never truncated; robust: ONE
+    setting for all sensors (a kernel name or types.robust_params(...)) or a sequence with one per sensor.
+    Returns (T_onew_oold, merged CROSS_STATISTICS of the last iteration, its weight, ROBUST_STATISTICS[n] in each sensor's frame)."""
+    sensors = list(sensors)
+    n = len(sensors)
+    per_sensor = list(robust) if isinstance(robust, (list, tuple)) else [robust] * n
+    if len(per_sensor) != n:
+        raise ValueError("micp_correct_once_robust: %d robust settings for %d sensors" % (len(per_sensor), n))
+    params = (_capi.RobustParams * max(n, 1))()
+    for k, r in enumerate(per_sensor):
+        p = robust_params(r, check=False)
+        for name, _ in _capi.RobustParams._fields_:
+            setattr(params[k], name, getattr(p, name))
+    for s in sensors:
+        s._push_params()
+    handles = (C.c_void_p * max(n, 1))(*[s._h for s in sensors])
+    a = np.ascontiguousarray(Tom, dtype=TRANSFORM).reshape(1)
+    b = np.ascontiguousarray(Tbo, dtype=TRANSFORM).reshape(-1)
+    if len(b) != n:
+        raise ValueError("micp_correct_once_robust: %d Tbo for %d sensors" % (len(b), n))
+    w = None if merge_weight_multiplier is None else np.ascontiguousarray(merge_weight_multiplier, dtype=np.float64).reshape(-1)
+    if w is not None and len(w) != n:
+        raise ValueError("micp_correct_once_robust: %d multipliers for %d sensors" % (len(w), n))
+    T, merged, W = np.zeros(1, dtype=TRANSFORM), np.zeros(1, dtype=CROSS_STATISTICS), C.c_double(0.0)
+    stats = np.zeros(max(n, 1), dtype=ROBUST_STATISTICS)
+    _capi.check(_capi.lib().rmclhip_micp_correct_once_robust(handles, n, _ptr(a), _ptr(b), _ptr(w), C.cast(params, C.c_void_p), int(n_iter),
+                                                             float(convergence_progress), _ptr(T), _ptr(merged), C.byref(W), _ptr(stats)))
+    for s in sensors:
+        s._last_nposes = 1
+    return T[0].copy(), merged[0].copy(), W.value, stats[:n].copy()
+
+
 class UmeyamaReductionConstraints:
     """rmagine::UmeyamaReductionConstraints (only max_dist is used, micp_localization.cpp:525-526)."""
 
@@ -450,6 +485,16 @@ class CorrespondencesHIP:
         _capi.check(_capi.lib().rmclhip_rcc_residual_scale(self._h, _ptr(T), float(convergence_progress), C.byref(p), C.byref(c),
                                                            C.byref(med), C.byref(m)))
         return np.float32(c.value), np.float32(med.value), int(m.value)
+
+    def pose_information_robust(self, T_snew_sold, convergence_progress=0.0, robust="huber"):
+        """computePoseInformation with the M-estimator weights, the scale selected as residual_scale selects it at T_snew_sold: a
+        POSE_INFORMATION_ROBUST record, sensor frame (rmclhip_rcc_pose_information_robust); reads the last find's buffers only"""
+        self._push_params()
+        T = np.ascontiguousarray(T_snew_sold, dtype=TRANSFORM).reshape(1)
+        p = robust_params(robust, check=False)
+        out = np.zeros(1, dtype=POSE_INFORMATION_ROBUST)
+        _capi.check(_capi.lib().rmclhip_rcc_pose_information_robust(self._h, _ptr(T), float(convergence_progress), C.byref(p), _ptr(out)))
+        return out[0].copy()
 
     def correct_once_robust(self, Tom, Tbo, n_iter, convergence_progress=0.0, robust="huber"):
         """correct_once (one find, n_iter x reduction + solve) with the weights re-evaluated every iteration, the scale selected once

@@ -31,6 +31,10 @@ ROBUST_STATISTICS = np.dtype([("stats", CROSS_STATISTICS), ("weight_sum", "<f8")
                               ("median_abs_residual", "<f4")])
 ROBUST_KERNELS = dict(none=_capi.ROBUST_NONE, huber=_capi.ROBUST_HUBER, cauchy=_capi.ROBUST_CAUCHY, tukey=_capi.ROBUST_TUKEY,
                       geman_mcclure=_capi.ROBUST_GEMAN_MCCLURE)
+# rmclhip_pose_information_robust (include/rmclhip.h, ROBUST MICP FOR SENSOR RIGS)
+POSE_INFORMATION_ROBUST = np.dtype([("info", POSE_INFORMATION), ("weight_sum", "<f8"), ("rss_unweighted", "<f8"), ("scale", "<f4"),
+                                    ("median_abs_residual", "<f4")])
+assert POSE_INFORMATION_ROBUST.itemsize == 376
 assert TRANSFORM.itemsize == 32 and CROSS_STATISTICS.itemsize == 64 and ROBUST_STATISTICS.itemsize == 96
 assert POSE_INFORMATION.itemsize == 352 and POSE_COVARIANCE.itemsize == 496
 assert PARTICLE_ATTRIBUTES.itemsize == 36 and RANGE_MEASUREMENT.itemsize == 64
@@ -94,6 +98,15 @@ def cross_statistics_merge(a, b):
     a, b, out = _one(a, CROSS_STATISTICS), _one(b, CROSS_STATISTICS), np.zeros(1, dtype=CROSS_STATISTICS)
     _capi.check(_capi.lib().rmclhip_cross_statistics_merge(_ptr(a), _ptr(b), _ptr(out)))
     return out[0].copy()
+
+
+def cross_statistics_merge_weighted(a, wa, b, wb):
+    """the merge with real-valued weights where cross_statistics_merge has the counts (rmclhip_cross_statistics_merge_weighted):
+    (merged, wa + wb); the counts add whatever the weights are"""
+    a, b, out = _one(a, CROSS_STATISTICS), _one(b, CROSS_STATISTICS), np.zeros(1, dtype=CROSS_STATISTICS)
+    W = C.c_double(0.0)
+    _capi.check(_capi.lib().rmclhip_cross_statistics_merge_weighted(_ptr(a), float(wa), _ptr(b), float(wb), _ptr(out), C.byref(W)))
+    return out[0].copy(), W.value
 
 
 def cross_statistics_transform(T, s):
@@ -182,6 +195,15 @@ def pose_covariance(info, params=None, **kw):
     p = params if params is not None else pose_covariance_params(**kw)
     info, out = _one(info, POSE_INFORMATION), np.zeros(1, dtype=POSE_COVARIANCE)
     _capi.check(_capi.lib().rmclhip_pose_covariance_host(_ptr(info), C.byref(p), _ptr(out)))
+    return out[0].copy()
+
+
+def pose_covariance_robust(info, params=None, **kw):
+    """pose_covariance of a POSE_INFORMATION_ROBUST record: the same algebra on its `info`, the estimated noise
+    s2 = rss / (weight_sum - 6) (rmclhip_pose_covariance_robust_host)"""
+    p = params if params is not None else pose_covariance_params(**kw)
+    info, out = _one(info, POSE_INFORMATION_ROBUST), np.zeros(1, dtype=POSE_COVARIANCE)
+    _capi.check(_capi.lib().rmclhip_pose_covariance_robust_host(_ptr(info), C.byref(p), _ptr(out)))
     return out[0].copy()
 
 
